@@ -12,7 +12,13 @@ plans): step k+1's build runs on its own stream beside step k's count, its count
 before the host waits for step k's all-reduce and histogram, and every step's histogram is
 produced and checked.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--no-paths] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--dump-outputs DIR]
+  python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-paths] [--no-cpu]
+
+A plain run does only what the headline needs: set up, settle and warm up, time the K steps,
+write the last step's histogram (--dump-outputs) and print the result line.  --full adds what
+takes runs of its own: the copy ceiling and the rooflines, the pair-enumerating kernel, the side
+paths and the CPU baseline (the keys marked (--full) below).
 
 --gpus N > 1 without a launcher: bench.py itself starts N rank processes (one per GPU,
 backend nccl = RCCL) before anything touches a GPU, and exits non-zero if fewer than N
@@ -20,16 +26,16 @@ GPUs are visible.  Under torchrun (WORLD_SIZE set) every process is one rank and
 WORLD_SIZE must equal --gpus.  Rank 0 prints one JSON line:
   value     all pairs of the whole job / max-over-ranks wall time of the K timed steps
   ranks     per-rank count / all-reduce / build / own step times
-  roofline  the dominant kernel priced by HIP events recorded around every one of its
+  roofline  (--full) the dominant kernel priced by HIP events recorded around every one of its
             launches in the K timed steps, on the stream the launches run on
             (sct_allpairs_timing); HBM against 8 TB/s and against a device copy measured
             in the same run; the issue-rate picture (VALU / matrix-pipe busy) from the
             committed PMC summary; the committed rocprof average beside the live one
-  paths     (N = 1) config 4 (100M-query nearest whitelist), config 5's 3.7M all-pairs and
+  paths     (--full, N = 1) config 4 (100M-query nearest whitelist), config 5's 3.7M all-pairs and
             its 1e9-read encode + GC, FASTQ CB/UMI extraction, whitelist-file ingest and
             base_frequency, each timed here with its own roofline and a sampled check against
             the oracle (none of them is inside the headline's timed region)
-  cpu_baseline  (N = 1) the C oracle restatement (test infrastructure, never the product)
+  cpu_baseline  (--full, N = 1) the C oracle restatement (test infrastructure, never the product)
             on this host's cores, the histogram checked against the GPU's
 """
 
@@ -68,16 +74,21 @@ def parse(argv=None):
                     help="untimed steps before the warmup while the GPU clock settles (-1: 30 x world, "
                          "the same count on every rank; 0: none)")
     ap.add_argument("--config", type=int, default=2, choices=[1, 2, 3, 5])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the histogram) as DIR/hist.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: copy ceiling and rooflines, the pair "
+                         "kernel, the side paths (configs 4 / 5, FASTQ, drop-in calls) and the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=30.0,
                     help="CPU baseline budget: the whole job if it fits, else a row sample")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-paths", action="store_true", help="skip configs 4 / 5 (N = 1 paths)")
-    ap.add_argument("--no-stream", action="store_true", help="skip the host-resident stream paths")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-paths", action="store_true", help="--full: skip configs 4 / 5 (N = 1 paths)")
+    ap.add_argument("--no-stream", action="store_true", help="--full: skip the host-resident stream paths")
     ap.add_argument("--path-steps", type=int, default=5)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL)")
     ap.add_argument("--scheme", default="auto", choices=["auto", "subsets", "moments", "spectral"])
     ap.add_argument("--pair-steps", type=int, default=5,
-                    help="steps of the pair-enumerating MOMENTS kernel timed beside SPECTRAL (N=1)")
+                    help="--full: steps of the pair-enumerating MOMENTS kernel timed beside SPECTRAL (N=1)")
     ap.add_argument("--allow-shared-gpu", action="store_true",
                     help="rehearsal only: let more ranks than GPUs share devices")
     ap.add_argument("--stub", action="store_true",
@@ -1373,16 +1384,23 @@ def run_rank(args, rank, world, local):
     P = job.plan.pairs
     assert int(hist.sum()) == P, "histogram does not cover every pair"
     summ = _lib.summary_from_hist(hist)
-    copy_gbs = copy_ceiling_gbs(dev) if rank == 0 else None
-    if spectral:
-        info = job.plan.spectral_info()
-        roofline = spectral_roofline(kt, min(info["chunk_slices"], job.end - job.begin), info["elem_bytes"],
-                                     tm["count_ms"], copy_gbs, column_bits=info["column_bits"])
-    else:
-        roofline = pair_roofline(job, job.my_pairs(), kt["count"][0] / max(1, kt["count"][1]), L)
-    pair_kernel = None
-    if spectral and world == 1 and args.pair_steps > 0:
-        pair_kernel = time_pair_kernel(job.d_codes, L, args.pair_steps)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the exact histogram
+        # (counts below 2^53, so float64 holds them exactly); the codes are seeded, so two
+        # builds given the same arguments can be compared bin for bin
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "hist.npy"), hist.astype(np.float64))
+    copy_gbs = roofline = pair_kernel = None
+    if args.full:
+        copy_gbs = copy_ceiling_gbs(dev) if rank == 0 else None
+        if spectral:
+            info = job.plan.spectral_info()
+            roofline = spectral_roofline(kt, min(info["chunk_slices"], job.end - job.begin), info["elem_bytes"],
+                                         tm["count_ms"], copy_gbs, column_bits=info["column_bits"])
+        else:
+            roofline = pair_roofline(job, job.my_pairs(), kt["count"][0] / max(1, kt["count"][1]), L)
+        if spectral and world == 1 and args.pair_steps > 0:
+            pair_kernel = time_pair_kernel(job.d_codes, L, args.pair_steps)
     job.close()
 
     out = None
@@ -1419,9 +1437,11 @@ def run_rank(args, rank, world, local):
                                 [float(x) for x in summ])),
             "hist": [int(x) for x in hist],
         }
+        if not args.full:
+            del out["roofline"]
         if pair_kernel is not None:
             out["pair_kernel"] = pair_kernel
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         threads, _ = host_threads()
         if not args.no_paths:
             # configs 4 and 5 (BASELINE.json), each timed on its own after the headline

@@ -13,8 +13,8 @@ rc=$?
 tail -3 $P/pytest_gpu.log
 [ $rc -eq 0 ] || exit 3
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $P/trace -o run --output-format csv -- \
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 > $P/trace.log 2>&1 || exit 3
-B="python3 bench.py --no-cpu --no-paths --pair-steps 0 --steps 5 --warmup 2"
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $P/trace.log 2>&1 || exit 3
+B="python3 bench.py --full --no-cpu --no-paths --pair-steps 0 --steps 5 --warmup 2"
 i=0
 for pmc in "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE GRBM_COUNT" \
            "FETCH_SIZE" "WRITE_SIZE" \
@@ -32,5 +32,5 @@ for pmc in "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES 
   timeout -s KILL 150 rocprofv3 --pmc $pmc -d $P/s5pmc$i -o run --output-format csv -- $C > $P/s5pmc$i.log 2>&1 || echo "s5 pmc pass $i failed"
 done
 timeout -k 10 300 python3 tools/fastq_flow_breakdown.py > $P/fastq_flow.json 2> $P/fastq_flow.err || exit 3
-timeout -k 10 500 python3 bench.py > $P/bench.log 2> $P/bench.err || exit 3
+timeout -k 10 500 python3 bench.py --full > $P/bench.log 2> $P/bench.err || exit 3
 echo done

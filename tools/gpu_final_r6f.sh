@@ -8,8 +8,8 @@ P=gpurun_out/prof6f
 mkdir -p $P
 export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $P/trace -o run --output-format csv -- \
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 > $P/trace.log 2>&1 || exit 3
-B="python3 bench.py --no-cpu --no-paths --pair-steps 0 --steps 5 --warmup 2 --settle-steps 0"
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $P/trace.log 2>&1 || exit 3
+B="python3 bench.py --full --no-cpu --no-paths --pair-steps 0 --steps 5 --warmup 2 --settle-steps 0"
 i=0
 for pmc in "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE GRBM_COUNT" \
            "FETCH_SIZE" "WRITE_SIZE"; do

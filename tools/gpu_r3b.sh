@@ -14,5 +14,5 @@ if [ "${PROFILE:-1}" = "1" ]; then
   mkdir -p gpurun_out/profiles_new
   cp profiles/r03_*kernel_stats.csv profiles/pmc_*_r03.json gpurun_out/profiles_new/ || exit 5
 fi
-timeout -k 10 400 python -u bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || exit $?
+timeout -k 10 400 python -u bench.py --full > "$TMPDIR/bench.json" 2> "$TMPDIR/bench.err" || exit $?
 exit 0

@@ -21,5 +21,5 @@ for pmc in "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES 
   i=$((i+1))
   timeout -s KILL 150 rocprofv3 --pmc $pmc -d $P/s5pmc$i -o run --output-format csv -- $C > $P/s5pmc$i.log 2>&1 || { echo "pmc pass $i failed"; exit 3; }
 done
-timeout -k 10 400 python3 bench.py > $P/bench.log 2>&1 || exit 3
+timeout -k 10 400 python3 bench.py --full > $P/bench.log 2>&1 || exit 3
 echo done

@@ -12,5 +12,5 @@ tail -3 $P/pytest_gpu.log
 timeout -k 10 300 python3 tools/ab_libs.py --path whitelist --variant base=sctools_amd/libsctools_hip_base.so \
   --variant spec= --variant nospec=:ingest_spec=0 --rounds 3 > $P/ab_whitelist.jsonl 2> $P/ab_whitelist.err || exit 3
 tail -1 $P/ab_whitelist.jsonl
-timeout -k 10 400 python3 bench.py > $P/bench.log 2> $P/bench.err || exit 3
+timeout -k 10 400 python3 bench.py --full > $P/bench.log 2> $P/bench.err || exit 3
 echo done

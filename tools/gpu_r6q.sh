@@ -13,7 +13,7 @@ for i in 1 2; do
   cat $P/w8_$i.json
 done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $P/trace -o run --output-format csv -- python3 tools/w8_share.py 8 40 > $P/trace.log 2>&1 || exit 3
-timeout -k 10 600 python3 bench.py --no-paths --no-cpu > $P/bench.log 2> $P/bench.err || { tail $P/bench.err; exit 3; }
+timeout -k 10 600 python3 bench.py --full --no-paths --no-cpu > $P/bench.log 2> $P/bench.err || { tail $P/bench.err; exit 3; }
 python3 -c "
 import json; d=json.loads(open('$P/bench.log').read().strip().splitlines()[-1]); print('bench ms_per_step', d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['other_kernel']['ms'])"
 echo done
