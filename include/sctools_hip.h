@@ -60,7 +60,9 @@ int sct_set_device(int device);        /* select the device for later calls (hip
 #define SCT_TUNE_INGEST_DIRECT 15       /* whitelist ingest: up to this many 16 KiB tiles (4096) the encode pass
                                            sums the per-tile counts itself, no reduction launch */
 #define SCT_TUNE_INGEST_SPEC 16         /* whitelist ingest: 1 tries 16-base lines in one read first (default), 0 never */
-#define SCT_TUNE_NKEYS 17
+#define SCT_TUNE_COUNT_PREAGG 17        /* counter insert: 0 one table row per code, 1 equal codes of a wave merged
+                                           first (default), 2 a per-workgroup LDS table per tile */
+#define SCT_TUNE_NKEYS 18
 int sct_tune_set(int key, int64_t value);
 int sct_tune_get(int key, int64_t* value);  /* -1 when unset */
 
@@ -359,6 +361,10 @@ int sct_nearest_multi_create_host(int kind, const uint64_t* whitelist, int64_t n
                                   const int* devices, int ndev, sct_nearest_multi** plan);
 int sct_nearest_multi_query_host(sct_nearest_multi* plan, const uint64_t* queries, int64_t nq, int32_t* index,
                                  uint8_t* dist);
+/* sct_nearest_count_host over the same split: every slot tallies into a host array of its own and
+ * the arrays are summed into counts / tally after the slots return. */
+int sct_nearest_multi_count_host(sct_nearest_multi* plan, const uint64_t* queries, int64_t nq, uint64_t* counts,
+                                 uint64_t* tally);
 int sct_nearest_multi_destroy(sct_nearest_multi* plan);
 /* Host encode stream (sct_encode_stream_host) over contiguous record ranges, one per slot. */
 int sct_encode_stream_host_devices(int kind, const uint8_t* seqs, int64_t n, int L, uint64_t* codes, uint8_t* gc,
@@ -436,6 +442,43 @@ int sct_nearest_plan_create_host(int kind, const uint64_t* whitelist, int64_t nw
                                  sct_nearest_plan** plan);
 int sct_nearest_query_host(sct_nearest_plan* plan, const uint64_t* queries, int64_t nq, int32_t* index,
                            uint8_t* dist);
+
+/* ---------------------------------------------------------------- counting observed barcodes
+ * Replaces the host Counter of Barcodes.from_iterable_encoded (src/sctools/barcode.py:100-102,
+ * `Counter(iterable)`) for codes below 2^64: a streaming device group-by with Counter's semantics.
+ * Per distinct code the counter keeps its count and the global position (over every update so far)
+ * of its first occurrence; fetch returns the rows ordered by that position, which is Counter's
+ * iteration order, whatever order the device counted in.
+ * The table is open addressing with 64-bit atomics (claim by compare-and-swap, bounded probes) and
+ * grows by itself: capacity_hint only sizes the first table (rounded up to a power of two, >= 64).
+ * Every code is legal, 2^64 - 1 (the table's empty mark) included.  update feeds sub-batches and
+ * reads the table's size between them when it may have to grow, so it is asynchronous on `stream`
+ * only while the table has room; a call on another stream waits for the counter's earlier work.
+ * info: nunique = distinct codes, total = codes seen, capacity = table slots (each nullable).
+ * fetch: keys / counts / first of the nunique rows; room < nunique is SCT_E_INVALID and leaves the
+ * counter as it was.  A table that fills up in spite of the growth rule is SCT_E_RANGE.
+ * destroy waits for the work the counter enqueued. */
+typedef struct sct_counter sct_counter;
+int sct_counter_create(int64_t capacity_hint, sct_counter** counter);
+int sct_counter_update(sct_counter* counter, const uint64_t* d_codes, int64_t n, void* stream);
+int sct_counter_update_host(sct_counter* counter, const uint64_t* codes, int64_t n);
+int sct_counter_info(sct_counter* counter, int64_t* nunique, int64_t* total, int64_t* capacity);
+int sct_counter_fetch_host(sct_counter* counter, uint64_t* keys, uint64_t* counts, int64_t* first, int64_t room);
+int sct_counter_fetch(sct_counter* counter, uint64_t* d_keys, uint64_t* d_counts, int64_t* d_first, int64_t room,
+                      void* stream);
+int sct_counter_destroy(sct_counter* counter);
+/* Reads per whitelist barcode (no reference function; the host form is np.bincount over
+ * sct_nearest_query's index): d_counts[j] += 1 for every index j in [0, nw), d_tally[0] += 1 for
+ * every -1 (no match) and d_tally[1] += 1 for every -2 (tie); d_counts: nw uint64, d_tally: 2 uint64,
+ * both ACCUMULATED.  An index outside [-2, nw) is not counted and makes the call SCT_E_RANGE; the
+ * call waits for the stream to learn that.
+ * sct_nearest_count_host: the queries in, sct_nearest_query and the tally on the thread's stream
+ * with pool scratch, and only nw counts + 2 tallies back, ADDED to the caller's host arrays (what
+ * sct_nearest_query_host returns is 5 bytes per query).  nq == 0 changes nothing. */
+int sct_index_tally(const int32_t* d_index, int64_t n, int64_t nw, uint64_t* d_counts, uint64_t* d_tally,
+                    void* stream);
+int sct_nearest_count_host(sct_nearest_plan* plan, const uint64_t* queries, int64_t nq, uint64_t* counts,
+                           uint64_t* tally);
 
 /* ---------------------------------------------------------------- FASTQ barcode extraction
  * Replaces the per-record path reader.Reader.__iter__ (src/sctools/reader.py:56-85) ->

@@ -8,7 +8,8 @@ all-pairs Hamming summary.  Compute runs in HIP kernels of ``libsctools_hip.so``
 Unlike the reference's ``__init__`` this package does not import pysam.
 """
 
-from . import encodings, barcode, stats  # noqa: F401
+from . import encodings, barcode, stats, counting  # noqa: F401
+from .counting import DeviceCounter  # noqa: F401
 
 
 def release_device_memory():

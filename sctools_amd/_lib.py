@@ -37,7 +37,7 @@ TUNE_KEYS = {"spectral_chunk": 1, "spectral_min_n": 2, "allpairs_grab": 3, "allp
              "allpairs_grid": 5, "nearest_scheme": 6, "nearest_load": 7, "scalar_server": 8,
              "scalar_idle_ms": 9, "spectral_columns": 10, "plan_cache": 11,
              "encode_grid": 12, "ingest_tiles": 13, "fastq_onepass": 14,
-             "ingest_direct": 15, "ingest_spec": 16}
+             "ingest_direct": 15, "ingest_spec": 16, "count_preagg": 17}
 NEAREST_AUTO, NEAREST_OA, NEAREST_CSR, NEAREST_HALVES = 0, 1, 2, 3
 
 _i32, _i64, _dbl = ctypes.c_int, ctypes.c_int64, ctypes.c_double
@@ -131,6 +131,16 @@ SIGNATURES = {
     "sct_nearest_multi_query_host": [_vp, _vp, _i64, _vp, _vp],
     "sct_nearest_multi_destroy": [_vp],
     "sct_encode_stream_host_devices": [_i32, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i32],
+    "sct_counter_create": [_i64, ctypes.POINTER(_vp)],
+    "sct_counter_update": [_vp, _vp, _i64, _vp],
+    "sct_counter_update_host": [_vp, _vp, _i64],
+    "sct_counter_info": [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    "sct_counter_fetch_host": [_vp, _vp, _vp, _vp, _i64],
+    "sct_counter_fetch": [_vp, _vp, _vp, _vp, _i64, _vp],
+    "sct_counter_destroy": [_vp],
+    "sct_index_tally": [_vp, _i64, _i64, _vp, _vp, _vp],
+    "sct_nearest_count_host": [_vp, _vp, _i64, _vp, _vp],
+    "sct_nearest_multi_count_host": [_vp, _vp, _i64, _vp, _vp],
 }
 _RESTYPES = {"sct_last_error": ctypes.c_char_p}
 
@@ -858,6 +868,19 @@ class HostNearestPlan:
             f = self._lib.sct_nearest_multi_query_host if self._multi else self._lib.sct_nearest_query_host
             check(f(self._h, _ptr(q), q.size, _ptr(index), _ptr(dist)))
         return index, dist
+
+    def count(self, queries, counts, tally):
+        """Add the batch's reads per whitelist barcode to ``counts`` (uint64[nw]) and its
+        no-match / tie numbers to ``tally`` (uint64[2]): only those cross PCIe on the way back
+        (sct_nearest_count_host / sct_nearest_multi_count_host)."""
+        q = np.ascontiguousarray(queries, dtype=np.uint64).reshape(-1)
+        if counts.dtype != np.uint64 or counts.size != self.nw or not counts.flags.c_contiguous:
+            raise ValueError("counts must be a contiguous uint64 array of the whitelist's size")
+        if tally.dtype != np.uint64 or tally.size != 2 or not tally.flags.c_contiguous:
+            raise ValueError("tally must be a contiguous uint64 array of 2")
+        if q.size:
+            f = self._lib.sct_nearest_multi_count_host if self._multi else self._lib.sct_nearest_count_host
+            check(f(self._h, _ptr(q), q.size, _ptr(counts), _ptr(tally)))
 
     def close(self):
         if self._h:

@@ -196,6 +196,25 @@ class Barcodes:
         return cls(Counter(iterable), barcode_length=barcode_length)
 
     @classmethod
+    def from_encoded_array(cls, codes, barcode_length):
+        """construct a barcode set from an array of encoded barcodes, counted on the device
+
+        No reference counterpart: the reference counts encoded barcodes with ``Counter(iterable)``
+        on the host (barcode.py:100-102), one Python step per observed code.  This is the same
+        mapping -- the same keys, counts and iteration order as
+        ``from_iterable_encoded(codes.tolist(), barcode_length)`` -- built by the device group-by
+        of ``sctools_amd.counting.DeviceCounter``.  The order is part of the contract, not a
+        nicety: ``nearest()`` answers with indices in iteration order, so the keys come back in
+        first-occurrence order, as ``Counter`` keeps them.  ``codes`` is an array of np.uint64 or
+        np.int64 (anything else is converted to np.uint64); arbitrary iterables and hashables
+        stay with ``from_iterable_encoded``."""
+        from .counting import DeviceCounter
+        codes = np.asarray(codes)
+        with DeviceCounter(capacity_hint=max(64, min(codes.size, 1 << 20))) as dc:
+            dc.update(codes)
+            return cls(dc.counter(), barcode_length=barcode_length)
+
+    @classmethod
     def from_iterable_strings(cls, iterable, barcode_length):
         """construct an ObservedBarcodeSet from an iterable of string barcodes"""
         return cls(Counter(_encode_items(iterable, lambda b: _item_bytes(b.encode()))), barcode_length=barcode_length)
@@ -294,6 +313,34 @@ class WhitelistCorrector:
         if self._plan is None:
             return np.full(q.size, -1, np.int32), np.full(q.size, 255, np.uint8)
         return self._plan.query(q)
+
+    def count(self, queries, out=None):
+        """Reads per whitelist barcode for one batch, tallied on the device: only the counts cross
+        PCIe on the way back, not an index and a distance per query.
+
+        :param out: optional accumulator from an earlier call, ``(counts, n_none, n_tie)`` or just
+            the counts array (np.int64, whitelist size): the batch is added to it, so a loop over
+            ``fastq.iter_arrays()`` keeps one array
+        :return (np.ndarray[int64], int, int): counts per whitelist index, queries with no
+            whitelist barcode within ``max_distance``, queries with a tie -- equal to
+            ``np.bincount(index[index >= 0], minlength=size)``, ``(index == -1).sum()`` and
+            ``(index == -2).sum()`` of ``nearest(queries)``
+        """
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64)).reshape(-1)
+        n_none = n_tie = 0
+        counts = out
+        if isinstance(out, tuple):
+            counts, n_none, n_tie = out
+        if counts is None:
+            counts = np.zeros(self.size, dtype=np.int64)
+        elif not (isinstance(counts, np.ndarray) and counts.dtype == np.int64 and counts.shape == (self.size,)
+                  and counts.flags.c_contiguous):
+            raise ValueError('out must be a contiguous np.int64 array of the whitelist size')
+        if self._plan is None:  # empty whitelist: nothing can match
+            return counts, int(n_none) + q.size, int(n_tie)
+        tally = np.zeros(2, dtype=np.uint64)
+        self._plan.count(q, counts.view(np.uint64), tally)
+        return counts, int(n_none) + int(tally[0]), int(n_tie) + int(tally[1])
 
     def close(self):
         if self._plan is not None:

@@ -132,6 +132,7 @@ extern "C" int sct_nearest_host_devices(int kind, const uint64_t* whitelist, int
 struct sct_nearest_multi {
   std::vector<int> devices;
   std::vector<sct_nearest_plan*> plans;
+  int64_t nw = 0;
 };
 
 extern "C" int sct_nearest_multi_create_host(int kind, const uint64_t* whitelist, int64_t nw, int code_bits, int max_d,
@@ -142,6 +143,7 @@ extern "C" int sct_nearest_multi_create_host(int kind, const uint64_t* whitelist
   auto* m = new sct_nearest_multi();
   m->devices.assign(devices, devices + ndev);
   m->plans.assign((size_t)ndev, nullptr);
+  m->nw = nw;
   const int rc = sct::run_on_devices(m->devices.data(), ndev, [&](int r) {
     return sct_nearest_plan_create_host(kind, whitelist, nw, code_bits, max_d, &m->plans[(size_t)r]);
   });
@@ -163,6 +165,32 @@ extern "C" int sct_nearest_multi_query_host(sct_nearest_multi* m, const uint64_t
     const int64_t b = split(nq, r, k), e = split(nq, r + 1, k);
     return sct_nearest_query_host(m->plans[(size_t)r], queries + b, e - b, index + b, dist + b);
   });
+}
+
+// every slot tallies its query range into a host array of its own; the arrays are summed here
+extern "C" int sct_nearest_multi_count_host(sct_nearest_multi* m, const uint64_t* queries, int64_t nq,
+                                            uint64_t* counts, uint64_t* tally) {
+  SCT_CHECK(nq >= 0, "nq must be >= 0");
+  SCT_CHECK(m != nullptr, "plan is NULL");
+  SCT_CHECK(tally != nullptr && (m->nw == 0 || counts != nullptr), "NULL counts");
+  if (nq == 0) return SCT_OK;
+  SCT_CHECK(queries != nullptr, "NULL queries");
+  const int k = (int)m->plans.size();
+  const size_t row = (size_t)m->nw + 2;  // counts, then the two tallies
+  std::vector<uint64_t> part((size_t)k * row, 0);
+  const int rc = sct::run_on_devices(m->devices.data(), k, [&](int r) {
+    const int64_t b = split(nq, r, k), e = split(nq, r + 1, k);
+    uint64_t* mine = part.data() + (size_t)r * row;
+    return sct_nearest_count_host(m->plans[(size_t)r], queries + b, e - b, mine, mine + m->nw);
+  });
+  if (rc != SCT_OK) return rc;
+  for (int r = 0; r < k; ++r) {
+    const uint64_t* mine = part.data() + (size_t)r * row;
+    for (int64_t j = 0; j < m->nw; ++j) counts[j] += mine[j];
+    tally[0] += mine[m->nw];
+    tally[1] += mine[m->nw + 1];
+  }
+  return SCT_OK;
 }
 
 extern "C" int sct_nearest_multi_destroy(sct_nearest_multi* m) {

@@ -1058,6 +1058,9 @@ extern "C" int sct_nearest_plan_create(int kind, const uint64_t* d_whitelist, in
   return SCT_OK;
 }
 
+// the whitelist size of a plan, for the counting entry points (count.hip)
+int64_t sct::nearest_plan_size(const sct_nearest_plan* p) { return p->nw; }
+
 extern "C" int sct_nearest_plan_info(const sct_nearest_plan* p, int* scheme, int64_t* index_bytes) {
   SCT_CHECK(p != nullptr, "plan is NULL");
   int64_t bytes = 0;

@@ -90,6 +90,9 @@ void pool_free(void* p, hipStream_t s);
 // Returns the first failing slot's status with its message.  One such call at a time per process.
 int run_on_devices(const int* devices, int ndev, const std::function<int(int)>& fn);
 
+// Whitelist codes a nearest plan indexes (nearest.hip; p is not NULL).
+int64_t nearest_plan_size(const sct_nearest_plan* p);
+
 // sct_tune_set value of `key`, or dflt when unset (host.cpp).
 int64_t tune(int key, int64_t dflt);
 

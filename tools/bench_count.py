@@ -1,0 +1,194 @@
+"""Counting on the device against the host ways of getting the same answer, on one box in one run.
+
+Input A (the corrected-flow shape): config 4's observed ThreeBit codes (synthetic.config4_queries
+against the 737,280 whitelist).  Input B (the worst case for a hash table): 3,686,400 pairwise
+distinct codes followed by the same array again -- every key new, then every key a hit.
+Per input and per pre-aggregation mode (SCT_TUNE_COUNT_PREAGG 0 none / 1 wave merge / 2 LDS table;
+interleaved rounds in one process): DeviceCounter.update_device time, the table's growth, nunique
+and the fraction of 8 TB/s the 8 B/code read reaches; the host-resident update; and the yardsticks
+Counter(codes.tolist()) and np.unique(codes, return_index=True, return_counts=True), whose reduced
+n is stated.  Then WhitelistCorrector.count against .nearest() + np.bincount on one batch, with
+the bytes each moves over PCIe.
+
+Every step runs in a child process of its own under its own time limit; a step that fails ends
+the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
+
+  python tools/bench_count.py --tag mi355x
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300}  # seconds
+MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
+HBM_BYTES_PER_S = 8e12
+
+
+def _time_ms(f):
+    t = time.perf_counter()
+    f()
+    return (time.perf_counter() - t) * 1e3
+
+
+def counter_step(which, args):
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, counting, synthetic
+
+    if which == "A":
+        n, L, seed = synthetic.CONFIGS[4]
+        wl3 = synthetic.two_to_three(synthetic.whitelist_codes(n, L, seed), L)
+        d, _, _ = synthetic.config4_queries(wl3, args.n_a, seed=4, device=torch.device("cuda"))
+    else:
+        n, L, seed = synthetic.CONFIGS[5]
+        once = synthetic.whitelist_codes(n, L, seed)
+        d = torch.from_numpy(np.concatenate([once, once]).view(np.int64)).cuda()
+    torch.cuda.synchronize()
+    n = d.numel()
+    out = {"input": which, "n": n, "modes": {}}
+
+    def run_device(mode):
+        with _lib.tuning(count_preagg=mode):
+            dc = counting.DeviceCounter()
+            cap0 = dc.info()["capacity"]
+
+            def go():
+                dc.update_device(d.data_ptr(), n)
+                torch.cuda.synchronize()
+            ms = _time_ms(go)
+            info = dc.info()
+            dc.close()
+        return ms, cap0, info
+
+    run_device(1)  # warm-up: code objects, pool
+    times = {m: [] for m in MODES}
+    for _ in range(args.rounds):
+        for m in MODES:
+            ms, cap0, info = run_device(m)
+            times[m].append(ms)
+            out["nunique"] = info["nunique"]
+            out["capacity_start"], out["capacity_end"] = cap0, info["capacity"]
+    out["growth_doublings"] = (out["capacity_end"] // out["capacity_start"]).bit_length() - 1
+    for m, name in MODES.items():
+        med = float(np.median(times[m]))
+        out["modes"][name] = {"update_device_ms": [round(t, 3) for t in times[m]], "median_ms": round(med, 3),
+                              "min_ms": round(min(times[m]), 3),
+                              "read_fraction_of_8TBps": round(n * 8 / (med * 1e-3) / HBM_BYTES_PER_S, 4)}
+    # a table sized up front (no growth on the way): what the growth costs
+    with counting.DeviceCounter(capacity_hint=out["capacity_end"]) as dc:
+        def go():
+            dc.update_device(d.data_ptr(), n)
+            torch.cuda.synchronize()
+        out["presized_update_device_ms"] = round(_time_ms(go), 3)
+        out["fetch_host_ms"] = round(_time_ms(dc.arrays), 3)
+    codes = d.cpu().numpy().view(np.uint64)
+    with counting.DeviceCounter() as dc:
+        out["update_host_ms"] = round(_time_ms(lambda: dc.update(codes)), 3)
+        assert len(dc) == out["nunique"] and dc.total == n
+        if which == "B":
+            keys, counts, first = dc.arrays()
+            assert keys.size == n // 2 and (counts == 2).all() and np.array_equal(first, np.arange(n // 2))
+    # the host ways to the same answer (reduced n, stated; the Python loop is linear in n)
+    nc = min(n, args.n_counter)
+    from collections import Counter
+    sub = codes[:nc]
+    t = _time_ms(lambda: Counter(sub.tolist()))
+    out["host_counter"] = {"n": nc, "ms": round(t, 1), "ns_per_code": round(t * 1e6 / nc, 1)}
+    nu = min(n, args.n_unique)
+    sub = codes[:nu]
+    t = _time_ms(lambda: np.unique(sub, return_index=True, return_counts=True))
+    out["host_np_unique"] = {"n": nu, "ms": round(t, 1), "ns_per_code": round(t * 1e6 / nu, 1)}
+    best = min(v["median_ms"] for v in out["modes"].values())
+    out["device_ns_per_code_best"] = round(best * 1e6 / n, 4)
+    return out
+
+
+def tally_step(args):
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, barcode, synthetic
+
+    n, L, seed = synthetic.CONFIGS[4]
+    wl3 = synthetic.two_to_three(synthetic.whitelist_codes(n, L, seed), L)
+    d, _, _ = synthetic.config4_queries(wl3, args.n_tally, seed=4, device=torch.device("cuda"))
+    q = _lib.pinned.empty(args.n_tally, np.uint64)  # page-locked, as the encoder returns its codes
+    q[:] = d.cpu().numpy().view(np.uint64)
+    del d
+    wc = barcode.WhitelistCorrector(wl3, max_distance=1, encoding="ThreeBit")
+
+    def old():
+        idx, _ = wc.nearest(q)
+        idx = np.asarray(idx)
+        return np.bincount(idx[idx >= 0], minlength=wc.size), int((idx == -1).sum()), int((idx == -2).sum())
+
+    ref = old()
+    got = wc.count(q)
+    assert np.array_equal(got[0], ref[0]) and got[1:] == ref[1:]
+    t_old, t_near, t_new = [], [], []
+    for _ in range(args.rounds + 2):
+        t_near.append(_time_ms(lambda: wc.nearest(q)))
+        t_old.append(_time_ms(old))
+        t_new.append(_time_ms(lambda: wc.count(q)))
+    wc.close()
+    nq = args.n_tally
+    med = lambda ts: round(float(np.median(ts[2:])), 3)  # noqa: E731
+    return {"nq": nq, "nw": int(wl3.size), "nearest_ms": med(t_near), "nearest_plus_bincount_ms": med(t_old),
+            "count_ms": med(t_new), "speedup_vs_nearest_plus_bincount": round(med(t_old) / med(t_new), 3),
+            "pcie_bytes_nearest": {"in": nq * 8, "out": nq * 5},
+            "pcie_bytes_count": {"in": nq * 8, "out": (int(wl3.size) + 3) * 8}}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--tag", default="run")
+    ap.add_argument("--step", choices=sorted(STEPS), help="run one step in this process (the launcher's children)")
+    ap.add_argument("--n-a", type=int, default=100_000_000, help="input A codes")
+    ap.add_argument("--n-counter", type=int, default=2_000_000, help="codes given to collections.Counter")
+    ap.add_argument("--n-unique", type=int, default=20_000_000, help="codes given to np.unique")
+    ap.add_argument("--n-tally", type=int, default=20_000_000, help="queries of the WhitelistCorrector batch")
+    ap.add_argument("--rounds", type=int, default=5)
+    args = ap.parse_args()
+    if args.step:
+        res = tally_step(args) if args.step == "tally" else counter_step(args.step[-1], args)
+        print("RESULT " + json.dumps(res))
+        return 0
+    detail = {"tag": args.tag, "argv": sys.argv[1:], "steps": {}}
+    rc = 0
+    for step, limit in STEPS.items():
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step,
+               "--n-a", str(args.n_a), "--n-counter", str(args.n_counter), "--n-unique", str(args.n_unique),
+               "--n-tally", str(args.n_tally), "--rounds", str(args.rounds)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+        if p.returncode != 0 or not lines:
+            detail["steps"][step] = {"failed": p.returncode, "stderr": p.stderr[-2000:]}
+            rc = 1
+            break  # nothing more is started on the GPU after a step that failed
+        detail["steps"][step] = json.loads(lines[-1][len("RESULT "):])
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    path = os.path.join(ROOT, "profiles", "count_%s.json" % args.tag)
+    with open(path, "w") as f:
+        json.dump(detail, f, indent=1, sort_keys=True)
+        f.write("\n")
+    short = {"tag": args.tag, "ok": rc == 0, "detail": os.path.relpath(path, ROOT)}
+    for step, res in detail["steps"].items():
+        if "modes" in res:
+            short[step] = {"n": res["n"], "nunique": res["nunique"],
+                           "ms": {k: v["median_ms"] for k, v in res["modes"].items()},
+                           "host_ms": res["update_host_ms"]}
+        elif "count_ms" in res:
+            short[step] = {"count_ms": res["count_ms"], "nearest_plus_bincount_ms": res["nearest_plus_bincount_ms"]}
+        else:
+            short[step] = res
+    print(json.dumps(short))
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main())
