@@ -653,71 +653,80 @@ __global__ __launch_bounds__(256) void tile_kernel(const T* __restrict__ buf, in
 }
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
-typedef long v2l_t __attribute__((ext_vector_type(2)));
 typedef short v2s_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2l_t pack_v2l(const uint32_t* w) {
-  return v2l_t{(long)(((uint64_t)w[1] << 32) | w[0]), (long)(((uint64_t)w[3] << 32) | w[2])};
-}
 
 // ---------------------------------------------------------------- register-resident tile (int8 seeds)
-// One WAVE transforms one whole slice with no LDS exchange and no barrier.  Column bits:
-// P = 0..5 (digits 0-2), Q = 6..11 (digits 3-5), R = 12, 13 (digit 6).  Lane l's 16-B load
-// (plane R, load mt) holds columns 16 (l >> 4) + 64 (l & 15) + 1024 mt + 4096 R + j: a wave
-// reads each kilobyte of the slice whole.
-//   stage 1 (per plane R): the bytes are the A operand of v_mfma_i32_16x16x64_i8 as loaded
-//     (A[m = Q bits 0..3 = l & 15][k = P = 16 (l >> 4) + j]) against B = a quarter qn of H_64:
-//     C1[m][n] = sum_P D * H -> transformed P' (n = P' bits 0..3 = l & 15, qn = bits 4, 5),
-//     output rows m = 4 (l >> 4) + i.  So lane l holds Q bits 0, 1 = i, 2, 3 = l >> 4 and,
-//     over the 4 loads, Q bits 4, 5 = mt: 16 values that ARE stage 2's B operand (k = 16 (l >> 4)
-//     + 4 mt + i, a relabeling of whole Q digits), packed into bytes in registers.
-//   stage 2: H_64 over Q (A = the same H quarters).  |v + 128| < 2^15 needs two bytes: with
-//     y = v + 128 = 256 h + l', v = 256 h + (l' - 128), so H v = (H h << 8) + H (l' - 128): two
-//     i8 MFMAs per output tile, the first shifted into the second's accumulator.  The byte
-//     split goes through int16 pairs (one v_perm packs two stage-1 outputs), which are also
-//     what the plane sums accumulate (v_pk_add_u16; the sum over the planes of v + 128 from
-//     -384 stays within +-32,640).  Outputs Q' rows 16 q2 + 4 (l >> 4) + i2: whole digits.
+// One WAVE transforms one whole slice with no LDS exchange and no barrier, on
+// v_mfma_i32_32x32x32_i8 (operands: A row / B column = l & 31, k = 16 (l >> 5) + j; C rows
+// 8 (i >> 2) + 4 (l >> 5) + (i & 3), column l & 31).  The 12 column bits of a plane R (bits 12,
+// 13) split into a stage-1 set P = {0, 1, 2, 3, 4, 10} and a stage-2 set Q = {5, 6, 7, 8, 9, 11},
+// which do not follow the 2-bit digits: what matters is that after both stages three whole
+// digits are lane bits and three are register / tile indices.
+//   loads: lane l's 16 B hold column bits 0..3 = j, 4 = l bit 5, 5 = l bit 3, 6, 7 = l bits 0, 1,
+//     8 = l bit 4, 9 = l bit 2; load (mt, ks) of plane R adds 1024 ks + 2048 mt + 4096 R: every
+//     load instruction of a wave reads one whole contiguous KiB of the slice.
+//   stage 1 (per plane): the bytes are the A operand as loaded (row m = l & 31: five Q bits, the
+//     sixth = mt; k = 16 (l >> 5) + j + 32 ks = P) against B = H_64 (column n = l & 31 + 32 nt):
+//     C1[m][n] = sum_P D * H, two chained K-steps ks per (nt, mt) tile.  Transformed P' = n:
+//     lane bits 0..4 = column bits 0..4, nt = bit 10.  A lane's 16 outputs are rows (m bits
+//     0, 1, 3, 4) = i and m bit 2 = l >> 5: exactly stage 2's B operand (k = 16 (l >> 5) + i
+//     + 32 mt, a relabeling of Q), packed into bytes in registers.
+//   stage 2: H_64 over Q (A = the same H registers, K-steps = stage 1's M-tiles mt).  |v + 128|
+//     < 2^15 needs two bytes: with y = v + 128 = 256 h + l', v = 256 h + (l' - 128), so H v =
+//     (H h << 8) + H (l' - 128): the high bytes' chain of two MFMAs, one shift of its 16
+//     results, then the low bytes' chain into that accumulator.  The byte split goes through
+//     int16 pairs (one v_perm packs two stage-1 outputs), which are also what the plane sums
+//     accumulate (v_pk_add_u16; the sum over the planes of v + 128 from -384 stays within
+//     +-32,640).  Output row bit t is the column bit of B's k bit t: i bits 0, 1 = column bits
+//     6, 7; l >> 5 = bit 5; i bits 2, 3 = bits 8, 9; the M-tile = bit 11.
 //   R (one base digit) by Parseval instead of a butterfly: with G_R = the 12-bit transform of
 //     plane R and F(R') = sum_R (-1)^<R, R'> G_R,  F(0) = transform of sum_R D_R = sum_R C1_R
 //     (added after stage 1) and sum_{R' != 0} F(R')^2 = 4 sum_R G_R^2 - F(0)^2.  So every
 //     (P', Q') adds F(0)^2 to weight w and 4 sum G_R^2 - F(0)^2 to weight w + 1: five stage-2
 //     transforms per slice (4 planes + the sum), no exchange between planes.
-//   Two quarters' MFMA chains are interleaved per wave (stage 1 of both, both byte splits, both
-//     high-byte and both low-byte stage-2 groups, then both sets of squares), and the next
-//     plane's loads are in flight while this one is transformed: 167 VGPRs, 3 waves per SIMD.
-// Weight of (P', Q', R'): digits of l & 3, (l >> 2) & 3, l >> 4 (thread constant) + qn + q2
-// + i2 (compile time) + the slice's + [R' != 0].  Each wave of the grid takes a contiguous run
+//   Per plane 8 + 16 MFMAs (one N-tile nt at a time: its two M-tiles' chains interleave), per
+//     slice 4 * 8 + 5 * 16 = 112 (94 issued: see H below), and the next plane's loads are in
+//     flight while this one is transformed -- across slices too: the next slice's first plane
+//     is loaded during this slice's last plane and the plane-sum transforms.
+// Weight of (P', Q', R'): digits (0, 1), (2, 3), (4, 5) = l & 3, (l >> 2) & 3, l >> 4 (thread
+// constant) + digits (6, 7), (8, 9), (10, 11) = i & 3, i >> 2, nt + 2 M-tile (compile time) +
+// the slice's + [R' != 0].  Each wave of the grid takes a contiguous run
 // of slice positions; position u is slice order[u] (a whole aligned chunk sorted by digit
 // weight, so the run's weight changes rarely and F^2 is binned in registers) or u.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void tile_reg_kernel(
+typedef int v16i_t __attribute__((ext_vector_type(16)));
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void tile_reg_kernel(
     const int8_t* __restrict__ buf, const uint16_t* __restrict__ order, int z0, int nslices,
     unsigned long long* __restrict__ counts, unsigned long long add_n, const unsigned long long* __restrict__ sumsq) {
   // int8 seeds: every column holds <= 127 codes, so sum_w S_w = 2^32 sum f^2 <= 2^32 * 2^14 * 127^2
   // < 2^62 and 64-bit register / LDS sums cannot wrap
   __shared__ unsigned long long bins[17];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // (the wave index through readfirstlane: the slice run, its loop and the order lookups
+  // become scalar)
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (tid < 17) bins[tid] = 0;
   __syncthreads();
-  v2l_t H[4];  // H_64 rows 16 q + (l & 15), columns 16 (l >> 4) + j: stage 1's B and stage 2's A
+  // H_64 rows 32 t + (l & 31), columns 32 ks + 16 (l >> 5) + j: stage 1's B (N-tile t) and
+  // stage 2's A (M-tile t), K-step ks.  H_64 = H_2 x H_32: the four blocks are H_32 and, for
+  // t = ks = 1, -H_32.  (So tiles t = 0 and 1 share the MFMA of a chain's first K-step when they
+  // start from the same accumulator, and the compiler issues it once.)
+  v4i_t H[2][2];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    uint32_t w[4];
+  for (int d = 0; d < 4; ++d) {
+    uint32_t v = 0;
 #pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      uint32_t v = 0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * q + (lane & 15), col = 16 * (lane >> 4) + 4 * d + r;
-        v |= ((__popc(row & col) & 1) ? 0xFFu : 0x01u) << (8 * r);
-      }
-      w[d] = v;
+    for (int r = 0; r < 4; ++r) {
+      const int row = lane & 31, col = 16 * (lane >> 5) + 4 * d + r;
+      v |= ((__popc(row & col) & 1) ? 0xFFu : 0x01u) << (8 * r);
     }
-    H[q] = v2l_t{(long)(((uint64_t)w[1] << 32) | w[0]), (long)(((uint64_t)w[3] << 32) | w[2])};
+    H[0][0][d] = H[0][1][d] = H[1][0][d] = (int)v;
+    H[1][1][d] = (int)(v ^ 0xFEFEFEFEu);  // bytes 0x01 <-> 0xFF
   }
-  const int wt_thread = digit_weight((uint32_t)(lane & 15)) + digit_weight((uint32_t)(lane >> 4));
-  const int lane_off = 16 * (lane >> 4) + 64 * (lane & 15);
+  const int wt_thread = digit_weight((uint32_t)lane);
+  const int lane_off = 16 * (lane >> 5) + 32 * ((lane >> 3) & 1) + 64 * (lane & 3) + 256 * ((lane >> 4) & 1) +
+                       512 * ((lane >> 2) & 1);
   const int gw = blockIdx.x * 4 + wave, GW = gridDim.x * 4;
   const int ub = (int)((int64_t)nslices * gw / GW), ue = (int)((int64_t)nslices * (gw + 1) / GW);
-  // the squares of the two interleaved quarters go to separate sums (two dependency chains per
+  // the squares of the two interleaved M-tiles go to separate sums (two dependency chains per
   // weight instead of one), added at the flush
   unsigned long long accA[4] = {0, 0, 0, 0}, accB[4] = {0, 0, 0, 0}, accB2[4] = {0, 0, 0, 0};
   int cur_w = -1;
@@ -732,127 +741,131 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
       accB2[k] = 0;
     }
   };
-  auto load_plane = [&](int sl, int R, v2l_t* dst) {
-    const int8_t* p = buf + (int64_t)sl * kLo + lane_off + 4096 * R;
+  // d[2 mt + ks]: M-tile mt (column bit 11), K-step ks (column bit 10)
+  auto load_plane = [&](int sl, int R, v4i_t* dst) {
+    const int8_t* p = buf + ((int64_t)sl * kLo + 4096 * R) + lane_off;
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-      dst[mt] = __builtin_nontemporal_load(reinterpret_cast<const v2l_t*>(p + 1024 * mt));
+    for (int k = 0; k < 4; ++k)
+      dst[k] = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(p + 1024 * k));
   };
-  // two quarters qa, qb of stage 2 from their byte splits, then their squares
-  auto stage2x2B = [&](const v2l_t& Bla, const v2l_t& Bha, const v2l_t& Blb, const v2l_t& Bhb, auto qa_c,
-                       auto qb_c, unsigned long long* acc, unsigned long long* acc2) {
-    constexpr int qa = decltype(qa_c)::value, qb = decltype(qb_c)::value;
-    v4i_t ca[4], cb[4];
+  // stage 2 of N-tile nt from its byte splits (Bl / Bh [K-step]), both M-tiles' chains
+  // interleaved, then their squares (M-tile 0 into acc, 1 into acc2)
+  auto stage2 = [&](const v4i_t* Bl, const v4i_t* Bh, auto nt_c, unsigned long long* acc,
+                    unsigned long long* acc2) {
+    constexpr int nt = decltype(nt_c)::value;
+    v16i_t c[2];
 #pragma unroll
-    for (int q2 = 0; q2 < 4; ++q2) {
-      ca[q2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(H[q2], Bha, v4i_t{0, 0, 0, 0}, 0, 0, 0);
-      cb[q2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(H[q2], Bhb, v4i_t{0, 0, 0, 0}, 0, 0, 0);
-    }
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int q2 = 0; q2 < 4; ++q2) {
+      for (int i = 0; i < 16; ++i) c[t][i] = 0;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) ca[q2][i] <<= 8;
-      ca[q2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(H[q2], Bla, ca[q2], 0, 0, 0);
+    for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) cb[q2][i] <<= 8;
-      cb[q2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(H[q2], Blb, cb[q2], 0, 0, 0);
-    }
+      for (int t = 0; t < 2; ++t) c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(H[t][ks], Bh[ks], c[t], 0, 0, 0);
 #pragma unroll
-    for (int q2 = 0; q2 < 4; ++q2)
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
+      for (int i = 0; i < 16; ++i) c[t][i] <<= 8;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(H[t][ks], Bl[ks], c[t], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      // digits (6, 7) = i & 3, (8, 9) = i >> 2, (10, 11) = nt + 2 M-tile
+      constexpr int w0 = digit_weight_c((uint32_t)nt), w1 = digit_weight_c((uint32_t)(nt | 2));
+      const int wi = digit_weight_c((uint32_t)(i & 3)) + digit_weight_c((uint32_t)(i >> 2));
 #ifdef SCT_TILE_SQ_ABL
-        // timing-only ablation (wrong results): the squares replaced by one full-rate XOR, the floor
-        // of any exact F^2 accumulate (ab_tile_squares_r06)
-        acc[digit_weight_c((uint32_t)qa) + digit_weight_c((uint32_t)q2) + digit_weight_c((uint32_t)i)] ^=
-            (uint32_t)ca[q2][i];
-        acc2[digit_weight_c((uint32_t)qb) + digit_weight_c((uint32_t)q2) + digit_weight_c((uint32_t)i)] ^=
-            (uint32_t)cb[q2][i];
+      // timing-only ablation (wrong results): the squares replaced by one full-rate XOR, the floor
+      // of any exact F^2 accumulate (ab_tile_squares_r06)
+      acc[wi + w0] ^= (uint32_t)c[0][i];
+      acc2[wi + w1] ^= (uint32_t)c[1][i];
 #else
-        acc[digit_weight_c((uint32_t)qa) + digit_weight_c((uint32_t)q2) + digit_weight_c((uint32_t)i)] +=
-            (unsigned long long)((int64_t)ca[q2][i] * ca[q2][i]);
-        acc2[digit_weight_c((uint32_t)qb) + digit_weight_c((uint32_t)q2) + digit_weight_c((uint32_t)i)] +=
-            (unsigned long long)((int64_t)cb[q2][i] * cb[q2][i]);
+      acc[wi + w0] += (unsigned long long)((int64_t)c[0][i] * c[0][i]);
+      acc2[wi + w1] += (unsigned long long)((int64_t)c[1][i] * c[1][i]);
 #endif
-      }
-  };
-  // int16 pairs (v + 128 of stage 1, |.| < 2^15) -> the high / low byte operands
-  auto split16 = [&](const uint32_t (*pr)[2], v2l_t& Bl, v2l_t& Bh) {
-    uint32_t lo[4], hi[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      lo[mt] = __builtin_amdgcn_perm(pr[mt][1], pr[mt][0], 0x06040200u) ^ 0x80808080u;
-      hi[mt] = __builtin_amdgcn_perm(pr[mt][1], pr[mt][0], 0x07050301u);
     }
-    Bl = pack_v2l(lo);
-    Bh = pack_v2l(hi);
   };
-  auto pairs16 = [&](const v4i_t* c1, uint32_t (*pr)[2]) {
+  // int16 pairs (v + 128 of stage 1, |.| < 2^15) of one M-tile -> its high / low byte operand
+  auto split16 = [&](const uint32_t* pr, v4i_t& Bl, v4i_t& Bh) {
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      pr[mt][0] = __builtin_amdgcn_perm((uint32_t)c1[mt][1], (uint32_t)c1[mt][0], 0x05040100u);
-      pr[mt][1] = __builtin_amdgcn_perm((uint32_t)c1[mt][3], (uint32_t)c1[mt][2], 0x05040100u);
+    for (int d = 0; d < 4; ++d) {
+      Bl[d] = (int)(__builtin_amdgcn_perm(pr[2 * d + 1], pr[2 * d], 0x06040200u) ^ 0x80808080u);
+      Bh[d] = (int)__builtin_amdgcn_perm(pr[2 * d + 1], pr[2 * d], 0x07050301u);
     }
+  };
+  auto pairs16 = [&](const v16i_t& c1, uint32_t* pr) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      pr[k] = __builtin_amdgcn_perm((uint32_t)c1[2 * k + 1], (uint32_t)c1[2 * k], 0x05040100u);
   };
   // planes in turn (a runtime loop: one plane's 16 VGPRs of bytes live at a time, the next
-  // plane's loads in flight), the per-plane sums of all four quarters carried across
+  // plane's loads in flight), the per-plane sums of all four stage-1 tiles carried across
+  // (a chunk of 2^k > kMaxOrder slices: each aligned 2^16 block in its own weight order)
+  auto slice_at = [&](int u) { return order ? ((u & ~(kMaxOrder - 1)) | (int)order[u & (kMaxOrder - 1)]) : u; };
+  // The first plane of the next slice is loaded during this slice's last plane and tail (dn is
+  // free then), so no load of a wave's run but its first is waited for right after its issue.
+  v4i_t dn[4];
+  int s_next = ub < ue ? slice_at(ub) : 0;
+  if (ub < ue) load_plane(s_next, 0, dn);
   for (int u = ub; u < ue; ++u) {
-    // (a chunk of 2^k > kMaxOrder slices: each aligned 2^16 block in its own weight order)
-    const int s = order ? ((u & ~(kMaxOrder - 1)) | (int)order[u & (kMaxOrder - 1)]) : u;
+    const int s = s_next;
+    const bool more = u + 1 < ue;
+    if (more) s_next = slice_at(u + 1);
     const int wz = digit_weight((uint32_t)(z0 + s));  // wave-uniform
     if (wz != cur_w) {
       if (cur_w >= 0) flush();
       cur_w = wz;
     }
-    uint32_t csp[4][4][2];  // [qn][mt]: sum over the planes of v + 128 as int16 pairs, from -384
+    uint32_t csp[2][2][8];  // [nt][mt]: sum over the planes of v + 128 as int16 pairs, from -384
 #pragma unroll
-    for (int qn = 0; qn < 4; ++qn)
+    for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-      for (int mt = 0; mt < 4; ++mt) csp[qn][mt][0] = csp[qn][mt][1] = 0xFE80FE80u;
-    v2l_t dn[4];
-    load_plane(s, 0, dn);
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) csp[nt][mt][k] = 0xFE80FE80u;
 #pragma unroll 1
     for (int R = 0; R < 4; ++R) {
-      v2l_t d[4];
+      v4i_t d[4];
 #pragma unroll
-      for (int mt = 0; mt < 4; ++mt) d[mt] = dn[mt];
-      if (R < 3) load_plane(s, R + 1, dn);
-      auto quarters16 = [&](auto qa_c, auto qb_c) {
-        constexpr int qa = decltype(qa_c)::value, qb = decltype(qb_c)::value;
-        v4i_t c1a[4], c1b[4];
+      for (int k = 0; k < 4; ++k) d[k] = dn[k];
+      if (R < 3 || more) load_plane(R < 3 ? s : s_next, R < 3 ? R + 1 : 0, dn);
+      auto ntile = [&](auto nt_c) {
+        constexpr int nt = decltype(nt_c)::value;
+        v16i_t c1[2];
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-          c1a[mt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(d[mt], H[qa], v4i_t{128, 128, 128, 128}, 0, 0, 0);
-          c1b[mt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(d[mt], H[qb], v4i_t{128, 128, 128, 128}, 0, 0, 0);
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) c1[mt][i] = 128;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt)
+            c1[mt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(d[2 * mt + ks], H[nt][ks], c1[mt], 0, 0, 0);
+        v4i_t Bl[2], Bh[2];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+          uint32_t pr[8];
+          pairs16(c1[mt], pr);
+#pragma unroll
+          for (int k = 0; k < 8; ++k)
+            csp[nt][mt][k] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(v2s_t, csp[nt][mt][k]) +
+                                                              __builtin_bit_cast(v2s_t, pr[k]));
+          split16(pr, Bl[mt], Bh[mt]);
         }
-        uint32_t pa[4][2], pb[4][2];
-        pairs16(c1a, pa);
-        pairs16(c1b, pb);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            csp[qa][mt][h] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(v2s_t, csp[qa][mt][h]) +
-                                                              __builtin_bit_cast(v2s_t, pa[mt][h]));
-            csp[qb][mt][h] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(v2s_t, csp[qb][mt][h]) +
-                                                              __builtin_bit_cast(v2s_t, pb[mt][h]));
-          }
-        v2l_t Bla, Bha, Blb, Bhb;
-        split16(pa, Bla, Bha);
-        split16(pb, Blb, Bhb);
-        stage2x2B(Bla, Bha, Blb, Bhb, qa_c, qb_c, accB, accB2);
+        stage2(Bl, Bh, nt_c, accB, accB2);
         __builtin_amdgcn_sched_barrier(0);
       };
-      quarters16(std::integral_constant<int, 0>(), std::integral_constant<int, 1>());
-      quarters16(std::integral_constant<int, 2>(), std::integral_constant<int, 3>());
+      ntile(std::integral_constant<int, 0>());
+      ntile(std::integral_constant<int, 1>());
     }
-    v2l_t Bla, Bha, Blb, Bhb;
-    split16(csp[0], Bla, Bha);
-    split16(csp[1], Blb, Bhb);
-    stage2x2B(Bla, Bha, Blb, Bhb, std::integral_constant<int, 0>(), std::integral_constant<int, 1>(), accA, accA);
-    split16(csp[2], Bla, Bha);
-    split16(csp[3], Blb, Bhb);
-    stage2x2B(Bla, Bha, Blb, Bhb, std::integral_constant<int, 2>(), std::integral_constant<int, 3>(), accA, accA);
+    v4i_t Bl[2], Bh[2];
+    split16(csp[0][0], Bl[0], Bh[0]);
+    split16(csp[0][1], Bl[1], Bh[1]);
+    stage2(Bl, Bh, std::integral_constant<int, 0>(), accA, accA);
+    split16(csp[1][0], Bl[0], Bh[0]);
+    split16(csp[1][1], Bl[1], Bh[1]);
+    stage2(Bl, Bh, std::integral_constant<int, 1>(), accA, accA);
   }
   if (cur_w >= 0) flush();
   __syncthreads();
