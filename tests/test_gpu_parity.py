@@ -548,8 +548,12 @@ def test_allpairs_spectral_column_sizes():
 
 def test_allpairs_spectral_high_energy_planes():
     """Planes (column bits 12, 13) of large seeds in every slice -- 120 columns of 120 codes,
-    110 of them sharing their high bits, in planes 0 and 2 -- beside sparse ones (squares
-    above 2^32 per plane, |G| above 2^16, the packed int16 plane sums near their range)."""
+    110 of them sharing their high bits, in planes 0 and 2 -- beside sparse ones: the squares
+    of a plane sum to 7.1e9 > 2^32.  The intermediates stay far inside their ranges (measured
+    with the host emulation of test_tile32_map_host.py on seeds computed from these codes, over
+    slice 0 and eleven others: stage-1 |v| <= 619 of the 8128 allowed, packed plane sums
+    |sum v| <= 1162 of 32,512, |G| <= 15,615); test_gpu_spectral_saturation.py drives them to
+    the bounds."""
     rng = np.random.default_rng(33)
     bg = synthetic.whitelist_codes(5000, 16, seed=8)
     parts = []

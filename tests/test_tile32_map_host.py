@@ -2,8 +2,11 @@
 sctools_amd/csrc/spectral.hip) for one 16 KiB slice of int8 seeds: the lane loads, the operand
 and result layouts of v_mfma_i32_32x32x32_i8, stage 1, the byte split, stage 2, the Parseval step
 over the four planes and the digit weight of every (lane, register, tile) -- against a direct
-14-bit Walsh-Hadamard transform binned by the digit weight of the true index.  The GPU parity and
-digit tests pin the kernel; this pins the index arithmetic on CPU."""
+14-bit Walsh-Hadamard transform binned by the digit weight of the true index.  The stage-1
+outputs and the plane sums are held as the kernel holds them -- two int16 halves per 32-bit word,
+added per half (v_pk_add_u16) from 0xFE80FE80, bytes taken out by the two v_perm selectors -- so a
+value past the int16 range, a wrong bias or a wrong byte changes the result.  The GPU parity and
+digit tests pin the kernel; this pins the index and range arithmetic on CPU."""
 import numpy as np
 import pytest
 
@@ -69,23 +72,63 @@ def mfma(a_regs, b_regs, c_regs):
     return c_regs + result_regs(operand(a_regs) @ operand(b_regs).T)
 
 
-def split16(y):
-    """int16 values y = v + 128 -> (low byte - 128, high byte) as signed bytes."""
-    assert np.all(np.abs(y) < 2 ** 15)
-    u = y & 0xFFFF
-    lo = ((u & 0xFF) ^ 0x80).astype(np.uint8).view(np.int8).astype(np.int64)
-    hi = (u >> 8).astype(np.uint8).view(np.int8).astype(np.int64)
-    return lo, hi
+# ---- packed words, as the hardware holds them ---------------------------------------------------
+def perm(s0, s1, sel):
+    """v_perm_b32: result byte b = byte sel[b] of the 64-bit value {s0, s1} (s1 = bytes 0-3)."""
+    src = (np.asarray(s0, np.uint64) << np.uint64(32)) | np.asarray(s1, np.uint64)
+    out = np.zeros(src.shape, np.uint64)
+    for b in range(4):
+        k = (sel >> (8 * b)) & 0xFF
+        assert k < 8
+        out |= ((src >> np.uint64(8 * k)) & np.uint64(0xFF)) << np.uint64(8 * b)
+    return out.astype(np.uint32)
 
 
-def stage2(y, H, nt):
-    """y[mt][lane][i] -> c[t][lane][i] (M-tile t), as the kernel's stage2 lambda."""
-    lo, hi = zip(*(split16(y[mt]) for mt in range(2)))
+def pk_add16(a, b):
+    """v_pk_add_u16: both 16-bit halves added modulo 2^16, no carry from the low into the high."""
+    a, b = np.asarray(a, np.uint32), np.asarray(b, np.uint32)
+    lo = (a + b) & np.uint32(0xFFFF)
+    hi = ((a >> np.uint32(16)) + (b >> np.uint32(16))) << np.uint32(16)
+    return lo | hi
+
+
+def halves(w):
+    """The two int16 halves of packed words [..., k] -> int64 values [..., 2 k]."""
+    w = np.asarray(w, np.uint32)
+    h = np.stack([w & np.uint32(0xFFFF), w >> np.uint32(16)], axis=-1).astype(np.uint16).view(np.int16)
+    return h.reshape(w.shape[:-1] + (2 * w.shape[-1],)).astype(np.int64)
+
+
+def signed_bytes(w):
+    """Packed words [..., k] -> their bytes as int8 values [..., 4 k] (an MFMA operand's k order)."""
+    w = np.ascontiguousarray(w, np.uint32)
+    return w.view(np.uint8).view(np.int8).reshape(w.shape[:-1] + (4 * w.shape[-1],)).astype(np.int64)
+
+
+def pairs16(c1):
+    """int32 accumulators [lane][16] -> eight words of int16 pairs (register 2 k low, 2 k + 1 high)."""
+    assert np.all(np.abs(c1) < 2 ** 31)
+    u = (c1 & 0xFFFFFFFF).astype(np.uint32)
+    return perm(u[:, 1::2], u[:, 0::2], 0x05040100)
+
+
+def split16(pr):
+    """int16 pairs pr[lane][8] (y = v + 128) -> (low byte - 128, high byte) as the signed bytes of
+    the two v_perm selections, four values per operand register."""
+    lo = perm(pr[:, 1::2], pr[:, 0::2], 0x06040200) ^ np.uint32(0x80808080)
+    hi = perm(pr[:, 1::2], pr[:, 0::2], 0x07050301)
+    return signed_bytes(lo), signed_bytes(hi)
+
+
+def stage2(pr, H, nt):
+    """int16 pairs pr[mt][lane][8] -> c[t][lane][i] (M-tile t), as the kernel's stage2 lambda."""
+    lo, hi = zip(*(split16(pr[mt]) for mt in range(2)))
     out = []
     for t in range(2):
         c = np.zeros((64, 16), np.int64)
         for ks in range(2):
             c = mfma(H[t][ks], hi[ks], c)
+        assert np.all(np.abs(c) < 2 ** 23)  # int32 after the shift
         c = c << 8
         for ks in range(2):
             c = mfma(H[t][ks], lo[ks], c)
@@ -103,13 +146,19 @@ def out_weight(l, i, nt, t):
     return digit_weight(l) + digit_weight(i & 3) + digit_weight(i >> 2) + digit_weight(nt | (2 * t))
 
 
-def emulate(row, z):
-    """The 17 per-weight sums of F^2 of one slice (slice index z) and the per-plane transforms."""
+CSP_START = 0xFE80FE80  # both halves -384
+
+
+def emulate(row, z, stats=None, csp_start=CSP_START):
+    """The 17 per-weight sums of F^2 of one slice (slice index z) and the per-plane transforms.
+    The stage-1 outputs and the plane sums are the kernel's packed words (two int16 halves per
+    uint32, added per half modulo 2^16), so a value past the int16 range or a wrong start wraps
+    and changes the result.  `stats` collects the extremes of y = v + 128 and of the plane sums."""
     H = h_regs()
     bins = np.zeros(17, dtype=object)
     accA = np.zeros((64, 4), dtype=object)
     accB = np.zeros((64, 4), dtype=object)
-    csp = np.full((2, 2, 64, 16), -384, np.int64)
+    csp = np.full((2, 2, 64, 8), csp_start, np.uint32)
     G = np.zeros((4, 4096), np.int64)
     i = np.arange(16)
 
@@ -124,15 +173,18 @@ def emulate(row, z):
     for R in range(4):
         d = load_plane(row, R)
         for nt in range(2):
-            y = []
+            pr = []
             for mt in range(2):
                 c1 = np.full((64, 16), 128, np.int64)
                 for ks in range(2):
                     c1 = mfma(d[2 * mt + ks], H[nt][ks], c1)
-                csp[nt][mt] += c1
-                assert np.all(np.abs(csp[nt][mt]) <= 32640)
-                y.append(c1)
-            squares(stage2(y, H, nt), nt, accB, G[R])
+                pr.append(pairs16(c1))
+                csp[nt][mt] = pk_add16(csp[nt][mt], pr[mt])
+                if stats is not None:
+                    stats.setdefault("y", []).extend([int(c1.min()), int(c1.max())])
+            squares(stage2(pr, H, nt), nt, accB, G[R])
+    if stats is not None:
+        stats.setdefault("csp", []).extend([int(halves(csp).min()), int(halves(csp).max())])
     for nt in range(2):
         squares(stage2(csp[nt], H, nt), nt, accA)
     wt = digit_weight(z) + digit_weight(LANES)
@@ -187,3 +239,62 @@ def test_tile32_matches_direct_wht(seed, z, amp):
     for R in range(4):
         assert np.array_equal(G[R], wht(row[4096 * R:4096 * (R + 1)].astype(np.int64))), R
     assert bins.tolist() == direct(row, z).tolist()
+
+
+def chi(mask, n=16384):
+    """The character (-1)^<mask, c> over n columns."""
+    c = np.arange(n)
+    par = np.zeros(n, np.int64)
+    for b in range(n.bit_length() - 1):
+        if (mask >> b) & 1:
+            par ^= (c >> b) & 1
+    return 1 - 2 * par
+
+
+# every column at the int8 limit: the seeds of the saturating families of spectral_families.py
+# (stage 1 bits 0-4 and 10, stage 2 bits 5-9 and 11, planes 12 and 13)
+SATURATED = [("plus", 0, 127), ("minus", 0, -127), ("bit0", 1, 127), ("bit5", 1 << 5, 127), ("bit10", 1 << 10, 127),
+             ("bit11", 1 << 11, 127), ("bit12", 1 << 12, 127), ("ones", 0x3FFF, 127), ("mixed", 0x2C63, 127),
+             ("bit5neg", 1 << 5, -127)]
+_reached = {}
+
+
+@pytest.mark.parametrize("name,mask,amp", SATURATED, ids=[s[0] for s in SATURATED])
+def test_tile32_saturated_rows(name, mask, amp):
+    row = (amp * chi(mask)).astype(np.int8)
+    stats = {}
+    bins, G = emulate(row, 0x155, stats)
+    for R in range(4):
+        assert np.array_equal(G[R], wht(row[4096 * R:4096 * (R + 1)].astype(np.int64))), R
+    assert bins.tolist() == direct(row, 0x155).tolist()
+    _reached[name] = stats
+
+
+def test_tile32_saturated_rows_sit_on_the_bounds():
+    """The rows above reach what the kernel's comments allow: y = v + 128 of +-8128 and plane
+    sums (from -384) of 32,640 and -32,384 -- the whole int16 pair range the kernel relies on."""
+    for name, mask, amp in SATURATED:
+        if name not in _reached:
+            emulate((amp * chi(mask)).astype(np.int8), 0, _reached.setdefault(name, {}))
+    y = [v for s in _reached.values() for v in s["y"]]
+    csp = [v for s in _reached.values() for v in s["csp"]]
+    assert (min(y), max(y)) == (-8000, 8256)
+    assert (min(csp), max(csp)) == (-32384, 32640)
+    for name in ("plus", "bit0", "bit5", "bit12"):  # a character is one transform point: +8128 somewhere
+        assert max(_reached[name]["y"]) == 8256, name
+    for name in ("minus", "bit5neg"):
+        assert min(_reached[name]["y"]) == -8000, name
+    assert max(_reached["plus"]["csp"]) == 32640 and min(_reached["minus"]["csp"]) == -32384
+
+
+def test_packed_words_carry_like_the_hardware():
+    """The emulation wraps where the kernel would: a start one off moves every plane sum, and a
+    sum past the int16 range changes the result instead of passing."""
+    row = np.full(16384, 127, np.int8)
+    assert emulate(row, 0, csp_start=CSP_START + 1)[0].tolist() != direct(row, 0).tolist()
+    assert emulate(row, 0, csp_start=0xFF00FF00)[0].tolist() != direct(row, 0).tolist()  # 32,768 wraps
+    a = np.array([0xFFFF0001, 0x7FFF8000], np.uint32)
+    assert pk_add16(a, np.array([0x0001FFFF, 0x00018000], np.uint32)).tolist() == [0x00000000, 0x80000000]
+    assert perm(np.uint32(0x44332211), np.uint32(0xDDCCBBAA), 0x07050301).tolist() == 0x4422DDBB
+    assert split16(np.array([[0x00FF0100, 0x80007FFF] + [0] * 6], np.uint32))[0][0, :4].tolist() == [-128, 127, 127, -128]
+    assert split16(np.array([[0x00FF0100, 0x80007FFF] + [0] * 6], np.uint32))[1][0, :4].tolist() == [1, 0, 127, -128]
