@@ -365,6 +365,16 @@ int sct_nearest_multi_query_host(sct_nearest_multi* plan, const uint64_t* querie
  * the arrays are summed into counts / tally after the slots return. */
 int sct_nearest_multi_count_host(sct_nearest_multi* plan, const uint64_t* queries, int64_t nq, uint64_t* counts,
                                  uint64_t* tally);
+/* sct_nearest_plan_set_posterior_host / sct_nearest_correct_host / sct_nearest_correct_count_host over
+ * the same split: the prior is replicated (every slot permutes it for its own index), queries and
+ * quality rows go to the slots as contiguous ranges, and the slots' statistics are summed. */
+int sct_nearest_multi_set_posterior_host(sct_nearest_multi* plan, const uint32_t* prior, const uint32_t* qweight,
+                                         int num, int den);
+int sct_nearest_multi_correct_host(sct_nearest_multi* plan, const uint64_t* queries, const uint8_t* qual,
+                                   int64_t qual_stride, int64_t nq, int32_t* index, uint8_t* dist, uint64_t* stats);
+int sct_nearest_multi_correct_count_host(sct_nearest_multi* plan, const uint64_t* queries, const uint8_t* qual,
+                                         int64_t qual_stride, int64_t nq, uint64_t* counts, uint64_t* tally,
+                                         uint64_t* stats);
 int sct_nearest_multi_destroy(sct_nearest_multi* plan);
 /* Host encode stream (sct_encode_stream_host) over contiguous record ranges, one per slot. */
 int sct_encode_stream_host_devices(int kind, const uint8_t* seqs, int64_t n, int L, uint64_t* codes, uint8_t* gc,
@@ -442,6 +452,47 @@ int sct_nearest_plan_create_host(int kind, const uint64_t* whitelist, int64_t nw
                                  sct_nearest_plan** plan);
 int sct_nearest_query_host(sct_nearest_plan* plan, const uint64_t* queries, int64_t nq, int32_t* index,
                            uint8_t* dist);
+
+/* Posterior correction of the queries sct_nearest_query gives up on: those with several whitelist
+ * barcodes at distance 1 (-2 there), resolved by base quality and whitelist priors as single-cell
+ * pipelines do.  No reference function exists; the distance d is the
+ * reference's (kind 2: TwoBit.hamming_distance, encodings.py:113-121; kind 3:
+ * ThreeBit.hamming_distance, encodings.py:194-202), over ALL whitelist indices (a duplicated code is
+ * two indices), and everything is integer arithmetic.  With L = the plan's positions
+ * (ceil(code_bits / kind)), for query q with quality row qual (L raw bytes; byte b belongs to base
+ * b, the first base, which is digit L - 1 - b of the code):
+ *   1. q has a bit at or above kind * L:            index -1, dist 255;
+ *   2. some index has d == 0:                       that index if it is the only one, else -2; dist 0;
+ *   3. candidates = every j with d(q, w_j) == 1 and prior[j] > 0, p_j the one base where they differ
+ *      (an N or an invalid ThreeBit triplet of the query is such a base),
+ *      score_j = prior[j] * qweight[qual[p_j]] (uint64);
+ *   4. no candidate:                                index -1, dist 255;
+ *   5. best = the largest score, total = their sum: index = its j if den * best >= num * total,
+ *      else -2; dist 1.
+ * prior: nw uint32 values < 2^30 (NULL: all ones); qweight: 256 HOST values in [1, 2^20] indexed by
+ * the raw quality byte; 1 <= num <= den <= 64 and 2 * num > den (the winner is unique); anything
+ * else is SCT_E_INVALID.  So a score is < 2^50, a total of at most 48 < 2^56, and den * total < 2^62.
+ * Only half-key plans qualify (kind 2 or 3, max_d == 1, an A/C/G/T whitelist of 2..16 positions):
+ * any other plan is SCT_E_RANGE.  set_posterior may be called again at any time (it waits for the
+ * plan's calls in flight and for `stream`); it holds for the calls after it.
+ * sct_nearest_correct is asynchronous on `stream`: the query pass appends the queries of case 3 to a
+ * device worklist instead of answering -2 (with a prior set, those with one candidate too), and a
+ * second kernel scores only those, so only their quality rows (qual_stride >= L bytes apart) are
+ * read.  d_stats (nullable, 2 uint64, ACCUMULATED): [0] queries scored, [1] those given an index.
+ * The host forms copy queries and rows in (rows packed to L bytes) and index / dist, or only the
+ * counts and tallies of sct_index_tally, out; stats (nullable) is accumulated there as well. */
+int sct_nearest_plan_set_posterior(sct_nearest_plan* plan, const uint32_t* d_prior, const uint32_t* qweight,
+                                   int num, int den, void* stream);
+int sct_nearest_plan_set_posterior_host(sct_nearest_plan* plan, const uint32_t* prior, const uint32_t* qweight,
+                                        int num, int den);
+int sct_nearest_correct(sct_nearest_plan* plan, const uint64_t* d_queries, const uint8_t* d_qual,
+                        int64_t qual_stride, int64_t nq, int32_t* d_index, uint8_t* d_dist, uint64_t* d_stats,
+                        void* stream);
+int sct_nearest_correct_host(sct_nearest_plan* plan, const uint64_t* queries, const uint8_t* qual,
+                             int64_t qual_stride, int64_t nq, int32_t* index, uint8_t* dist, uint64_t* stats);
+int sct_nearest_correct_count_host(sct_nearest_plan* plan, const uint64_t* queries, const uint8_t* qual,
+                                   int64_t qual_stride, int64_t nq, uint64_t* counts, uint64_t* tally,
+                                   uint64_t* stats);
 
 /* ---------------------------------------------------------------- counting observed barcodes
  * Replaces the host Counter of Barcodes.from_iterable_encoded (src/sctools/barcode.py:100-102,

@@ -141,6 +141,14 @@ SIGNATURES = {
     "sct_index_tally": [_vp, _i64, _i64, _vp, _vp, _vp],
     "sct_nearest_count_host": [_vp, _vp, _i64, _vp, _vp],
     "sct_nearest_multi_count_host": [_vp, _vp, _i64, _vp, _vp],
+    "sct_nearest_plan_set_posterior": [_vp, _vp, _vp, _i32, _i32, _vp],
+    "sct_nearest_plan_set_posterior_host": [_vp, _vp, _vp, _i32, _i32],
+    "sct_nearest_correct": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "sct_nearest_correct_host": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "sct_nearest_correct_count_host": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "sct_nearest_multi_set_posterior_host": [_vp, _vp, _vp, _i32, _i32],
+    "sct_nearest_multi_correct_host": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "sct_nearest_multi_correct_count_host": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
 }
 _RESTYPES = {"sct_last_error": ctypes.c_char_p}
 
@@ -882,6 +890,46 @@ class HostNearestPlan:
             f = self._lib.sct_nearest_multi_count_host if self._multi else self._lib.sct_nearest_count_host
             check(f(self._h, _ptr(q), q.size, _ptr(counts), _ptr(tally)))
 
+    def set_posterior(self, prior, qweight, num, den):
+        """Priors (uint32[nw] or None for all ones), the weight per raw quality byte (uint32[256]) and
+        the acceptance threshold num/den of ``correct`` (sct_nearest_plan_set_posterior_host /
+        sct_nearest_multi_set_posterior_host); holds for the calls after it."""
+        w = np.ascontiguousarray(qweight, dtype=np.uint32).reshape(-1)
+        if w.size != 256:
+            raise ValueError("quality weights: 256 values, one per raw quality byte")
+        pr = None
+        if prior is not None:
+            pr = np.ascontiguousarray(prior, dtype=np.uint32).reshape(-1)
+            if pr.size != self.nw:
+                raise ValueError("prior must have one value per whitelist barcode (%d)" % self.nw)
+        f = self._lib.sct_nearest_multi_set_posterior_host if self._multi else self._lib.sct_nearest_plan_set_posterior_host
+        check(f(self._h, _ptr(pr), _ptr(w), int(num), int(den)))
+
+    def correct(self, queries, qualities):
+        """(index, dist, stats) of sct_nearest_correct_host for uint64 queries and their (n, L) uint8
+        quality rows; stats = uint64[2]: queries scored, and those of them given an index."""
+        q = np.ascontiguousarray(queries, dtype=np.uint64).reshape(-1)
+        index = pinned.empty(q.size, np.int32)
+        dist = pinned.empty(q.size, np.uint8)
+        stats = np.zeros(2, dtype=np.uint64)
+        f = self._lib.sct_nearest_multi_correct_host if self._multi else self._lib.sct_nearest_correct_host
+        check(f(self._h, _ptr(q), _ptr(qualities), qualities.strides[0] if q.size else 0, q.size, _ptr(index),
+                _ptr(dist), _ptr(stats)))
+        return index, dist, stats
+
+    def correct_count(self, queries, qualities, counts, tally):
+        """``count`` over ``correct``'s indices (sct_nearest_correct_count_host); returns stats."""
+        q = np.ascontiguousarray(queries, dtype=np.uint64).reshape(-1)
+        if counts.dtype != np.uint64 or counts.size != self.nw or not counts.flags.c_contiguous:
+            raise ValueError("counts must be a contiguous uint64 array of the whitelist's size")
+        if tally.dtype != np.uint64 or tally.size != 2 or not tally.flags.c_contiguous:
+            raise ValueError("tally must be a contiguous uint64 array of 2")
+        stats = np.zeros(2, dtype=np.uint64)
+        f = self._lib.sct_nearest_multi_correct_count_host if self._multi else self._lib.sct_nearest_correct_count_host
+        check(f(self._h, _ptr(q), _ptr(qualities), qualities.strides[0] if q.size else 0, q.size, _ptr(counts),
+                _ptr(tally), _ptr(stats)))
+        return stats
+
     def close(self):
         if self._h:
             (self._lib.sct_nearest_multi_destroy if self._multi else self._lib.sct_nearest_plan_destroy)(self._h)
@@ -912,6 +960,21 @@ class NearestPlan:
     def query(self, d_queries_ptr, nq, d_index_ptr, d_dist_ptr, stream=0):
         check(self._lib.sct_nearest_query(self._h, _vp(d_queries_ptr), nq, _vp(d_index_ptr),
                                           _vp(d_dist_ptr), _vp(stream)))
+
+    def set_posterior(self, d_prior_ptr, qweight, num, den, stream=0):
+        """Priors (device uint32[nw], or 0 / None for all ones), host weights per raw quality byte
+        (uint32[256]) and the threshold num/den of ``correct`` (sct_nearest_plan_set_posterior)."""
+        w = np.ascontiguousarray(qweight, dtype=np.uint32).reshape(-1)
+        if w.size != 256:
+            raise ValueError("quality weights: 256 values, one per raw quality byte")
+        check(self._lib.sct_nearest_plan_set_posterior(self._h, _vp(d_prior_ptr or None), _ptr(w), int(num),
+                                                       int(den), _vp(stream)))
+
+    def correct(self, d_queries_ptr, d_qual_ptr, qual_stride, nq, d_index_ptr, d_dist_ptr, d_stats_ptr=0, stream=0):
+        """sct_nearest_correct on device arrays, asynchronous on ``stream``; d_stats (2 uint64,
+        optional) accumulates the queries scored and those of them given an index."""
+        check(self._lib.sct_nearest_correct(self._h, _vp(d_queries_ptr), _vp(d_qual_ptr), qual_stride, nq,
+                                            _vp(d_index_ptr), _vp(d_dist_ptr), _vp(d_stats_ptr or None), _vp(stream)))
 
     def close(self):
         if self._h:

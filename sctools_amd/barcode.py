@@ -19,7 +19,8 @@ from . import _lib, _pykeys
 from .encodings import TwoBit
 from .stats import base4_entropy
 
-__all__ = ["Barcodes", "ObservedBarcodeSet", "PriorBarcodeSet", "WhitelistCorrector", "nearest_whitelist"]
+__all__ = ["Barcodes", "ObservedBarcodeSet", "PriorBarcodeSet", "WhitelistCorrector", "nearest_whitelist",
+           "phred_weights"]
 
 _MIXED_SIGNS = ('barcode codes mix negative and non-negative integers: their XOR is negative and the '
                 'reference\'s distance loop (encodings.py:118, `while difference:`) never terminates on it')
@@ -286,6 +287,16 @@ def _encode_lines(seqs):
     return out
 
 
+def phred_weights(offset=33, cap=33):
+    """The default weight of ``WhitelistCorrector.correct`` per raw quality byte b, np.uint32[256]:
+    the base's error probability 10^(-Q/10) in units of 2^-20, ``round(2^20 * 10^(-Q/10))`` with
+    Q = min(max(b - offset, 0), cap) -- Phred+33 capped at Q33, as Cell Ranger caps it.  Bytes
+    below the offset (0 from a zero-padded short read among them) weigh 2^20, an error for certain.
+    No value lies within 0.01 of a rounding boundary, so float64 ``round`` gives the exact table."""
+    q = np.clip(np.arange(256, dtype=np.int64) - int(offset), 0, int(cap))
+    return np.array([int(round((1 << 20) * 10.0 ** (-int(v) / 10.0))) for v in q], dtype=np.uint32)
+
+
 class WhitelistCorrector:
     """``nearest_whitelist`` against one whitelist for a stream of query batches: the device
     index of the whitelist is built once, here, and every ``nearest(queries)`` call only copies
@@ -298,15 +309,30 @@ class WhitelistCorrector:
         ``nearest_whitelist``
     """
 
-    def __init__(self, whitelist, max_distance=1, encoding='ThreeBit', devices=None):
+    def __init__(self, whitelist, max_distance=1, encoding='ThreeBit', devices=None, barcode_length=None):
         self.kind = {'ThreeBit': 3, 'TwoBit': 2, 3: 3, 2: 2}[encoding]
         self.max_distance = max_distance
         wl = np.ascontiguousarray(np.asarray(whitelist, dtype=np.uint64)).reshape(-1)
         self.size = wl.size
         self._plan = None
+        self._prior = None
+        self._applied = None  # the (prior, threshold, weights) the plan holds
+        top = int(np.bitwise_or.reduce(wl)).bit_length() if wl.size else 0
+        if barcode_length is not None:
+            # the index covers exactly barcode_length positions, whatever the leading bases are (a
+            # TwoBit whitelist whose first bases are all A has fewer significant bits)
+            bits = self.kind * int(barcode_length)
+            if not 1 <= bits <= 64:
+                raise ValueError('barcode_length %r: %d bits per code, outside [1, 64]' % (barcode_length, bits))
+            if top > bits:
+                raise ValueError('a whitelist code has bits at or above 2**%d: longer than barcode_length=%d'
+                                 % (bits, barcode_length))
+        else:
+            bits = min(64, max(top, self.kind * (max_distance + 1)))
+        #: base positions of the index: the width of a quality row
+        self.barcode_length = -(-bits // self.kind)
         if wl.size:
-            bits = max(int(np.bitwise_or.reduce(wl)).bit_length(), self.kind * (max_distance + 1))
-            self._plan = _lib.HostNearestPlan(self.kind, wl, min(64, bits), max_distance, devices=devices)
+            self._plan = _lib.HostNearestPlan(self.kind, wl, bits, max_distance, devices=devices)
 
     def nearest(self, queries):
         q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64)).reshape(-1)
@@ -342,6 +368,92 @@ class WhitelistCorrector:
         self._plan.count(q, counts.view(np.uint64), tally)
         return counts, int(n_none) + int(tally[0]), int(n_tie) + int(tally[1])
 
+    # ------------------------------------------------------------ posterior correction
+    def set_prior(self, prior=None):
+        """Prior abundance per whitelist barcode for ``correct`` / ``count_corrected``: integers in
+        [0, 2**30), one per whitelist index (a first ``count`` pass plus one is the usual choice); a
+        barcode with prior 0 is never a candidate.  None: every barcode weighs 1.  Holds for the
+        calls after it."""
+        if prior is not None:
+            pr = np.asarray(prior)
+            if pr.shape != (self.size,):
+                raise ValueError('prior must have one value per whitelist barcode (%d)' % self.size)
+            if pr.size and (int(pr.min()) < 0 or int(pr.max()) >= 1 << 30):
+                raise ValueError('priors must lie in [0, 2**30)')
+            prior = np.ascontiguousarray(pr, dtype=np.uint32).copy()
+        self._prior = prior
+        self._applied = None
+
+    def _apply_posterior(self, threshold, quality_weights):
+        num, den = (int(v) for v in threshold)
+        w = phred_weights() if quality_weights is None else np.ascontiguousarray(quality_weights, dtype=np.uint32)
+        key = (num, den, w.tobytes())
+        if self._applied != key:
+            self._plan.set_posterior(self._prior, w, num, den)
+            self._applied = key
+
+    def _quality_rows(self, qualities, n):
+        """Quality rows as a contiguous uint8 (n, barcode_length) array: the 'S{L}' array
+        ``fastq.iter_arrays`` yields, or uint8 rows."""
+        a = np.asarray(qualities)
+        if a.dtype.kind == 'S':
+            width = a.dtype.itemsize
+            a = np.ascontiguousarray(a).reshape(-1).view(np.uint8).reshape(-1, width)
+        elif a.dtype == np.uint8 and a.ndim == 2:
+            a = np.ascontiguousarray(a)
+        else:
+            raise ValueError('qualities must be an S{L} array or uint8 rows of shape (n, L)')
+        if a.shape[1] != self.barcode_length:
+            raise ValueError('quality rows are %d bytes wide, the index has %d positions: build the corrector '
+                             'with barcode_length=%d' % (a.shape[1], self.barcode_length, a.shape[1]))
+        if a.shape[0] != n:
+            raise ValueError('%d quality rows for %d queries' % (a.shape[0], n))
+        return a
+
+    def correct(self, queries, qualities, threshold=(39, 40), quality_weights=None):
+        """``nearest`` with the distance-1 ties resolved by base quality and the priors of
+        ``set_prior``, as Cell Ranger resolves them (contract: include/sctools_hip.h,
+        sct_nearest_correct).  A query with no exact match scores every whitelist barcode j at
+        distance 1 with ``prior[j] * quality_weights[quality byte of the differing base]`` and takes
+        the best one when its share of the total is at least ``threshold`` = (num, den), default
+        39/40 = 0.975; otherwise -2.  Needs ``max_distance=1`` and an A/C/G/T whitelist of 2..16
+        bases (ValueError otherwise).
+
+        :param qualities: the quality rows of the queries, the 'S{L}' array ``fastq.iter_arrays``
+            yields or uint8 (n, L), L = ``barcode_length``
+        :param quality_weights: np.uint32[256] in [1, 2**20] per raw quality byte (default
+            ``phred_weights()``)
+        :return (np.ndarray[int32], np.ndarray[uint8]): index, distance (255 for -1)
+        """
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64)).reshape(-1)
+        if self._plan is None:
+            return np.full(q.size, -1, np.int32), np.full(q.size, 255, np.uint8)
+        rows = self._quality_rows(qualities, q.size)
+        self._apply_posterior(threshold, quality_weights)
+        index, dist, self.last_stats = self._plan.correct(q, rows)
+        return index, dist
+
+    def count_corrected(self, queries, qualities, out=None, threshold=(39, 40), quality_weights=None):
+        """``count`` over ``correct``'s indices, tallied on the device; ``out`` and the result as in
+        ``count``: (counts, n_none, n_ambiguous)."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64)).reshape(-1)
+        n_none = n_amb = 0
+        counts = out
+        if isinstance(out, tuple):
+            counts, n_none, n_amb = out
+        if counts is None:
+            counts = np.zeros(self.size, dtype=np.int64)
+        elif not (isinstance(counts, np.ndarray) and counts.dtype == np.int64 and counts.shape == (self.size,)
+                  and counts.flags.c_contiguous):
+            raise ValueError('out must be a contiguous np.int64 array of the whitelist size')
+        if self._plan is None:  # empty whitelist: nothing can match
+            return counts, int(n_none) + q.size, int(n_amb)
+        rows = self._quality_rows(qualities, q.size)
+        self._apply_posterior(threshold, quality_weights)
+        tally = np.zeros(2, dtype=np.uint64)
+        self.last_stats = self._plan.correct_count(q, rows, counts.view(np.uint64), tally)
+        return counts, int(n_none) + int(tally[0]), int(n_amb) + int(tally[1])
+
     def close(self):
         if self._plan is not None:
             self._plan.close()
@@ -374,3 +486,23 @@ class ObservedBarcodeSet(Barcodes):
 
 class PriorBarcodeSet(Barcodes):
     """README.md:33 name for a set of expected (whitelist) barcodes."""
+
+    def corrector(self, max_distance=1, encoding='TwoBit', devices=None):
+        """A ``WhitelistCorrector`` over this set's barcodes, in ``codes_array()``'s order, with
+        their counts as the priors of ``correct`` (no reference counterpart).  ``encoding`` is the
+        queries': the TwoBit keys are re-encoded for 'ThreeBit' queries."""
+        codes = self.codes_array(mask_negative=False)
+        if codes.ndim != 1:
+            raise ValueError('corrector needs barcode codes below 2**64')
+        counts = [int(self._data[k]) for k in self._data]
+        if any(c < 0 or c >= 1 << 30 for c in counts):
+            raise ValueError('barcode counts must lie in [0, 2**30) to serve as priors')
+        if {'ThreeBit': 3, 'TwoBit': 2, 3: 3, 2: 2}[encoding] == 3:
+            from .synthetic import two_to_three
+            if codes.size and int(codes.max()).bit_length() > 2 * self._barcode_length:
+                raise ValueError('a barcode code is longer than barcode_length=%d' % self._barcode_length)
+            codes = two_to_three(codes, self._barcode_length)
+        wc = WhitelistCorrector(codes, max_distance=max_distance, encoding=encoding, devices=devices,
+                                barcode_length=self._barcode_length)
+        wc.set_prior(np.array(counts, dtype=np.uint32))
+        return wc

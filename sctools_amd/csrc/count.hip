@@ -692,3 +692,54 @@ extern "C" int sct_nearest_count_host(sct_nearest_plan* p, const uint64_t* queri
   tally[1] += h[nw + 1];
   return SCT_OK;
 }
+
+// sct_nearest_count_host with sct_nearest_correct in place of the query: the final indices feed the
+// same tally, and only the counts, the two tallies and the two statistics come back.
+extern "C" int sct_nearest_correct_count_host(sct_nearest_plan* p, const uint64_t* queries, const uint8_t* qual,
+                                              int64_t qual_stride, int64_t nq, uint64_t* counts, uint64_t* tally,
+                                              uint64_t* stats) {
+  SCT_CHECK(nq >= 0, "nq must be >= 0");
+  SCT_CHECK(p != nullptr, "plan is NULL");
+  const int64_t nw = sct::nearest_plan_size(p);
+  const int L = sct::nearest_plan_positions(p);
+  SCT_CHECK(tally != nullptr && (nw == 0 || counts != nullptr), "NULL counts");
+  if (L == 0)  // not a half-key plan: the device call says why
+    return sct_nearest_correct(p, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr);
+  if (nq == 0) return SCT_OK;
+  SCT_CHECK(queries != nullptr && qual != nullptr, "NULL queries or qualities");
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return SCT_E_HIP;
+  hipStream_t s = hs->stream;
+  const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t qb = al((size_t)nq * 8), ub = al((size_t)nq * L), ib = al((size_t)nq * 4), db = al((size_t)nq);
+  const size_t cw = (size_t)nw + 5;  // counts, tally[2], error word, stats[2]
+  if (int rc = sct::stage_reserve(hs, cw * 8, 0); rc != SCT_OK) return rc;
+  void* blk = nullptr;
+  SCT_HIP(sct::pool_alloc(&blk, qb + ub + ib + db + cw * 8, s));
+  uint8_t* b = static_cast<uint8_t*>(blk);
+  uint64_t* d_counts = reinterpret_cast<uint64_t*>(b + qb + ub + ib + db);
+  uint64_t* h = reinterpret_cast<uint64_t*>(hs->pinned);
+  hipError_t e = hipMemsetAsync(d_counts, 0, cw * 8, s);
+  int rc = e == hipSuccess ? sct::nearest_correct_stage(p, queries, qual, qual_stride, nq, b, b + qb, s) : SCT_OK;
+  if (e == hipSuccess && rc == SCT_OK) {
+    rc = sct_nearest_correct(p, (const uint64_t*)b, b + qb, L, nq, (int32_t*)(b + qb + ub), b + qb + ub + ib,
+                             d_counts + nw + 3, s);
+    if (rc == SCT_OK)
+      rc = tally_launch((const int32_t*)(b + qb + ub), nq, nw, d_counts, d_counts + nw, d_counts + nw + 2, s);
+    if (rc == SCT_OK) e = hipMemcpyAsync(h, d_counts, cw * 8, hipMemcpyDeviceToHost, s);
+  }
+  sct::pool_free(blk, s);
+  const hipError_t se = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = se;
+  if (rc == SCT_OK && e != hipSuccess) rc = sct::fail(SCT_E_HIP, "nearest correct count: %s", hipGetErrorString(e));
+  if (rc != SCT_OK) return rc;
+  if (h[nw + 2]) return sct::fail(SCT_E_RANGE, "nearest index outside [-2, %lld)", (long long)nw);
+  for (int64_t j = 0; j < nw; ++j) counts[j] += h[j];
+  tally[0] += h[nw];
+  tally[1] += h[nw + 1];
+  if (stats) {
+    stats[0] += h[nw + 3];
+    stats[1] += h[nw + 4];
+  }
+  return SCT_OK;
+}

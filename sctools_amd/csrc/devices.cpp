@@ -193,6 +193,67 @@ extern "C" int sct_nearest_multi_count_host(sct_nearest_multi* m, const uint64_t
   return SCT_OK;
 }
 
+// the prior replicated: every slot permutes it into its own plan's table order
+extern "C" int sct_nearest_multi_set_posterior_host(sct_nearest_multi* m, const uint32_t* prior,
+                                                    const uint32_t* qweight, int num, int den) {
+  SCT_CHECK(m != nullptr, "plan is NULL");
+  return sct::run_on_devices(m->devices.data(), (int)m->plans.size(), [&](int r) {
+    return sct_nearest_plan_set_posterior_host(m->plans[(size_t)r], prior, qweight, num, den);
+  });
+}
+
+extern "C" int sct_nearest_multi_correct_host(sct_nearest_multi* m, const uint64_t* queries, const uint8_t* qual,
+                                              int64_t qual_stride, int64_t nq, int32_t* index, uint8_t* dist,
+                                              uint64_t* stats) {
+  SCT_CHECK(m != nullptr, "plan is NULL");
+  SCT_CHECK(nq >= 0 && (nq == 0 || (queries && qual && index && dist)), "bad arguments");
+  if (nq == 0) return SCT_OK;
+  const int k = (int)m->plans.size();
+  std::vector<uint64_t> part((size_t)k * 2, 0);
+  const int rc = sct::run_on_devices(m->devices.data(), k, [&](int r) {
+    const int64_t b = split(nq, r, k), e = split(nq, r + 1, k);
+    return sct_nearest_correct_host(m->plans[(size_t)r], queries + b, qual + b * qual_stride, qual_stride, e - b,
+                                    index + b, dist + b, part.data() + 2 * (size_t)r);
+  });
+  if (rc != SCT_OK) return rc;
+  for (int r = 0; stats && r < k; ++r) {
+    stats[0] += part[2 * (size_t)r];
+    stats[1] += part[2 * (size_t)r + 1];
+  }
+  return SCT_OK;
+}
+
+extern "C" int sct_nearest_multi_correct_count_host(sct_nearest_multi* m, const uint64_t* queries,
+                                                    const uint8_t* qual, int64_t qual_stride, int64_t nq,
+                                                    uint64_t* counts, uint64_t* tally, uint64_t* stats) {
+  SCT_CHECK(nq >= 0, "nq must be >= 0");
+  SCT_CHECK(m != nullptr, "plan is NULL");
+  SCT_CHECK(tally != nullptr && (m->nw == 0 || counts != nullptr), "NULL counts");
+  if (nq == 0) return SCT_OK;
+  SCT_CHECK(queries != nullptr && qual != nullptr, "NULL queries or qualities");
+  const int k = (int)m->plans.size();
+  const size_t row = (size_t)m->nw + 4;  // counts, the two tallies, the two statistics
+  std::vector<uint64_t> part((size_t)k * row, 0);
+  const int rc = sct::run_on_devices(m->devices.data(), k, [&](int r) {
+    const int64_t b = split(nq, r, k), e = split(nq, r + 1, k);
+    uint64_t* mine = part.data() + (size_t)r * row;
+    return sct_nearest_correct_count_host(m->plans[(size_t)r], queries + b, qual + b * qual_stride, qual_stride,
+                                          e - b, mine, mine + m->nw, mine + m->nw + 2);
+  });
+  if (rc != SCT_OK) return rc;
+  for (int r = 0; r < k; ++r) {
+    const uint64_t* mine = part.data() + (size_t)r * row;
+    for (int64_t j = 0; j < m->nw; ++j) counts[j] += mine[j];
+    tally[0] += mine[m->nw];
+    tally[1] += mine[m->nw + 1];
+    if (stats) {
+      stats[0] += mine[m->nw + 2];
+      stats[1] += mine[m->nw + 3];
+    }
+  }
+  return SCT_OK;
+}
+
 extern "C" int sct_nearest_multi_destroy(sct_nearest_multi* m) {
   if (!m) return SCT_OK;
   // each index freed on its own slot (its device current), after the work it enqueued

@@ -462,19 +462,41 @@ __device__ __forceinline__ int32_t unpack_perm(const uint32_t* __restrict__ pack
   return (int32_t)(((((uint64_t)d.y << 32) | d.x) >> (bo & 31)) & ((1ull << pbits) - 1));
 }
 
+// The worklist of the deferring query pass (sct_nearest_correct): the numbers of the queries whose
+// distance-1 candidates halves_resolve_kernel scores, and its length, both on the device.  It is
+// kept as kSegs segments, workgroup b appending to segment b % kSegs, each with a counter in a
+// 128-byte line of its own: with priors set a third of config 4's queries are deferred, nearly
+// every wave appends, and 1.56M atomics on ONE word took 18 ms per 100M queries (12 ns each,
+// serialised where the XCDs meet; profiles/ab_nearest_correct_r08.jsonl).
+constexpr int kSegs = 256, kSegStride = 32;  // counters kSegStride words apart
+struct Defer {
+  uint32_t* list;    // [kSegs][seg_cap]
+  unsigned* count;   // [kSegs * kSegStride]
+  uint32_t seg_cap;  // WG * ceil(workgroups / kSegs): a segment holds all of its workgroups' queries
+  int all_d1;        // priors are set: a unique distance-1 winner is deferred too (its prior may be 0)
+};
+
 // IDX (Halves::ident_a): out_pos receives whitelist indices (a B-table winner's through the packed
-// permutation, read here), else table positions for halves_index_kernel
-template <int KIND, bool IDX>
+// permutation, read here), else table positions for halves_index_kernel.
+// DEFER (max_d == 1): a query with bits above the table's positions is no match (-1, 255), and a
+// lane that would write -2 at distance 1 -- or, with priors set, a unique distance-1 winner --
+// appends its query number to df.list instead, one atomic per wave; it leaves (-2, 1) behind for
+// the resolve kernel to overwrite.  The quality rows are not touched here.
+// The worklist is a trailing argument of the DEFER instantiations only (DF = Defer): the others keep
+// the arguments they had.
+template <int KIND, bool IDX, bool DEFER = false, typename... DF>
 __global__ __launch_bounds__(WG) void halves_query_kernel(const uint64_t* __restrict__ queries, int64_t nq, Halves h,
                                                           int max_d, int32_t* __restrict__ out_pos,
-                                                          uint8_t* __restrict__ out_dist) {
+                                                          uint8_t* __restrict__ out_dist, DF... dfs) {
+  static_assert(sizeof...(DF) == (DEFER ? 1 : 0), "the worklist goes with DEFER");
   const int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x;
   if (i >= nq) return;
   const uint64_t q = __builtin_nontemporal_load(queries + i);
   uint32_t kA, sA, kB, sB;
   int E;
   halves_of<KIND>(q, h, kA, sA, kB, sB, E);
-  const int eff = max_d - E;  // in-table distance allowed
+  int eff = max_d - E;  // in-table distance allowed
+  if constexpr (DEFER) eff = E ? -1 : eff;
   int nA0 = 0, nA1 = 0, nB0 = 0, nB1 = 0;
   uint32_t pA0 = 0, pA1 = 0, pB0 = 0, pB1 = 0, vA1 = 0, vB1 = 0;
   if (eff >= 0 && sA == 0)  // the A bucket: codes agreeing with q on A
@@ -485,11 +507,14 @@ __global__ __launch_bounds__(WG) void halves_query_kernel(const uint64_t* __rest
     scan_half<false>(h.entB, h.offB[kB], h.offB[kB + 1], kA, sA, nB0, pB0, nB1, pB1, vB1);
   int32_t pos = -1;
   uint8_t dist = 255;
+  [[maybe_unused]] bool defer = false;
   if (nA0) {
     pos = nA0 == 1 ? (int32_t)pA0 : -2;
     dist = (uint8_t)E;
   } else if (eff >= 1 && nA1 + nB1) {
+    if constexpr (DEFER) defer = nA1 + nB1 >= 2 || (dfs.all_d1, ...);
     if (nA1 + nB1 >= 2) pos = -2;
+    else if (DEFER && defer) pos = -2;
     else if (nA1) pos = (int32_t)pA1;
     else if (!IDX) pos = (int32_t)(h.nw + pB1);
     else if (h.rankB) pos = (int32_t)(h.offA[vB1] + h.rankB[pB1]);  // both loads at once
@@ -498,6 +523,151 @@ __global__ __launch_bounds__(WG) void halves_query_kernel(const uint64_t* __rest
   }
   __builtin_nontemporal_store(pos, out_pos + i);
   __builtin_nontemporal_store(dist, out_dist + i);
+  if constexpr (DEFER) {
+    const Defer df = (dfs, ...);
+    const uint64_t b = __ballot(defer);  // (the lanes past nq have left)
+    if (b) {
+      const int lane = threadIdx.x & 63, leader = __ffsll((unsigned long long)b) - 1;
+      const uint32_t seg = blockIdx.x & (kSegs - 1);
+      uint32_t base = 0;
+      if (lane == leader) base = atomicAdd(df.count + seg * kSegStride, (unsigned)__popcll(b));
+      base = __shfl(base, leader);
+      if (defer) df.list[(uint64_t)seg * df.seg_cap + base + __popcll(b & ((1ull << lane) - 1ull))] = (uint32_t)i;
+    }
+  }
+}
+
+// The scoring pass of sct_nearest_correct over the worklist.  A deferred query has no exact match
+// and no bits above the table, so its candidates are the entries at half distance exactly 1 of its
+// A bucket (they differ from it in one B digit) and of its B bucket (one A digit; the entries that
+// agree on A too are at half distance 0 and pass by).  The m mask of the half-key scan has one bit
+// set then, at twice the differing digit: digit d of the code is base G - 1 - d, whose quality
+// byte weighs the candidate's prior.  Priors are kept in table order (priorAB[p] = the prior of
+// the code at A-order position p, then B-order), so a candidate costs one load at its position;
+// the whitelist index is looked up for the winner alone.
+struct Posterior {
+  const uint32_t* priorAB;  // [2 nw], null: all ones
+  const uint32_t* qweight;  // [256], by raw quality byte
+  uint32_t num, den;        // accepted when den * best >= num * total
+};
+
+__device__ __forceinline__ void score_bucket(const uint16_t* __restrict__ ent, uint32_t b, uint32_t e, uint32_t k,
+                                             uint32_t sp, int digit0, uint32_t pos0, int G,
+                                             const uint32_t* __restrict__ priorAB, const uint8_t* __restrict__ qrow,
+                                             const uint32_t* wq, uint64_t& total, uint64_t& best, uint32_t& best_pos) {
+  for (uint32_t c = b & ~1u; c < e; c += 8) {  // 8 entries per 16-B load, to the bucket's end
+    const u32x4_a4 v = *reinterpret_cast<const u32x4_a4*>(ent + c);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    // the chunk's candidates first, then one step per candidate: a wave makes as many steps as
+    // its fullest lane has candidates, not one per entry
+    uint32_t cand = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t t = c + j;
+      const uint32_t x = (((w[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) ^ k) | sp;
+      const uint32_t m = (x | (x >> 1)) & 0x5555u;
+      if (t >= b && t < e && m && !(m & (m - 1))) cand |= 1u << j;
+    }
+    while (cand) {
+      const int j = __ffs(cand) - 1, jw = j >> 1;
+      cand &= cand - 1;
+      const uint32_t dw = jw == 0 ? v.x : jw == 1 ? v.y : jw == 2 ? v.z : v.w;
+      const uint32_t x = (((dw >> (16 * (j & 1))) & 0xFFFFu) ^ k) | sp;
+      const uint32_t m = (x | (x >> 1)) & 0x5555u;  // one bit, at twice the differing digit
+      const uint32_t t = pos0 + c + j;
+      const int d = digit0 + ((__ffs(m) - 1) >> 1);
+      const uint32_t pr = priorAB ? priorAB[t] : 1u;  // (both loads in flight together)
+      const uint32_t wt = wq[qrow[G - 1 - d]];
+      const uint64_t sc = (uint64_t)pr * wt;  // < 2^50
+      total += sc;                            // <= 48 candidates: < 2^56
+      if (sc > best) {                        // a prior of 0 scores 0: no candidate
+        best = sc;
+        best_pos = t;
+      }
+    }
+  }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(WG) void halves_resolve_kernel(const uint64_t* __restrict__ queries,
+                                                            const uint8_t* __restrict__ qual, int64_t qual_stride,
+                                                            Halves h, Posterior ps, Defer df,
+                                                            int32_t* __restrict__ out_index,
+                                                            uint8_t* __restrict__ out_dist,
+                                                            unsigned long long* __restrict__ stats) {
+  __shared__ uint32_t wq[256];
+  static_assert(WG == 256, "one weight per thread");
+  static_assert(kSegs == WG, "one segment counter per thread");
+  // pre[s] = the worklist entries before segment s (an exclusive scan of the counters)
+  __shared__ uint32_t pre[kSegs + 1], wsum[WG / 64];
+  wq[threadIdx.x] = ps.qweight[threadIdx.x];
+  {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t is = df.count[threadIdx.x * kSegStride];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t a = __shfl_up(is, d);
+      if (lane >= d) is += a;
+    }
+    if (lane == 63) wsum[wave] = is;
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) is += wsum[w];
+    pre[threadIdx.x + 1] = is;
+    if (threadIdx.x == 0) pre[0] = 0;
+  }
+  __syncthreads();
+  const uint64_t n = pre[kSegs];
+  uint32_t accepted = 0;
+  for (uint64_t t = (uint64_t)blockIdx.x * WG + threadIdx.x; t < n; t += (uint64_t)gridDim.x * WG) {
+    uint32_t sg = 0;  // the last segment that starts at or before t
+#pragma unroll
+    for (int step = kSegs / 2; step; step >>= 1)
+      if (pre[sg + step] <= (uint32_t)t) sg += step;
+    const uint32_t i = df.list[(uint64_t)sg * df.seg_cap + ((uint32_t)t - pre[sg])];
+    const uint64_t q = queries[i];
+    uint32_t kA, sA, kB, sB;
+    int E;
+    halves_of<KIND>(q, h, kA, sA, kB, sB, E);
+    const uint8_t* qrow = qual + (int64_t)i * qual_stride;
+    uint64_t total = 0, best = 0;
+    uint32_t best_pos = 0;
+    if (sA == 0)
+      score_bucket(h.entA, h.offA[kA], h.offA[kA + 1], kB, sB, 0, 0u, h.G, ps.priorAB, qrow, wq, total, best,
+                   best_pos);
+    if (sB == 0)
+      score_bucket(h.entB, h.offB[kB], h.offB[kB + 1], kA, sA, h.GB, (uint32_t)h.nw, h.G, ps.priorAB, qrow, wq,
+                   total, best, best_pos);
+    int32_t idx = -2;
+    uint8_t dist = 1;
+    if (total == 0) {  // every candidate's prior is 0
+      idx = -1;
+      dist = 255;
+    } else if ((uint64_t)ps.den * best >= (uint64_t)ps.num * total) {  // < 2^62 both
+      idx = h.ident_a && best_pos < (uint32_t)h.nw ? (int32_t)best_pos
+                                                   : unpack_perm(h.perm_packed, h.pbits, (int32_t)best_pos);
+      ++accepted;
+    }
+    out_index[i] = idx;
+    out_dist[i] = dist;
+  }
+  if (stats) {  // [0] queries scored, [1] accepted
+    for (int o = 32; o; o >>= 1) accepted += __shfl_xor(accepted, o);
+    if ((threadIdx.x & 63) == 0 && accepted) atomicAdd(stats + 1, (unsigned long long)accepted);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && n) atomicAdd(stats, (unsigned long long)n);
+  }
+}
+
+// priorAB[p] = prior[the whitelist index of table position p]; *bad = 1 for a prior >= 2^30
+__global__ void prior_permute_kernel(const uint32_t* __restrict__ prior, int64_t n2,
+                                     const uint32_t* __restrict__ packed, int pbits, uint32_t* __restrict__ priorAB,
+                                     unsigned* __restrict__ bad) {
+  bool b = false;
+  for (int64_t p = (int64_t)blockIdx.x * WG + threadIdx.x; p < n2; p += (int64_t)gridDim.x * WG) {
+    const uint32_t v = prior[unpack_perm(packed, pbits, (int32_t)p)];
+    b |= v >= (1u << 30);
+    priorAB[p] = v;
+  }
+  if (b) atomicOr(bad, 1u);
 }
 
 // permAB packed to pbits per entry (the whitelist index needs ceil(log2 nw) bits: 20 at 737K,
@@ -784,6 +954,11 @@ struct sct_nearest_plan {
   // recorded after every query on its stream: destroy waits on it, so freeing the tables never
   // races a query still in flight (a caller may destroy right after enqueueing one)
   hipEvent_t last_query = nullptr;
+  // posterior scoring of sct_nearest_correct (sct_nearest_plan_set_posterior)
+  bool post_set = false;
+  uint32_t post_num = 0, post_den = 0;
+  uint32_t* d_priorAB = nullptr;  // the priors in table order, [2 nw]; null: all ones
+  uint32_t* d_qweight = nullptr;  // [256]
 };
 
 extern "C" int sct_nearest_plan_destroy(sct_nearest_plan* p) {
@@ -792,6 +967,8 @@ extern "C" int sct_nearest_plan_destroy(sct_nearest_plan* p) {
     (void)hipEventSynchronize(p->last_query);
     (void)hipEventDestroy(p->last_query);
   }
+  if (p->d_priorAB) (void)hipFree(p->d_priorAB);
+  if (p->d_qweight) (void)hipFree(p->d_qweight);
   for (void* m : p->hv_mem)
     if (m) (void)hipFree(m);
   for (int k = 0; k < MAX_KEYS; ++k)
@@ -1138,6 +1315,181 @@ static int nearest_query_launch(sct_nearest_plan* p, const uint64_t* d_queries, 
     launch_query<3>(p->nparts, blocks, s, d_queries, nq, tb, p->max_d, d_index, d_dist);
   SCT_LAUNCH_CHECK();
   return SCT_OK;
+}
+
+// ---------------------------------------------------------------- posterior correction
+int sct::nearest_plan_positions(const sct_nearest_plan* p) { return p->halves ? p->hv.G : 0; }
+
+// the plans sct_nearest_correct takes: the half-key scheme at max_d == 1
+static int correct_plan_check(const sct_nearest_plan* p) {
+  SCT_CHECK(p != nullptr, "plan is NULL");
+  if (!p->halves || p->max_d != 1)
+    return sct::fail(SCT_E_RANGE,
+                     "posterior correction needs a half-key plan (max_d == 1, an A/C/G/T whitelist of 2..16 "
+                     "positions): this plan has max_d %d, %lld codes of %d bits%s",
+                     p->max_d, (long long)p->nw, p->code_bits,
+                     p->halves ? "" : " and a whitelist with other digits, or another layout forced");
+  return SCT_OK;
+}
+
+extern "C" int sct_nearest_plan_set_posterior(sct_nearest_plan* p, const uint32_t* d_prior, const uint32_t* qweight,
+                                              int num, int den, void* stream) {
+  if (int rc = correct_plan_check(p); rc != SCT_OK) return rc;
+  SCT_CHECK(qweight != nullptr, "qweight is NULL");
+  SCT_CHECK(num >= 1 && num <= den && den <= 64 && 2 * num > den,
+            "threshold %d/%d: needs 1 <= num <= den <= 64 and 2 * num > den", num, den);
+  for (int b = 0; b < 256; ++b)
+    SCT_CHECK(qweight[b] >= 1u && qweight[b] <= (1u << 20), "qweight[%d] = %u outside [1, 2^20]", b, qweight[b]);
+  hipStream_t s = sct::as_stream(stream);
+  // calls still in flight read the tables this one replaces
+  if (p->last_query) SCT_HIP(hipStreamWaitEvent(s, p->last_query, 0));
+  if (!p->d_qweight) SCT_HIP(hipMalloc(&p->d_qweight, 256 * 4));
+  uint32_t* fresh = nullptr;
+  unsigned h_bad = 0;
+  if (d_prior) {
+    const int64_t n2 = 2 * p->nw;
+    void* d_bad = nullptr;
+    SCT_HIP(hipMalloc(&fresh, (size_t)n2 * 4));
+    hipError_t e = sct::pool_alloc(&d_bad, 4, s);
+    if (e == hipSuccess) {
+      e = hipMemsetAsync(d_bad, 0, 4, s);
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(prior_permute_kernel, dim3(grid_for(n2, 4096)), dim3(WG), 0, s, d_prior, n2,
+                           (const uint32_t*)p->perm_packed, p->pbits, fresh, (unsigned*)d_bad);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, s);
+      sct::pool_free(d_bad, s);
+    }
+    const hipError_t se = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess || h_bad) {
+      (void)hipFree(fresh);
+      if (e != hipSuccess) return sct::fail(SCT_E_HIP, "set posterior: %s", hipGetErrorString(e));
+      return sct::fail(SCT_E_INVALID, "a prior is >= 2^30");
+    }
+  }
+  SCT_HIP(hipMemcpyAsync(p->d_qweight, qweight, 256 * 4, hipMemcpyHostToDevice, s));
+  SCT_HIP(hipStreamSynchronize(s));  // the old priors are idle now, and qweight is the caller's again
+  if (p->d_priorAB) (void)hipFree(p->d_priorAB);
+  p->d_priorAB = fresh;
+  p->post_num = (uint32_t)num;
+  p->post_den = (uint32_t)den;
+  p->post_set = true;
+  return SCT_OK;
+}
+
+extern "C" int sct_nearest_plan_set_posterior_host(sct_nearest_plan* p, const uint32_t* prior, const uint32_t* qweight,
+                                                   int num, int den) {
+  if (int rc = correct_plan_check(p); rc != SCT_OK) return rc;
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return SCT_E_HIP;
+  hipStream_t s = hs->stream;
+  if (!prior) return sct_nearest_plan_set_posterior(p, nullptr, qweight, num, den, s);
+  void* dp = nullptr;
+  SCT_HIP(sct::pool_alloc(&dp, (size_t)p->nw * 4, s));
+  const hipError_t e = hipMemcpyAsync(dp, prior, (size_t)p->nw * 4, hipMemcpyHostToDevice, s);
+  const int rc = e == hipSuccess ? sct_nearest_plan_set_posterior(p, (const uint32_t*)dp, qweight, num, den, s)
+                                 : sct::fail(SCT_E_HIP, "prior copy: %s", hipGetErrorString(e));
+  sct::pool_free(dp, s);
+  (void)hipStreamSynchronize(s);
+  return rc;
+}
+
+extern "C" int sct_nearest_correct(sct_nearest_plan* p, const uint64_t* d_queries, const uint8_t* d_qual,
+                                   int64_t qual_stride, int64_t nq, int32_t* d_index, uint8_t* d_dist,
+                                   uint64_t* d_stats, void* stream) {
+  if (int rc = correct_plan_check(p); rc != SCT_OK) return rc;
+  SCT_CHECK(p->post_set, "sct_nearest_plan_set_posterior has not been called on this plan");
+  SCT_CHECK(nq >= 0 && nq <= (int64_t)UINT32_MAX, "nq %lld outside [0, 2^32)", (long long)nq);
+  if (nq == 0) return SCT_OK;
+  SCT_CHECK(d_queries && d_qual && d_index && d_dist, "NULL pointer");
+  SCT_CHECK(qual_stride >= p->hv.G, "qual_stride %lld below the %d positions of the plan", (long long)qual_stride,
+            p->hv.G);
+  hipStream_t s = sct::as_stream(stream);
+  const unsigned blocks = (unsigned)sct::ceil_div(nq, WG);
+  // the worklist: the segments' counters, then the segments
+  const size_t cnt_bytes = (size_t)kSegs * kSegStride * 4;
+  const uint32_t seg_cap = (uint32_t)(sct::ceil_div(blocks, kSegs) * WG);
+  void* wl = nullptr;
+  SCT_HIP(sct::pool_alloc(&wl, cnt_bytes + (size_t)kSegs * seg_cap * 4, s));
+  Defer df{reinterpret_cast<uint32_t*>(static_cast<char*>(wl) + cnt_bytes), static_cast<unsigned*>(wl), seg_cap,
+           p->d_priorAB != nullptr};
+  const Posterior ps{p->d_priorAB, p->d_qweight, p->post_num, p->post_den};
+  hipError_t e = hipMemsetAsync(wl, 0, cnt_bytes, s);
+  if (e == hipSuccess) {
+    if (p->hv.ident_a) {
+      auto kern = p->kind == 2 ? halves_query_kernel<2, true, true, Defer> : halves_query_kernel<3, true, true, Defer>;
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(WG), 0, s, d_queries, nq, p->hv, 1, d_index, d_dist, df);
+    } else {
+      auto kern = p->kind == 2 ? halves_query_kernel<2, false, true, Defer> : halves_query_kernel<3, false, true, Defer>;
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(WG), 0, s, d_queries, nq, p->hv, 1, d_index, d_dist, df);
+      hipLaunchKernelGGL(halves_index_kernel, dim3(grid_for(sct::ceil_div(nq, 4), 8192)), dim3(WG), 0, s, d_index,
+                         nq, (const uint32_t*)p->perm_packed, p->pbits, ((uintptr_t)d_index & 15) == 0);
+    }
+    auto res = p->kind == 2 ? halves_resolve_kernel<2> : halves_resolve_kernel<3>;
+    hipLaunchKernelGGL(res, dim3(grid_for(nq, 2048)), dim3(WG), 0, s, d_queries, d_qual, qual_stride, p->hv, ps,
+                       df, d_index, d_dist,
+                       reinterpret_cast<unsigned long long*>(d_stats));
+    e = hipGetLastError();
+  }
+  sct::pool_free(wl, s);
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "nearest correct: %s", hipGetErrorString(e));
+  if (!p->last_query) SCT_HIP(hipEventCreateWithFlags(&p->last_query, hipEventDisableTiming));
+  SCT_HIP(hipEventRecord(p->last_query, s));
+  return SCT_OK;
+}
+
+// queries and quality rows (packed to the plan's L bytes) into one pool block at `b`
+int sct::nearest_correct_stage(sct_nearest_plan* p, const uint64_t* queries, const uint8_t* qual,
+                               int64_t qual_stride, int64_t nq, uint8_t* d_q, uint8_t* d_qual, hipStream_t s) {
+  const int L = p->hv.G;
+  SCT_CHECK(qual_stride >= L, "qual_stride %lld below the %d positions of the plan", (long long)qual_stride, L);
+  SCT_HIP(hipMemcpyAsync(d_q, queries, (size_t)nq * 8, hipMemcpyHostToDevice, s));
+  if (qual_stride == L)
+    SCT_HIP(hipMemcpyAsync(d_qual, qual, (size_t)nq * L, hipMemcpyHostToDevice, s));
+  else
+    SCT_HIP(hipMemcpy2DAsync(d_qual, (size_t)L, qual, (size_t)qual_stride, (size_t)L, (size_t)nq,
+                             hipMemcpyHostToDevice, s));
+  return SCT_OK;
+}
+
+extern "C" int sct_nearest_correct_host(sct_nearest_plan* p, const uint64_t* queries, const uint8_t* qual,
+                                        int64_t qual_stride, int64_t nq, int32_t* index, uint8_t* dist,
+                                        uint64_t* stats) {
+  if (int rc = correct_plan_check(p); rc != SCT_OK) return rc;
+  SCT_CHECK(nq >= 0 && (nq == 0 || (queries && qual && index && dist)), "bad arguments");
+  if (nq == 0) return SCT_OK;
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return SCT_E_HIP;
+  hipStream_t s = hs->stream;
+  const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t qb = al((size_t)nq * 8), ub = al((size_t)nq * p->hv.G), ib = al((size_t)nq * 4), db = al((size_t)nq);
+  void* blk = nullptr;
+  SCT_HIP(sct::pool_alloc(&blk, qb + ub + ib + db + 16, s));
+  uint8_t* b = static_cast<uint8_t*>(blk);
+  uint64_t* d_stats = reinterpret_cast<uint64_t*>(b + qb + ub + ib + db);
+  uint64_t h_stats[2] = {0, 0};
+  hipError_t e = hipMemsetAsync(d_stats, 0, 16, s);
+  int rc = e == hipSuccess ? sct::nearest_correct_stage(p, queries, qual, qual_stride, nq, b, b + qb, s) : SCT_OK;
+  if (e == hipSuccess && rc == SCT_OK) {
+    rc = sct_nearest_correct(p, (const uint64_t*)b, b + qb, p->hv.G, nq, (int32_t*)(b + qb + ub),
+                             b + qb + ub + ib, d_stats, s);
+    if (rc == SCT_OK) {
+      e = hipMemcpyAsync(index, b + qb + ub, (size_t)nq * 4, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(dist, b + qb + ub + ib, (size_t)nq, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(h_stats, d_stats, 16, hipMemcpyDeviceToHost, s);
+    }
+  }
+  sct::pool_free(blk, s);
+  const hipError_t se = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = se;
+  if (rc == SCT_OK && e != hipSuccess) rc = sct::fail(SCT_E_HIP, "nearest correct: %s", hipGetErrorString(e));
+  if (rc == SCT_OK && stats) {
+    stats[0] += h_stats[0];
+    stats[1] += h_stats[1];
+  }
+  return rc;
 }
 
 extern "C" int sct_nearest_host(int kind, const uint64_t* whitelist, int64_t nw, const uint64_t* queries,

@@ -92,6 +92,11 @@ int run_on_devices(const int* devices, int ndev, const std::function<int(int)>& 
 
 // Whitelist codes a nearest plan indexes (nearest.hip; p is not NULL).
 int64_t nearest_plan_size(const sct_nearest_plan* p);
+// Base positions of a half-key plan (0 for any other plan), and the host staging of
+// sct_nearest_correct's inputs: queries to d_q, quality rows packed to that many bytes to d_qual.
+int nearest_plan_positions(const sct_nearest_plan* p);
+int nearest_correct_stage(sct_nearest_plan* p, const uint64_t* queries, const uint8_t* qual, int64_t qual_stride,
+                          int64_t nq, uint8_t* d_q, uint8_t* d_qual, hipStream_t s);
 
 // sct_tune_set value of `key`, or dflt when unset (host.cpp).
 int64_t tune(int key, int64_t dflt);
