@@ -168,6 +168,14 @@ struct State {
   // borrowed workspace goes back only once they have passed (the next plan may use another stream)
   std::vector<std::pair<hipStream_t, hipEvent_t>> used;
 };
+// slot `slot` of the plan's workspace (ws_get) as a typed pointer
+template <typename T>
+int get_slot(State& st, int slot, size_t bytes, T** out) {
+  void* p = nullptr;
+  const int rc = ws_get(st.ws, slot, bytes, &p);
+  if (rc == SCT_OK) *out = static_cast<T*>(p);
+  return rc;
+}
 // record that work of the plan was enqueued on s (call after the enqueue)
 void note_stream(State& st, hipStream_t s);
 

@@ -30,43 +30,16 @@
 
 #include "sct_common.h"
 #include "spectral.h"
+#include "spectral_seed.h"
 
 namespace sct_spectral {
 namespace {
 
-constexpr int kLo = 1 << kLoBits;         // columns (= tile values)
-constexpr int kHiBits = kSpaceBits - kLoBits;  // 18 bit planes
-constexpr int kWalk = 64;                 // slices per wave in the seed's Gray walk
-constexpr int kWalkBits = 6;
-constexpr int kRegGroups = 2;             // seed: 32-code groups whose planes stay in registers
-constexpr int kSeedWalks = 16;            // seed: walks per workgroup (4-32 within noise, round 3)
+using Cols = Columns<kLoBits>;
+constexpr int kLo = Cols::kLo;            // columns (= tile values)
+constexpr int kHiBits = Cols::kHiBits;    // 18 bit planes
+constexpr int kRegGroups = 2;             // int16 / int32 seeds: groups whose planes stay in registers
 constexpr int kMaxOrder = 1 << 16;        // largest slice range with a digit-weight order table
-
-// Bit planes of a 32-code group: planes + g * kPlaneWords holds its 18 planes (plane k bit j =
-// bit k of (code >> 14) of the group's j-th code) and 2 words of padding, so a group's planes
-// are five aligned 16-B words: one lane's group is 5 loads from 2 lines, not 18 from 18.
-constexpr int kPlaneWords = 20;
-__device__ __forceinline__ void load_planes(const uint32_t* __restrict__ planes, int64_t g, uint32_t* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(planes + g * kPlaneWords);
-  uint32_t w[kPlaneWords];
-#pragma unroll
-  for (int i = 0; i < kPlaneWords / 4; ++i) {
-    const uint4 v = q[i];
-    w[4 * i] = v.x;
-    w[4 * i + 1] = v.y;
-    w[4 * i + 2] = v.z;
-    w[4 * i + 3] = v.w;
-  }
-#pragma unroll
-  for (int k = 0; k < 18; ++k) p[k] = w[k];
-}
-__device__ __forceinline__ void store_planes(uint32_t* __restrict__ planes, int64_t g, const uint32_t* p) {
-  uint4* q = reinterpret_cast<uint4*>(planes + g * kPlaneWords);
-#pragma unroll
-  for (int i = 0; i < kPlaneWords / 4; ++i)
-    q[i] = make_uint4(4 * i < 18 ? p[4 * i] : 0u, 4 * i + 1 < 18 ? p[4 * i + 1] : 0u,
-                      4 * i + 2 < 18 ? p[4 * i + 2] : 0u, 4 * i + 3 < 18 ? p[4 * i + 3] : 0u);
-}
 
 // in-register WHT of N values
 template <int N>
@@ -90,11 +63,6 @@ __device__ __forceinline__ void wht(int32_t* x) {
 //   scatter   workgroup g: LDS cursors off[c] + H[g][c], one LDS atomic per code
 constexpr int kSortWGs = 128;
 constexpr int kSortThreads = 1024;
-
-__device__ __forceinline__ void wg_range(int64_t n, int64_t& b, int64_t& e) {
-  b = n * blockIdx.x / gridDim.x;
-  e = n * (blockIdx.x + 1) / gridDim.x;
-}
 
 __global__ __launch_bounds__(kSortThreads) void column_hist_wg_kernel(const uint64_t* __restrict__ codes, int64_t n,
                                                                       uint32_t* __restrict__ H) {
@@ -199,29 +167,6 @@ __global__ __launch_bounds__(kSortThreads) void column_scatter_wg_kernel(const u
   }
 }
 
-// planes of group slot k of column c (thread (c, k); columns of <= 32 * kSlots codes)
-template <int kSlots>
-__global__ __launch_bounds__(256) void planes_slot_kernel(const uint32_t* __restrict__ hi,
-                                                          const uint32_t* __restrict__ off,
-                                                          const uint32_t* __restrict__ gofs, int64_t max_groups,
-                                                          uint32_t* __restrict__ planes) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int c = t / kSlots, k = t % kSlots;
-  const uint32_t g0 = gofs[c];
-  if (k >= (int)(gofs[c + 1] - g0)) return;
-  const uint32_t first = off[c] + 32u * k, last = min(first + 32u, off[c + 1]);
-  uint32_t p[kHiBits];
-#pragma unroll
-  for (int b = 0; b < kHiBits; ++b) p[b] = 0;
-  for (uint32_t i = first; i < last; ++i) {
-    const uint32_t h = hi[i], bit = 1u << (i - first);
-#pragma unroll
-    for (int b = 0; b < kHiBits; ++b) p[b] |= (h >> b) & 1u ? bit : 0u;
-  }
-  const int64_t g = g0 + k;
-  store_planes(planes, g, p);
-}
-
 // group g's planes (load_planes layout)
 __global__ void planes_kernel(const uint32_t* __restrict__ hi, const uint32_t* __restrict__ off,
                               const uint32_t* __restrict__ gofs, int64_t max_groups,
@@ -244,7 +189,7 @@ __global__ void planes_kernel(const uint32_t* __restrict__ hi, const uint32_t* _
 #pragma unroll
     for (int k = 0; k < kHiBits; ++k) p[k] |= (h >> k) & 1u ? bit : 0u;
   }
-  store_planes(planes, g, p);
+  store_planes<Cols>(planes, g, p);
 }
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
@@ -294,7 +239,7 @@ __device__ __forceinline__ void seed_body(const uint32_t* __restrict__ planes, c
 #pragma unroll
   for (int g = 0; g < kRegGroups; ++g)
     if (g < ng) {
-      load_planes(planes, (int64_t)g0 + g, pr[g]);
+      load_planes<Cols>(planes, (int64_t)g0 + g, pr[g]);
     } else {
 #pragma unroll
       for (int k = 0; k < kHiBits; ++k) pr[g][k] = 0u;
@@ -334,7 +279,7 @@ __device__ __forceinline__ void seed_body(const uint32_t* __restrict__ planes, c
     for (int g = kRegGroups; g < wng; ++g) {  // dense columns: the rest from L2
       uint32_t p[kHiBits];
       if (g < ng) {
-        load_planes(planes, (int64_t)g0 + g, p);
+        load_planes<Cols>(planes, (int64_t)g0 + g, p);
       } else {
 #pragma unroll
         for (int k = 0; k < kHiBits; ++k) p[k] = 0u;
@@ -392,166 +337,13 @@ __device__ __forceinline__ void seed_body(const uint32_t* __restrict__ planes, c
   }
 }
 
-// int8 seeds, step-major walk: per step every group's XOR and popcount, and the step's sum
-// goes to the byte stage at once -- no 64-value accumulator array, so the first three groups'
-// planes stay in registers at 4+ waves per SIMD.  G = the wave's group count (<= 3; a fourth
-// and later group, columns of > 96 codes, is walked afterwards from L2 into the lane's own
-// stage bytes).  Store-out as seed_body<int8_t>.
-// the walk's start state: every group's planes XORed for the slice bits 6..17 of zblk
-template <int G>
-__device__ __forceinline__ void walk_start(const uint32_t (*pr)[kHiBits], int zblk, uint32_t* x) {
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = kWalkBits; k < kHiBits; ++k)
-      if ((zblk >> k) & 1) v ^= pr[g][k];
-    x[g] = v;
-  }
-}
-
-// 64 Gray steps from the start state x; x is left at the last slice's state, which is the
-// start state with plane 5 flipped (gray(63) = 32)
-template <int G>
-__device__ __forceinline__ void walk_from(const uint32_t (*pr)[kHiBits], uint32_t* x, uint8_t* st8, int tid) {
-#pragma unroll
-  for (int i = 0; i < kWalk; ++i) {
-    uint32_t a = 0;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      if (i) x[g] ^= pr[g][ctz_c(i)];
-      a = g ? popc_add(x[g], a) : (uint32_t)__popc(x[g]);  // one v_bcnt per group, no v_add3
-    }
-    st8[gray(i) * 256 + tid] = (uint8_t)a;
-    if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);  // keep the scheduler from hoisting steps
-  }
-}
-
-constexpr int kRegGroupsSM = 3;
-constexpr int kMaxWalkBlockBits = 4;  // walks per Gray-ordered block: <= 16
-
-// after the register groups' walk of slices zblk..zblk + 63: the groups beyond them (columns of
-// > 96 codes) from L2 into the lane's stage bytes, then the stage to HBM as int8 m - 2 * sum
-__device__ __forceinline__ void seed_finish(const uint32_t* __restrict__ planes, uint32_t g0, int ng, int wng,
-                                            uint8_t* st8, int tid, int co, const uint32_t* mx, int mcb, int c0,
-                                            int zblk, int z0, int z1, int8_t* __restrict__ buf) {
-  constexpr int NT = 256;
-  for (int g = kRegGroupsSM; g < wng; ++g) {
-    uint32_t p[kHiBits];
-    if (g < ng) {
-      load_planes(planes, (int64_t)g0 + g, p);
-    } else {
-#pragma unroll
-      for (int k = 0; k < kHiBits; ++k) p[k] = 0u;
-    }
-    uint32_t x = 0;
-#pragma unroll
-    for (int k = kWalkBits; k < kHiBits; ++k)
-      if ((zblk >> k) & 1) x ^= p[k];
-#pragma unroll
-    for (int i = 0; i < kWalk; ++i) {
-      if (i) x ^= p[ctz_c(i)];
-      st8[gray(i) * NT + co] += (uint8_t)__popc(x);
-      if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kWalk / 16; ++r) {
-    const int row = tid / (NT / 16) + 16 * r, z = zblk + row;
-    const uint4 v = *reinterpret_cast<const uint4*>(st8 + row * NT + mcb);
-    const uint4 o = make_uint4((mx[0] - (v.x + v.x)) ^ 0x80808080u, (mx[1] - (v.y + v.y)) ^ 0x80808080u,
-                               (mx[2] - (v.z + v.z)) ^ 0x80808080u, (mx[3] - (v.w + v.w)) ^ 0x80808080u);
-    if (z >= z0 && z < z1) *reinterpret_cast<uint4*>(buf + (int64_t)(z - z0) * kLo + c0 + mcb) = o;
-  }
-}
-
-// the workgroup's walks for a wave group count G: walks in blocks of 2^lp aligned on the
-// absolute walk index, each block in Gray order -- consecutive walks differ in one slice
-// bit (6 + t), so a walk starts from the previous one's last state with planes 5 and 6 + t
-// flipped: two XORs per group instead of the start state's twelve planes
-template <int G>
-__device__ __forceinline__ void seed_walks(const uint32_t (*pr)[kHiBits], const uint32_t* __restrict__ planes,
-                                           uint32_t g0, int ng, int wng, uint8_t* st8, int tid, int co,
-                                           const uint32_t* mx, int mcb, int c0, int z0, int z1,
-                                           int8_t* __restrict__ buf, int lp) {
-  const int wa = (z0 & ~(kWalk - 1)) >> kWalkBits, we = (z1 + kWalk - 1) >> kWalkBits, P = 1 << lp;
-  const int b1 = (we + P - 1) >> lp;
-  for (int b = (wa >> lp) + blockIdx.y; b < b1; b += gridDim.y) {
-    uint32_t x[G];
-    walk_start<G>(pr, (b << lp) << kWalkBits, x);
-    for (int j = 0; j < P; ++j) {  // workgroup-uniform
-      if (j) {
-        const int t = __builtin_ctz(j);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          uint32_t f = pr[g][kWalkBits - 1];
-#pragma unroll
-          for (int k = 0; k < kMaxWalkBlockBits; ++k)
-            if (k == t) f ^= pr[g][kWalkBits + k];
-          x[g] ^= f;
-        }
-      }
-      const int w = (b << lp) + (j ^ (j >> 1));
-      if (w < wa || w >= we) {  // outside the range: the state as if walked
-#pragma unroll
-        for (int g = 0; g < G; ++g) x[g] ^= pr[g][kWalkBits - 1];
-        continue;
-      }
-      __syncthreads();  // the previous walk's store-out reads of `stage` are done
-      walk_from<G>(pr, x, st8, co);
-      seed_finish(planes, g0, ng, wng, st8, tid, co, mx, mcb, c0, w << kWalkBits, z0, z1, buf);
-    }
-  }
-}
-
+// int8 seeds: the step-major walk shared with the 16-bit columns (seed_sm_body, spectral_seed.h).
 // 96 VGPRs: 5 waves per SIMD (the Gray-block state costs two more registers; at this bound the
 // compiler spills one 8-byte value, reloaded once per walk)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void seed_sm_kernel(
     const uint32_t* __restrict__ planes, const uint32_t* __restrict__ gofs, const uint32_t* __restrict__ off, int z0,
     int z1, int8_t* __restrict__ buf, int lp) {
-  constexpr int NT = 256;
-  __shared__ uint32_t stage[kWalk * NT / 4];
-  uint8_t* st8 = reinterpret_cast<uint8_t*>(stage);
-  const int tid = threadIdx.x;
-  const int c0 = blockIdx.x * NT;
-  // columns to lanes by group count (seed_lane_column); the stage rows and the store-out stay in
-  // column order
-  const int co = seed_lane_column(gofs, c0, tid);
-  const int c = c0 + co;
-  const uint32_t g0 = gofs[c];
-  const int ng = (int)(gofs[c + 1] - g0);
-  int wng = ng;
-#pragma unroll
-  for (int s = 32; s; s >>= 1) wng = max(wng, __shfl_xor(wng, s));
-  uint32_t pr[kRegGroupsSM][kHiBits];
-#pragma unroll
-  for (int g = 0; g < kRegGroupsSM; ++g)
-    if (g < ng) {
-      load_planes(planes, (int64_t)g0 + g, pr[g]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < kHiBits; ++k) pr[g][k] = 0u;
-    }
-  const int mcb = (tid % (NT / 16)) * 16;
-  uint32_t mx[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    mx[k] = 0x80808080u;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int cc = c0 + mcb + 4 * k + b;
-      mx[k] |= (off[cc + 1] - off[cc]) << (8 * b);
-    }
-  }
-  {
-    const int ph = (blockIdx.x + blockIdx.y) % 3;
-    if (ph >= 1) __builtin_amdgcn_s_sleep(24);
-    if (ph == 2) __builtin_amdgcn_s_sleep(24);
-  }
-  if (wng <= 1) seed_walks<1>(pr, planes, g0, ng, wng, st8, tid, co, mx, mcb, c0, z0, z1, buf, lp);
-  else if (wng == 2) seed_walks<2>(pr, planes, g0, ng, wng, st8, tid, co, mx, mcb, c0, z0, z1, buf, lp);
-  else seed_walks<3>(pr, planes, g0, ng, wng, st8, tid, co, mx, mcb, c0, z0, z1, buf, lp);
+  seed_sm_body<Cols>(planes, gofs, off, z0, z1, buf, lp);
 }
 
 template <typename T>
@@ -978,22 +770,18 @@ __global__ __launch_bounds__(256) void probe_max_kernel(const uint32_t* __restri
 template <typename T>
 int launch_seed(State& st, int z0, int z1, hipStream_t s) {
   T* buf = reinterpret_cast<T*>(st.d_buf);
-  const int walks = (z1 - (z0 & ~(kWalk - 1)) + kWalk - 1) / kWalk;
-  // 16 walks per workgroup for a full chunk (measured best at 65,536 slices); smaller chunks
-  // keep >= 64 workgroup rows so the grid still fills the chip
-  const int per_wg = std::max(1, std::min(kSeedWalks, walks / 64));
-  const dim3 sgrid(kLo / 256, (unsigned)((walks + per_wg - 1) / per_wg));
   if constexpr (sizeof(T) == 1) {
-    int lp = 0;  // walks per Gray-ordered block: the largest power of two <= per_wg, <= 16
-    while (lp < kMaxWalkBlockBits && (2 << lp) <= per_wg) ++lp;
-    const int wa = (z0 & ~(kWalk - 1)) / kWalk, we = (z1 + kWalk - 1) / kWalk;
-    const int nb = ((we + (1 << lp) - 1) >> lp) - (wa >> lp);
-    hipLaunchKernelGGL(seed_sm_kernel, dim3(kLo / 256, (unsigned)nb), dim3(256), 0, s, st.d_planes, st.d_gofs, st.d_off,
-                       z0, z1, buf, lp);
-  } else
+    return launch_seed_sm<Cols>(seed_sm_kernel, st, buf, z0, z1, s);
+  } else {
+    // 16 walks per workgroup for a full chunk; smaller chunks keep >= 64 workgroup rows (as
+    // launch_seed_sm)
+    const int walks = (z1 - (z0 & ~(kWalk - 1)) + kWalk - 1) / kWalk;
+    const int per_wg = std::max(1, std::min(kSeedWalks, walks / 64));
+    const dim3 sgrid(kLo / 256, (unsigned)((walks + per_wg - 1) / per_wg));
     hipLaunchKernelGGL(seed_kernel<T>, sgrid, dim3(256), 0, s, st.d_planes, st.d_gofs, st.d_off, z0, z1, buf);
-  SCT_LAUNCH_CHECK();
-  return SCT_OK;
+    SCT_LAUNCH_CHECK();
+    return SCT_OK;
+  }
 }
 
 template <typename T>
@@ -1017,45 +805,17 @@ int launch_tile(State& st, int z0, int z1, unsigned long long* counts, hipStream
 
 template <typename T>
 int launch_chunk(State& st, int z0, int z1, unsigned long long* counts, hipStream_t s, unsigned long long add_n) {
-  hipEvent_t t0 = st.timer ? st.timer->start(s) : nullptr;
-  int rc = launch_seed<T>(st, z0, z1, s);
-  if (st.timer) st.timer->stop(s, t0, sct::LaunchTimer::SEED);
-  if (rc != SCT_OK) return rc;
-  t0 = st.timer ? st.timer->start(s) : nullptr;
-  rc = launch_tile<T>(st, z0, z1, counts, s, add_n);
-  if (st.timer) st.timer->stop(s, t0, sct::LaunchTimer::TILE);
-  return rc;
+  return launch_seed_tile(
+      st, s, [&] { return launch_seed<T>(st, z0, z1, s); },
+      [&] { return launch_tile<T>(st, z0, z1, counts, s, add_n); });
 }
 
-// Bench aid: seed and tile kernels timed apart, each as `repeats` back-to-back launches on
-// one chunk bracketed by HIP events (the timestamps of events between dependent kernels of
-// one stream do not split the kernels reliably).  counts receives garbage.
 template <typename T>
 int time_chunk(State& st, int z0, int z1, unsigned long long* counts, int repeats, hipStream_t s,
                double* seed_ms, double* tile_ms) {
-  hipEvent_t e[3];
-  for (auto& x : e) SCT_HIP(hipEventCreate(&x));
-  struct Free {
-    hipEvent_t* e;
-    ~Free() {
-      for (int i = 0; i < 3; ++i) (void)hipEventDestroy(e[i]);
-    }
-  } guard{e};
-  int rc = launch_seed<T>(st, z0, z1, s);  // warm
-  if (rc == SCT_OK) rc = launch_tile<T>(st, z0, z1, counts, s);
-  SCT_HIP(hipEventRecord(e[0], s));
-  for (int r = 0; rc == SCT_OK && r < repeats; ++r) rc = launch_seed<T>(st, z0, z1, s);
-  SCT_HIP(hipEventRecord(e[1], s));
-  for (int r = 0; rc == SCT_OK && r < repeats; ++r) rc = launch_tile<T>(st, z0, z1, counts, s);
-  SCT_HIP(hipEventRecord(e[2], s));
-  if (rc != SCT_OK) return rc;
-  SCT_HIP(hipEventSynchronize(e[2]));
-  float a = 0, b = 0;
-  SCT_HIP(hipEventElapsedTime(&a, e[0], e[1]));
-  SCT_HIP(hipEventElapsedTime(&b, e[1], e[2]));
-  *seed_ms = a / repeats;
-  *tile_ms = b / repeats;
-  return SCT_OK;
+  return time_seed_tile(
+      st, repeats, s, [&] { return launch_seed<T>(st, z0, z1, s); },
+      [&] { return launch_tile<T>(st, z0, z1, counts, s); }, seed_ms, tile_ms);
 }
 
 }  // namespace
@@ -1296,15 +1056,9 @@ int create(State& st, const uint64_t* d_codes, int64_t n, int64_t chunk, int cus
   const int64_t force = sct::tune(SCT_TUNE_SPECTRAL_COLUMNS, 0);
   if (((maxm > 127 && force != kLoBits) || force == kLoBits16) && max16 <= 127)
     return create16(st, d_codes, n, max16, chunk, cus);
-  void* p = nullptr;
-  auto get = [&](int slot, size_t bytes, auto** out) {
-    const int rc = ws_get(st.ws, slot, bytes, &p);
-    if (rc == SCT_OK) *out = reinterpret_cast<std::remove_reference_t<decltype(**out)>*>(p);
-    return rc;
-  };
-  if (int rc = get(W_HI, (size_t)n * 4, &st.d_hi); rc != SCT_OK) return rc;
-  if (int rc = get(W_OFF, (size_t)(kLo + 1) * 4, &st.d_off); rc != SCT_OK) return rc;
-  if (int rc = get(W_CNT, (size_t)2 * kLo * 4, &st.d_cnt); rc != SCT_OK) return rc;  // counts, then cursors
+  if (int rc = get_slot(st, W_HI, (size_t)n * 4, &st.d_hi); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_OFF, (size_t)(kLo + 1) * 4, &st.d_off); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_CNT, (size_t)2 * kLo * 4, &st.d_cnt); rc != SCT_OK) return rc;  // counts, then cursors
   st.max_m = maxm;
   st.elem_bytes = maxm <= 127 ? 1 : (maxm <= 32767 ? 2 : 4);
   // the intermediate holds one chunk: at most 4 GiB (all 2^18 slices at int8: one seed and one
@@ -1318,12 +1072,13 @@ int create(State& st, const uint64_t* d_codes, int64_t n, int64_t chunk, int cus
   st.tile_wgs = per_cu;
   if (int rc = make_order_table(st); rc != SCT_OK) return rc;
   st.max_groups = sct::ceil_div(n, 32) + kLo;
-  if (int rc = get(W_GOFS, (size_t)(kLo + 1) * 4, &st.d_gofs); rc != SCT_OK) return rc;
-  if (int rc = get(W_HIST, (size_t)kSortWGs * kLo * 4, &st.d_hist); rc != SCT_OK) return rc;
-  if (int rc = get(W_PLANES, (size_t)st.max_groups * kPlaneWords * 4, &st.d_planes); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_GOFS, (size_t)(kLo + 1) * 4, &st.d_gofs); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_HIST, (size_t)kSortWGs * kLo * 4, &st.d_hist); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_PLANES, (size_t)st.max_groups * Cols::kPlaneWords * 4, &st.d_planes); rc != SCT_OK)
+    return rc;
   if (int rc = alloc_buf(st, &st.chunk, std::min<int64_t>(st.chunk, 4096), (size_t)kLo * st.elem_bytes); rc != SCT_OK)
     return rc;
-  if (int rc = get(W_SUMSQ, sizeof(unsigned long long), &st.d_sumsq); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_SUMSQ, sizeof(unsigned long long), &st.d_sumsq); rc != SCT_OK) return rc;
   return SCT_OK;
 }
 
@@ -1385,9 +1140,9 @@ int build(State& st, const uint64_t* d_codes, hipStream_t s) {
   hipLaunchKernelGGL(column_scatter_wg_kernel, dim3(kSortWGs), dim3(kSortThreads), 0, s, d_codes, st.n, st.d_hist,
                      st.d_off, st.d_hi);
   SCT_LAUNCH_CHECK();
-  if (st.max_m <= 128) {
-    hipLaunchKernelGGL(planes_slot_kernel<4>, dim3(kLo * 4 / 256), dim3(256), 0, s, st.d_hi, st.d_off, st.d_gofs,
-                       st.max_groups, st.d_planes);
+  if (st.max_m <= 32 * kPlaneSlots) {
+    hipLaunchKernelGGL(planes_slot_kernel<Cols>, dim3(kLo * kPlaneSlots / 256), dim3(256), 0, s, st.d_hi, st.d_off,
+                       st.d_gofs, st.d_planes);
   } else {
     hipLaunchKernelGGL(planes_kernel, dim3((unsigned)sct::ceil_div(st.max_groups, 256)), dim3(256), 0, s,
                        st.d_hi, st.d_off, st.d_gofs, st.max_groups, st.d_planes);

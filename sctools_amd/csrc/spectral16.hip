@@ -6,7 +6,8 @@
 // a column has at most 4 groups of 32 codes, and the seed -> tile intermediate stays 1 byte per
 // value: 1 GiB per 16,384 slices of 64 KiB.
 //
-//   seed   as seed_body in spectral.hip with 16 bit planes per group (four 16-B words)
+//   seed   the shared int8 seed (seed_sm_body, spectral_seed.h) with 16 bit planes per group (four
+//          16-B words); the plane build is the shared planes_slot_kernel
 //   tile   one WORKGROUP per 64-KiB slice, wave s holding column digit 7 (bits 14, 15) = s:
 //          each wave runs the register tile of spectral.hip over its 16 KiB (two 64-point
 //          MFMA stages over column digits 0-5 and Parseval over digit 6 = R), and digit 7
@@ -27,22 +28,15 @@
 
 #include "sct_common.h"
 #include "spectral.h"
+#include "spectral_seed.h"
 
 namespace sct_spectral {
 namespace {
 
-constexpr int kLo16 = 1 << kLoBits16;               // columns
-constexpr int kHi16 = kSpaceBits - kLoBits16;       // 16 bit planes
-constexpr int kPW16 = 16;                           // plane words per group: four 16-B words
-constexpr int kWalk16 = 64, kWalkBits16 = 6;
-constexpr int kSeedWalks16 = 16;
+using Cols = Columns<kLoBits16>;
+constexpr int kLo16 = Cols::kLo;                    // columns
 constexpr int kSortWGs16 = 128, kSortThreads16 = 1024;
 constexpr int kChunk16 = kSlices16;                 // at most every real slice in one seed / tile pass: 4 GiB
-
-__device__ __forceinline__ void wg_range16(int64_t n, int64_t& b, int64_t& e) {
-  b = n * blockIdx.x / gridDim.x;
-  e = n * (blockIdx.x + 1) / gridDim.x;
-}
 
 // ---------------------------------------------------------------- build
 // workgroup g: byte counts of its contiguous share of the codes per column -> H[g][.] (bytes)
@@ -52,7 +46,7 @@ __global__ __launch_bounds__(kSortThreads16) void hist16_wg_kernel(const uint64_
   for (int w = threadIdx.x; w < kLo16 / 4; w += kSortThreads16) h[w] = 0;
   __syncthreads();
   int64_t b, e;
-  wg_range16(n, b, e);
+  wg_range(n, b, e);
   for (int64_t i = b + threadIdx.x; i < e; i += kSortThreads16) {
     const uint32_t c = (uint32_t)codes[i] & (kLo16 - 1);
     atomicAdd(&h[c >> 2], 1u << (8 * (c & 3)));
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(kSortThreads16) void scatter16_wg_kernel(const uint
   for (int w = threadIdx.x; w < kLo16 / 4; w += kSortThreads16) cur[w] = pre[w];
   __syncthreads();
   int64_t b, e;
-  wg_range16(n, b, e);
+  wg_range(n, b, e);
   for (int64_t i = b + threadIdx.x; i < e; i += kSortThreads16) {
     const uint64_t x = codes[i];
     const uint32_t c = (uint32_t)x & (kLo16 - 1), sh = 8 * (c & 3);
@@ -146,194 +140,12 @@ __global__ __launch_bounds__(kSortThreads16) void scatter16_wg_kernel(const uint
   }
 }
 
-// planes of group slot k (< 4) of column c: 16 words, plane b bit j = bit b of (code >> 16)
-// of the group's j-th code
-__global__ __launch_bounds__(256) void planes16_kernel(const uint32_t* __restrict__ hi, const uint32_t* __restrict__ off,
-                                                       const uint32_t* __restrict__ gofs, uint32_t* __restrict__ planes) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int c = t >> 2, k = t & 3;
-  const uint32_t g0 = gofs[c];
-  if (k >= (int)(gofs[c + 1] - g0)) return;
-  const uint32_t first = off[c] + 32u * k, last = min(first + 32u, off[c + 1]);
-  uint32_t p[kHi16];
-#pragma unroll
-  for (int b = 0; b < kHi16; ++b) p[b] = 0;
-  for (uint32_t i = first; i < last; ++i) {
-    const uint32_t h = hi[i], bit = 1u << (i - first);
-#pragma unroll
-    for (int b = 0; b < kHi16; ++b) p[b] |= (h >> b) & 1u ? bit : 0u;
-  }
-  uint4* q = reinterpret_cast<uint4*>(planes + (int64_t)(g0 + k) * kPW16);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = make_uint4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]);
-}
-
-__device__ __forceinline__ void load_planes16(const uint32_t* __restrict__ planes, int64_t g, uint32_t* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(planes + g * kPW16);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint4 v = q[i];
-    p[4 * i] = v.x;
-    p[4 * i + 1] = v.y;
-    p[4 * i + 2] = v.z;
-    p[4 * i + 3] = v.w;
-  }
-}
-
-// ---------------------------------------------------------------- seed (int8)
-// buf[(z - z0) 2^16 + c] = m(c) - 2 sum over groups of popc(XOR of the planes of z's bits), a
-// workgroup = 256 columns x walks of 64 slices: the step-major walk of seed_sm_kernel in
-// spectral.hip (per step every group's XOR and popcount, the sum straight into the byte stage;
-// the first three groups' planes in registers, a fourth from L2), int8 byte staging and
-// store-out as there.
-template <int G>
-__device__ __forceinline__ void walk_start16(const uint32_t (*pr)[kHi16], int zblk, uint32_t* x) {
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = kWalkBits16; k < kHi16; ++k)
-      if ((zblk >> k) & 1) v ^= pr[g][k];
-    x[g] = v;
-  }
-}
-
-// 64 Gray steps from the start state x, which is left at the last slice's state (plane 5 flipped)
-template <int G>
-__device__ __forceinline__ void walk_from16(const uint32_t (*pr)[kHi16], uint32_t* x, uint8_t* st8, int tid) {
-#pragma unroll
-  for (int i = 0; i < kWalk16; ++i) {
-    uint32_t a = 0;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      if (i) x[g] ^= pr[g][ctz_c(i)];
-      a = g ? popc_add(x[g], a) : (uint32_t)__popc(x[g]);  // one v_bcnt per group, no v_add3
-    }
-    st8[gray(i) * 256 + tid] = (uint8_t)a;
-    if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-constexpr int kRegGroups16 = 3;           // groups whose planes stay in registers
-constexpr int kMaxWalkBlockBits16 = 4;    // walks per Gray-ordered block: <= 16
-
-// after the register groups' walk of slices zblk..zblk + 63: the groups past them from L2, then
-// the stage to HBM
-__device__ __forceinline__ void seed16_finish(const uint32_t* __restrict__ planes, uint32_t g0, int ng, int wng,
-                                              uint8_t* st8, int tid, int co, const uint32_t* mx, int mcb, int c0,
-                                              int zblk, int z0, int z1, int8_t* __restrict__ buf) {
-  constexpr int NT = 256;
-  for (int g = kRegGroups16; g < wng; ++g) {  // the groups past the register-resident ones, from L2
-    uint32_t p[kHi16];
-    if (g < ng) {
-      load_planes16(planes, (int64_t)g0 + g, p);
-    } else {
-#pragma unroll
-      for (int k = 0; k < kHi16; ++k) p[k] = 0u;
-    }
-    uint32_t x = 0;
-#pragma unroll
-    for (int k = kWalkBits16; k < kHi16; ++k)
-      if ((zblk >> k) & 1) x ^= p[k];
-#pragma unroll
-    for (int i = 0; i < kWalk16; ++i) {
-      if (i) x ^= p[ctz_c(i)];
-      st8[gray(i) * NT + co] += (uint8_t)__popc(x);
-      if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kWalk16 / 16; ++r) {
-    const int row = tid / (NT / 16) + 16 * r, z = zblk + row;
-    const uint4 v = *reinterpret_cast<const uint4*>(st8 + row * NT + mcb);
-    const uint4 o = make_uint4((mx[0] - (v.x + v.x)) ^ 0x80808080u, (mx[1] - (v.y + v.y)) ^ 0x80808080u,
-                               (mx[2] - (v.z + v.z)) ^ 0x80808080u, (mx[3] - (v.w + v.w)) ^ 0x80808080u);
-    if (z >= z0 && z < z1) *reinterpret_cast<uint4*>(buf + (int64_t)(z - z0) * kLo16 + c0 + mcb) = o;
-  }
-}
-
-// the walks in Gray-ordered blocks of 2^lp, as seed_walks in spectral.hip
-template <int G>
-__device__ __forceinline__ void seed16_walks(const uint32_t (*pr)[kHi16], const uint32_t* __restrict__ planes,
-                                             uint32_t g0, int ng, int wng, uint8_t* st8, int tid, int co,
-                                             const uint32_t* mx, int mcb, int c0, int z0, int z1,
-                                             int8_t* __restrict__ buf, int lp) {
-  const int wa = (z0 & ~(kWalk16 - 1)) >> kWalkBits16, we = (z1 + kWalk16 - 1) >> kWalkBits16, P = 1 << lp;
-  const int b1 = (we + P - 1) >> lp;
-  for (int b = (wa >> lp) + blockIdx.y; b < b1; b += gridDim.y) {
-    uint32_t x[G];
-    walk_start16<G>(pr, (b << lp) << kWalkBits16, x);
-    for (int j = 0; j < P; ++j) {  // workgroup-uniform
-      if (j) {
-        const int t = __builtin_ctz(j);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          uint32_t f = pr[g][kWalkBits16 - 1];
-#pragma unroll
-          for (int k = 0; k < kMaxWalkBlockBits16; ++k)
-            if (k == t) f ^= pr[g][kWalkBits16 + k];
-          x[g] ^= f;
-        }
-      }
-      const int w = (b << lp) + (j ^ (j >> 1));
-      if (w < wa || w >= we) {  // outside the range: the state as if walked
-#pragma unroll
-        for (int g = 0; g < G; ++g) x[g] ^= pr[g][kWalkBits16 - 1];
-        continue;
-      }
-      __syncthreads();  // the previous walk's store-out reads of `stage` are done
-      walk_from16<G>(pr, x, st8, co);
-      seed16_finish(planes, g0, ng, wng, st8, tid, co, mx, mcb, c0, w << kWalkBits16, z0, z1, buf);
-    }
-  }
-}
-
+// the shared int8 seed with 16 planes (spectral_seed.h): a column holds at most four groups, three
+// walked from registers and a fourth from L2.  90 VGPRs: 5 waves per SIMD
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void seed16_sm_kernel(
     const uint32_t* __restrict__ planes, const uint32_t* __restrict__ gofs, const uint32_t* __restrict__ off, int z0,
     int z1, int8_t* __restrict__ buf, int lp) {
-  constexpr int NT = 256;
-  __shared__ uint32_t stage[kWalk16 * NT / 4];
-  uint8_t* st8 = reinterpret_cast<uint8_t*>(stage);
-  const int tid = threadIdx.x;
-  const int c0 = blockIdx.x * NT;
-  // columns to lanes by group count (seed_lane_column, spectral.h): at config 5's density 1 in 8
-  // columns holds more than 64 codes, so in column order nearly every wave walks 3 groups
-  const int co = seed_lane_column(gofs, c0, tid);
-  const int c = c0 + co;
-  const uint32_t g0 = gofs[c];
-  const int ng = (int)(gofs[c + 1] - g0);
-  int wng = ng;
-#pragma unroll
-  for (int s = 32; s; s >>= 1) wng = max(wng, __shfl_xor(wng, s));
-  uint32_t pr[kRegGroups16][kHi16];
-#pragma unroll
-  for (int g = 0; g < kRegGroups16; ++g)
-    if (g < ng) {
-      load_planes16(planes, (int64_t)g0 + g, pr[g]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < kHi16; ++k) pr[g][k] = 0u;
-    }
-  const int mcb = (tid % (NT / 16)) * 16;
-  uint32_t mx[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    mx[k] = 0x80808080u;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int cc = c0 + mcb + 4 * k + b;
-      mx[k] |= (off[cc + 1] - off[cc]) << (8 * b);
-    }
-  }
-  {
-    const int ph = (blockIdx.x + blockIdx.y) % 3;
-    if (ph >= 1) __builtin_amdgcn_s_sleep(24);
-    if (ph == 2) __builtin_amdgcn_s_sleep(24);
-  }
-  if (wng <= 1) seed16_walks<1>(pr, planes, g0, ng, wng, st8, tid, co, mx, mcb, c0, z0, z1, buf, lp);
-  else if (wng == 2) seed16_walks<2>(pr, planes, g0, ng, wng, st8, tid, co, mx, mcb, c0, z0, z1, buf, lp);
-  else seed16_walks<3>(pr, planes, g0, ng, wng, st8, tid, co, mx, mcb, c0, z0, z1, buf, lp);
+  seed_sm_body<Cols>(planes, gofs, off, z0, z1, buf, lp);
 }
 
 // ---------------------------------------------------------------- tile
@@ -589,35 +401,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
   add_job_constants(counts, add_n, sumsq);
 }
 
-void launch_seed16(State& st, int8_t* buf, int z0, int z1, hipStream_t s) {
-  const int walks = (z1 - (z0 & ~(kWalk16 - 1)) + kWalk16 - 1) / kWalk16;
-  const int per_wg = std::max(1, std::min(kSeedWalks16, walks / 16));
-  int lp = 0;  // walks per Gray-ordered block: the largest power of two <= per_wg, <= 16
-  while (lp < kMaxWalkBlockBits16 && (2 << lp) <= per_wg) ++lp;
-  const int wa = (z0 & ~(kWalk16 - 1)) / kWalk16, we = (z1 + kWalk16 - 1) / kWalk16;
-  const int nb = ((we + (1 << lp) - 1) >> lp) - (wa >> lp);
-  hipLaunchKernelGGL(seed16_sm_kernel, dim3(kLo16 / 256, (unsigned)nb), dim3(256), 0, s, st.d_planes, st.d_gofs, st.d_off,
-                     z0, z1, buf, lp);
+int launch_seed16(State& st, int z0, int z1, hipStream_t s) {
+  return launch_seed_sm<Cols>(seed16_sm_kernel, st, reinterpret_cast<int8_t*>(st.d_buf), z0, z1, s);
 }
 
-void launch_tile16(State& st, const int8_t* buf, int z0, int z1, unsigned long long* counts, hipStream_t s,
-                   unsigned long long add_n, int wgs_per_cu) {
+int launch_tile16(State& st, int z0, int z1, unsigned long long* counts, hipStream_t s, unsigned long long add_n) {
   const int ns = z1 - z0;
   const uint16_t* order = ((ns & (ns - 1)) == 0 && ns <= (1 << 16) && z0 % ns == 0) ? st.d_order + ns : nullptr;
-  hipLaunchKernelGGL(tile16_kernel, dim3((unsigned)std::max(1, std::min(st.grid * wgs_per_cu, ns))), dim3(256), 0, s,
-                     buf, order, z0, ns, counts, add_n, st.sumsq_ptr());
-}
-
-int launch_chunk16(State& st, int z0, int z1, unsigned long long* counts, hipStream_t s, unsigned long long add_n) {
-  int8_t* buf = reinterpret_cast<int8_t*>(st.d_buf);
-  hipEvent_t t0 = st.timer ? st.timer->start(s) : nullptr;
-  launch_seed16(st, buf, z0, z1, s);
+  hipLaunchKernelGGL(tile16_kernel, dim3((unsigned)std::max(1, std::min(st.grid * st.tile_wgs, ns))), dim3(256), 0, s,
+                     reinterpret_cast<const int8_t*>(st.d_buf), order, z0, ns, counts, add_n, st.sumsq_ptr());
   SCT_LAUNCH_CHECK();
-  if (st.timer) st.timer->stop(s, t0, sct::LaunchTimer::SEED);
-  t0 = st.timer ? st.timer->start(s) : nullptr;
-  launch_tile16(st, buf, z0, z1, counts, s, add_n, st.tile_wgs);
-  SCT_LAUNCH_CHECK();
-  if (st.timer) st.timer->stop(s, t0, sct::LaunchTimer::TILE);
   return SCT_OK;
 }
 
@@ -631,7 +424,7 @@ int create16(State& st, const uint64_t* d_codes, int64_t n, unsigned max16, int6
   st.lo_bits = kLoBits16;
   st.max_m = max16;
   st.elem_bytes = 1;
-  st.chunk16 = std::max<int64_t>(kWalk16, std::min<int64_t>(kChunk16, chunk / 4));
+  st.chunk16 = std::max<int64_t>(kWalk, std::min<int64_t>(kChunk16, chunk / 4));
   st.chunk = 4 * st.chunk16;  // in virtual slices (the plan's items)
   static const int per_cu = [] {
     int v = 0;
@@ -641,21 +434,16 @@ int create16(State& st, const uint64_t* d_codes, int64_t n, unsigned max16, int6
   st.tile_wgs = per_cu;
   if (int rc = make_order_table(st); rc != SCT_OK) return rc;
   st.max_groups = sct::ceil_div(n, 32) + kLo16;
-  void* p = nullptr;
-  auto get = [&](int slot, size_t bytes, auto** out) {
-    const int rc = ws_get(st.ws, slot, bytes, &p);
-    if (rc == SCT_OK) *out = reinterpret_cast<std::remove_reference_t<decltype(**out)>*>(p);
+  if (int rc = get_slot(st, W_HI, (size_t)n * 4, &st.d_hi); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_OFF, (size_t)(kLo16 + 1) * 4, &st.d_off); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_CNT, (size_t)kLo16 * 4, &st.d_cnt); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_GOFS, (size_t)(kLo16 + 1) * 4, &st.d_gofs); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_HIST, (size_t)kSortWGs16 * kLo16, &st.d_hist); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_PLANES, (size_t)st.max_groups * Cols::kPlaneWords * 4, &st.d_planes); rc != SCT_OK)
     return rc;
-  };
-  if (int rc = get(W_HI, (size_t)n * 4, &st.d_hi); rc != SCT_OK) return rc;
-  if (int rc = get(W_OFF, (size_t)(kLo16 + 1) * 4, &st.d_off); rc != SCT_OK) return rc;
-  if (int rc = get(W_CNT, (size_t)kLo16 * 4, &st.d_cnt); rc != SCT_OK) return rc;
-  if (int rc = get(W_GOFS, (size_t)(kLo16 + 1) * 4, &st.d_gofs); rc != SCT_OK) return rc;
-  if (int rc = get(W_HIST, (size_t)kSortWGs16 * kLo16, &st.d_hist); rc != SCT_OK) return rc;
-  if (int rc = get(W_PLANES, (size_t)st.max_groups * kPW16 * 4, &st.d_planes); rc != SCT_OK) return rc;
   if (int rc = alloc_buf(st, &st.chunk16, std::min<int64_t>(st.chunk16, 1024), (size_t)kLo16); rc != SCT_OK) return rc;
   st.chunk = 4 * st.chunk16;
-  if (int rc = get(W_SUMSQ, sizeof(unsigned long long), &st.d_sumsq); rc != SCT_OK) return rc;
+  if (int rc = get_slot(st, W_SUMSQ, sizeof(unsigned long long), &st.d_sumsq); rc != SCT_OK) return rc;
   return SCT_OK;
 }
 
@@ -670,8 +458,8 @@ int build16(State& st, const uint64_t* d_codes, hipStream_t s) {
   hipLaunchKernelGGL(scatter16_wg_kernel, dim3(kSortWGs16), dim3(kSortThreads16), 0, s, d_codes, st.n, st.d_hist,
                      st.d_off, st.d_hi);
   SCT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(planes16_kernel, dim3(kLo16 * 4 / 256), dim3(256), 0, s, st.d_hi, st.d_off, st.d_gofs,
-                     st.d_planes);
+  hipLaunchKernelGGL(planes_slot_kernel<Cols>, dim3(kLo16 * kPlaneSlots / 256), dim3(256), 0, s, st.d_hi, st.d_off,
+                     st.d_gofs, st.d_planes);
   SCT_LAUNCH_CHECK();
   if (st.timer) st.timer->stop(s, t0, sct::LaunchTimer::BUILD);
   return SCT_OK;
@@ -682,7 +470,10 @@ int count16(State& st, int64_t z_begin, int64_t z_end, unsigned long long* d_cou
   for (int64_t z0 = rb; z0 < re; z0 += st.chunk16) {
     const int z1 = (int)std::min<int64_t>(re, z0 + st.chunk16);
     const unsigned long long add_n = z0 == 0 ? (unsigned long long)st.n : 0ull;
-    if (int rc = launch_chunk16(st, (int)z0, z1, d_counts, s, add_n); rc != SCT_OK) return rc;
+    const int rc = launch_seed_tile(
+        st, s, [&] { return launch_seed16(st, (int)z0, z1, s); },
+        [&] { return launch_tile16(st, (int)z0, z1, d_counts, s, add_n); });
+    if (rc != SCT_OK) return rc;
   }
   return SCT_OK;
 }
@@ -692,36 +483,9 @@ int time_kernels16(State& st, int64_t z_begin, int64_t z_end, unsigned long long
   const int64_t rb = real16(z_begin), re = std::min<int64_t>(real16(z_end), rb + st.chunk16);
   SCT_CHECK(rb < re, "time_kernels: empty 16-bit slice range");
   *slices = 4 * (re - rb);  // virtual slices (the bench prices 16 KiB per virtual slice)
-  hipEvent_t e[3];
-  for (auto& x : e) SCT_HIP(hipEventCreate(&x));
-  struct Free {
-    hipEvent_t* e;
-    ~Free() {
-      for (int i = 0; i < 3; ++i) (void)hipEventDestroy(e[i]);
-    }
-  } guard{e};
-  sct::LaunchTimer* keep = st.timer;
-  st.timer = nullptr;
-  int rc = launch_chunk16(st, (int)rb, (int)re, d_counts, s, 0);  // warm
-  int8_t* buf = reinterpret_cast<int8_t*>(st.d_buf);
-  const int ns = (int)(re - rb);
-  const uint16_t* order = ((ns & (ns - 1)) == 0 && ns <= (1 << 16) && rb % ns == 0) ? st.d_order + ns : nullptr;
-  SCT_HIP(hipEventRecord(e[0], s));
-  for (int r = 0; rc == SCT_OK && r < repeats; ++r) launch_seed16(st, buf, (int)rb, (int)re, s);
-  SCT_HIP(hipEventRecord(e[1], s));
-  for (int r = 0; rc == SCT_OK && r < repeats; ++r)
-    hipLaunchKernelGGL(tile16_kernel, dim3((unsigned)std::max(1, std::min(st.grid * st.tile_wgs, ns))), dim3(256), 0,
-                       s, buf, order, (int)rb, ns, d_counts, 0ull, st.sumsq_ptr());
-  SCT_HIP(hipEventRecord(e[2], s));
-  st.timer = keep;
-  if (rc != SCT_OK) return rc;
-  SCT_HIP(hipEventSynchronize(e[2]));
-  float a = 0, b = 0;
-  SCT_HIP(hipEventElapsedTime(&a, e[0], e[1]));
-  SCT_HIP(hipEventElapsedTime(&b, e[1], e[2]));
-  *seed_ms = a / repeats;
-  *tile_ms = b / repeats;
-  return SCT_OK;
+  return time_seed_tile(
+      st, repeats, s, [&] { return launch_seed16(st, (int)rb, (int)re, s); },
+      [&] { return launch_tile16(st, (int)rb, (int)re, d_counts, s, 0); }, seed_ms, tile_ms);
 }
 
 }  // namespace sct_spectral

@@ -1185,19 +1185,21 @@ def test_allpairs_spectral_column_width_edges(m):
     assert hist.astype(np.int64).tolist() == O.c_hist16(codes)[0][:17].tolist()
 
 
-@pytest.mark.parametrize("case", ["m127", "m97", "m65", "ragged"])
+@pytest.mark.parametrize("case", ["m127", "m97", "m65", "ragged", "ragged127"])
 def test_allpairs_spectral_seed_group_counts(case):
     """The int8 seed's step-major walk against the C oracle for every group count: a column
     of 127 codes (a fourth group from L2), 97 (the first fourth group), 65 (three groups in
-    registers) beside columns of one or two groups, and slice ranges that cut walks."""
-    m = {"m127": 127, "m97": 97, "m65": 65, "ragged": 40}[case]
+    registers) beside columns of one or two groups, and slice ranges that cut walks (ragged127:
+    with the fourth group from L2)."""
+    m = {"m127": 127, "m97": 97, "m65": 65, "ragged": 40, "ragged127": 127}[case]
     rng = np.random.default_rng(m)
     hi = np.unique(rng.integers(0, 1 << 18, 4 * m).astype(np.uint64))[:m]
     col = (hi << np.uint64(14)) | np.uint64(0x2345)
     rest = synthetic.whitelist_codes(7000, 16, seed=m)
     rest = rest[(rest & np.uint64(0x3FFF)) != np.uint64(0x2345)]
     codes = np.concatenate([col, rest])
-    ranges = [(0, 1 << 18)] if case != "ragged" else [(0, 1001), (1001, 70001), (70001, 1 << 18)]
+    assert np.bincount((codes & np.uint64(0x3FFF)).astype(np.int64)).max() == m
+    ranges = [(0, 1001), (1001, 70001), (70001, 1 << 18)] if case.startswith("ragged") else [(0, 1 << 18)]
     hist = _spectral_hist(codes, ranges)
     assert hist.astype(np.int64).tolist() == O.c_hist16(codes)[0][:17].tolist()
 
@@ -1223,20 +1225,21 @@ def _dense_columns(splits, n_rand, seed):
     return codes
 
 
-@pytest.mark.parametrize("case", ["two_columns", "sub127", "ragged", "small_chunk"])
+@pytest.mark.parametrize("case", ["two_columns", "sub127", "ragged", "small_chunk", "ragged127"])
 def test_allpairs_spectral_16bit_columns(case):
     """Sets whose densest 14-bit column needs int16 seeds but whose 16-bit columns hold <= 127
     codes take the 16-bit-column transform (spectral16.hip): bin for bin against the C oracle.
     Sub-columns of 127 (four groups, the int8 limit), 65 (the first third group), 0 and 1
-    codes; slice ranges cutting walks and chunks; a small chunk (several seed / tile passes
-    and their digit-weight orders)."""
+    codes; slice ranges cutting walks and chunks (ragged127: with a four-group sub-column); a
+    small chunk (several seed / tile passes and their digit-weight orders)."""
     torch = pytest.importorskip("torch")
     splits = {"two_columns": [(40, 40, 40, 40), (100, 0, 1, 60)], "sub127": [(127, 65, 0, 3)],
-              "ragged": [(90, 90, 0, 0)], "small_chunk": [(33, 64, 96, 127)]}[case]
+              "ragged": [(90, 90, 0, 0)], "small_chunk": [(33, 64, 96, 127)],
+              "ragged127": [(127, 40, 0, 0)]}[case]
     codes = _dense_columns(splits, 6000, seed=len(case))
     ranges = [(0, 1 << 18)]
     chunk = None
-    if case == "ragged":
+    if case.startswith("ragged"):
         ranges = [(0, 1001), (1001, 70001), (70001, 1 << 18)]
     if case == "small_chunk":
         chunk, ranges = 4096, [(0, 8192), (8192, 100000), (100000, 1 << 18)]

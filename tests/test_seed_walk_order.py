@@ -1,6 +1,6 @@
-"""Host-only check of the seed kernels' walk bookkeeping (sctools_amd/csrc/spectral.hip
-seed_walks / walk_from, spectral16.hip seed16_walks), restated in
-Python: every 64-slice walk runs from the XOR of the planes of its slice bits 6 and up, its
+"""Host-only check of the int8 seed's walk bookkeeping (sctools_amd/csrc/spectral_seed.h
+seed_walks / walk_from, one copy for the 18 planes of 14-bit columns and the 16 planes of 16-bit
+columns), restated in Python: every 64-slice walk runs from the XOR of the planes of its slice bits 6 and up, its
 last state is that start with plane 5 flipped, and the Gray-ordered blocks of 2^lp walks
 reach every walk of a range exactly once with the state the direct computation gives."""
 import random
