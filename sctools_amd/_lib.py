@@ -868,13 +868,26 @@ class HostNearestPlan:
             check(self._lib.sct_nearest_plan_create_host(kind, _ptr(wl), wl.size, code_bits, max_d,
                                                          ctypes.byref(self._h)))
 
-    def query(self, queries):
+    def _form(self, name):
+        """The C entry point of a form on this plan: sct_nearest_{name}_host, or its multi form."""
+        return getattr(self._lib, ("sct_nearest_multi_%s_host" if self._multi else "sct_nearest_%s_host") % name)
+
+    @staticmethod
+    def _queries_out(queries):
+        """The queries as uint64, and page-locked index / dist arrays for them."""
         q = np.ascontiguousarray(queries, dtype=np.uint64).reshape(-1)
-        index = pinned.empty(q.size, np.int32)
-        dist = pinned.empty(q.size, np.uint8)
+        return q, pinned.empty(q.size, np.int32), pinned.empty(q.size, np.uint8)
+
+    def _check_accumulators(self, counts, tally):
+        if counts.dtype != np.uint64 or counts.size != self.nw or not counts.flags.c_contiguous:
+            raise ValueError("counts must be a contiguous uint64 array of the whitelist's size")
+        if tally.dtype != np.uint64 or tally.size != 2 or not tally.flags.c_contiguous:
+            raise ValueError("tally must be a contiguous uint64 array of 2")
+
+    def query(self, queries):
+        q, index, dist = self._queries_out(queries)
         if q.size:
-            f = self._lib.sct_nearest_multi_query_host if self._multi else self._lib.sct_nearest_query_host
-            check(f(self._h, _ptr(q), q.size, _ptr(index), _ptr(dist)))
+            check(self._form("query")(self._h, _ptr(q), q.size, _ptr(index), _ptr(dist)))
         return index, dist
 
     def count(self, queries, counts, tally):
@@ -882,13 +895,9 @@ class HostNearestPlan:
         no-match / tie numbers to ``tally`` (uint64[2]): only those cross PCIe on the way back
         (sct_nearest_count_host / sct_nearest_multi_count_host)."""
         q = np.ascontiguousarray(queries, dtype=np.uint64).reshape(-1)
-        if counts.dtype != np.uint64 or counts.size != self.nw or not counts.flags.c_contiguous:
-            raise ValueError("counts must be a contiguous uint64 array of the whitelist's size")
-        if tally.dtype != np.uint64 or tally.size != 2 or not tally.flags.c_contiguous:
-            raise ValueError("tally must be a contiguous uint64 array of 2")
+        self._check_accumulators(counts, tally)
         if q.size:
-            f = self._lib.sct_nearest_multi_count_host if self._multi else self._lib.sct_nearest_count_host
-            check(f(self._h, _ptr(q), q.size, _ptr(counts), _ptr(tally)))
+            check(self._form("count")(self._h, _ptr(q), q.size, _ptr(counts), _ptr(tally)))
 
     def set_posterior(self, prior, qweight, num, den):
         """Priors (uint32[nw] or None for all ones), the weight per raw quality byte (uint32[256]) and
@@ -908,26 +917,19 @@ class HostNearestPlan:
     def correct(self, queries, qualities):
         """(index, dist, stats) of sct_nearest_correct_host for uint64 queries and their (n, L) uint8
         quality rows; stats = uint64[2]: queries scored, and those of them given an index."""
-        q = np.ascontiguousarray(queries, dtype=np.uint64).reshape(-1)
-        index = pinned.empty(q.size, np.int32)
-        dist = pinned.empty(q.size, np.uint8)
+        q, index, dist = self._queries_out(queries)
         stats = np.zeros(2, dtype=np.uint64)
-        f = self._lib.sct_nearest_multi_correct_host if self._multi else self._lib.sct_nearest_correct_host
-        check(f(self._h, _ptr(q), _ptr(qualities), qualities.strides[0] if q.size else 0, q.size, _ptr(index),
-                _ptr(dist), _ptr(stats)))
+        check(self._form("correct")(self._h, _ptr(q), _ptr(qualities), qualities.strides[0] if q.size else 0, q.size,
+                                    _ptr(index), _ptr(dist), _ptr(stats)))
         return index, dist, stats
 
     def correct_count(self, queries, qualities, counts, tally):
         """``count`` over ``correct``'s indices (sct_nearest_correct_count_host); returns stats."""
         q = np.ascontiguousarray(queries, dtype=np.uint64).reshape(-1)
-        if counts.dtype != np.uint64 or counts.size != self.nw or not counts.flags.c_contiguous:
-            raise ValueError("counts must be a contiguous uint64 array of the whitelist's size")
-        if tally.dtype != np.uint64 or tally.size != 2 or not tally.flags.c_contiguous:
-            raise ValueError("tally must be a contiguous uint64 array of 2")
+        self._check_accumulators(counts, tally)
         stats = np.zeros(2, dtype=np.uint64)
-        f = self._lib.sct_nearest_multi_correct_count_host if self._multi else self._lib.sct_nearest_correct_count_host
-        check(f(self._h, _ptr(q), _ptr(qualities), qualities.strides[0] if q.size else 0, q.size, _ptr(counts),
-                _ptr(tally), _ptr(stats)))
+        check(self._form("correct_count")(self._h, _ptr(q), _ptr(qualities), qualities.strides[0] if q.size else 0,
+                                          q.size, _ptr(counts), _ptr(tally), _ptr(stats)))
         return stats
 
     def close(self):

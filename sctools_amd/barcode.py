@@ -340,6 +340,20 @@ class WhitelistCorrector:
             return np.full(q.size, -1, np.int32), np.full(q.size, 255, np.uint8)
         return self._plan.query(q)
 
+    def _accumulator(self, out):
+        """``out`` of ``count`` / ``count_corrected`` unpacked: (counts, n_none, n_other), the counts
+        array made when there is none."""
+        n_none = n_other = 0
+        counts = out
+        if isinstance(out, tuple):
+            counts, n_none, n_other = out
+        if counts is None:
+            counts = np.zeros(self.size, dtype=np.int64)
+        elif not (isinstance(counts, np.ndarray) and counts.dtype == np.int64 and counts.shape == (self.size,)
+                  and counts.flags.c_contiguous):
+            raise ValueError('out must be a contiguous np.int64 array of the whitelist size')
+        return counts, int(n_none), int(n_other)
+
     def count(self, queries, out=None):
         """Reads per whitelist barcode for one batch, tallied on the device: only the counts cross
         PCIe on the way back, not an index and a distance per query.
@@ -353,20 +367,12 @@ class WhitelistCorrector:
             ``(index == -2).sum()`` of ``nearest(queries)``
         """
         q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64)).reshape(-1)
-        n_none = n_tie = 0
-        counts = out
-        if isinstance(out, tuple):
-            counts, n_none, n_tie = out
-        if counts is None:
-            counts = np.zeros(self.size, dtype=np.int64)
-        elif not (isinstance(counts, np.ndarray) and counts.dtype == np.int64 and counts.shape == (self.size,)
-                  and counts.flags.c_contiguous):
-            raise ValueError('out must be a contiguous np.int64 array of the whitelist size')
+        counts, n_none, n_tie = self._accumulator(out)
         if self._plan is None:  # empty whitelist: nothing can match
-            return counts, int(n_none) + q.size, int(n_tie)
+            return counts, n_none + q.size, n_tie
         tally = np.zeros(2, dtype=np.uint64)
         self._plan.count(q, counts.view(np.uint64), tally)
-        return counts, int(n_none) + int(tally[0]), int(n_tie) + int(tally[1])
+        return counts, n_none + int(tally[0]), n_tie + int(tally[1])
 
     # ------------------------------------------------------------ posterior correction
     def set_prior(self, prior=None):
@@ -437,22 +443,14 @@ class WhitelistCorrector:
         """``count`` over ``correct``'s indices, tallied on the device; ``out`` and the result as in
         ``count``: (counts, n_none, n_ambiguous)."""
         q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64)).reshape(-1)
-        n_none = n_amb = 0
-        counts = out
-        if isinstance(out, tuple):
-            counts, n_none, n_amb = out
-        if counts is None:
-            counts = np.zeros(self.size, dtype=np.int64)
-        elif not (isinstance(counts, np.ndarray) and counts.dtype == np.int64 and counts.shape == (self.size,)
-                  and counts.flags.c_contiguous):
-            raise ValueError('out must be a contiguous np.int64 array of the whitelist size')
+        counts, n_none, n_amb = self._accumulator(out)
         if self._plan is None:  # empty whitelist: nothing can match
-            return counts, int(n_none) + q.size, int(n_amb)
+            return counts, n_none + q.size, n_amb
         rows = self._quality_rows(qualities, q.size)
         self._apply_posterior(threshold, quality_weights)
         tally = np.zeros(2, dtype=np.uint64)
         self.last_stats = self._plan.correct_count(q, rows, counts.view(np.uint64), tally)
-        return counts, int(n_none) + int(tally[0]), int(n_amb) + int(tally[1])
+        return counts, n_none + int(tally[0]), n_amb + int(tally[1])
 
     def close(self):
         if self._plan is not None:

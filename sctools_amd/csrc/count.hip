@@ -488,15 +488,15 @@ int fetch_device(sct_counter* c, uint64_t* d_keys, uint64_t* d_counts, int64_t* 
   return leave(c, s);
 }
 
-int tally_launch(const int32_t* d_index, int64_t n, int64_t nw, uint64_t* d_counts, uint64_t* d_tally,
-                 uint64_t* d_err, hipStream_t s) {
+}  // namespace
+
+int sct::tally_launch(const int32_t* d_index, int64_t n, int64_t nw, uint64_t* d_counts, uint64_t* d_tally,
+                      uint64_t* d_err, hipStream_t s) {
   hipLaunchKernelGGL(index_tally_kernel, dim3(grid_for(n, kTile)), dim3(WG), 0, s, d_index, n, nw,
                      reinterpret_cast<u64*>(d_counts), reinterpret_cast<u64*>(d_tally), reinterpret_cast<u64*>(d_err));
   SCT_LAUNCH_CHECK();
   return SCT_OK;
 }
-
-}  // namespace
 
 extern "C" int sct_counter_create(int64_t capacity_hint, sct_counter** out) {
   SCT_CHECK(out != nullptr, "counter is NULL");
@@ -561,20 +561,15 @@ extern "C" int sct_counter_update_host(sct_counter* c, const uint64_t* codes, in
   hipStream_t s = hs->stream;
   // pieces through one pool buffer: a piece's copy is ordered after the previous piece's kernels
   const int64_t piece = std::min<int64_t>(n, 1LL << 24);
-  void* buf = nullptr;
-  SCT_HIP(sct::pool_alloc(&buf, (size_t)piece * 8, s));
+  sct::PoolBlock buf(s);
+  if (int rc = buf.alloc((size_t)piece * 8); rc != SCT_OK) return rc;
   int rc = SCT_OK;
-  hipError_t e = hipSuccess;
-  for (int64_t b = 0; b < n && rc == SCT_OK && e == hipSuccess; b += piece) {
+  for (int64_t b = 0; b < n && rc == SCT_OK && buf.ok(); b += piece) {
     const int64_t m = std::min(piece, n - b);
-    e = hipMemcpyAsync(buf, codes + b, (size_t)m * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) rc = update_device(c, static_cast<const uint64_t*>(buf), m, s);
+    buf.note(hipMemcpyAsync(buf.p, codes + b, (size_t)m * 8, hipMemcpyHostToDevice, s));
+    if (buf.ok()) rc = update_device(c, static_cast<const uint64_t*>(buf.p), m, s);
   }
-  sct::pool_free(buf, s);
-  const hipError_t se = hipStreamSynchronize(s);  // no caller pointer is kept past the return
-  if (e == hipSuccess) e = se;
-  if (rc == SCT_OK && e != hipSuccess) rc = sct::fail(SCT_E_HIP, "counter update: %s", hipGetErrorString(e));
-  return rc;
+  return buf.finish(rc, "counter update");  // no caller pointer is kept past the return
 }
 
 extern "C" int sct_counter_info(sct_counter* c, int64_t* nunique, int64_t* total, int64_t* capacity) {
@@ -611,21 +606,16 @@ extern "C" int sct_counter_fetch_host(sct_counter* c, uint64_t* keys, uint64_t* 
   SCT_CHECK(room >= rows, "room for %lld rows, the counter holds %lld", (long long)room, (long long)rows);
   if (rows == 0) return SCT_OK;
   const size_t b8 = ((size_t)rows * 8 + 255) & ~(size_t)255;
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, 3 * b8, s));
-  uint8_t* b = static_cast<uint8_t*>(blk);
-  int rc = fetch_device(c, (uint64_t*)b, (uint64_t*)(b + b8), (int64_t*)(b + 2 * b8), rows, s);
-  hipError_t e = hipSuccess;
+  sct::PoolBlock blk(s);
+  if (int rc = blk.alloc(3 * b8); rc != SCT_OK) return rc;
+  uint8_t* b = blk.bytes();
+  const int rc = fetch_device(c, (uint64_t*)b, (uint64_t*)(b + b8), (int64_t*)(b + 2 * b8), rows, s);
   if (rc == SCT_OK) {
-    e = hipMemcpyAsync(keys, b, (size_t)rows * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, b + b8, (size_t)rows * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(first, b + 2 * b8, (size_t)rows * 8, hipMemcpyDeviceToHost, s);
+    blk.note(hipMemcpyAsync(keys, b, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok()) blk.note(hipMemcpyAsync(counts, b + b8, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok()) blk.note(hipMemcpyAsync(first, b + 2 * b8, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
   }
-  sct::pool_free(blk, s);
-  const hipError_t se = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = se;
-  if (rc == SCT_OK && e != hipSuccess) rc = sct::fail(SCT_E_HIP, "counter fetch: %s", hipGetErrorString(e));
-  return rc;
+  return blk.finish(rc, "counter fetch");
 }
 
 extern "C" int sct_index_tally(const int32_t* d_index, int64_t n, int64_t nw, uint64_t* d_counts, uint64_t* d_tally,
@@ -636,110 +626,15 @@ extern "C" int sct_index_tally(const int32_t* d_index, int64_t n, int64_t nw, ui
   if (n == 0) return SCT_OK;
   SCT_CHECK(d_index != nullptr, "NULL index");
   hipStream_t s = sct::as_stream(stream);
-  void* d_err = nullptr;
-  SCT_HIP(sct::pool_alloc(&d_err, 8, s));
+  sct::PoolBlock d_err(s);
+  if (int rc = d_err.alloc(8); rc != SCT_OK) return rc;
   uint64_t h_err = 0;
-  hipError_t e = hipMemsetAsync(d_err, 0, 8, s);
+  d_err.note(hipMemsetAsync(d_err.p, 0, 8, s));
   int rc = SCT_OK;
-  if (e == hipSuccess) rc = tally_launch(d_index, n, nw, d_counts, d_tally, (uint64_t*)d_err, s);
-  if (e == hipSuccess && rc == SCT_OK) e = hipMemcpyAsync(&h_err, d_err, 8, hipMemcpyDeviceToHost, s);
-  sct::pool_free(d_err, s);
-  const hipError_t se = hipStreamSynchronize(s);  // the status below is the error word's
-  if (e == hipSuccess) e = se;
-  if (rc == SCT_OK && e != hipSuccess) rc = sct::fail(SCT_E_HIP, "index tally: %s", hipGetErrorString(e));
+  if (d_err.ok()) rc = sct::tally_launch(d_index, n, nw, d_counts, d_tally, (uint64_t*)d_err.p, s);
+  if (d_err.ok() && rc == SCT_OK) d_err.note(hipMemcpyAsync(&h_err, d_err.p, 8, hipMemcpyDeviceToHost, s));
+  rc = d_err.finish(rc, "index tally");  // the status below is the error word's
   if (rc == SCT_OK && h_err)
     rc = sct::fail(SCT_E_RANGE, "index outside [-2, %lld) (not counted)", (long long)nw);
   return rc;
-}
-
-extern "C" int sct_nearest_count_host(sct_nearest_plan* p, const uint64_t* queries, int64_t nq, uint64_t* counts,
-                                      uint64_t* tally) {
-  SCT_CHECK(nq >= 0, "nq must be >= 0");
-  SCT_CHECK(p != nullptr, "plan is NULL");
-  const int64_t nw = sct::nearest_plan_size(p);
-  SCT_CHECK(tally != nullptr && (nw == 0 || counts != nullptr), "NULL counts");
-  if (nq == 0) return SCT_OK;
-  SCT_CHECK(queries != nullptr, "NULL queries");
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t qb = al((size_t)nq * 8), ib = al((size_t)nq * 4), db = al((size_t)nq);
-  const size_t cw = (size_t)nw + 3;  // counts, tally[2], error word
-  if (int rc = sct::stage_reserve(hs, cw * 8, 0); rc != SCT_OK) return rc;
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, qb + ib + db + cw * 8, s));
-  uint8_t* b = static_cast<uint8_t*>(blk);
-  uint64_t* d_counts = reinterpret_cast<uint64_t*>(b + qb + ib + db);
-  uint64_t* h = reinterpret_cast<uint64_t*>(hs->pinned);
-  int rc = SCT_OK;
-  hipError_t e = hipMemcpyAsync(b, queries, (size_t)nq * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, cw * 8, s);
-  if (e == hipSuccess) {
-    rc = sct_nearest_query(p, (const uint64_t*)b, nq, (int32_t*)(b + qb), b + qb + ib, s);
-    if (rc == SCT_OK)
-      rc = tally_launch((const int32_t*)(b + qb), nq, nw, d_counts, d_counts + nw, d_counts + nw + 2, s);
-    if (rc == SCT_OK) e = hipMemcpyAsync(h, d_counts, cw * 8, hipMemcpyDeviceToHost, s);
-  }
-  sct::pool_free(blk, s);
-  const hipError_t se = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = se;
-  if (rc == SCT_OK && e != hipSuccess) rc = sct::fail(SCT_E_HIP, "nearest count: %s", hipGetErrorString(e));
-  if (rc != SCT_OK) return rc;
-  if (h[nw + 2]) return sct::fail(SCT_E_RANGE, "nearest index outside [-2, %lld)", (long long)nw);
-  for (int64_t j = 0; j < nw; ++j) counts[j] += h[j];
-  tally[0] += h[nw];
-  tally[1] += h[nw + 1];
-  return SCT_OK;
-}
-
-// sct_nearest_count_host with sct_nearest_correct in place of the query: the final indices feed the
-// same tally, and only the counts, the two tallies and the two statistics come back.
-extern "C" int sct_nearest_correct_count_host(sct_nearest_plan* p, const uint64_t* queries, const uint8_t* qual,
-                                              int64_t qual_stride, int64_t nq, uint64_t* counts, uint64_t* tally,
-                                              uint64_t* stats) {
-  SCT_CHECK(nq >= 0, "nq must be >= 0");
-  SCT_CHECK(p != nullptr, "plan is NULL");
-  const int64_t nw = sct::nearest_plan_size(p);
-  const int L = sct::nearest_plan_positions(p);
-  SCT_CHECK(tally != nullptr && (nw == 0 || counts != nullptr), "NULL counts");
-  if (L == 0)  // not a half-key plan: the device call says why
-    return sct_nearest_correct(p, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr);
-  if (nq == 0) return SCT_OK;
-  SCT_CHECK(queries != nullptr && qual != nullptr, "NULL queries or qualities");
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t qb = al((size_t)nq * 8), ub = al((size_t)nq * L), ib = al((size_t)nq * 4), db = al((size_t)nq);
-  const size_t cw = (size_t)nw + 5;  // counts, tally[2], error word, stats[2]
-  if (int rc = sct::stage_reserve(hs, cw * 8, 0); rc != SCT_OK) return rc;
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, qb + ub + ib + db + cw * 8, s));
-  uint8_t* b = static_cast<uint8_t*>(blk);
-  uint64_t* d_counts = reinterpret_cast<uint64_t*>(b + qb + ub + ib + db);
-  uint64_t* h = reinterpret_cast<uint64_t*>(hs->pinned);
-  hipError_t e = hipMemsetAsync(d_counts, 0, cw * 8, s);
-  int rc = e == hipSuccess ? sct::nearest_correct_stage(p, queries, qual, qual_stride, nq, b, b + qb, s) : SCT_OK;
-  if (e == hipSuccess && rc == SCT_OK) {
-    rc = sct_nearest_correct(p, (const uint64_t*)b, b + qb, L, nq, (int32_t*)(b + qb + ub), b + qb + ub + ib,
-                             d_counts + nw + 3, s);
-    if (rc == SCT_OK)
-      rc = tally_launch((const int32_t*)(b + qb + ub), nq, nw, d_counts, d_counts + nw, d_counts + nw + 2, s);
-    if (rc == SCT_OK) e = hipMemcpyAsync(h, d_counts, cw * 8, hipMemcpyDeviceToHost, s);
-  }
-  sct::pool_free(blk, s);
-  const hipError_t se = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = se;
-  if (rc == SCT_OK && e != hipSuccess) rc = sct::fail(SCT_E_HIP, "nearest correct count: %s", hipGetErrorString(e));
-  if (rc != SCT_OK) return rc;
-  if (h[nw + 2]) return sct::fail(SCT_E_RANGE, "nearest index outside [-2, %lld)", (long long)nw);
-  for (int64_t j = 0; j < nw; ++j) counts[j] += h[j];
-  tally[0] += h[nw];
-  tally[1] += h[nw + 1];
-  if (stats) {
-    stats[0] += h[nw + 3];
-    stats[1] += h[nw + 4];
-  }
-  return SCT_OK;
 }

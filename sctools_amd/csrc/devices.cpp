@@ -20,7 +20,7 @@
 #include <thread>
 #include <vector>
 
-#include "sct_common.h"
+#include "nearest_host.h"
 
 namespace sct {
 namespace {
@@ -155,42 +155,54 @@ extern "C" int sct_nearest_multi_create_host(int kind, const uint64_t* whitelist
   return SCT_OK;
 }
 
+// One batch over the slots (the forms of sct::nearest_host_batch): slot r takes the contiguous query
+// range [nq r / k, nq (r + 1) / k) -- an empty one is fine -- and writes its index / dist range in
+// place; what a form ADDS to (counts and the two tallies, the two statistics of correct) each slot
+// adds to a host row of its own, and the rows are summed here once every slot has succeeded.
+static int nearest_multi_batch(sct_nearest_multi* m, const sct::NearestIn& in, const sct::NearestWant& want) {
+  if (in.nq == 0) return SCT_OK;
+  const int k = (int)m->plans.size();
+  const bool tallied = want.tally != nullptr;
+  const size_t nw = tallied ? (size_t)m->nw : 0, o_stats = tallied ? nw + 2 : 0, row = o_stats + (in.qual ? 2 : 0);
+  std::vector<uint64_t> part((size_t)k * row, 0);
+  const int rc = sct::run_on_devices(m->devices.data(), k, [&](int r) {
+    const int64_t b = split(in.nq, r, k), e = split(in.nq, r + 1, k);
+    uint64_t* mine = part.data() + (size_t)r * row;
+    return sct::nearest_host_batch(
+        m->plans[(size_t)r], {in.queries + b, in.qual ? in.qual + b * in.qual_stride : nullptr, in.qual_stride, e - b},
+        {tallied ? nullptr : want.index + b, tallied ? nullptr : want.dist + b, tallied ? mine : nullptr,
+         tallied ? mine + nw : nullptr, in.qual ? mine + o_stats : nullptr});
+  });
+  if (rc != SCT_OK) return rc;
+  for (int r = 0; r < k; ++r) {
+    const uint64_t* mine = part.data() + (size_t)r * row;
+    for (size_t j = 0; j < nw; ++j) want.counts[j] += mine[j];
+    if (tallied) {
+      want.tally[0] += mine[nw];
+      want.tally[1] += mine[nw + 1];
+    }
+    if (in.qual && want.stats) {
+      want.stats[0] += mine[o_stats];
+      want.stats[1] += mine[o_stats + 1];
+    }
+  }
+  return SCT_OK;
+}
+
 extern "C" int sct_nearest_multi_query_host(sct_nearest_multi* m, const uint64_t* queries, int64_t nq, int32_t* index,
                                             uint8_t* dist) {
   SCT_CHECK(m != nullptr, "plan is NULL");
   SCT_CHECK(nq >= 0 && (nq == 0 || (queries && index && dist)), "bad arguments");
-  if (nq == 0) return SCT_OK;
-  const int k = (int)m->plans.size();
-  return sct::run_on_devices(m->devices.data(), k, [&](int r) {
-    const int64_t b = split(nq, r, k), e = split(nq, r + 1, k);
-    return sct_nearest_query_host(m->plans[(size_t)r], queries + b, e - b, index + b, dist + b);
-  });
+  return nearest_multi_batch(m, {queries, nullptr, 0, nq}, {index, dist, nullptr, nullptr, nullptr});
 }
 
-// every slot tallies its query range into a host array of its own; the arrays are summed here
 extern "C" int sct_nearest_multi_count_host(sct_nearest_multi* m, const uint64_t* queries, int64_t nq,
                                             uint64_t* counts, uint64_t* tally) {
   SCT_CHECK(nq >= 0, "nq must be >= 0");
   SCT_CHECK(m != nullptr, "plan is NULL");
   SCT_CHECK(tally != nullptr && (m->nw == 0 || counts != nullptr), "NULL counts");
-  if (nq == 0) return SCT_OK;
-  SCT_CHECK(queries != nullptr, "NULL queries");
-  const int k = (int)m->plans.size();
-  const size_t row = (size_t)m->nw + 2;  // counts, then the two tallies
-  std::vector<uint64_t> part((size_t)k * row, 0);
-  const int rc = sct::run_on_devices(m->devices.data(), k, [&](int r) {
-    const int64_t b = split(nq, r, k), e = split(nq, r + 1, k);
-    uint64_t* mine = part.data() + (size_t)r * row;
-    return sct_nearest_count_host(m->plans[(size_t)r], queries + b, e - b, mine, mine + m->nw);
-  });
-  if (rc != SCT_OK) return rc;
-  for (int r = 0; r < k; ++r) {
-    const uint64_t* mine = part.data() + (size_t)r * row;
-    for (int64_t j = 0; j < m->nw; ++j) counts[j] += mine[j];
-    tally[0] += mine[m->nw];
-    tally[1] += mine[m->nw + 1];
-  }
-  return SCT_OK;
+  SCT_CHECK(nq == 0 || queries != nullptr, "NULL queries");
+  return nearest_multi_batch(m, {queries, nullptr, 0, nq}, {nullptr, nullptr, counts, tally, nullptr});
 }
 
 // the prior replicated: every slot permutes it into its own plan's table order
@@ -207,20 +219,7 @@ extern "C" int sct_nearest_multi_correct_host(sct_nearest_multi* m, const uint64
                                               uint64_t* stats) {
   SCT_CHECK(m != nullptr, "plan is NULL");
   SCT_CHECK(nq >= 0 && (nq == 0 || (queries && qual && index && dist)), "bad arguments");
-  if (nq == 0) return SCT_OK;
-  const int k = (int)m->plans.size();
-  std::vector<uint64_t> part((size_t)k * 2, 0);
-  const int rc = sct::run_on_devices(m->devices.data(), k, [&](int r) {
-    const int64_t b = split(nq, r, k), e = split(nq, r + 1, k);
-    return sct_nearest_correct_host(m->plans[(size_t)r], queries + b, qual + b * qual_stride, qual_stride, e - b,
-                                    index + b, dist + b, part.data() + 2 * (size_t)r);
-  });
-  if (rc != SCT_OK) return rc;
-  for (int r = 0; stats && r < k; ++r) {
-    stats[0] += part[2 * (size_t)r];
-    stats[1] += part[2 * (size_t)r + 1];
-  }
-  return SCT_OK;
+  return nearest_multi_batch(m, {queries, qual, qual_stride, nq}, {index, dist, nullptr, nullptr, stats});
 }
 
 extern "C" int sct_nearest_multi_correct_count_host(sct_nearest_multi* m, const uint64_t* queries,
@@ -229,29 +228,8 @@ extern "C" int sct_nearest_multi_correct_count_host(sct_nearest_multi* m, const 
   SCT_CHECK(nq >= 0, "nq must be >= 0");
   SCT_CHECK(m != nullptr, "plan is NULL");
   SCT_CHECK(tally != nullptr && (m->nw == 0 || counts != nullptr), "NULL counts");
-  if (nq == 0) return SCT_OK;
-  SCT_CHECK(queries != nullptr && qual != nullptr, "NULL queries or qualities");
-  const int k = (int)m->plans.size();
-  const size_t row = (size_t)m->nw + 4;  // counts, the two tallies, the two statistics
-  std::vector<uint64_t> part((size_t)k * row, 0);
-  const int rc = sct::run_on_devices(m->devices.data(), k, [&](int r) {
-    const int64_t b = split(nq, r, k), e = split(nq, r + 1, k);
-    uint64_t* mine = part.data() + (size_t)r * row;
-    return sct_nearest_correct_count_host(m->plans[(size_t)r], queries + b, qual + b * qual_stride, qual_stride,
-                                          e - b, mine, mine + m->nw, mine + m->nw + 2);
-  });
-  if (rc != SCT_OK) return rc;
-  for (int r = 0; r < k; ++r) {
-    const uint64_t* mine = part.data() + (size_t)r * row;
-    for (int64_t j = 0; j < m->nw; ++j) counts[j] += mine[j];
-    tally[0] += mine[m->nw];
-    tally[1] += mine[m->nw + 1];
-    if (stats) {
-      stats[0] += mine[m->nw + 2];
-      stats[1] += mine[m->nw + 3];
-    }
-  }
-  return SCT_OK;
+  SCT_CHECK(nq == 0 || (queries != nullptr && qual != nullptr), "NULL queries or qualities");
+  return nearest_multi_batch(m, {queries, qual, qual_stride, nq}, {nullptr, nullptr, counts, tally, stats});
 }
 
 extern "C" int sct_nearest_multi_destroy(sct_nearest_multi* m) {

@@ -1013,9 +1013,9 @@ static int build_halves(sct_nearest_plan* p, const uint64_t* d_wl, int64_t nw, i
   // scratch: bucket counts / cursors of both tables, permAB unpacked, the layout flag and the
   // out-of-key-order flag
   const size_t sCnt = 0, sPerm = sCnt + al((nA + nB) * 4), sBad = sPerm + al(2 * n * 4), sTotal = sBad + 256;  // (flags: 1 + kOrders words)
-  void* scratch = nullptr;
-  SCT_HIP(sct::pool_alloc(&scratch, sTotal, s));
-  char* sb = reinterpret_cast<char*>(scratch);
+  sct::PoolBlock scratch(s);
+  if (int rc = scratch.alloc(sTotal); rc != SCT_OK) return rc;
+  char* sb = reinterpret_cast<char*>(scratch.p);
   uint32_t* cntA = reinterpret_cast<uint32_t*>(sb + sCnt);
   uint32_t* cntB = cntA + nA;
   uint32_t* perm = reinterpret_cast<uint32_t*>(sb + sPerm);
@@ -1058,9 +1058,8 @@ static int build_halves(sct_nearest_plan* p, const uint64_t* d_wl, int64_t nw, i
   // layout not applicable, (unsorted flags), dinv, dalpha, ident_a, an A bucket of > 256 codes
   unsigned hflags[2 + 2 * kOrders] = {1u};
   if (e == hipSuccess) e = hipMemcpyAsync(hflags, bad, sizeof(hflags), hipMemcpyDeviceToHost, s);
-  sct::pool_free(scratch, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "half-key build: %s", hipGetErrorString(e));
+  scratch.note(e);
+  if (int rc = scratch.finish(SCT_OK, "half-key build"); rc != SCT_OK) return rc;
   if (hflags[0]) {  // not applicable: another layout
     (void)hipFree(p->hv_mem[0]);
     p->hv_mem[0] = nullptr;
@@ -1260,14 +1259,35 @@ extern "C" int sct_nearest_plan_info(const sct_nearest_plan* p, int* scheme, int
 static int nearest_query_launch(sct_nearest_plan* p, const uint64_t* d_queries, int64_t nq, int32_t* d_index,
                                 uint8_t* d_dist, void* stream);
 
+// after every query pass enqueued on `s` (sct_nearest_plan::last_query)
+static int record_last_query(sct_nearest_plan* p, hipStream_t s) {
+  if (!p->last_query) SCT_HIP(hipEventCreateWithFlags(&p->last_query, hipEventDisableTiming));
+  SCT_HIP(hipEventRecord(p->last_query, s));
+  return SCT_OK;
+}
+
 extern "C" int sct_nearest_query(sct_nearest_plan* p, const uint64_t* d_queries, int64_t nq,
                                  int32_t* d_index, uint8_t* d_dist, void* stream) {
   const int rc = nearest_query_launch(p, d_queries, nq, d_index, d_dist, stream);
-  if (rc == SCT_OK && p && nq > 0) {
-    if (!p->last_query) SCT_HIP(hipEventCreateWithFlags(&p->last_query, hipEventDisableTiming));
-    SCT_HIP(hipEventRecord(p->last_query, sct::as_stream(stream)));
-  }
-  return rc;
+  return rc == SCT_OK && p && nq > 0 ? record_last_query(p, sct::as_stream(stream)) : rc;
+}
+
+// The half-key query pass of a plan on `s`: halves_query_kernel for its code kind and key order --
+// the deferring instantiation when the worklist `df` is given (sct_nearest_correct), else the plain
+// one -- then halves_index_kernel where the query kernel left table positions.  The caller reads the
+// launch status (hipGetLastError).
+template <typename... DF>
+static void launch_halves_query(const sct_nearest_plan* p, const uint64_t* d_queries, int64_t nq, int32_t* d_index,
+                                uint8_t* d_dist, hipStream_t s, DF... df) {
+  constexpr bool kDefer = sizeof...(DF) != 0;
+  const unsigned blocks = (unsigned)sct::ceil_div(nq, WG);  // one query per thread
+  const bool idx = p->hv.ident_a;  // whitelist indices straight from the query kernel
+  auto kern = idx ? (p->kind == 2 ? halves_query_kernel<2, true, kDefer, DF...> : halves_query_kernel<3, true, kDefer, DF...>)
+                  : (p->kind == 2 ? halves_query_kernel<2, false, kDefer, DF...> : halves_query_kernel<3, false, kDefer, DF...>);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(WG), 0, s, d_queries, nq, p->hv, p->max_d, d_index, d_dist, df...);
+  if (!idx)
+    hipLaunchKernelGGL(halves_index_kernel, dim3(grid_for(sct::ceil_div(nq, 4), 8192)), dim3(WG), 0, s, d_index, nq,
+                       (const uint32_t*)p->perm_packed, p->pbits, ((uintptr_t)d_index & 15) == 0);
 }
 
 static int nearest_query_launch(sct_nearest_plan* p, const uint64_t* d_queries, int64_t nq, int32_t* d_index,
@@ -1280,17 +1300,7 @@ static int nearest_query_launch(sct_nearest_plan* p, const uint64_t* d_queries, 
   const unsigned blocks = (unsigned)sct::ceil_div(nq, WG);  // one query per thread
   SCT_CHECK(sct::ceil_div(nq, WG) < (1LL << 31), "too many queries for one launch");
   if (p->halves) {
-    if (p->hv.ident_a) {  // whitelist indices straight from the query kernel
-      auto kern = p->kind == 2 ? halves_query_kernel<2, true> : halves_query_kernel<3, true>;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(WG), 0, s, d_queries, nq, p->hv, p->max_d, d_index, d_dist);
-      SCT_LAUNCH_CHECK();
-      return SCT_OK;
-    }
-    auto kern = p->kind == 2 ? halves_query_kernel<2, false> : halves_query_kernel<3, false>;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(WG), 0, s, d_queries, nq, p->hv, p->max_d, d_index, d_dist);
-    SCT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(halves_index_kernel, dim3(grid_for(sct::ceil_div(nq, 4), 8192)), dim3(WG), 0, s, d_index, nq,
-                       (const uint32_t*)p->perm_packed, p->pbits, ((uintptr_t)d_index & 15) == 0);
+    launch_halves_query(p, d_queries, nq, d_index, d_dist, s);
     SCT_LAUNCH_CHECK();
     return SCT_OK;
   }
@@ -1321,7 +1331,7 @@ static int nearest_query_launch(sct_nearest_plan* p, const uint64_t* d_queries, 
 int sct::nearest_plan_positions(const sct_nearest_plan* p) { return p->halves ? p->hv.G : 0; }
 
 // the plans sct_nearest_correct takes: the half-key scheme at max_d == 1
-static int correct_plan_check(const sct_nearest_plan* p) {
+int sct::correct_plan_check(const sct_nearest_plan* p) {
   SCT_CHECK(p != nullptr, "plan is NULL");
   if (!p->halves || p->max_d != 1)
     return sct::fail(SCT_E_RANGE,
@@ -1334,7 +1344,7 @@ static int correct_plan_check(const sct_nearest_plan* p) {
 
 extern "C" int sct_nearest_plan_set_posterior(sct_nearest_plan* p, const uint32_t* d_prior, const uint32_t* qweight,
                                               int num, int den, void* stream) {
-  if (int rc = correct_plan_check(p); rc != SCT_OK) return rc;
+  if (int rc = sct::correct_plan_check(p); rc != SCT_OK) return rc;
   SCT_CHECK(qweight != nullptr, "qweight is NULL");
   SCT_CHECK(num >= 1 && num <= den && den <= 64 && 2 * num > den,
             "threshold %d/%d: needs 1 <= num <= den <= 64 and 2 * num > den", num, den);
@@ -1344,62 +1354,38 @@ extern "C" int sct_nearest_plan_set_posterior(sct_nearest_plan* p, const uint32_
   // calls still in flight read the tables this one replaces
   if (p->last_query) SCT_HIP(hipStreamWaitEvent(s, p->last_query, 0));
   if (!p->d_qweight) SCT_HIP(hipMalloc(&p->d_qweight, 256 * 4));
-  uint32_t* fresh = nullptr;
-  unsigned h_bad = 0;
+  sct::DevBuf fresh;  // the plan takes it only at the end: every failure before that frees it
   if (d_prior) {
     const int64_t n2 = 2 * p->nw;
-    void* d_bad = nullptr;
-    SCT_HIP(hipMalloc(&fresh, (size_t)n2 * 4));
-    hipError_t e = sct::pool_alloc(&d_bad, 4, s);
-    if (e == hipSuccess) {
-      e = hipMemsetAsync(d_bad, 0, 4, s);
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(prior_permute_kernel, dim3(grid_for(n2, 4096)), dim3(WG), 0, s, d_prior, n2,
-                           (const uint32_t*)p->perm_packed, p->pbits, fresh, (unsigned*)d_bad);
-        e = hipGetLastError();
-      }
-      if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, s);
-      sct::pool_free(d_bad, s);
+    unsigned h_bad = 0;
+    SCT_HIP(fresh.alloc((size_t)n2 * 4));
+    sct::PoolBlock bad(s);
+    if (int rc = bad.alloc(4); rc != SCT_OK) return rc;
+    bad.note(hipMemsetAsync(bad.p, 0, 4, s));
+    if (bad.ok()) {
+      hipLaunchKernelGGL(prior_permute_kernel, dim3(grid_for(n2, 4096)), dim3(WG), 0, s, d_prior, n2,
+                         (const uint32_t*)p->perm_packed, p->pbits, (uint32_t*)fresh.p, (unsigned*)bad.p);
+      bad.note(hipGetLastError());
     }
-    const hipError_t se = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = se;
-    if (e != hipSuccess || h_bad) {
-      (void)hipFree(fresh);
-      if (e != hipSuccess) return sct::fail(SCT_E_HIP, "set posterior: %s", hipGetErrorString(e));
-      return sct::fail(SCT_E_INVALID, "a prior is >= 2^30");
-    }
+    if (bad.ok()) bad.note(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
+    if (int rc = bad.finish(SCT_OK, "set posterior"); rc != SCT_OK) return rc;
+    SCT_CHECK(!h_bad, "a prior is >= 2^30");
   }
   SCT_HIP(hipMemcpyAsync(p->d_qweight, qweight, 256 * 4, hipMemcpyHostToDevice, s));
   SCT_HIP(hipStreamSynchronize(s));  // the old priors are idle now, and qweight is the caller's again
   if (p->d_priorAB) (void)hipFree(p->d_priorAB);
-  p->d_priorAB = fresh;
+  p->d_priorAB = static_cast<uint32_t*>(fresh.p);
+  fresh.p = nullptr;
   p->post_num = (uint32_t)num;
   p->post_den = (uint32_t)den;
   p->post_set = true;
   return SCT_OK;
 }
 
-extern "C" int sct_nearest_plan_set_posterior_host(sct_nearest_plan* p, const uint32_t* prior, const uint32_t* qweight,
-                                                   int num, int den) {
-  if (int rc = correct_plan_check(p); rc != SCT_OK) return rc;
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  if (!prior) return sct_nearest_plan_set_posterior(p, nullptr, qweight, num, den, s);
-  void* dp = nullptr;
-  SCT_HIP(sct::pool_alloc(&dp, (size_t)p->nw * 4, s));
-  const hipError_t e = hipMemcpyAsync(dp, prior, (size_t)p->nw * 4, hipMemcpyHostToDevice, s);
-  const int rc = e == hipSuccess ? sct_nearest_plan_set_posterior(p, (const uint32_t*)dp, qweight, num, den, s)
-                                 : sct::fail(SCT_E_HIP, "prior copy: %s", hipGetErrorString(e));
-  sct::pool_free(dp, s);
-  (void)hipStreamSynchronize(s);
-  return rc;
-}
-
 extern "C" int sct_nearest_correct(sct_nearest_plan* p, const uint64_t* d_queries, const uint8_t* d_qual,
                                    int64_t qual_stride, int64_t nq, int32_t* d_index, uint8_t* d_dist,
                                    uint64_t* d_stats, void* stream) {
-  if (int rc = correct_plan_check(p); rc != SCT_OK) return rc;
+  if (int rc = sct::correct_plan_check(p); rc != SCT_OK) return rc;
   SCT_CHECK(p->post_set, "sct_nearest_plan_set_posterior has not been called on this plan");
   SCT_CHECK(nq >= 0 && nq <= (int64_t)UINT32_MAX, "nq %lld outside [0, 2^32)", (long long)nq);
   if (nq == 0) return SCT_OK;
@@ -1418,139 +1404,15 @@ extern "C" int sct_nearest_correct(sct_nearest_plan* p, const uint64_t* d_querie
   const Posterior ps{p->d_priorAB, p->d_qweight, p->post_num, p->post_den};
   hipError_t e = hipMemsetAsync(wl, 0, cnt_bytes, s);
   if (e == hipSuccess) {
-    if (p->hv.ident_a) {
-      auto kern = p->kind == 2 ? halves_query_kernel<2, true, true, Defer> : halves_query_kernel<3, true, true, Defer>;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(WG), 0, s, d_queries, nq, p->hv, 1, d_index, d_dist, df);
-    } else {
-      auto kern = p->kind == 2 ? halves_query_kernel<2, false, true, Defer> : halves_query_kernel<3, false, true, Defer>;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(WG), 0, s, d_queries, nq, p->hv, 1, d_index, d_dist, df);
-      hipLaunchKernelGGL(halves_index_kernel, dim3(grid_for(sct::ceil_div(nq, 4), 8192)), dim3(WG), 0, s, d_index,
-                         nq, (const uint32_t*)p->perm_packed, p->pbits, ((uintptr_t)d_index & 15) == 0);
-    }
+    launch_halves_query(p, d_queries, nq, d_index, d_dist, s, df);
     auto res = p->kind == 2 ? halves_resolve_kernel<2> : halves_resolve_kernel<3>;
     hipLaunchKernelGGL(res, dim3(grid_for(nq, 2048)), dim3(WG), 0, s, d_queries, d_qual, qual_stride, p->hv, ps,
                        df, d_index, d_dist,
                        reinterpret_cast<unsigned long long*>(d_stats));
     e = hipGetLastError();
   }
-  sct::pool_free(wl, s);
+  sct::pool_free(wl, s);  // stream-ordered, after the kernels: the call stays asynchronous
   if (e != hipSuccess) return sct::fail(SCT_E_HIP, "nearest correct: %s", hipGetErrorString(e));
-  if (!p->last_query) SCT_HIP(hipEventCreateWithFlags(&p->last_query, hipEventDisableTiming));
-  SCT_HIP(hipEventRecord(p->last_query, s));
-  return SCT_OK;
+  return record_last_query(p, s);
 }
 
-// queries and quality rows (packed to the plan's L bytes) into one pool block at `b`
-int sct::nearest_correct_stage(sct_nearest_plan* p, const uint64_t* queries, const uint8_t* qual,
-                               int64_t qual_stride, int64_t nq, uint8_t* d_q, uint8_t* d_qual, hipStream_t s) {
-  const int L = p->hv.G;
-  SCT_CHECK(qual_stride >= L, "qual_stride %lld below the %d positions of the plan", (long long)qual_stride, L);
-  SCT_HIP(hipMemcpyAsync(d_q, queries, (size_t)nq * 8, hipMemcpyHostToDevice, s));
-  if (qual_stride == L)
-    SCT_HIP(hipMemcpyAsync(d_qual, qual, (size_t)nq * L, hipMemcpyHostToDevice, s));
-  else
-    SCT_HIP(hipMemcpy2DAsync(d_qual, (size_t)L, qual, (size_t)qual_stride, (size_t)L, (size_t)nq,
-                             hipMemcpyHostToDevice, s));
-  return SCT_OK;
-}
-
-extern "C" int sct_nearest_correct_host(sct_nearest_plan* p, const uint64_t* queries, const uint8_t* qual,
-                                        int64_t qual_stride, int64_t nq, int32_t* index, uint8_t* dist,
-                                        uint64_t* stats) {
-  if (int rc = correct_plan_check(p); rc != SCT_OK) return rc;
-  SCT_CHECK(nq >= 0 && (nq == 0 || (queries && qual && index && dist)), "bad arguments");
-  if (nq == 0) return SCT_OK;
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t qb = al((size_t)nq * 8), ub = al((size_t)nq * p->hv.G), ib = al((size_t)nq * 4), db = al((size_t)nq);
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, qb + ub + ib + db + 16, s));
-  uint8_t* b = static_cast<uint8_t*>(blk);
-  uint64_t* d_stats = reinterpret_cast<uint64_t*>(b + qb + ub + ib + db);
-  uint64_t h_stats[2] = {0, 0};
-  hipError_t e = hipMemsetAsync(d_stats, 0, 16, s);
-  int rc = e == hipSuccess ? sct::nearest_correct_stage(p, queries, qual, qual_stride, nq, b, b + qb, s) : SCT_OK;
-  if (e == hipSuccess && rc == SCT_OK) {
-    rc = sct_nearest_correct(p, (const uint64_t*)b, b + qb, p->hv.G, nq, (int32_t*)(b + qb + ub),
-                             b + qb + ub + ib, d_stats, s);
-    if (rc == SCT_OK) {
-      e = hipMemcpyAsync(index, b + qb + ub, (size_t)nq * 4, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(dist, b + qb + ub + ib, (size_t)nq, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(h_stats, d_stats, 16, hipMemcpyDeviceToHost, s);
-    }
-  }
-  sct::pool_free(blk, s);
-  const hipError_t se = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = se;
-  if (rc == SCT_OK && e != hipSuccess) rc = sct::fail(SCT_E_HIP, "nearest correct: %s", hipGetErrorString(e));
-  if (rc == SCT_OK && stats) {
-    stats[0] += h_stats[0];
-    stats[1] += h_stats[1];
-  }
-  return rc;
-}
-
-extern "C" int sct_nearest_host(int kind, const uint64_t* whitelist, int64_t nw, const uint64_t* queries,
-                                int64_t nq, int code_bits, int max_d, int32_t* index, uint8_t* dist) {
-  SCT_CHECK(nw >= 0 && nq >= 0, "bad sizes");
-  // a host-whitelist plan and one host query pass (both through the library's stream-ordered
-  // pool on the thread's stream: no per-call hipMalloc / hipFree); the results are read back
-  // before the plan goes
-  sct_nearest_plan* plan = nullptr;
-  int rc = sct_nearest_plan_create_host(kind, whitelist, nw, code_bits, max_d, &plan);
-  if (rc != SCT_OK) return rc;
-  rc = sct_nearest_query_host(plan, queries, nq, index, dist);
-  sct_nearest_plan_destroy(plan);
-  return rc;
-}
-
-extern "C" int sct_nearest_plan_create_host(int kind, const uint64_t* whitelist, int64_t nw, int code_bits, int max_d,
-                                            sct_nearest_plan** out) {
-  SCT_CHECK(out != nullptr, "plan is NULL");
-  SCT_CHECK(nw >= 0 && (nw == 0 || whitelist), "bad whitelist");
-  // the whitelist through the library's stream-ordered pool on the thread's stream (no per-call
-  // hipMalloc / hipFree: a stream of batches builds its index once, but the flows that build
-  // one per file set pay it each time)
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  void* dw = nullptr;
-  SCT_HIP(sct::pool_alloc(&dw, std::max<size_t>((size_t)nw * 8, 8), s));
-  hipError_t e = nw ? hipMemcpyAsync(dw, whitelist, (size_t)nw * 8, hipMemcpyHostToDevice, s) : hipSuccess;
-  int rc = e == hipSuccess ? sct_nearest_plan_create(kind, (const uint64_t*)dw, nw, code_bits, max_d, s, out)
-                           : sct::fail(SCT_E_HIP, "whitelist copy: %s", hipGetErrorString(e));
-  sct::pool_free(dw, s);  // (ordered after the build's reads of it)
-  e = hipStreamSynchronize(s);
-  if (rc == SCT_OK && e != hipSuccess) rc = sct::fail(SCT_E_HIP, "nearest plan: %s", hipGetErrorString(e));
-  return rc;
-}
-
-extern "C" int sct_nearest_query_host(sct_nearest_plan* p, const uint64_t* queries, int64_t nq, int32_t* index,
-                                      uint8_t* dist) {
-  SCT_CHECK(p != nullptr, "plan is NULL");
-  SCT_CHECK(nq >= 0 && (nq == 0 || (queries && index && dist)), "bad arguments");
-  if (nq == 0) return SCT_OK;
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  const size_t qb = ((size_t)nq * 8 + 255) & ~(size_t)255, ib = ((size_t)nq * 4 + 255) & ~(size_t)255;
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, qb + ib + (size_t)nq, s));
-  uint8_t* b = static_cast<uint8_t*>(blk);
-  int rc = SCT_OK;
-  hipError_t e = hipMemcpyAsync(b, queries, (size_t)nq * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    rc = sct_nearest_query(p, (const uint64_t*)b, nq, (int32_t*)(b + qb), b + qb + ib, s);
-    if (rc == SCT_OK) {
-      e = hipMemcpyAsync(index, b + qb, (size_t)nq * 4, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(dist, b + qb + ib, (size_t)nq, hipMemcpyDeviceToHost, s);
-    }
-  }
-  sct::pool_free(blk, s);
-  const hipError_t se = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = se;
-  if (rc == SCT_OK && e != hipSuccess) rc = sct::fail(SCT_E_HIP, "nearest query: %s", hipGetErrorString(e));
-  return rc;
-}

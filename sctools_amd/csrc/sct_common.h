@@ -90,13 +90,17 @@ void pool_free(void* p, hipStream_t s);
 // Returns the first failing slot's status with its message.  One such call at a time per process.
 int run_on_devices(const int* devices, int ndev, const std::function<int(int)>& fn);
 
-// Whitelist codes a nearest plan indexes (nearest.hip; p is not NULL).
+// Whitelist codes a nearest plan indexes (nearest.hip; p is not NULL), and the base positions of a
+// half-key plan (0 for any other plan).
 int64_t nearest_plan_size(const sct_nearest_plan* p);
-// Base positions of a half-key plan (0 for any other plan), and the host staging of
-// sct_nearest_correct's inputs: queries to d_q, quality rows packed to that many bytes to d_qual.
 int nearest_plan_positions(const sct_nearest_plan* p);
-int nearest_correct_stage(sct_nearest_plan* p, const uint64_t* queries, const uint8_t* qual, int64_t qual_stride,
-                          int64_t nq, uint8_t* d_q, uint8_t* d_qual, hipStream_t s);
+// SCT_OK for the plans sct_nearest_correct takes (the half-key scheme at max_d == 1), else the
+// status with its message (nearest.hip).
+int correct_plan_check(const sct_nearest_plan* p);
+// index_tally_kernel over n device indices on `s` (count.hip): counts[nw], tally[2] and the error
+// word are added to.
+int tally_launch(const int32_t* d_index, int64_t n, int64_t nw, uint64_t* d_counts, uint64_t* d_tally,
+                 uint64_t* d_err, hipStream_t s);
 
 // sct_tune_set value of `key`, or dflt when unset (host.cpp).
 int64_t tune(int key, int64_t dflt);
@@ -205,3 +209,45 @@ constexpr int kMomNCounts = 1 + kMomNProd + kMomOrder;  // [pairs, products..., 
       return ::sct::fail(SCT_E_HIP, "kernel launch: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
                          __LINE__);                                                             \
   } while (0)
+
+namespace sct {
+
+// The tail every staged *_host call ends with.  One stream-ordered pool block on `s`; note() keeps
+// the first HIP error of the call; finish() gives the block back on the stream, synchronises the
+// stream once and makes that error the status ("what: error") unless the call had failed already.
+// A call that returns before finish() still frees the block and waits for the stream, so no
+// caller pointer is in use after any return.
+struct PoolBlock {
+  hipStream_t s;
+  void* p = nullptr;
+  hipError_t e = hipSuccess;
+  explicit PoolBlock(hipStream_t stream) : s(stream) {}
+  PoolBlock(const PoolBlock&) = delete;
+  PoolBlock& operator=(const PoolBlock&) = delete;
+  ~PoolBlock() {
+    if (p) (void)release();
+  }
+  int alloc(size_t bytes) {
+    SCT_HIP(pool_alloc(&p, bytes, s));
+    return SCT_OK;
+  }
+  uint8_t* bytes() const { return static_cast<uint8_t*>(p); }
+  bool ok() const { return e == hipSuccess; }
+  void note(hipError_t x) {
+    if (e == hipSuccess) e = x;
+  }
+  int finish(int rc, const char* what) {
+    note(release());
+    if (rc == SCT_OK && e != hipSuccess) rc = fail(SCT_E_HIP, "%s: %s", what, hipGetErrorString(e));
+    return rc;
+  }
+
+ private:
+  hipError_t release() {
+    if (p) pool_free(p, s);
+    p = nullptr;
+    return hipStreamSynchronize(s);
+  }
+};
+
+}  // namespace sct

@@ -9,11 +9,16 @@ synthetic.config4_queries with seeded quality rows (bytes 35..74, uniform).
   correct  sct_nearest_correct, device-resident: no prior (the worklist holds the distance-1 ties),
            and priors = the first pass's counts + 1 (every distance-1 query is scored); time, the
            worklist share of the queries and the share of the worklist that was accepted
-  host     WhitelistCorrector.correct / .count_corrected on page-locked arrays against the copy
-           time of 24 B in and 5 B out per query at the box's measured pinned copy rates
+  host     WhitelistCorrector.nearest / .count / .correct / .count_corrected on page-locked arrays
+           against the copy time of 24 B in and 5 B out per query at the box's measured pinned copy
+           rates, and the wall time per call of --calls small batches of --batch queries each (the
+           fixed cost of a staged call); with --base-lib under that library too, rounds interleaved,
+           and a host_verdict line: each form's median against the base's, within the base's own
+           round-to-round spread or not
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends the
-run.  One JSON line per step and round on stdout and in profiles/ab_nearest_correct_<tag>.jsonl.
+run.  One JSON line per step and round on stdout and in profiles/<profile>_<tag>.jsonl (--profile,
+default ab_nearest_correct).
 
   python tools/bench_correct.py --tag mi355x [--base-lib sctools_amd/libsctools_hip_base.so]
 """
@@ -140,9 +145,13 @@ def correct_step(args):
     return out
 
 
+FORMS = ("nearest", "count", "correct", "count_corrected")
+
+
 def host_step(args):
     import numpy as np
     import torch
+    _tolerate_older_library()
     from sctools_amd import _lib, barcode
     dev = torch.device("cuda", 0)
     nq = args.nq_host
@@ -160,23 +169,58 @@ def host_step(args):
     wc = barcode.WhitelistCorrector(wl, barcode_length=L)
     counts, _, _ = wc.count(hq)
     wc.set_prior(counts + 1)
+    acc = np.zeros(wl.size, dtype=np.int64)
 
-    def wall(f):
+    def forms(a, b):
+        return {"nearest": lambda: wc.nearest(hq[a:b]), "count": lambda: wc.count(hq[a:b], out=acc),
+                "correct": lambda: wc.correct(hq[a:b], hqual[a:b]),
+                "count_corrected": lambda: wc.count_corrected(hq[a:b], hqual[a:b], out=acc)}
+
+    def wall(f, unit):
         t = time.perf_counter()
         f()
-        return round((time.perf_counter() - t) * 1e3, 3)
-    t_near, t_corr, t_cnt = [], [], []
+        return round((time.perf_counter() - t) * unit, 3)
+    big = {name: [] for name in FORMS}
+    whole = forms(0, nq)
     for _ in range(args.reps + 1):
-        t_near.append(wall(lambda: wc.nearest(hq)))
-        t_corr.append(wall(lambda: wc.correct(hq, hqual)))
-        t_cnt.append(wall(lambda: wc.count_corrected(hq, hqual)))
+        for name in FORMS:
+            big[name].append(wall(whole[name], 1e3))
     share = float(wc.last_stats[0]) / nq
+    # small batches, as fastq.iter_arrays hands them over: every call pays the fixed cost of the
+    # staging (allocation, copies, one synchronisation), so a HIP call too many shows here
+    nb, calls = args.batch, args.calls
+    small = {}
+    for name in FORMS:
+        us = []
+        for k in range(calls + 20):
+            a = (k * nb) % (nq - nb)
+            us.append(wall(forms(a, a + nb)[name], 1e6))
+        us = np.array(us[20:])
+        small[name + "_small_us"] = {"median": round(float(np.median(us)), 2), "mean": round(float(us.mean()), 2),
+                                     "p90": round(float(np.percentile(us, 90)), 2)}
     wc.close()
-    return {"nq": nq, "nearest_host_ms": t_near[1:], "correct_host_ms": t_corr[1:], "count_corrected_host_ms": t_cnt[1:],
+    return {"nq": nq, **{name + "_host_ms": big[name][1:] for name in FORMS},
+            "small_batch": nb, "small_calls": calls, **small,
             "worklist_share": round(share, 6),
             "copy_in_24B_per_query_ms": h2d, "copy_out_5B_per_query_ms": d2h,
             "pinned_h2d_gbs": round(24 * nq / (float(np.median(h2d)) * 1e-3) / 1e9, 2),
             "pinned_d2h_gbs": round(5 * nq / (float(np.median(d2h)) * 1e-3) / 1e9, 2)}
+
+
+def host_verdict(recs):
+    """Per form and batch size: the new library's median against the base's, within the base's own
+    round-to-round spread (max - min of its per-round medians)?"""
+    import statistics
+    out = {"step": "host_verdict"}
+    for name in FORMS:
+        for key, pick in ((name + "_host_ms", statistics.median), (name + "_small_us", lambda v: v["median"])):
+            per = {lib: [pick(r[key]) for r in recs if r["library"] == lib] for lib in ("base", "new")}
+            base, new = statistics.median(per["base"]), statistics.median(per["new"])
+            spread = max(per["base"]) - min(per["base"])
+            out[key] = {"base_rounds": per["base"], "new_rounds": per["new"], "base": base, "new": new,
+                        "base_spread": round(spread, 4), "within": abs(new - base) <= spread,
+                        "slower": new - base > spread}
+    return out
 
 
 def main():
@@ -184,42 +228,54 @@ def main():
     ap.add_argument("--tag", default="run")
     ap.add_argument("--step", choices=sorted(LIMITS), help="run one step in this process (the launcher's children)")
     ap.add_argument("--steps", default="query,correct,host")
-    ap.add_argument("--base-lib", default=None, help="another build of the library for the query step's A/B")
+    ap.add_argument("--base-lib", default=None, help="another build of the library for the A/B of the query and host steps")
+    ap.add_argument("--profile", default="ab_nearest_correct", help="profiles/<profile>_<tag>.jsonl takes the lines")
     ap.add_argument("--nq", type=int, default=100_000_000)
     ap.add_argument("--nq-host", type=int, default=20_000_000)
+    ap.add_argument("--batch", type=int, default=1000, help="queries per call of the host step's small batches")
+    ap.add_argument("--calls", type=int, default=2000, help="small-batch calls per form")
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3, help="interleaved rounds of the query step")
+    ap.add_argument("--rounds", type=int, default=3, help="interleaved rounds of the query and host steps' A/B")
     args = ap.parse_args()
     if args.step:
         res = {"query": query_step, "correct": correct_step, "host": host_step}[args.step](args)
         print("RESULT " + json.dumps(res))
         return 0
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    path = os.path.join(ROOT, "profiles", "ab_nearest_correct_%s.jsonl" % args.tag)
+    path = os.path.join(ROOT, "profiles", "%s_%s.jsonl" % (args.profile, args.tag))
     runs = []
     for step in args.steps.split(","):
-        if step == "query":
-            libs = ([("base", os.path.join(ROOT, args.base_lib))] if args.base_lib else []) + [("new", None)]
+        if step in ("query", "host") and args.base_lib:
+            libs = [("base", os.path.join(ROOT, args.base_lib)), ("new", None)]
             runs += [(step, name, lib) for _ in range(args.rounds) for name, lib in libs]
+        elif step == "query":
+            runs += [(step, "new", None)] * args.rounds
         else:
             runs.append((step, "new", None))
+    recs = []
     with open(path, "a") as f:
+        def emit(rec):
+            line = json.dumps(rec, sort_keys=True)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
         for step, name, lib in runs:
             env = dict(os.environ)
             if lib:
                 env["SCTOOLS_HIP_LIB"] = lib
             cmd = ["timeout", "-k", "10", str(LIMITS[step]), sys.executable, os.path.abspath(__file__), "--step", step,
-                   "--nq", str(args.nq), "--nq-host", str(args.nq_host), "--reps", str(args.reps)]
+                   "--nq", str(args.nq), "--nq-host", str(args.nq_host), "--reps", str(args.reps),
+                   "--batch", str(args.batch), "--calls", str(args.calls)]
             p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
             lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
             if p.returncode != 0 or not lines:
                 print(json.dumps({"step": step, "library": name, "failed": p.returncode, "stderr": p.stderr[-2000:]}))
                 return 1  # nothing more is started on the GPU after a step that failed
-            rec = {"tag": args.tag, "step": step, "library": name, **json.loads(lines[-1][len("RESULT "):])}
-            line = json.dumps(rec, sort_keys=True)
-            print(line, flush=True)
-            f.write(line + "\n")
-            f.flush()
+            recs.append({"tag": args.tag, "step": step, "library": name, **json.loads(lines[-1][len("RESULT "):])})
+            emit(recs[-1])
+        host = [r for r in recs if r["step"] == "host"]
+        if args.base_lib and host:
+            emit({"tag": args.tag, **host_verdict(host)})
     return 0
 
 
