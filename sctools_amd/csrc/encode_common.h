@@ -1,5 +1,6 @@
-// Byte -> code table shared by the encoders (encode.hip) and the fused whitelist ingest
-// (lines.hip).  Reference maps: TwoBit encodings.py:53-69, ThreeBit encodings.py:139-149.
+// Byte -> code table and record encoder shared by the encoders (encode.hip), the resident scalar
+// server (scalar_server.hip) and the fused whitelist ingest (lines.hip).
+// Reference maps: TwoBit encodings.py:53-69, ThreeBit encodings.py:139-149.
 #pragma once
 
 #include <hip/hip_runtime.h>

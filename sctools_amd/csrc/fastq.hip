@@ -1095,14 +1095,6 @@ extern "C" int sct_fastq_extract_spans(sct_fastq_index* ix, const uint8_t* d_buf
   return SCT_OK;
 }
 
-namespace {
-#define SCT_TRY(x)                 \
-  do {                             \
-    int rc_ = (x);                 \
-    if (rc_ != SCT_OK) return rc_; \
-  } while (0)
-}  // namespace
-
 // Extraction without an index (fq_count_kernel, tile_sums_reduce_kernel, fastq_range_kernel),
 // asynchronous on `stream`: the concatenated files in d_buf, their cumulative ends in d_file_ends
 // (DEVICE memory, nfiles entries, the last = nbytes).  Rows are laid out by cap_records (span

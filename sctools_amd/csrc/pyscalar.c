@@ -1,6 +1,7 @@
 /* CPython entry points of the drop-in's scalar methods (TwoBit / ThreeBit .encode, .decode,
  * .gc_content, .hamming_distance: encodings.py:75-121, 155-202), each a batch of one through the
- * library's *_host calls and its resident scalar server (encode.hip).
+ * library's *_host calls (encode_host.cpp) and its resident scalar server (scalar_server.hip,
+ * DESIGN.md §3.9).
  *
  * The ctypes path cost about 1.1 us per call on top of the 2.1-us C call (argument conversion,
  * thread-local buffers, addressof, the status check: profiles/scalar_floor_r06/), about as much

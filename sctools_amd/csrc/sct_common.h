@@ -52,8 +52,9 @@ struct HostStage {
   size_t pinned_cap = 0;
   uint8_t* dev = nullptr;
   size_t dev_cap = 0;
-  // the host stream paths' pipeline streams (sct_encode_stream_host), created on first use and
-  // kept: a stream's creation and destruction cost more than a piece's copies (round 5)
+  // the chunked host pipeline's streams (encode_host.cpp: host_items, behind sct_encode_stream_host
+  // and the large element-wise calls), created on first use and kept: a stream's creation and
+  // destruction cost more than a piece's copies (round 5)
   hipStream_t pipe[3] = {nullptr, nullptr, nullptr};
 };
 // nullptr (with the error set) if the stage cannot be created.
@@ -105,7 +106,7 @@ int tally_launch(const int32_t* d_index, int64_t n, int64_t nw, uint64_t* d_coun
 // sct_tune_set value of `key`, or dflt when unset (host.cpp).
 int64_t tune(int key, int64_t dflt);
 
-// Stop the resident scalar servers (encode.hip) before a launch whose grid is sized to the
+// Stop the resident scalar servers (scalar_server.hip) before a launch whose grid is sized to the
 // resident workgroups, so none of its workgroups waits behind a server wave's registers.
 // Cheap when no server runs.
 void scalar_quiesce();
@@ -200,6 +201,13 @@ constexpr int kMomNCounts = 1 + kMomNProd + kMomOrder;  // [pairs, products..., 
 #define SCT_CHECK(cond, ...)                                 \
   do {                                                       \
     if (!(cond)) return ::sct::fail(SCT_E_INVALID, __VA_ARGS__); \
+  } while (0)
+
+// returns a status that is not SCT_OK (its message is already set)
+#define SCT_TRY(x)                 \
+  do {                             \
+    int rc_ = (x);                 \
+    if (rc_ != SCT_OK) return rc_; \
   } while (0)
 
 #define SCT_LAUNCH_CHECK()                                                                      \

@@ -1,8 +1,10 @@
-"""GPU: every path of the record encoders (sctools_amd/csrc/encode.hip) byte for byte against
-tests/encode_reference.py, on inputs that carry all 256 byte values at every position; and the
-limb seams of the decode, gc and hamming kernels against the oracle on Python ints.  Exact integer
-equality on every record: nothing is sampled and nothing has a tolerance."""
+"""GPU: every path of the record encoders (the kernels of sctools_amd/csrc/encode.hip, the host
+stream and array calls of encode_host.cpp) byte for byte against tests/encode_reference.py, on
+inputs that carry all 256 byte values at every position; and the limb seams of the decode, gc and
+hamming kernels against the oracle on Python ints.  Exact integer equality on every record: nothing
+is sampled and nothing has a tolerance."""
 
+import ctypes
 import random
 
 import numpy as np
@@ -274,6 +276,64 @@ def test_encode_stream_every_record(kind, L):
     want = R.encode(kind, recs)
     codes, gc, flags = _lib.encode_stream(kind, recs, chunk=1 << 18)
     _same((codes, gc, flags), want, "stream kind %d L %d" % (kind, L))
+
+
+def _guarded_host(n, dtype, sentinel, page_locked):
+    """n + 2 GUARD rows of the sentinel in host memory, page-locked (the library's pool) or pageable."""
+    rows = n + 2 * GUARD
+    a = _lib.pinned.empty(rows, dtype) if page_locked else np.empty(rows, dtype)
+    assert _lib.host_pinned(a) == page_locked
+    a[:] = sentinel
+    return a
+
+
+def _stream_into(kind, src, n, L, outs, chunk):
+    """sct_encode_stream_host itself, the outputs GUARD rows into `outs` (codes, gc, flags)."""
+    at = [ctypes.c_void_p(a.ctypes.data + GUARD * a.itemsize) for a in outs]
+    return _lib.lib().sct_encode_stream_host(kind, _lib._ptr(src), n, L, at[0], at[1], at[2], chunk)
+
+
+@pytest.mark.parametrize("kind", [2, 3])
+@pytest.mark.parametrize("L", [5, 16])
+def test_encode_stream_mixed_outputs(kind, L):
+    """Page-locked and pageable arrays in one call: each array is copied in place or through the
+    stage on its own.  Five chunks of 2^18 records, so stages 0 and 1 are each used twice; the last
+    chunk's 37 records are fewer than a tile and take encode_kernel.  L = 5: the tiled kernel's byte
+    path and staging tail."""
+    n = 4 * (1 << 18) + 37
+    recs = R.records(n, L, seed=900 + 10 * kind + L)
+    R.check_input(recs, full=True)
+    want = R.encode(kind, recs)
+    pin_in = _lib.pinned.empty((n, L), np.uint8)
+    pin_in[:] = recs
+    assert _lib.host_pinned(pin_in) and not _lib.host_pinned(recs)
+    for codes_locked in (True, False):
+        for src in (pin_in, recs):
+            outs = (_guarded_host(n, np.uint64, CODE_SENTINEL, codes_locked),
+                    _guarded_host(n, np.uint8, BYTE_SENTINEL, not codes_locked),
+                    _guarded_host(n, np.uint8, BYTE_SENTINEL, not codes_locked))
+            _lib.check(_stream_into(kind, src, n, L, outs, 1 << 18))
+            for a, s in zip(outs, (CODE_SENTINEL, BYTE_SENTINEL, BYTE_SENTINEL)):
+                assert (a[:GUARD] == s).all() and (a[GUARD + n:] == s).all(), "guard rows overwritten"
+            _same(tuple(a[GUARD:GUARD + n] for a in outs), want,
+                  "stream kind %d L %d codes %s input %s" % (kind, L, "page-locked" if codes_locked else "pageable",
+                                                            "page-locked" if src is pin_in else "pageable"))
+
+
+def test_encode_stream_one_chunk_and_none():
+    kind, L = 2, 16
+    n = (1 << 18) + 1
+    recs = R.records(n, L, seed=262)
+    R.check_input(recs, full=True)
+    want = R.encode(kind, recs)
+    # chunk = 0: the floor of 2^18 records a chunk, so a full chunk and one of a single record
+    _same(_lib.encode_stream(kind, recs, chunk=0), want, "stream n 2^18 + 1")
+    _same(_lib.encode_stream(kind, recs[:1]), tuple(w[:1] for w in want), "stream n 1")
+    outs = (_guarded_host(0, np.uint64, CODE_SENTINEL, False), _guarded_host(0, np.uint8, BYTE_SENTINEL, False),
+            _guarded_host(0, np.uint8, BYTE_SENTINEL, False))
+    assert _stream_into(kind, recs, 0, L, outs, 0) == _lib.SCT_OK
+    for a, s in zip(outs, (CODE_SENTINEL, BYTE_SENTINEL, BYTE_SENTINEL)):
+        assert (a == s).all(), "n = 0 wrote something"
 
 
 # ---------------------------------------------------------------- f. the drop-in, end to end

@@ -1,4 +1,4 @@
-"""GPU: the resident scalar server behind the drop-in's scalar calls (encode.hip,
+"""GPU: the resident scalar server behind the drop-in's scalar calls (scalar_server.hip,
 `scalar_server_kernel`).  Calls of <= 64 records are answered by a one-wave kernel that
 polls a host-coherent mailbox; these tests check its answers against the oracle (the
 reference's own per-call semantics, encodings.py:75-202) and its life cycle: first-call
