@@ -13,6 +13,11 @@
 // streams (a record may span two files) and an incomplete trailing record is dropped.
 // Mode 'rb' splits lines at '\n' only; mode 'r' (text) at '\n', "\r\n" and a lone '\r',
 // each read back as '\n' (Python's universal newlines), and only ASCII input is accepted.
+// File ends: the reference reads one file at a time, so every file with bytes whose last byte is
+// no terminator ends a line there (any number of such files within a few bytes of each other, a
+// one-byte file included; an empty file ends nothing), and in text mode a '\r' that is a file's
+// last byte and a '\n' that is the next file's first byte are two line ends, never one "\r\n"
+// (tests/fastq_reference.py, tests/test_gpu_fastq_seams.py).
 //
 // Device layout: the files' bytes concatenated in one buffer, read in 8 KiB tiles (32 bytes
 // per thread as two 16-byte loads, SWAR byte compares).  Two passes: count_kernel counts each tile's line
@@ -50,16 +55,6 @@ struct Files {
   const int64_t* ends;  // cumulative end offsets, nfiles entries
   int nfiles;
 };
-
-// file f ends at e (> its start) without a terminator on its last byte -> virtual terminator
-__device__ __forceinline__ bool virtual_end(const uint8_t* __restrict__ buf, int64_t n, Files fs, int f,
-                                            int text) {
-  const int64_t e = fs.ends[f], s = f ? fs.ends[f - 1] : 0;
-  if (e <= s) return false;
-  // a "\r\n" split across the file boundary is two files' bytes: only bytes of this file count
-  const uint8_t c = buf[e - 1];
-  return !(c == '\n' || (text && c == '\r'));
-}
 
 // Each 16-byte load: terminators as a 16-bit mask; a thread owns SEG of them (thread_span);
 // a tile = 256 threads = 8 KiB (half the barriers and scans per byte of 4 KiB tiles: 0.87 vs
@@ -119,18 +114,39 @@ __device__ __forceinline__ uint32_t load_mask(const uint8_t* __restrict__ buf, i
   return m;
 }
 
-// file f's end e lies in (p0, p0 + 16] and its last byte is not a terminator -> virtual
-// terminator at e; returns the in-span offset e - p0 - 1 of its last byte, or -1
-__device__ __forceinline__ int virtual_in(const uint8_t* __restrict__ buf, int64_t n, Files fs,
-                                          int64_t p0, int text) {
-  int lo = 0, hi = fs.nfiles;  // first file with end > p0
+// The file ends that touch a thread's TB bytes at p0 (bit j = byte p0 + j), for the tiles that hold one:
+//  a file ending at e in (p0, p0 + TB] whose last byte is no terminator gets a virtual terminator
+//    on that byte; every such file of the span does (files of a few bytes);
+//  text mode: a '\r' that is a file's last byte ends a line whatever the next file starts with
+//    (universal newlines work per file), and a byte that is the first after a file end is never
+//    the '\n' of a "\r\n".
+// load_mask pairs '\r' with '\n' knowing nothing of files; thread_span corrects its masks with these:
+// the bits to set in m (x) and in vbits (y) and to clear in crlf (z).  Not inlined: it runs in the few
+// tiles that hold a file end, and inlined its registers pushed fastq_range_kernel from 79 to 81 VGPRs
+// (6 -> 5 waves per SIMD).
+__device__ __attribute__((noinline)) uint3 file_end_bits(const uint8_t* __restrict__ buf, int64_t n,
+                                                         const int64_t* __restrict__ ends, int nfiles,
+                                                         int64_t p0, int text) {
+  int lo = 0, hi = nfiles;  // first file with end >= p0
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
-    if (fs.ends[mid] <= p0) lo = mid + 1; else hi = mid;
+    if (ends[mid] < p0) lo = mid + 1; else hi = mid;
   }
-  for (int f = lo; f < fs.nfiles && fs.ends[f] <= p0 + 16; ++f)
-    if (virtual_end(buf, n, fs, f, text)) return (int)(fs.ends[f] - p0 - 1);
-  return -1;
+  uint3 b = make_uint3(0u, 0u, 0u);
+  int64_t prev = lo ? ends[lo - 1] : 0;  // the previous file's end
+  for (int f = lo; f < nfiles; ++f) {
+    const int64_t e = ends[f];
+    if (e > p0 + TB) break;
+    const int j = (int)(e - p0);  // 0..TB
+    if (j > 0 && e > prev) {  // a file with bytes: only bytes of this file count
+      const uint8_t c = buf[e - 1];
+      if (text && c == '\r') b.x |= 1u << (j - 1);
+      else if (c != '\n') b.y |= 1u << (j - 1);
+    }
+    if (text && e > 0 && j < TB && e < n) b.z |= 1u << j;
+    prev = e;
+  }
+  return b;
 }
 
 // A thread's TB bytes at p0 (SEG 16-B segments v): terminator mask m, "\r\n" mask crlf and
@@ -150,21 +166,23 @@ __device__ __forceinline__ Span thread_span(const uint8_t* __restrict__ buf, int
     s.m |= load_mask(buf, n, q, text, &cr, &na, v[k]) << (16 * k);
     s.crlf |= cr << (16 * k);
     s.na |= na;
-    if (ends_here) {
-      const int x = virtual_in(buf, n, fs, q, text);
-      if (x >= 0) s.vbits |= 1u << (16 * k + x);
-    }
+  }
+  if (ends_here) {
+    const uint3 b = file_end_bits(buf, n, fs.ends, fs.nfiles, p0, text);
+    s.m |= b.x;
+    s.vbits |= b.y;
+    s.crlf &= ~b.z;
   }
   return s;
 }
 
-// A workgroup's walk over increasing tile starts t0: f = the first file ending after t0 (loads
+// A workgroup's walk over increasing tile starts t0: f = the first file ending at or after t0 (loads
 // of uniform addresses: scalar), so a tile holding no file end (almost all of them) skips the
 // per-thread virtual-terminator search.
 struct FileCursor {
   int f = 0;
   __device__ __forceinline__ bool advance(Files fs, int64_t t0) {
-    while (f < fs.nfiles && fs.ends[f] <= t0) ++f;
+    while (f < fs.nfiles && fs.ends[f] < t0) ++f;  // (an end at t0 itself: the tile's first byte starts a file)
     return f < fs.nfiles && fs.ends[f] <= t0 + TILE + 16;
   }
 };
@@ -465,7 +483,7 @@ __global__ __launch_bounds__(WG) void fq_count_kernel(const uint8_t* __restrict_
     int lo = 0, hi = fs.nfiles;
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      if (fs.ends[mid] <= t0) lo = mid + 1; else hi = mid;
+      if (fs.ends[mid] < t0) lo = mid + 1; else hi = mid;
     }
     ends_here = lo < fs.nfiles && fs.ends[lo] <= t0 + TILE + 16;
   }

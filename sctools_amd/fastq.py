@@ -256,14 +256,21 @@ def _piece_reader(files, chunk_bytes, head):
     return _PieceReader(files, [_lib.pinned.empty(head + chunk_bytes, np.uint8) for _ in range(2)], head)
 
 
-def _last_line_end(buf, have):
+def _last_line_end(buf, have, text=False):
     """1 + the position of the last '\\n' in buf[:have] (0 if none), searching back from the end
-    in growing windows (a piece's last line end is normally within its last record)."""
+    in growing windows (a piece's last line end is normally within its last record).  text: a
+    '\\r' followed inside buf[:have] by a byte other than '\\n' ends a line too (universal
+    newlines; the last byte is never taken: it may be the first half of a "\\r\\n"), so a file
+    of lone '\\r' line ends is cut into pieces like any other."""
     w = 1 << 16
     hi = have
     while hi > 0:
         lo = max(0, hi - w)
-        hits = np.flatnonzero(buf[lo:hi] == 10)
+        hit = buf[lo:hi] == 10
+        if text:
+            nxt = buf[lo + 1:min(hi + 1, have)]
+            hit[:nxt.size] |= (buf[lo:lo + nxt.size] == 13) & (nxt != 10)
+        hits = np.flatnonzero(hit)
         if hits.size:
             return lo + int(hits[-1]) + 1
         hi = lo
@@ -305,6 +312,7 @@ class EmbeddedBarcodeGenerator:
         is merged with the next piece in a new buffer)."""
         chunk_bytes = max(1, int(chunk_bytes or CHUNK_BYTES))
         head = _HEADROOM
+        text = self._mode == 'r'
         st = _lib.FastqStream([(eb.start, eb.end) for eb in self.embedded_barcodes], self._mode == 'r', qualities)
         reader = _piece_reader(self._files, chunk_bytes, head)
         reader.start()
@@ -313,7 +321,7 @@ class EmbeddedBarcodeGenerator:
 
         def prepare(got):
             """A segment from the reader -> (piece, file ends in it, last?, buffer to hand back,
-            bytes of the chunk call to come: the cut after the last '\\n', the whole final piece)."""
+            bytes of the chunk call to come: the cut after the last line end, the whole final piece)."""
             buf, n, seg_ends, last = got
             c = carry.size
             if c <= head:  # the tail goes in front of the segment, in the same buffer
@@ -327,7 +335,7 @@ class EmbeddedBarcodeGenerator:
                 reader.free.put(buf)
                 release = None
             ends = carry_ends + [c + e for e in seg_ends]
-            return piece, ends, last, release, (piece.size if last else _last_line_end(piece, piece.size))
+            return piece, ends, last, release, (piece.size if last else _last_line_end(piece, piece.size, text))
 
         done = 0
         nxt, pending = None, None
