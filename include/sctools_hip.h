@@ -61,7 +61,8 @@ int sct_set_device(int device);        /* select the device for later calls (hip
                                            sums the per-tile counts itself, no reduction launch */
 #define SCT_TUNE_INGEST_SPEC 16         /* whitelist ingest: 1 tries 16-base lines in one read first (default), 0 never */
 #define SCT_TUNE_COUNT_PREAGG 17        /* counter insert: 0 one table row per code, 1 equal codes of a wave merged
-                                           first (default), 2 a per-workgroup LDS table per tile */
+                                           first (default), 2 a per-workgroup LDS table per tile; the molecule
+                                           counter's insert has the same three forms and default */
 #define SCT_TUNE_NKEYS 18
 int sct_tune_set(int key, int64_t value);
 int sct_tune_get(int key, int64_t* value);  /* -1 when unset */
@@ -530,6 +531,52 @@ int sct_index_tally(const int32_t* d_index, int64_t n, int64_t nw, uint64_t* d_c
                     void* stream);
 int sct_nearest_count_host(sct_nearest_plan* plan, const uint64_t* queries, int64_t nq, uint64_t* counts,
                            uint64_t* tally);
+
+/* Counting molecules: distinct (corrected barcode, UMI) pairs per whitelist barcode, which removes
+ * PCR duplicates.  No reference function exists (the reference extracts the UMI, fastq.py:181-200,
+ * and counts nothing with it); the contract is the one below, restated in plain Python by
+ * tests/molecules_reference.py.
+ * A counter is created for nw whitelist barcodes (1 <= nw < 2^31), a UMI encoding kind (2 TwoBit,
+ * 3 ThreeBit) and a UMI length L.  With umi_bits = kind * L and idx_bits = max(1, bit_length(nw - 1)),
+ * 1 <= umi_bits and idx_bits + umi_bits <= 63 are required (else SCT_E_INVALID).  A molecule's key is
+ * (index << umi_bits) | umi; its top bit is always 0, so the table's empty mark 2^64 - 1 is never
+ * a key and no side slot is needed.  For read i of an update, with index[i] as sct_nearest_query /
+ * sct_nearest_correct leave it and umi[i] the UMI's code:
+ *   1. index == -1:                  tally[0] += 1 (no match);
+ *   2. index == -2:                  tally[1] += 1 (ambiguous);
+ *   3. index outside [-2, nw):       not counted, nothing is stored through it, and the call is
+ *                                    SCT_E_RANGE; the rest of the batch is counted (sct_index_tally's rule);
+ *   4. index >= 0 and a bad UMI:     tally[2] += 1 and the read counts nowhere else.  A UMI is bad if it
+ *                                    has a bit at or above umi_bits, or (kind 3) if any of its L triplets
+ *                                    is not C 1, A 2, G 3 or T 4: N = 6, the invalid 0 / 5 / 7, and a
+ *                                    zero leading triplet.  For kind 2 every value below 2^umi_bits is good;
+ *   5. otherwise                     reads[index] += 1, and molecules[index] += 1 if the key has not been
+ *                                    seen in this counter's lifetime.
+ * reads[nw], molecules[nw] (uint64) and tally[3] live on the device with the counter, are zeroed at
+ * create and accumulate over every update; everything is exact integers.
+ * The table holds keys only (8 B per slot), claimed by a 64-bit compare-and-swap with bounded probes
+ * as the counter's is, and grows by the counter's rule: capacity_hint sizes the first table (a power
+ * of two >= 64), 2^31 slots at most; a table that fills up all the same is SCT_E_RANGE.  update
+ * enqueues its sub-batches on `stream` (reading the table's size between them only when it may have
+ * to grow, as sct_counter_update does) and then waits for the stream once, as sct_index_tally does,
+ * to learn of an out-of-range index (rule 3): it returns after the batch's kernels.  A call on
+ * another stream waits for the counter's earlier work.  n == 0 changes nothing and needs no pointer.
+ * info: nmolecules = distinct keys, total = reads fed whatever became of them, capacity = table
+ * slots (each nullable).  counts: nw + nw + 3 words out, each array nullable.  fetch: the distinct
+ * molecules in ascending key order (by barcode index, then by UMI code); room < nmolecules is
+ * SCT_E_INVALID and leaves the counter as it was.  The counter lives on the device current at
+ * create; destroy waits for the work the counter enqueued, and destroy(NULL) is SCT_OK. */
+typedef struct sct_molecules sct_molecules;
+int sct_molecules_create(int64_t nw, int kind, int L, int64_t capacity_hint, sct_molecules** mol);
+int sct_molecules_update(sct_molecules* mol, const int32_t* d_index, const uint64_t* d_umi, int64_t n, void* stream);
+int sct_molecules_update_host(sct_molecules* mol, const int32_t* index, const uint64_t* umi, int64_t n);
+int sct_molecules_info(sct_molecules* mol, int64_t* nmolecules, int64_t* total, int64_t* capacity);
+int sct_molecules_counts_host(sct_molecules* mol, uint64_t* reads, uint64_t* molecules, uint64_t* tally);
+int sct_molecules_counts(sct_molecules* mol, uint64_t* d_reads, uint64_t* d_molecules, uint64_t* d_tally,
+                         void* stream);
+int sct_molecules_fetch_host(sct_molecules* mol, int32_t* index, uint64_t* umi, int64_t room);
+int sct_molecules_fetch(sct_molecules* mol, int32_t* d_index, uint64_t* d_umi, int64_t room, void* stream);
+int sct_molecules_destroy(sct_molecules* mol);
 
 /* ---------------------------------------------------------------- FASTQ barcode extraction
  * Replaces the per-record path reader.Reader.__iter__ (src/sctools/reader.py:56-85) ->

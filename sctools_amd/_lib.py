@@ -149,6 +149,15 @@ SIGNATURES = {
     "sct_nearest_multi_set_posterior_host": [_vp, _vp, _vp, _i32, _i32],
     "sct_nearest_multi_correct_host": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "sct_nearest_multi_correct_count_host": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "sct_molecules_create": [_i64, _i32, _i32, _i64, ctypes.POINTER(_vp)],
+    "sct_molecules_update": [_vp, _vp, _vp, _i64, _vp],
+    "sct_molecules_update_host": [_vp, _vp, _vp, _i64],
+    "sct_molecules_info": [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    "sct_molecules_counts_host": [_vp, _vp, _vp, _vp],
+    "sct_molecules_counts": [_vp, _vp, _vp, _vp, _vp],
+    "sct_molecules_fetch_host": [_vp, _vp, _vp, _i64],
+    "sct_molecules_fetch": [_vp, _vp, _vp, _i64, _vp],
+    "sct_molecules_destroy": [_vp],
 }
 _RESTYPES = {"sct_last_error": ctypes.c_char_p}
 

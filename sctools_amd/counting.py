@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["DeviceCounter"]
+__all__ = ["DeviceCounter", "MoleculeCounter"]
 
 _vp, _i64 = ctypes.c_void_p, ctypes.c_int64
 
@@ -100,6 +100,127 @@ class DeviceCounter:
     def close(self):
         if self._h:
             self._lib.sct_counter_destroy(self._h)
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _exact(values, dtype, what):
+    """``values`` as a flat contiguous array of ``dtype``: as is when it has that dtype, else
+    converted only if every value survives the round trip (ValueError otherwise)."""
+    if isinstance(values, np.ndarray) and values.dtype == dtype:
+        return np.ascontiguousarray(values).reshape(-1)
+    # (a Python sequence is looked at as objects: numpy would make [3, 2**64 - 1] a float array)
+    src = values if isinstance(values, np.ndarray) else np.asarray(values, dtype=object)
+    if src.size:
+        lim = np.iinfo(dtype)
+        whole = src.dtype.kind in "iub" or (src.dtype.kind == "O" and all(
+            isinstance(v, (int, np.integer)) for v in src.reshape(-1).tolist()))
+        if not whole or int(src.min()) < lim.min or int(src.max()) > lim.max:
+            raise ValueError("%s: %s values do not all fit %s" % (what, src.dtype.name, np.dtype(dtype).name))
+    return np.ascontiguousarray(src.astype(dtype)).reshape(-1)
+
+
+class MoleculeCounter:
+    """Molecules per whitelist barcode on the device (sct_molecules_*): the distinct
+    (corrected barcode index, UMI code) pairs, which removes PCR duplicates.
+
+    ``whitelist_size`` barcodes (1 .. 2**31 - 1), UMIs of ``umi_length`` bases in ``encoding``
+    ('ThreeBit' or 'TwoBit'); the index bits and the UMI bits must fit a 63-bit key.  Feed it the
+    ``index`` of ``WhitelistCorrector.correct`` / ``nearest`` and the encoded UMIs of the same
+    reads.  ``capacity_hint`` sizes the first table; it grows by itself.  Use as a context manager
+    or ``close()`` it to free the device arrays."""
+
+    def __init__(self, whitelist_size, umi_length, encoding='ThreeBit', capacity_hint=1 << 20):
+        kinds = {'ThreeBit': 3, 'TwoBit': 2, 3: 3, 2: 2}
+        if encoding not in kinds:
+            raise ValueError("encoding must be 'ThreeBit' or 'TwoBit'")
+        nw, L, kind = int(whitelist_size), int(umi_length), kinds[encoding]
+        if not 1 <= nw < 2 ** 31:
+            raise ValueError("whitelist_size %d outside [1, 2**31)" % nw)
+        if L < 1:
+            raise ValueError("umi_length must be >= 1")
+        idx_bits = max(1, (nw - 1).bit_length())
+        if idx_bits + kind * L > 63:
+            raise ValueError("index bits %d + UMI bits %d do not fit a 63-bit key" % (idx_bits, kind * L))
+        if not 0 <= int(capacity_hint) <= 2 ** 31:
+            raise ValueError("capacity_hint outside [0, 2**31]")
+        self.size, self.umi_length, self.kind = nw, L, kind
+        self._lib = _lib.lib()
+        self._h = _vp()
+        _lib.check(self._lib.sct_molecules_create(nw, kind, L, int(capacity_hint), ctypes.byref(self._h)))
+
+    def update(self, index, umis):
+        """Count a host batch: ``index`` int32 (-1 no match, -2 ambiguous, else a whitelist index)
+        and the reads' uint64 UMI codes.  An index outside [-2, whitelist_size) raises ValueError
+        after the rest of the batch was counted."""
+        idx = _exact(index, np.int32, "index")
+        umi = _exact(umis, np.uint64, "umis")
+        if idx.size != umi.size:
+            raise ValueError("index and umis differ in length: %d vs %d" % (idx.size, umi.size))
+        if idx.size:
+            _lib.check(self._lib.sct_molecules_update_host(self._h, _lib._ptr(idx), _lib._ptr(umi), idx.size))
+        return self
+
+    def update_device(self, index_ptr, umi_ptr, n, stream=0):
+        """Count ``n`` reads from device pointers (int32 indices, uint64 UMI codes) on ``stream``."""
+        if n:
+            _lib.check(self._lib.sct_molecules_update(self._h, _vp(index_ptr), _vp(umi_ptr), int(n), _vp(stream)))
+        return self
+
+    def counts(self):
+        """(reads, molecules, n_none, n_ambiguous, n_bad_umi): np.int64[whitelist_size] twice --
+        reads and distinct molecules per barcode -- and the reads that had no barcode, an ambiguous
+        one, or a barcode and a bad UMI."""
+        reads = np.empty(self.size, np.uint64)
+        molecules = np.empty(self.size, np.uint64)
+        tally = np.empty(3, np.uint64)
+        _lib.check(self._lib.sct_molecules_counts_host(self._h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)))
+        return (reads.view(np.int64), molecules.view(np.int64), int(tally[0]), int(tally[1]), int(tally[2]))
+
+    def pairs(self, room=None):
+        """(index int32, umi uint64) of the distinct molecules, ascending by index, then by UMI code.
+        ``room`` (default: the number of molecules) sizes the output; too little raises ValueError."""
+        got = len(self)
+        n = got if room is None else int(room)
+        index = np.empty(n, np.int32)
+        umi = np.empty(n, np.uint64)
+        _lib.check(self._lib.sct_molecules_fetch_host(self._h, _lib._ptr(index), _lib._ptr(umi), n))
+        return index[:got], umi[:got]
+
+    def fetch_device(self, index_ptr, umi_ptr, room, stream=0):
+        """The same rows into device arrays with room for ``room`` rows (sct_molecules_fetch)."""
+        _lib.check(self._lib.sct_molecules_fetch(self._h, _vp(index_ptr), _vp(umi_ptr), int(room), _vp(stream)))
+
+    def info(self):
+        """dict(nmolecules, total, capacity)."""
+        nm, tot, cap = _i64(0), _i64(0), _i64(0)
+        _lib.check(self._lib.sct_molecules_info(self._h, ctypes.byref(nm), ctypes.byref(tot), ctypes.byref(cap)))
+        return {"nmolecules": nm.value, "total": tot.value, "capacity": cap.value}
+
+    def __len__(self):
+        return self.info()["nmolecules"]
+
+    def saturation(self):
+        """Sequencing saturation 1 - molecules / reads over the counted reads (nan when none)."""
+        reads, molecules = self.counts()[:2]
+        total = int(reads.sum())
+        return 1.0 - int(molecules.sum()) / total if total else float("nan")
+
+    def close(self):
+        if self._h:
+            self._lib.sct_molecules_destroy(self._h)
             self._h = _vp()
 
     def __enter__(self):

@@ -41,6 +41,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "mix64.h"
 #include "sct_common.h"
 
 namespace {
@@ -68,14 +69,7 @@ struct Table {
   u64 mask;  // capacity - 1
 };
 
-__device__ __forceinline__ u64 mix64(u64 x) {  // murmur3's finaliser: every input bit reaches the low bits
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
+using sct::mix64;
 
 // One (code, count, first) row into the table; true when this call claimed a new slot.
 __device__ __forceinline__ bool table_add(const Table& t, u64 code, u64 count, long long first) {

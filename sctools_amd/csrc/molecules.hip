@@ -1,0 +1,578 @@
+// Counting molecules on the device: distinct (whitelist index, UMI) pairs per barcode (no reference
+// kernel: the reference slices the UMI out of the read, fastq.py:181-200, and never counts with it).
+//
+// sct_molecules: a device *set* of molecule keys, key = (index << umi_bits) | umi (molecules_key.h),
+// whose claim event drives a per-barcode tally.  The table is count.hip's open addressing reduced to
+// the keys: one array of `capacity` (a power of two) uint64 slots, EMPTY = 2^64 - 1.  A key's top
+// bit is always 0 (idx_bits + umi_bits <= 63), so EMPTY is never a key and there is no side slot.
+// A lane claims a slot with one 64-bit atomicCAS(&keys[s], EMPTY, key); a plain load that already
+// shows the key skips the CAS (a key is written once and never changes; a stale load can only show
+// EMPTY, and then the CAS decides).  The probe loop is bounded by the capacity: a full table sets the
+// overflow word and never spins.  The lane whose CAS claimed the slot, and only that lane, adds 1 to
+// molecules[index]; claims are summed per wave into the size word.
+//
+// Per read the insert loads 12 B once (int32 index, uint64 umi).  The answers -1 / -2 and the bad
+// UMIs are counted by wave ballots into registers and added to the tally once per wave; an index
+// outside [-2, nw) sets the error word and is never stored through.  Good reads are pre-aggregated
+// before the global atomics (SCT_TUNE_COUNT_PREAGG, the counter's knob; every form gives the same
+// numbers):
+//   0  none: one probe and one reads[index] add per read;
+//   1  (default) equal keys of a wave merged first (one lane per distinct key carries the count);
+//   2  a per-workgroup LDS table of the tile's keys: every distinct key of the tile costs one global
+//      probe and one reads[index] add that carries the tile's count for that key.
+// DESIGN.md §3.10 has the A/B: 1 and 2 are level when a molecule's reads are adjacent (both twice as
+// fast as 0 there), and 1 is ahead of 2 when they are far apart.
+//
+// The host keeps the load factor bounded by the counter's rule: sub-batches of at most capacity / 4
+// reads, the size word read when the bound of claimed slots passes capacity / 2, growth x4 or x2,
+// 2^31 slots at most.  The rehash kernel re-inserts keys only: molecules, reads and the size word are
+// not touched by it.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+
+#include "mix64.h"
+#include "molecules_key.h"
+#include "sct_common.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int WG = 256;
+constexpr u64 EMPTY = ~0ull;
+constexpr int64_t kMinCapacity = 64;
+constexpr int64_t kMaxCapacity = 1LL << 31;
+// device words of a molecule counter; W_TALLY .. W_TALLY + 2 = no match, ambiguous, bad UMI
+enum { W_SIZE = 0, W_OVERFLOW = 1, W_ERROR = 2, W_CURSOR = 3, W_TALLY = 4, W_NWORDS = 8 };
+// LDS pre-aggregation: a tile of kTile reads in a table of 2 * kTile slots (load <= 1/2)
+constexpr int kItems = 4;
+constexpr int kTile = WG * kItems;
+constexpr int kLdsSlots = 2 * kTile;
+
+struct Set {
+  u64* keys;
+  u64* reads;      // nw
+  u64* molecules;  // nw
+  u64* words;
+  u64 mask;  // capacity - 1
+  int64_t nw;
+  int kind;
+  int umi_bits;
+};
+
+// The key into the table; true when this call claimed a new slot.
+__device__ __forceinline__ bool set_claim(u64* __restrict__ keys, u64 mask, u64* __restrict__ words, u64 key) {
+  u64 s = sct::mix64(key) & mask;
+  for (u64 probe = 0; probe <= mask; ++probe) {
+    u64 k = keys[s];
+    bool claimed = false;
+    if (k == EMPTY) {
+      k = atomicCAS(&keys[s], EMPTY, key);
+      claimed = k == EMPTY;
+      if (claimed) k = key;
+    }
+    if (k == key) return claimed;
+    s = (s + 1) & mask;
+  }
+  atomicOr(&words[W_OVERFLOW], 1ull);  // full table: the host fails with SCT_E_RANGE
+  return false;
+}
+
+// `count` reads of one molecule: reads[index] += count, and molecules[index] += 1 from the lane that
+// claimed the key's slot.  The index comes out of a key built from a checked index: index < nw.
+__device__ __forceinline__ int set_add(const Set& t, u64 key, u64 count) {
+  const uint32_t index = sct::mol_key_index(key, t.umi_bits);
+  atomicAdd(&t.reads[index], count);
+  if (!set_claim(t.keys, t.mask, t.words, key)) return 0;
+  atomicAdd(&t.molecules[index], 1ull);
+  return 1;
+}
+
+// What one read is: rule 1..5 of the contract.  `key` is set for GOOD only.
+enum { R_SKIP = 0, R_NONE, R_TIE, R_BADUMI, R_ERROR, R_GOOD };
+__device__ __forceinline__ int classify(const Set& t, int32_t v, u64 umi, u64* key) {
+  if (v == -1) return R_NONE;
+  if (v == -2) return R_TIE;
+  if (v < 0 || (int64_t)v >= t.nw) return R_ERROR;
+  if (sct::mol_umi_bad(umi, t.kind, t.umi_bits)) return R_BADUMI;
+  *key = sct::mol_key((uint32_t)v, umi, t.umi_bits);
+  return R_GOOD;
+}
+
+// The three popular non-answers of a wave's reads, summed in registers (the same in every lane).
+struct WaveTally {
+  uint32_t n[3] = {0, 0, 0};
+  bool error = false;
+  __device__ __forceinline__ void see(int what) {
+    n[0] += (uint32_t)__popcll(__ballot(what == R_NONE));
+    n[1] += (uint32_t)__popcll(__ballot(what == R_TIE));
+    n[2] += (uint32_t)__popcll(__ballot(what == R_BADUMI));
+    error |= what == R_ERROR;
+  }
+  // one add per wave and non-zero tally, the claimed slots into the size word, the error word
+  __device__ __forceinline__ void flush(const Set& t, int claims) {
+    for (int o = 32; o > 0; o >>= 1) claims += __shfl_xor(claims, o);
+    const bool any_error = __ballot(error) != 0;
+    if ((threadIdx.x & 63) != 0) return;
+    for (int k = 0; k < 3; ++k)
+      if (n[k]) atomicAdd(&t.words[W_TALLY + k], (u64)n[k]);
+    if (claims > 0) atomicAdd(&t.words[W_SIZE], (u64)claims);
+    if (any_error) atomicOr(&t.words[W_ERROR], 1ull);
+  }
+};
+
+// MERGE = false: one probe per read.  MERGE = true: equal keys of a wave are merged first -- the
+// lowest lane holding a key carries the count of its copies, the others add nothing.
+template <bool MERGE>
+__global__ void __launch_bounds__(WG) molecules_insert_kernel(Set t, const int32_t* __restrict__ index,
+                                                              const u64* __restrict__ umi, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * WG;
+  const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
+  const int64_t iters = (n + stride - 1) / stride;  // the same for every lane: the wave stays whole
+  WaveTally wt;
+  int claims = 0;
+  for (int64_t it = 0; it < iters; ++it) {
+    const int64_t i = it * stride + gid;
+    u64 key = 0;
+    int what = R_SKIP;
+    if (i < n) what = classify(t, __builtin_nontemporal_load(&index[i]), __builtin_nontemporal_load(&umi[i]), &key);
+    wt.see(what);
+    const bool good = what == R_GOOD;
+    u64 count = 1;
+    bool rep = good;
+    if (MERGE) {
+      const int lane = threadIdx.x & 63;
+      u64 todo = __ballot(good);
+      while (todo) {  // wave-uniform: one distinct key leaves per pass
+        const int leader = __ffsll((long long)todo) - 1;
+        const u64 lk = __shfl(key, leader);
+        const u64 m = __ballot(good && key == lk);
+        if (lane == leader) count = (u64)__popcll(m);
+        else if (good && key == lk) rep = false;
+        todo &= ~m;
+      }
+    }
+    if (rep) claims += set_add(t, key, count);
+  }
+  wt.flush(t, claims);
+}
+
+// A tile of kTile reads is grouped in an LDS table first (keys, counts), then every occupied LDS slot
+// becomes one global probe and one reads[index] add.  A key that finds no LDS slot within kLdsSlots
+// probes (the table holds twice a tile's reads, so none does) goes to the global path directly.
+__global__ void __launch_bounds__(WG) molecules_insert_lds_kernel(Set t, const int32_t* __restrict__ index,
+                                                                  const u64* __restrict__ umi, int64_t n) {
+  __shared__ u64 lkey[kLdsSlots];
+  __shared__ uint32_t lcnt[kLdsSlots];
+  for (int s = threadIdx.x; s < kLdsSlots; s += WG) {
+    lkey[s] = EMPTY;
+    lcnt[s] = 0;
+  }
+  __syncthreads();
+  const int64_t ntiles = (n + kTile - 1) / kTile;
+  WaveTally wt;
+  int claims = 0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // block-uniform
+    const int64_t t0 = tile * kTile;
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+      const int64_t i = t0 + k * WG + threadIdx.x;
+      u64 key = 0;
+      int what = R_SKIP;
+      if (i < n) what = classify(t, __builtin_nontemporal_load(&index[i]), __builtin_nontemporal_load(&umi[i]), &key);
+      wt.see(what);
+      if (what != R_GOOD) continue;
+      bool placed = false;
+      uint32_t s = (uint32_t)sct::mix64(key) & (kLdsSlots - 1);
+      for (int probe = 0; probe < kLdsSlots; ++probe) {
+        u64 k0 = lkey[s];
+        if (k0 == EMPTY) {
+          k0 = atomicCAS(&lkey[s], EMPTY, key);
+          if (k0 == EMPTY) k0 = key;
+        }
+        if (k0 == key) {
+          atomicAdd(&lcnt[s], 1u);
+          placed = true;
+          break;
+        }
+        s = (s + 1) & (kLdsSlots - 1);
+      }
+      if (!placed) claims += set_add(t, key, 1);
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < kLdsSlots; s += WG) {
+      const u64 key = lkey[s];
+      if (key == EMPTY) continue;
+      claims += set_add(t, key, (u64)lcnt[s]);
+      lkey[s] = EMPTY;
+      lcnt[s] = 0;
+    }
+    __syncthreads();
+  }
+  wt.flush(t, claims);
+}
+
+// every key of the old table into the new one: keys only (molecules, reads and the size word stay)
+__global__ void __launch_bounds__(WG) molecules_rehash_kernel(const u64* __restrict__ from, int64_t from_capacity,
+                                                              u64* __restrict__ to, u64 to_mask,
+                                                              u64* __restrict__ words) {
+  for (int64_t s = (int64_t)blockIdx.x * WG + threadIdx.x; s < from_capacity; s += (int64_t)gridDim.x * WG) {
+    const u64 key = from[s];
+    if (key != EMPTY) (void)set_claim(to, to_mask, words, key);
+  }
+}
+
+// fetch: the occupied slots' keys, in any order (the sort fixes the order); at most `room` are written
+__global__ void __launch_bounds__(WG) molecules_compact_kernel(const u64* __restrict__ keys, int64_t capacity,
+                                                               u64* __restrict__ cursor, int64_t room,
+                                                               u64* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * WG;
+  const int64_t iters = (capacity + stride - 1) / stride;
+  for (int64_t it = 0; it < iters; ++it) {
+    const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
+    const u64 key = s < capacity ? keys[s] : EMPTY;
+    const bool occ = key != EMPTY;
+    const u64 m = __ballot(occ);
+    if (m == 0) continue;
+    u64 at = 0;
+    const int leader = __ffsll((long long)m) - 1;
+    if (lane == leader) at = atomicAdd(cursor, (u64)__popcll(m));
+    at = __shfl(at, leader) + (u64)__popcll(m & ((1ull << lane) - 1ull));
+    if (occ && (int64_t)at < room) out[at] = key;
+  }
+}
+
+__global__ void __launch_bounds__(WG) molecules_split_kernel(const u64* __restrict__ keys, int64_t rows, int umi_bits,
+                                                             int32_t* __restrict__ index, u64* __restrict__ umi) {
+  for (int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WG) {
+    const u64 key = keys[r];
+    index[r] = (int32_t)sct::mol_key_index(key, umi_bits);
+    umi[r] = sct::mol_key_umi(key, umi_bits);
+  }
+}
+
+inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap = 256 * 8) {
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, sct::ceil_div(n, per_block)));
+}
+
+}  // namespace
+
+struct sct_molecules {
+  int device = 0;
+  int64_t capacity = 0;
+  int idx_bits = 0;
+  Set t{};
+  u64* h_words = nullptr;  // page-locked read-back of the device words
+  int64_t total = 0;       // reads fed
+  int64_t size_bound = 0;  // claimed slots: the last size read plus the reads fed since
+  hipEvent_t last = nullptr;  // the last work enqueued (another stream's call waits for it)
+  hipStream_t last_stream = nullptr;
+  bool used = false;
+};
+
+namespace {
+
+int alloc_keys(u64** keys, int64_t capacity, hipStream_t s) {
+  hipError_t e = hipMalloc((void**)keys, (size_t)capacity * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(*keys, 0xFF, (size_t)capacity * 8, s);  // every slot EMPTY
+  if (e != hipSuccess) {
+    if (*keys) (void)hipFree(*keys);
+    *keys = nullptr;
+    return sct::fail(e == hipErrorOutOfMemory ? SCT_E_NOMEM : SCT_E_HIP, "molecule table of %lld slots: %s",
+                     (long long)capacity, hipGetErrorString(e));
+  }
+  return SCT_OK;
+}
+
+// work on `s` starts after whatever the counter enqueued last on another stream
+int enter(sct_molecules* c, hipStream_t s) {
+  if (c->used && c->last_stream != s) SCT_HIP(hipStreamWaitEvent(s, c->last, 0));
+  return SCT_OK;
+}
+
+int leave(sct_molecules* c, hipStream_t s) {
+  SCT_HIP(hipEventRecord(c->last, s));
+  c->last_stream = s;
+  c->used = true;
+  return SCT_OK;
+}
+
+// the device words, read back after everything enqueued on `s`
+int read_words(sct_molecules* c, hipStream_t s) {
+  SCT_HIP(hipMemcpyAsync(c->h_words, c->t.words, W_NWORDS * 8, hipMemcpyDeviceToHost, s));
+  SCT_HIP(hipStreamSynchronize(s));
+  if (c->h_words[W_OVERFLOW])
+    return sct::fail(SCT_E_RANGE, "molecule table of %lld slots is full", (long long)c->capacity);
+  c->size_bound = (int64_t)c->h_words[W_SIZE];
+  return SCT_OK;
+}
+
+int grow(sct_molecules* c, int64_t factor, hipStream_t s) {
+  const int64_t cap = c->capacity * factor;
+  if (cap > kMaxCapacity)
+    return sct::fail(SCT_E_RANGE, "molecule table cannot grow past %lld slots", (long long)kMaxCapacity);
+  u64* nk = nullptr;
+  if (int rc = alloc_keys(&nk, cap, s); rc != SCT_OK) return rc;
+  hipLaunchKernelGGL(molecules_rehash_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
+                     c->capacity, nk, (u64)cap - 1, c->t.words);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // the old array is read until here
+  if (e != hipSuccess) {
+    (void)hipFree(nk);
+    return sct::fail(SCT_E_HIP, "molecule table rehash: %s", hipGetErrorString(e));
+  }
+  (void)hipFree(c->t.keys);
+  c->t.keys = nk;
+  c->t.mask = (u64)cap - 1;
+  c->capacity = cap;
+  return SCT_OK;
+}
+
+int range_error(const sct_molecules* c) {
+  return sct::fail(SCT_E_RANGE, "index outside [-2, %lld) (not counted)", (long long)c->t.nw);
+}
+
+// *range is set when the batch held an index outside [-2, nw) (rule 3; the status stays SCT_OK)
+int update_device(sct_molecules* c, const int32_t* d_index, const uint64_t* d_umi, int64_t n, hipStream_t s,
+                  bool* range) {
+  if (int rc = enter(c, s); rc != SCT_OK) return rc;
+  const int64_t mode = sct::tune(SCT_TUNE_COUNT_PREAGG, 1);
+  int64_t done = 0;
+  while (done < n) {
+    if (c->size_bound > c->capacity / 2) {
+      if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+      if (c->size_bound > c->capacity / 2) {
+        if (int rc = grow(c, n - done > c->capacity / 2 ? 4 : 2, s); rc != SCT_OK) return rc;
+        continue;
+      }
+    }
+    const int64_t m = std::min(n - done, c->capacity / 4);
+    const int32_t* idx = d_index + done;
+    const u64* umi = reinterpret_cast<const u64*>(d_umi) + done;
+    if (mode == 0)
+      hipLaunchKernelGGL(molecules_insert_kernel<false>, dim3(grid_for(m, 4 * WG)), dim3(WG), 0, s, c->t, idx, umi, m);
+    else if (mode == 1)
+      hipLaunchKernelGGL(molecules_insert_kernel<true>, dim3(grid_for(m, 4 * WG)), dim3(WG), 0, s, c->t, idx, umi, m);
+    else
+      hipLaunchKernelGGL(molecules_insert_lds_kernel, dim3(grid_for(m, kTile)), dim3(WG), 0, s, c->t, idx, umi, m);
+    SCT_LAUNCH_CHECK();
+    c->size_bound += m;
+    done += m;
+  }
+  c->total += n;
+  // rule 3: the error word of this call's kernels (the read-back also makes the size exact)
+  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  if (c->h_words[W_ERROR]) {
+    *range = true;
+    SCT_HIP(hipMemsetAsync(&c->t.words[W_ERROR], 0, 8, s));
+  }
+  return leave(c, s);
+}
+
+// the distinct molecules in ascending key order into device arrays with room for `room` rows
+int fetch_device(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, int64_t room, hipStream_t s) {
+  if (int rc = enter(c, s); rc != SCT_OK) return rc;
+  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  const int64_t rows = c->size_bound;
+  SCT_CHECK(room >= rows, "room for %lld molecules, the counter holds %lld", (long long)room, (long long)rows);
+  if (rows == 0) return SCT_OK;
+  SCT_CHECK(d_index && d_umi, "NULL output");
+  const int end_bit = c->idx_bits + c->t.umi_bits;
+  size_t sort_bytes = 0;
+  (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr, (int)rows, 0,
+                                          end_bit, s);
+  const size_t b8 = ((size_t)rows * 8 + 255) & ~(size_t)255;
+  void* blk = nullptr;
+  SCT_HIP(sct::pool_alloc(&blk, 2 * b8 + sort_bytes, s));
+  uint8_t* b = static_cast<uint8_t*>(blk);
+  u64* keys_in = reinterpret_cast<u64*>(b);
+  u64* keys_out = reinterpret_cast<u64*>(b + b8);
+  hipError_t e = hipMemsetAsync(&c->t.words[W_CURSOR], 0, 8, s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(molecules_compact_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
+                       c->capacity, &c->t.words[W_CURSOR], rows, keys_in);
+    e = hipcub::DeviceRadixSort::SortKeys(b + 2 * b8, sort_bytes, keys_in, keys_out, (int)rows, 0, end_bit, s);
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(molecules_split_kernel, dim3(grid_for(rows, 1024)), dim3(WG), 0, s, keys_out, rows,
+                       c->t.umi_bits, d_index, reinterpret_cast<u64*>(d_umi));
+    e = hipGetLastError();
+  }
+  sct::pool_free(blk, s);
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule fetch: %s", hipGetErrorString(e));
+  return leave(c, s);
+}
+
+// reads, molecules and the tally copied out on `s` (each destination nullable)
+int counts_copy(sct_molecules* c, uint64_t* reads, uint64_t* molecules, uint64_t* tally, hipMemcpyKind kind,
+                hipStream_t s) {
+  if (int rc = enter(c, s); rc != SCT_OK) return rc;
+  const size_t nb = (size_t)c->t.nw * 8;
+  if (reads) SCT_HIP(hipMemcpyAsync(reads, c->t.reads, nb, kind, s));
+  if (molecules) SCT_HIP(hipMemcpyAsync(molecules, c->t.molecules, nb, kind, s));
+  if (tally) SCT_HIP(hipMemcpyAsync(tally, &c->t.words[W_TALLY], 3 * 8, kind, s));
+  return leave(c, s);
+}
+
+}  // namespace
+
+extern "C" int sct_molecules_create(int64_t nw, int kind, int L, int64_t capacity_hint, sct_molecules** out) {
+  SCT_CHECK(out != nullptr, "molecule counter is NULL");
+  *out = nullptr;
+  SCT_CHECK(nw >= 1 && nw < (1LL << 31), "nw %lld outside [1, 2^31)", (long long)nw);
+  SCT_CHECK(kind == 2 || kind == 3, "kind must be 2 (TwoBit) or 3 (ThreeBit)");
+  SCT_CHECK(L >= 1, "UMI length L must be >= 1");
+  const int umi_bits = sct::mol_umi_bits(nw, kind, L);
+  SCT_CHECK(umi_bits > 0, "index bits %d + UMI bits %lld do not fit a 63-bit key", sct::mol_idx_bits(nw),
+            (long long)kind * L);
+  SCT_CHECK(capacity_hint >= 0 && capacity_hint <= kMaxCapacity, "capacity hint %lld outside [0, 2^31]",
+            (long long)capacity_hint);
+  int64_t cap = kMinCapacity;
+  while (cap < capacity_hint) cap *= 2;
+  auto* c = new sct_molecules();
+  const auto fail_with = [&](int rc) {
+    sct_molecules_destroy(c);
+    return rc;
+  };
+  hipError_t e = hipGetDevice(&c->device);
+  if (e != hipSuccess) return fail_with(sct::fail(SCT_E_HIP, "molecule counter: %s", hipGetErrorString(e)));
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return fail_with(SCT_E_HIP);
+  c->capacity = cap;
+  c->idx_bits = sct::mol_idx_bits(nw);
+  c->t.nw = nw;
+  c->t.kind = kind;
+  c->t.umi_bits = umi_bits;
+  c->t.mask = (u64)cap - 1;
+  if (int rc = alloc_keys(&c->t.keys, cap, hs->stream); rc != SCT_OK) return fail_with(rc);
+  // reads and molecules are one allocation of 2 * nw words, the tally lives in the device words
+  e = hipMalloc((void**)&c->t.reads, (size_t)nw * 16);
+  if (e == hipSuccess) {
+    c->t.molecules = c->t.reads + nw;
+    e = hipMemsetAsync(c->t.reads, 0, (size_t)nw * 16, hs->stream);
+  }
+  if (e == hipSuccess) e = hipMalloc((void**)&c->t.words, W_NWORDS * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(c->t.words, 0, W_NWORDS * 8, hs->stream);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_words, W_NWORDS * 8, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->last, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipStreamSynchronize(hs->stream);
+  if (e != hipSuccess)
+    return fail_with(sct::fail(e == hipErrorOutOfMemory ? SCT_E_NOMEM : SCT_E_HIP, "molecule counter: %s",
+                               hipGetErrorString(e)));
+  *out = c;
+  return SCT_OK;
+}
+
+extern "C" int sct_molecules_destroy(sct_molecules* c) {
+  if (!c) return SCT_OK;
+  if (c->last) {
+    if (c->used) (void)hipEventSynchronize(c->last);  // the work it enqueued reads these arrays
+    (void)hipEventDestroy(c->last);
+  }
+  if (c->t.keys) (void)hipFree(c->t.keys);
+  if (c->t.reads) (void)hipFree(c->t.reads);
+  if (c->t.words) (void)hipFree(c->t.words);
+  if (c->h_words) (void)hipHostFree(c->h_words);
+  delete c;
+  return SCT_OK;
+}
+
+extern "C" int sct_molecules_update(sct_molecules* c, const int32_t* d_index, const uint64_t* d_umi, int64_t n,
+                                    void* stream) {
+  SCT_CHECK(n >= 0, "n must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (n == 0) return SCT_OK;
+  SCT_CHECK(d_index != nullptr && d_umi != nullptr, "NULL index or umi");
+  bool range = false;
+  const int rc = update_device(c, d_index, d_umi, n, sct::as_stream(stream), &range);
+  return rc == SCT_OK && range ? range_error(c) : rc;
+}
+
+extern "C" int sct_molecules_update_host(sct_molecules* c, const int32_t* index, const uint64_t* umi, int64_t n) {
+  SCT_CHECK(n >= 0, "n must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (n == 0) return SCT_OK;
+  SCT_CHECK(index != nullptr && umi != nullptr, "NULL index or umi");
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return SCT_E_HIP;
+  hipStream_t s = hs->stream;
+  // pieces through one pool buffer (umis, then indices): a piece's copies are ordered after the
+  // previous piece's kernels.  An out-of-range index in one piece does not stop the others.
+  const int64_t piece = std::min<int64_t>(n, 1LL << 24);
+  sct::PoolBlock buf(s);
+  if (int rc = buf.alloc((size_t)piece * 12); rc != SCT_OK) return rc;
+  uint64_t* d_umi = static_cast<uint64_t*>(buf.p);
+  int32_t* d_index = reinterpret_cast<int32_t*>(d_umi + piece);
+  int rc = SCT_OK;
+  bool range = false;
+  for (int64_t b = 0; b < n && rc == SCT_OK && buf.ok(); b += piece) {
+    const int64_t m = std::min(piece, n - b);
+    buf.note(hipMemcpyAsync(d_umi, umi + b, (size_t)m * 8, hipMemcpyHostToDevice, s));
+    if (buf.ok()) buf.note(hipMemcpyAsync(d_index, index + b, (size_t)m * 4, hipMemcpyHostToDevice, s));
+    if (buf.ok()) rc = update_device(c, d_index, d_umi, m, s, &range);
+  }
+  rc = buf.finish(rc, "molecule update");  // no caller pointer is kept past the return
+  return rc == SCT_OK && range ? range_error(c) : rc;
+}
+
+extern "C" int sct_molecules_info(sct_molecules* c, int64_t* nmolecules, int64_t* total, int64_t* capacity) {
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (nmolecules) {
+    sct::HostStage* hs = sct::host_stage();
+    if (!hs) return SCT_E_HIP;
+    if (int rc = enter(c, hs->stream); rc != SCT_OK) return rc;
+    if (int rc = read_words(c, hs->stream); rc != SCT_OK) return rc;
+    *nmolecules = c->size_bound;
+  }
+  if (total) *total = c->total;
+  if (capacity) *capacity = c->capacity;
+  return SCT_OK;
+}
+
+extern "C" int sct_molecules_counts(sct_molecules* c, uint64_t* d_reads, uint64_t* d_molecules, uint64_t* d_tally,
+                                    void* stream) {
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  return counts_copy(c, d_reads, d_molecules, d_tally, hipMemcpyDeviceToDevice, sct::as_stream(stream));
+}
+
+extern "C" int sct_molecules_counts_host(sct_molecules* c, uint64_t* reads, uint64_t* molecules, uint64_t* tally) {
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return SCT_E_HIP;
+  const int rc = counts_copy(c, reads, molecules, tally, hipMemcpyDeviceToHost, hs->stream);
+  const hipError_t e = hipStreamSynchronize(hs->stream);  // the caller's arrays are written until here
+  if (rc == SCT_OK && e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule counts: %s", hipGetErrorString(e));
+  return rc;
+}
+
+extern "C" int sct_molecules_fetch(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, int64_t room, void* stream) {
+  SCT_CHECK(room >= 0, "room must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  return fetch_device(c, d_index, d_umi, room, sct::as_stream(stream));
+}
+
+extern "C" int sct_molecules_fetch_host(sct_molecules* c, int32_t* index, uint64_t* umi, int64_t room) {
+  SCT_CHECK(room >= 0, "room must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_CHECK(room == 0 || (index && umi), "NULL output");
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return SCT_E_HIP;
+  hipStream_t s = hs->stream;
+  if (int rc = enter(c, s); rc != SCT_OK) return rc;
+  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  const int64_t rows = c->size_bound;
+  SCT_CHECK(room >= rows, "room for %lld molecules, the counter holds %lld", (long long)room, (long long)rows);
+  if (rows == 0) return SCT_OK;
+  const size_t b8 = ((size_t)rows * 8 + 255) & ~(size_t)255;
+  sct::PoolBlock blk(s);
+  if (int rc = blk.alloc(b8 + (size_t)rows * 4); rc != SCT_OK) return rc;
+  uint8_t* b = blk.bytes();
+  const int rc = fetch_device(c, (int32_t*)(b + b8), (uint64_t*)b, rows, s);
+  if (rc == SCT_OK) {
+    blk.note(hipMemcpyAsync(umi, b, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok()) blk.note(hipMemcpyAsync(index, b + b8, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+  }
+  return blk.finish(rc, "molecule fetch");
+}

@@ -8,12 +8,15 @@ interleaved rounds in one process): DeviceCounter.update_device time, the table'
 and the fraction of 8 TB/s the 8 B/code read reaches; the host-resident update; and the yardsticks
 Counter(codes.tolist()) and np.unique(codes, return_index=True, return_counts=True), whose reduced
 n is stated.  Then WhitelistCorrector.count against .nearest() + np.bincount on one batch, with
-the bytes each moves over PCIe.
+the bytes each moves over PCIe.  Then MoleculeCounter.update_device on 100M (index, UMI) reads
+against DeviceCounter on composite keys plus sct_index_tally, with a molecule's reads far apart and
+adjacent (molecules_step; its rounds also go to profiles/ab_molecules_<tag>.jsonl).
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends
 the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
 
   python tools/bench_count.py --tag mi355x
+  python tools/bench_count.py --tag mi355x --only molecules
 """
 import argparse
 import json
@@ -25,7 +28,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300}  # seconds
+STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420}  # seconds
 MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
 HBM_BYTES_PER_S = 8e12
 
@@ -144,6 +147,122 @@ def tally_step(args):
             "pcie_bytes_count": {"in": nq * 8, "out": (int(wl3.size) + 3) * 8}}
 
 
+def molecules_step(args):
+    """MoleculeCounter.update_device, device-resident, against what the library could do before it
+    with the same data: DeviceCounter.update_device on precomputed composite keys (8 B/read, 24 B
+    slots) plus sct_index_tally on the indices (4 B/read).  Input: config 4's queries against the
+    737,280 whitelist answered by the nearest plan (so -1 / -2 are in), and 10-base ThreeBit UMIs
+    drawn per barcode from a pool sized for a mean of about four reads per molecule, 1 % with an N.
+    Tables are sized up front (the growth is counter_A's subject); both sides alternate within every
+    round, per pre-aggregation mode.  Every round is one line of profiles/ab_molecules_<tag>.jsonl."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, counting, synthetic
+
+    nw, L, seed = synthetic.CONFIGS[4]
+    UL, n = 10, args.n_a
+    wl3 = synthetic.two_to_three(synthetic.whitelist_codes(nw, L, seed), L)
+    dev = torch.device("cuda")
+    q, _, _ = synthetic.config4_queries(wl3, n, seed=4, device=dev)
+    d_wl = torch.from_numpy(wl3.view(np.int64)).cuda()
+    d_index = torch.empty(n, dtype=torch.int32, device=dev)
+    d_dist = torch.empty(n, dtype=torch.uint8, device=dev)
+    plan = _lib.NearestPlan(3, d_wl.data_ptr(), nw, 3 * L, 1)
+    plan.query(q.data_ptr(), n, d_index.data_ptr(), d_dist.data_ptr())
+    torch.cuda.synchronize()
+    plan.close()
+    del q, d_dist
+    g = torch.Generator(device=dev).manual_seed(7)
+    # reads per barcode r = (matched reads) / nw; a pool of r / 4 UMIs per barcode gives ~4 reads per molecule
+    matched = int((d_index >= 0).sum())
+    pool = max(1, round(matched / nw / 4))
+    table = torch.zeros(4096, dtype=torch.int64, device=dev)  # 4096 distinct good UMI codes
+    t = torch.randperm(4 ** UL, device=dev, generator=g)[:4096]
+    for p in range(UL):
+        table |= (((t >> (2 * p)) & 3) + 1) << (3 * p)
+    pick = (torch.randint(0, pool, (n,), device=dev, generator=g) + d_index.to(torch.int64) * 31) % 4096
+    d_umi = table[pick]
+    with_n = torch.rand(n, device=dev, generator=g) < 0.01
+    d_umi = torch.where(with_n, d_umi | 6, d_umi)
+    d_keys = (d_index.to(torch.int64) << (3 * UL)) | d_umi  # the yardstick's composite keys
+    del pick, with_n, t
+    torch.cuda.synchronize()
+    lib = _lib.lib()
+    vp = ctypes.c_void_p
+    hint = 1 << max(6, (n // 2).bit_length())  # at most n / 4 molecules expected: load stays below 1/2
+    out = {"n": n, "nw": nw, "umi_length": UL, "umi_pool_per_barcode": pool, "capacity_hint": hint, "inputs": {}}
+    # the same reads in two orders: as drawn (a molecule's reads far apart), and with every molecule's
+    # reads adjacent (molecules in hash order) -- the two ends of how close PCR duplicates can lie
+    # (an odd multiplier permutes the int64 keys: equal keys stay together, their order is scrambled)
+    order = torch.argsort(d_keys * -7046029254386353131)
+    inputs = {"shuffled": (d_index, d_umi, d_keys),
+              "adjacent": (d_index[order].contiguous(), d_umi[order].contiguous(), d_keys[order].contiguous())}
+    del order
+    torch.cuda.synchronize()
+
+    def run_molecules(mode, d_index, d_umi):
+        with _lib.tuning(count_preagg=mode), counting.MoleculeCounter(nw, UL, capacity_hint=hint) as mc:
+            def go():
+                mc.update_device(d_index.data_ptr(), d_umi.data_ptr(), n)
+                torch.cuda.synchronize()
+            ms = _time_ms(go)
+            reads, molecules, n_none, n_amb, n_bad = mc.counts()
+            info = mc.info()
+        return ms, (int(reads.sum()), int(molecules.sum()), n_none, n_amb, n_bad, info["nmolecules"], info["capacity"])
+
+    def run_yardstick(mode, d_index, d_keys):
+        d_counts = torch.zeros(nw, dtype=torch.int64, device=dev)
+        d_tally = torch.zeros(2, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        with _lib.tuning(count_preagg=mode), counting.DeviceCounter(capacity_hint=hint) as dc:
+            def go():
+                dc.update_device(d_keys.data_ptr(), n)
+                _lib.check(lib.sct_index_tally(vp(d_index.data_ptr()), n, nw, vp(d_counts.data_ptr()),
+                                               vp(d_tally.data_ptr()), None))
+                torch.cuda.synchronize()
+            ms = _time_ms(go)
+            nunique = len(dc)
+        return ms, nunique
+
+    run_molecules(2, d_index, d_umi), run_yardstick(1, d_index, d_keys)  # warm-up: code objects, pool
+    facts = None
+    lines = []
+    for which, (di, du, dk) in inputs.items():
+        rounds = []
+        for r in range(args.rounds):
+            row = {"input": which, "round": r, "n": n, "nw": nw}
+            for m, name in MODES.items():
+                ms, f = run_molecules(m, di, du)
+                assert facts is None or f == facts, (f, facts)  # every mode, order and round: the same numbers
+                facts = f
+                yms, nunique = run_yardstick(m, di, dk)
+                row[name] = {"molecules_ms": round(ms, 3), "counter_plus_tally_ms": round(yms, 3)}
+            rounds.append(row)
+        lines += rounds
+        res = out["inputs"][which] = {}
+        for name in MODES.values():
+            a = [row[name]["molecules_ms"] for row in rounds]
+            b = [row[name]["counter_plus_tally_ms"] for row in rounds]
+            med = float(np.median(a))
+            res[name] = {
+                "molecules_ms": {"median": round(med, 3), "min": min(a), "max": max(a)},
+                "counter_plus_tally_ms": {"median": round(float(np.median(b)), 3), "min": min(b), "max": max(b)},
+                "bytes_per_read_algorithmic": 12,
+                "read_fraction_of_8TBps": round(n * 12 / (med * 1e-3) / HBM_BYTES_PER_S, 4)}
+    reads, molecules, n_none, n_amb, n_bad, nmol, cap = facts
+    assert reads + n_none + n_amb + n_bad == n and molecules == nmol
+    out.update(reads=reads, molecules=molecules, n_none=n_none, n_ambiguous=n_amb, n_bad_umi=n_bad, capacity=cap,
+               reads_per_molecule=round(reads / max(1, molecules), 3), yardstick_nunique=nunique)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "ab_molecules_%s.jsonl" % args.tag), "w") as f:
+        for row in lines:
+            f.write(json.dumps(row, sort_keys=True) + "\n")
+        f.write(json.dumps(out, sort_keys=True) + "\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tag", default="run")
@@ -153,15 +272,22 @@ def main():
     ap.add_argument("--n-unique", type=int, default=20_000_000, help="codes given to np.unique")
     ap.add_argument("--n-tally", type=int, default=20_000_000, help="queries of the WhitelistCorrector batch")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--only", nargs="+", choices=sorted(STEPS), help="launch only these steps")
     args = ap.parse_args()
     if args.step:
-        res = tally_step(args) if args.step == "tally" else counter_step(args.step[-1], args)
+        if args.step == "molecules":
+            res = molecules_step(args)
+        else:
+            res = tally_step(args) if args.step == "tally" else counter_step(args.step[-1], args)
         print("RESULT " + json.dumps(res))
         return 0
     detail = {"tag": args.tag, "argv": sys.argv[1:], "steps": {}}
     rc = 0
     for step, limit in STEPS.items():
+        if args.only and step not in args.only:
+            continue
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step,
+               "--tag", args.tag,
                "--n-a", str(args.n_a), "--n-counter", str(args.n_counter), "--n-unique", str(args.n_unique),
                "--n-tally", str(args.n_tally), "--rounds", str(args.rounds)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
@@ -178,7 +304,11 @@ def main():
         f.write("\n")
     short = {"tag": args.tag, "ok": rc == 0, "detail": os.path.relpath(path, ROOT)}
     for step, res in detail["steps"].items():
-        if "modes" in res:
+        if "reads_per_molecule" in res:
+            short[step] = {"n": res["n"], "molecules": res["molecules"], "reads_per_molecule": res["reads_per_molecule"],
+                           "ms": {which: {k: [v["molecules_ms"]["median"], v["counter_plus_tally_ms"]["median"]]
+                                          for k, v in modes.items()} for which, modes in res["inputs"].items()}}
+        elif "modes" in res:
             short[step] = {"n": res["n"], "nunique": res["nunique"],
                            "ms": {k: v["median_ms"] for k, v in res["modes"].items()},
                            "host_ms": res["update_host_ms"]}
