@@ -63,7 +63,9 @@ int sct_set_device(int device);        /* select the device for later calls (hip
 #define SCT_TUNE_COUNT_PREAGG 17        /* counter insert: 0 one table row per code, 1 equal codes of a wave merged
                                            first (default), 2 a per-workgroup LDS table per tile; the molecule
                                            counter's insert has the same three forms and default */
-#define SCT_TUNE_NKEYS 18
+#define SCT_TUNE_COLLAPSE_FORM 18       /* UMI collapse: 0 one lane per table slot probes the molecule's 3 * L
+                                           neighbours, 1 a wave shares one molecule's neighbours (default) */
+#define SCT_TUNE_NKEYS 19
 int sct_tune_set(int key, int64_t value);
 int sct_tune_get(int key, int64_t* value);  /* -1 when unset */
 
@@ -577,6 +579,45 @@ int sct_molecules_counts(sct_molecules* mol, uint64_t* d_reads, uint64_t* d_mole
 int sct_molecules_fetch_host(sct_molecules* mol, int32_t* index, uint64_t* umi, int64_t room);
 int sct_molecules_fetch(sct_molecules* mol, int32_t* d_index, uint64_t* d_umi, int64_t room, void* stream);
 int sct_molecules_destroy(sct_molecules* mol);
+
+/* Collapsing UMIs one base apart: a sequencing error in a UMI base makes one molecule look like two,
+ * so a UMI one base away from a better-supported UMI of the same barcode is merged into it before
+ * molecules are counted.  The contract is restated in plain Python by tests/umi_collapse_reference.py.
+ * A *counted* molecule counter (sct_molecules_create_counted; the same checks as create) is a
+ * molecule counter that also keeps mreads[key] for every stored key: the number of rule-5 reads of
+ * that molecule over the counter's lifetime, uint64 and exact, in a second array of 8 B per slot
+ * beside the keys.  Everything above (rules 1-5, tally, growth, streams, info, counts, fetch) holds
+ * for it unchanged; a counter made by sct_molecules_create keeps no such array and runs the code it
+ * ran before there were counted ones.
+ * Neighbours: N1(umi) is the 3 * L codes that differ from umi in exactly one base position and carry
+ * another of the four bases there: for kind 2 a digit d becomes one of the three other values of
+ * 0..3, for kind 3 a triplet t of {1, 2, 3, 4} becomes one of the three other values of {1, 2, 3, 4}
+ * (N and the invalid triplets are never neighbours).  Index bits never change: the same UMI under
+ * two barcodes is unrelated.
+ * Parent (one step, evaluated for every molecule against the uncorrected counts): parent(i, u) is
+ * the UMI v that maximises the pair (mreads[(i, v)], v), where (a, x) > (b, y) means a > b, or
+ * a == b and x > y (the order of the codes, not of the ASCII text), over u itself and the members of
+ * N1(u) stored under index i.  A molecule is a root when parent == u.  The rule is not transitive
+ * and no read moves twice.
+ * collapse describes the state at the call; its results are written, not accumulated:
+ *   collapsed[i]  the number of distinct values of parent(i, u) over the molecules (i, u) of barcode
+ *                 i -- the images, not the roots.  ThreeBit L = 2 under one barcode, AA x 1, AC x 2,
+ *                 GC x 5: parent(AA) = AC, parent(AC) = GC, GC is a root; molecules = 3,
+ *                 collapsed = 2 (AC and GC both receive reads), n_corrected = 2, and there is 1 root;
+ *   n_corrected   the number of molecules with parent != u (nullable).
+ * Reads per barcode do not change (correction never crosses a barcode).  collapse reads the table and
+ * mreads only: calling it twice gives the same answer, and later updates are unaffected by it.
+ * fetch_counted: exactly fetch's rows in fetch's order, with each row's mreads and, if d_parent is
+ * not NULL, its parent's UMI beside them; the room rule is fetch's.  collapse and fetch_counted on a
+ * counter that is not counted are SCT_E_INVALID and change nothing.  Both order themselves after
+ * the counter's earlier work on other streams, as every call does. */
+int sct_molecules_create_counted(int64_t nw, int kind, int L, int64_t capacity_hint, sct_molecules** mol);
+int sct_molecules_collapse(sct_molecules* mol, uint64_t* d_collapsed, uint64_t* d_ncorrected, void* stream);
+int sct_molecules_collapse_host(sct_molecules* mol, uint64_t* collapsed, uint64_t* ncorrected);
+int sct_molecules_fetch_counted(sct_molecules* mol, int32_t* d_index, uint64_t* d_umi, uint64_t* d_mreads,
+                                uint64_t* d_parent, int64_t room, void* stream);
+int sct_molecules_fetch_counted_host(sct_molecules* mol, int32_t* index, uint64_t* umi, uint64_t* mreads,
+                                     uint64_t* parent, int64_t room);
 
 /* ---------------------------------------------------------------- FASTQ barcode extraction
  * Replaces the per-record path reader.Reader.__iter__ (src/sctools/reader.py:56-85) ->

@@ -140,9 +140,14 @@ class MoleculeCounter:
     ('ThreeBit' or 'TwoBit'); the index bits and the UMI bits must fit a 63-bit key.  Feed it the
     ``index`` of ``WhitelistCorrector.correct`` / ``nearest`` and the encoded UMIs of the same
     reads.  ``capacity_hint`` sizes the first table; it grows by itself.  Use as a context manager
-    or ``close()`` it to free the device arrays."""
+    or ``close()`` it to free the device arrays.
 
-    def __init__(self, whitelist_size, umi_length, encoding='ThreeBit', capacity_hint=1 << 20):
+    ``read_counts=True`` also keeps the reads of every molecule (8 more bytes per table slot), which
+    ``collapse()``, ``pairs(reads=True)`` and ``saturation(collapsed=True)`` need: they merge a UMI
+    into the best-supported UMI one base away under the same barcode (include/sctools_hip.h,
+    "collapsing UMIs one base apart")."""
+
+    def __init__(self, whitelist_size, umi_length, encoding='ThreeBit', capacity_hint=1 << 20, read_counts=False):
         kinds = {'ThreeBit': 3, 'TwoBit': 2, 3: 3, 2: 2}
         if encoding not in kinds:
             raise ValueError("encoding must be 'ThreeBit' or 'TwoBit'")
@@ -159,7 +164,13 @@ class MoleculeCounter:
         self.size, self.umi_length, self.kind = nw, L, kind
         self._lib = _lib.lib()
         self._h = _vp()
-        _lib.check(self._lib.sct_molecules_create(nw, kind, L, int(capacity_hint), ctypes.byref(self._h)))
+        self.read_counts = bool(read_counts)
+        create = self._lib.sct_molecules_create_counted if self.read_counts else self._lib.sct_molecules_create
+        _lib.check(create(nw, kind, L, int(capacity_hint), ctypes.byref(self._h)))
+
+    def _need_read_counts(self, what):
+        if not self.read_counts:
+            raise ValueError("%s needs MoleculeCounter(..., read_counts=True)" % what)
 
     def update(self, index, umis):
         """Count a host batch: ``index`` int32 (-1 no match, -2 ambiguous, else a whitelist index)
@@ -189,19 +200,55 @@ class MoleculeCounter:
         _lib.check(self._lib.sct_molecules_counts_host(self._h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)))
         return (reads.view(np.int64), molecules.view(np.int64), int(tally[0]), int(tally[1]), int(tally[2]))
 
-    def pairs(self, room=None):
+    def pairs(self, room=None, reads=False, parents=False):
         """(index int32, umi uint64) of the distinct molecules, ascending by index, then by UMI code.
-        ``room`` (default: the number of molecules) sizes the output; too little raises ValueError."""
+        ``room`` (default: the number of molecules) sizes the output; too little raises ValueError.
+        ``reads=True`` (a counter with ``read_counts``) adds each molecule's reads (int64), and
+        ``parents=True`` with it the UMI each molecule collapses into (its own if it stays)."""
+        if parents and not reads:
+            raise ValueError("parents=True needs reads=True")
+        if reads:
+            self._need_read_counts("pairs(reads=True)")
         got = len(self)
         n = got if room is None else int(room)
         index = np.empty(n, np.int32)
         umi = np.empty(n, np.uint64)
-        _lib.check(self._lib.sct_molecules_fetch_host(self._h, _lib._ptr(index), _lib._ptr(umi), n))
-        return index[:got], umi[:got]
+        if not reads:
+            _lib.check(self._lib.sct_molecules_fetch_host(self._h, _lib._ptr(index), _lib._ptr(umi), n))
+            return index[:got], umi[:got]
+        mreads = np.empty(n, np.uint64)
+        parent = np.empty(n, np.uint64) if parents else None
+        _lib.check(self._lib.sct_molecules_fetch_counted_host(self._h, _lib._ptr(index), _lib._ptr(umi),
+                                                              _lib._ptr(mreads), _lib._ptr(parent), n))
+        out = (index[:got], umi[:got], mreads[:got].view(np.int64))
+        return out + (parent[:got],) if parents else out
 
     def fetch_device(self, index_ptr, umi_ptr, room, stream=0):
         """The same rows into device arrays with room for ``room`` rows (sct_molecules_fetch)."""
         _lib.check(self._lib.sct_molecules_fetch(self._h, _vp(index_ptr), _vp(umi_ptr), int(room), _vp(stream)))
+
+    def fetch_counted_device(self, index_ptr, umi_ptr, reads_ptr, parent_ptr, room, stream=0):
+        """fetch_device's rows with uint64 reads and, unless ``parent_ptr`` is 0 / None, uint64 parent
+        UMIs beside them (sct_molecules_fetch_counted)."""
+        self._need_read_counts("fetch_counted_device")
+        _lib.check(self._lib.sct_molecules_fetch_counted(self._h, _vp(index_ptr), _vp(umi_ptr), _vp(reads_ptr),
+                                                         _vp(parent_ptr or None), int(room), _vp(stream)))
+
+    def collapse(self):
+        """(collapsed np.int64[whitelist_size], n_corrected int): the molecules per barcode after every
+        UMI went to the best-supported UMI one base away (ties to the larger code), and how many moved."""
+        self._need_read_counts("collapse")
+        collapsed = np.empty(self.size, np.uint64)
+        ncorr = np.zeros(1, np.uint64)
+        _lib.check(self._lib.sct_molecules_collapse_host(self._h, _lib._ptr(collapsed), _lib._ptr(ncorr)))
+        return collapsed.view(np.int64), int(ncorr[0])
+
+    def collapse_device(self, collapsed_ptr, ncorrected_ptr=None, stream=0):
+        """collapse() into device memory: uint64[whitelist_size] and, unless 0 / None, one uint64
+        (sct_molecules_collapse), on ``stream``."""
+        self._need_read_counts("collapse_device")
+        _lib.check(self._lib.sct_molecules_collapse(self._h, _vp(collapsed_ptr), _vp(ncorrected_ptr or None),
+                                                    _vp(stream)))
 
     def info(self):
         """dict(nmolecules, total, capacity)."""
@@ -212,9 +259,12 @@ class MoleculeCounter:
     def __len__(self):
         return self.info()["nmolecules"]
 
-    def saturation(self):
-        """Sequencing saturation 1 - molecules / reads over the counted reads (nan when none)."""
+    def saturation(self, collapsed=False):
+        """Sequencing saturation 1 - molecules / reads over the counted reads (nan when none);
+        ``collapsed=True`` takes the molecules of ``collapse()``."""
         reads, molecules = self.counts()[:2]
+        if collapsed:
+            molecules = self.collapse()[0]
         total = int(reads.sum())
         return 1.0 - int(molecules.sum()) / total if total else float("nan")
 

@@ -27,6 +27,22 @@
 // reads, the size word read when the bound of claimed slots passes capacity / 2, growth x4 or x2,
 // 2^31 slots at most.  The rehash kernel re-inserts keys only: molecules, reads and the size word are
 // not touched by it.
+//
+// A *counted* counter (sct_molecules_create_counted) keeps a second array cnt[capacity] of uint64
+// beside the keys: the reads of every molecule.  COUNTED is a template parameter of the insert
+// kernels, so a plain counter runs the instantiations without it: the claim returns the slot, and
+// the lane that carries a key's pre-aggregated count adds it to cnt[slot] as it adds it to
+// reads[index].  cnt is zero wherever keys is EMPTY, so the add needs no ordering against the claim.
+// The counted rehash moves each count with its key by a plain store (a key is unique in the old
+// table).  On such a table the UMI collapse (include/sctools_hip.h, "collapsing UMIs one base
+// apart") is one read-only pass: per molecule the 3 * L neighbour keys (umi_neighbours.h) are probed
+// with the insert's hash and bounded linear probe, the best (mreads, code) among the molecule and
+// its stored neighbours is its parent, and the parent's *slot* is claimed in a scratch bitmap of one
+// bit per slot -- the lane whose atomicOr flips the bit adds 1 to collapsed[index], which is the
+// molecules[index] idiom again and counts every distinct parent once however many children it has.
+// Every shared write of the pass is an atomic and nothing it reads changes, so there is no
+// inter-workgroup protocol.  fetch_counted sorts (key, slot) pairs and recomputes each row's parent
+// with the same device function.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -34,6 +50,7 @@
 #include "mix64.h"
 #include "molecules_key.h"
 #include "sct_common.h"
+#include "umi_neighbours.h"
 
 namespace {
 
@@ -52,6 +69,7 @@ constexpr int kLdsSlots = 2 * kTile;
 
 struct Set {
   u64* keys;
+  u64* cnt;        // mreads per slot, counted counters only (else NULL and never touched)
   u64* reads;      // nw
   u64* molecules;  // nw
   u64* words;
@@ -61,8 +79,12 @@ struct Set {
   int umi_bits;
 };
 
-// The key into the table; true when this call claimed a new slot.
-__device__ __forceinline__ bool set_claim(u64* __restrict__ keys, u64 mask, u64* __restrict__ words, u64 key) {
+// The key into the table; true when this call claimed a new slot.  SLOT: *slot is the key's slot,
+// or NO_SLOT when the table is full.
+constexpr u64 NO_SLOT = ~0ull;
+template <bool SLOT = false>
+__device__ __forceinline__ bool set_claim(u64* __restrict__ keys, u64 mask, u64* __restrict__ words, u64 key,
+                                          u64* slot = nullptr) {
   u64 s = sct::mix64(key) & mask;
   for (u64 probe = 0; probe <= mask; ++probe) {
     u64 k = keys[s];
@@ -72,19 +94,34 @@ __device__ __forceinline__ bool set_claim(u64* __restrict__ keys, u64 mask, u64*
       claimed = k == EMPTY;
       if (claimed) k = key;
     }
-    if (k == key) return claimed;
+    if (k == key) {
+      if (SLOT) *slot = s;
+      return claimed;
+    }
     s = (s + 1) & mask;
   }
   atomicOr(&words[W_OVERFLOW], 1ull);  // full table: the host fails with SCT_E_RANGE
+  if (SLOT) *slot = NO_SLOT;
   return false;
 }
 
 // `count` reads of one molecule: reads[index] += count, and molecules[index] += 1 from the lane that
 // claimed the key's slot.  The index comes out of a key built from a checked index: index < nw.
+// COUNTED: the carrier of the key also adds its count to the slot's mreads (cnt is zero at every
+// empty slot, so it does not matter whether the claiming lane or another one adds first).
+template <bool COUNTED>
 __device__ __forceinline__ int set_add(const Set& t, u64 key, u64 count) {
   const uint32_t index = sct::mol_key_index(key, t.umi_bits);
   atomicAdd(&t.reads[index], count);
-  if (!set_claim(t.keys, t.mask, t.words, key)) return 0;
+  bool claimed;
+  if (COUNTED) {
+    u64 slot;
+    claimed = set_claim<true>(t.keys, t.mask, t.words, key, &slot);
+    if (slot != NO_SLOT) atomicAdd(&t.cnt[slot], count);
+  } else {
+    claimed = set_claim(t.keys, t.mask, t.words, key);
+  }
+  if (!claimed) return 0;
   atomicAdd(&t.molecules[index], 1ull);
   return 1;
 }
@@ -124,7 +161,7 @@ struct WaveTally {
 
 // MERGE = false: one probe per read.  MERGE = true: equal keys of a wave are merged first -- the
 // lowest lane holding a key carries the count of its copies, the others add nothing.
-template <bool MERGE>
+template <bool MERGE, bool COUNTED>
 __global__ void __launch_bounds__(WG) molecules_insert_kernel(Set t, const int32_t* __restrict__ index,
                                                               const u64* __restrict__ umi, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * WG;
@@ -153,7 +190,7 @@ __global__ void __launch_bounds__(WG) molecules_insert_kernel(Set t, const int32
         todo &= ~m;
       }
     }
-    if (rep) claims += set_add(t, key, count);
+    if (rep) claims += set_add<COUNTED>(t, key, count);
   }
   wt.flush(t, claims);
 }
@@ -161,6 +198,7 @@ __global__ void __launch_bounds__(WG) molecules_insert_kernel(Set t, const int32
 // A tile of kTile reads is grouped in an LDS table first (keys, counts), then every occupied LDS slot
 // becomes one global probe and one reads[index] add.  A key that finds no LDS slot within kLdsSlots
 // probes (the table holds twice a tile's reads, so none does) goes to the global path directly.
+template <bool COUNTED>
 __global__ void __launch_bounds__(WG) molecules_insert_lds_kernel(Set t, const int32_t* __restrict__ index,
                                                                   const u64* __restrict__ umi, int64_t n) {
   __shared__ u64 lkey[kLdsSlots];
@@ -198,13 +236,13 @@ __global__ void __launch_bounds__(WG) molecules_insert_lds_kernel(Set t, const i
         }
         s = (s + 1) & (kLdsSlots - 1);
       }
-      if (!placed) claims += set_add(t, key, 1);
+      if (!placed) claims += set_add<COUNTED>(t, key, 1);
     }
     __syncthreads();
     for (int s = threadIdx.x; s < kLdsSlots; s += WG) {
       const u64 key = lkey[s];
       if (key == EMPTY) continue;
-      claims += set_add(t, key, (u64)lcnt[s]);
+      claims += set_add<COUNTED>(t, key, (u64)lcnt[s]);
       lkey[s] = EMPTY;
       lcnt[s] = 0;
     }
@@ -221,6 +259,124 @@ __global__ void __launch_bounds__(WG) molecules_rehash_kernel(const u64* __restr
     const u64 key = from[s];
     if (key != EMPTY) (void)set_claim(to, to_mask, words, key);
   }
+}
+
+// the counted table's rehash: the count moves with its key.  A key is unique in the old table, so
+// exactly one lane meets it and that lane's plain store is the only write to the new slot's count.
+__global__ void __launch_bounds__(WG) molecules_rehash_counted_kernel(const u64* __restrict__ from,
+                                                                      const u64* __restrict__ from_cnt,
+                                                                      int64_t from_capacity, u64* __restrict__ to,
+                                                                      u64* __restrict__ to_cnt, u64 to_mask,
+                                                                      u64* __restrict__ words) {
+  for (int64_t s = (int64_t)blockIdx.x * WG + threadIdx.x; s < from_capacity; s += (int64_t)gridDim.x * WG) {
+    const u64 key = from[s];
+    if (key == EMPTY) continue;
+    u64 slot;
+    (void)set_claim<true>(to, to_mask, words, key, &slot);
+    if (slot != NO_SLOT) to_cnt[slot] = from_cnt[s];
+  }
+}
+
+// ---- UMI collapse (the contract's "parent" rule; one implementation for collapse and fetch_counted)
+
+// the slot that holds `key`, or NO_SLOT: a read-only probe, bounded by the capacity
+__device__ __forceinline__ u64 set_find(const u64* __restrict__ keys, u64 mask, u64 key) {
+  u64 s = sct::mix64(key) & mask;
+  for (u64 probe = 0; probe <= mask; ++probe) {
+    const u64 k = keys[s];
+    if (k == key) return s;
+    if (k == EMPTY) return NO_SLOT;
+    s = (s + 1) & mask;
+  }
+  return NO_SLOT;
+}
+
+// The parent rule over the candidates j0, j0 + step, ... of the molecule `key` held in `slot`: the
+// stored key that maximises (mreads, code) over the key itself and those of its 3 * L one-base
+// neighbours under the same index.  (0, 1) is the whole rule in one lane; (lane, 64) is a wave's
+// share of it, to be reduced by the same order.
+struct Best {
+  u64 code, reads, slot;
+};
+__device__ __forceinline__ Best parent_scan(const Set& t, u64 key, u64 slot, int j0, int step) {
+  Best b{key, t.cnt[slot], slot};
+  const int n1 = 3 * (t.umi_bits / t.kind);
+  for (int j = j0; j < n1; j += step) {
+    const u64 nb = sct::umi_neighbour(key, t.kind, j);
+    const u64 s = set_find(t.keys, t.mask, nb);
+    if (s == NO_SLOT) continue;
+    const u64 r = t.cnt[s];
+    if (sct::umi_support_less(b.reads, b.code, r, nb)) b = Best{nb, r, s};
+  }
+  return b;
+}
+
+__device__ __forceinline__ u64 parent_of(const Set& t, u64 key, u64 slot, u64* at) {
+  const Best b = parent_scan(t, key, slot, 0, 1);
+  *at = b.slot;
+  return b.code;
+}
+
+// the claim of a parent's slot: true in the one lane that flips its bit 0 -> 1
+__device__ __forceinline__ bool bitmap_claim(uint32_t* __restrict__ bitmap, u64 at) {
+  const uint32_t bit = 1u << (at & 31);
+  return (atomicOr(&bitmap[at >> 5], bit) & bit) == 0;
+}
+
+// One lane per slot (SCT_TUNE_COLLAPSE_FORM 0).  The lane of an occupied slot finds the molecule's
+// parent and claims the parent's slot in the bitmap; the lane that flips the bit 0 -> 1, and only
+// that lane, adds 1 to collapsed[index].  Molecules that move are summed per wave, one add per wave.
+__global__ void __launch_bounds__(WG) molecules_collapse_kernel(Set t, int64_t capacity, uint32_t* __restrict__ bitmap,
+                                                                u64* __restrict__ collapsed,
+                                                                u64* __restrict__ ncorrected) {
+  const int64_t stride = (int64_t)gridDim.x * WG;
+  const int64_t iters = (capacity + stride - 1) / stride;  // the same for every lane: the wave stays whole
+  uint32_t moved = 0;
+  for (int64_t it = 0; it < iters; ++it) {
+    const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
+    const u64 key = s < capacity ? t.keys[s] : EMPTY;
+    bool moves = false;
+    if (key != EMPTY) {
+      u64 at;
+      const u64 parent = parent_of(t, key, (u64)s, &at);
+      moves = parent != key;
+      if (bitmap_claim(bitmap, at)) atomicAdd(&collapsed[sct::mol_key_index(key, t.umi_bits)], 1ull);
+    }
+    moved += (uint32_t)__popcll(__ballot(moves));
+  }
+  if ((threadIdx.x & 63) == 0 && moved) atomicAdd(ncorrected, (u64)moved);
+}
+
+// A wave per 64 slots (SCT_TUNE_COLLAPSE_FORM 1, the default: DESIGN.md §3.10.1 has the A/B).  The
+// occupied slots are taken one after the other: every lane probes its share of the molecule's
+// neighbours, the wave reduces the lanes' winners by the rule's own order, and lane 0 claims.  The
+// same answers as one lane per slot.
+__global__ void __launch_bounds__(WG) molecules_collapse_wave_kernel(Set t, int64_t capacity,
+                                                                     uint32_t* __restrict__ bitmap,
+                                                                     u64* __restrict__ collapsed,
+                                                                     u64* __restrict__ ncorrected) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (WG / 64);
+  uint32_t moved = 0;  // the same in every lane
+  // capacity is a multiple of 64, so base + lane < capacity and the loop is wave-uniform
+  for (int64_t base = (((int64_t)blockIdx.x * WG + threadIdx.x) >> 6) * 64; base < capacity; base += nwaves * 64) {
+    const u64 mine = t.keys[base + lane];
+    u64 todo = __ballot(mine != EMPTY);
+    while (todo) {
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const u64 key = __shfl(mine, src);
+      Best b = parent_scan(t, key, (u64)(base + src), lane, 64);
+      for (int o = 32; o > 0; o >>= 1) {
+        const Best c{__shfl_xor(b.code, o), __shfl_xor(b.reads, o), __shfl_xor(b.slot, o)};
+        if (sct::umi_support_less(b.reads, b.code, c.reads, c.code)) b = c;
+      }
+      if (lane == 0 && bitmap_claim(bitmap, b.slot))
+        atomicAdd(&collapsed[sct::mol_key_index(key, t.umi_bits)], 1ull);
+      moved += b.code != key;
+    }
+  }
+  if (lane == 0 && moved) atomicAdd(ncorrected, (u64)moved);
 }
 
 // fetch: the occupied slots' keys, in any order (the sort fixes the order); at most `room` are written
@@ -241,6 +397,49 @@ __global__ void __launch_bounds__(WG) molecules_compact_kernel(const u64* __rest
     if (lane == leader) at = atomicAdd(cursor, (u64)__popcll(m));
     at = __shfl(at, leader) + (u64)__popcll(m & ((1ull << lane) - 1ull));
     if (occ && (int64_t)at < room) out[at] = key;
+  }
+}
+
+// fetch_counted: the occupied slots as (key, slot) pairs, in any order; at most `room` are written
+__global__ void __launch_bounds__(WG) molecules_compact_pairs_kernel(const u64* __restrict__ keys, int64_t capacity,
+                                                                     u64* __restrict__ cursor, int64_t room,
+                                                                     u64* __restrict__ out_key,
+                                                                     uint32_t* __restrict__ out_slot) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * WG;
+  const int64_t iters = (capacity + stride - 1) / stride;
+  for (int64_t it = 0; it < iters; ++it) {
+    const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
+    const u64 key = s < capacity ? keys[s] : EMPTY;
+    const bool occ = key != EMPTY;
+    const u64 m = __ballot(occ);
+    if (m == 0) continue;
+    u64 at = 0;
+    const int leader = __ffsll((long long)m) - 1;
+    if (lane == leader) at = atomicAdd(cursor, (u64)__popcll(m));
+    at = __shfl(at, leader) + (u64)__popcll(m & ((1ull << lane) - 1ull));
+    if (occ && (int64_t)at < room) {
+      out_key[at] = key;
+      out_slot[at] = (uint32_t)s;  // capacity <= 2^31
+    }
+  }
+}
+
+// the sorted (key, slot) pairs as rows: index, UMI, mreads and, if asked, the parent's UMI
+__global__ void __launch_bounds__(WG) molecules_emit_kernel(Set t, const u64* __restrict__ keys,
+                                                            const uint32_t* __restrict__ slots, int64_t rows,
+                                                            int32_t* __restrict__ index, u64* __restrict__ umi,
+                                                            u64* __restrict__ mreads, u64* __restrict__ parent) {
+  for (int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WG) {
+    const u64 key = keys[r];
+    const u64 slot = slots[r];
+    index[r] = (int32_t)sct::mol_key_index(key, t.umi_bits);
+    umi[r] = sct::mol_key_umi(key, t.umi_bits);
+    mreads[r] = t.cnt[slot];
+    if (parent) {
+      u64 at;
+      parent[r] = sct::mol_key_umi(parent_of(t, key, slot, &at), t.umi_bits);
+    }
   }
 }
 
@@ -270,6 +469,7 @@ struct sct_molecules {
   hipEvent_t last = nullptr;  // the last work enqueued (another stream's call waits for it)
   hipStream_t last_stream = nullptr;
   bool used = false;
+  bool counted = false;  // keeps t.cnt beside t.keys
 };
 
 namespace {
@@ -281,6 +481,19 @@ int alloc_keys(u64** keys, int64_t capacity, hipStream_t s) {
     if (*keys) (void)hipFree(*keys);
     *keys = nullptr;
     return sct::fail(e == hipErrorOutOfMemory ? SCT_E_NOMEM : SCT_E_HIP, "molecule table of %lld slots: %s",
+                     (long long)capacity, hipGetErrorString(e));
+  }
+  return SCT_OK;
+}
+
+// a counted table's mreads: every slot 0 (an insert adds to it, a rehash stores into it)
+int alloc_counts(u64** cnt, int64_t capacity, hipStream_t s) {
+  hipError_t e = hipMalloc((void**)cnt, (size_t)capacity * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(*cnt, 0, (size_t)capacity * 8, s);
+  if (e != hipSuccess) {
+    if (*cnt) (void)hipFree(*cnt);
+    *cnt = nullptr;
+    return sct::fail(e == hipErrorOutOfMemory ? SCT_E_NOMEM : SCT_E_HIP, "molecule read counts of %lld slots: %s",
                      (long long)capacity, hipGetErrorString(e));
   }
   return SCT_OK;
@@ -314,17 +527,32 @@ int grow(sct_molecules* c, int64_t factor, hipStream_t s) {
   if (cap > kMaxCapacity)
     return sct::fail(SCT_E_RANGE, "molecule table cannot grow past %lld slots", (long long)kMaxCapacity);
   u64* nk = nullptr;
+  u64* nc = nullptr;
   if (int rc = alloc_keys(&nk, cap, s); rc != SCT_OK) return rc;
-  hipLaunchKernelGGL(molecules_rehash_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
-                     c->capacity, nk, (u64)cap - 1, c->t.words);
+  if (c->counted) {
+    if (int rc = alloc_counts(&nc, cap, s); rc != SCT_OK) {
+      (void)hipFree(nk);
+      return rc;
+    }
+    hipLaunchKernelGGL(molecules_rehash_counted_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
+                       c->t.cnt, c->capacity, nk, nc, (u64)cap - 1, c->t.words);
+  } else {
+    hipLaunchKernelGGL(molecules_rehash_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
+                       c->capacity, nk, (u64)cap - 1, c->t.words);
+  }
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(s);  // the old array is read until here
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // the old arrays are read until here
   if (e != hipSuccess) {
     (void)hipFree(nk);
+    if (nc) (void)hipFree(nc);
     return sct::fail(SCT_E_HIP, "molecule table rehash: %s", hipGetErrorString(e));
   }
   (void)hipFree(c->t.keys);
   c->t.keys = nk;
+  if (c->counted) {
+    (void)hipFree(c->t.cnt);
+    c->t.cnt = nc;
+  }
   c->t.mask = (u64)cap - 1;
   c->capacity = cap;
   return SCT_OK;
@@ -351,12 +579,14 @@ int update_device(sct_molecules* c, const int32_t* d_index, const uint64_t* d_um
     const int64_t m = std::min(n - done, c->capacity / 4);
     const int32_t* idx = d_index + done;
     const u64* umi = reinterpret_cast<const u64*>(d_umi) + done;
+    const dim3 grid(mode <= 1 ? grid_for(m, 4 * WG) : grid_for(m, kTile));
+    const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(WG), 0, s, c->t, idx, umi, m); };
     if (mode == 0)
-      hipLaunchKernelGGL(molecules_insert_kernel<false>, dim3(grid_for(m, 4 * WG)), dim3(WG), 0, s, c->t, idx, umi, m);
+      c->counted ? launch(molecules_insert_kernel<false, true>) : launch(molecules_insert_kernel<false, false>);
     else if (mode == 1)
-      hipLaunchKernelGGL(molecules_insert_kernel<true>, dim3(grid_for(m, 4 * WG)), dim3(WG), 0, s, c->t, idx, umi, m);
+      c->counted ? launch(molecules_insert_kernel<true, true>) : launch(molecules_insert_kernel<true, false>);
     else
-      hipLaunchKernelGGL(molecules_insert_lds_kernel, dim3(grid_for(m, kTile)), dim3(WG), 0, s, c->t, idx, umi, m);
+      c->counted ? launch(molecules_insert_lds_kernel<true>) : launch(molecules_insert_lds_kernel<false>);
     SCT_LAUNCH_CHECK();
     c->size_bound += m;
     done += m;
@@ -405,6 +635,81 @@ int fetch_device(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, int64_t ro
   return leave(c, s);
 }
 
+int need_counted(const sct_molecules* c) {
+  SCT_CHECK(c->counted, "the molecule counter keeps no read counts (sct_molecules_create_counted does)");
+  return SCT_OK;
+}
+
+// collapsed[nw] and, if asked, n_corrected, written on `s` from the table as it stands.  Scratch from
+// the pool: one word for n_corrected, then one bit per slot.
+int collapse_device(sct_molecules* c, uint64_t* d_collapsed, uint64_t* d_ncorrected, hipStream_t s) {
+  if (int rc = enter(c, s); rc != SCT_OK) return rc;
+  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  const size_t head = 256, bitmap_bytes = (size_t)c->capacity / 8;  // capacity >= 64: whole 32-bit words
+  void* blk = nullptr;
+  SCT_HIP(sct::pool_alloc(&blk, head + bitmap_bytes, s));
+  uint8_t* b = static_cast<uint8_t*>(blk);
+  u64* ncorr = reinterpret_cast<u64*>(b);
+  hipError_t e = hipMemsetAsync(b, 0, head + bitmap_bytes, s);
+  if (e == hipSuccess) e = hipMemsetAsync(d_collapsed, 0, (size_t)c->t.nw * 8, s);
+  if (e == hipSuccess && c->size_bound > 0) {
+    const bool wave = sct::tune(SCT_TUNE_COLLAPSE_FORM, 1) == 1;
+    const auto kernel = wave ? molecules_collapse_wave_kernel : molecules_collapse_kernel;
+    hipLaunchKernelGGL(kernel, dim3(grid_for(c->capacity, WG)), dim3(WG), 0, s, c->t, c->capacity,
+                       reinterpret_cast<uint32_t*>(b + head), reinterpret_cast<u64*>(d_collapsed), ncorr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && d_ncorrected) e = hipMemcpyAsync(d_ncorrected, ncorr, 8, hipMemcpyDeviceToDevice, s);
+  sct::pool_free(blk, s);
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule collapse: %s", hipGetErrorString(e));
+  return leave(c, s);
+}
+
+// the number of molecules, read on `s` after the counter's earlier work; `room` must hold them
+int rows_for_fetch(sct_molecules* c, int64_t room, hipStream_t s, int64_t* rows) {
+  if (int rc = enter(c, s); rc != SCT_OK) return rc;
+  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  *rows = c->size_bound;
+  SCT_CHECK(room >= *rows, "room for %lld molecules, the counter holds %lld", (long long)room, (long long)*rows);
+  return SCT_OK;
+}
+
+// fetch's rows with each row's mreads and, if asked, its parent's UMI beside them: `rows` > 0 rows,
+// as rows_for_fetch gave them on `s`
+int fetch_counted_rows(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, uint64_t* d_mreads, uint64_t* d_parent,
+                       int64_t rows, hipStream_t s) {
+  SCT_CHECK(d_index && d_umi && d_mreads, "NULL output");
+  const int end_bit = c->idx_bits + c->t.umi_bits;
+  size_t sort_bytes = 0;
+  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr,
+                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)rows, 0, end_bit, s);
+  const size_t b8 = ((size_t)rows * 8 + 255) & ~(size_t)255;
+  const size_t b4 = ((size_t)rows * 4 + 255) & ~(size_t)255;
+  void* blk = nullptr;
+  SCT_HIP(sct::pool_alloc(&blk, 2 * b8 + 2 * b4 + sort_bytes, s));
+  uint8_t* b = static_cast<uint8_t*>(blk);
+  u64* keys_in = reinterpret_cast<u64*>(b);
+  u64* keys_out = reinterpret_cast<u64*>(b + b8);
+  uint32_t* slots_in = reinterpret_cast<uint32_t*>(b + 2 * b8);
+  uint32_t* slots_out = reinterpret_cast<uint32_t*>(b + 2 * b8 + b4);
+  hipError_t e = hipMemsetAsync(&c->t.words[W_CURSOR], 0, 8, s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(molecules_compact_pairs_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
+                       c->capacity, &c->t.words[W_CURSOR], rows, keys_in, slots_in);
+    e = hipcub::DeviceRadixSort::SortPairs(b + 2 * b8 + 2 * b4, sort_bytes, keys_in, keys_out, slots_in, slots_out,
+                                           (int)rows, 0, end_bit, s);
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(molecules_emit_kernel, dim3(grid_for(rows, WG)), dim3(WG), 0, s, c->t, keys_out, slots_out, rows,
+                       d_index, reinterpret_cast<u64*>(d_umi), reinterpret_cast<u64*>(d_mreads),
+                       reinterpret_cast<u64*>(d_parent));
+    e = hipGetLastError();
+  }
+  sct::pool_free(blk, s);
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule fetch: %s", hipGetErrorString(e));
+  return leave(c, s);
+}
+
 // reads, molecules and the tally copied out on `s` (each destination nullable)
 int counts_copy(sct_molecules* c, uint64_t* reads, uint64_t* molecules, uint64_t* tally, hipMemcpyKind kind,
                 hipStream_t s) {
@@ -418,7 +723,9 @@ int counts_copy(sct_molecules* c, uint64_t* reads, uint64_t* molecules, uint64_t
 
 }  // namespace
 
-extern "C" int sct_molecules_create(int64_t nw, int kind, int L, int64_t capacity_hint, sct_molecules** out) {
+namespace {
+
+int create(int64_t nw, int kind, int L, int64_t capacity_hint, bool counted, sct_molecules** out) {
   SCT_CHECK(out != nullptr, "molecule counter is NULL");
   *out = nullptr;
   SCT_CHECK(nw >= 1 && nw < (1LL << 31), "nw %lld outside [1, 2^31)", (long long)nw);
@@ -441,12 +748,15 @@ extern "C" int sct_molecules_create(int64_t nw, int kind, int L, int64_t capacit
   sct::HostStage* hs = sct::host_stage();
   if (!hs) return fail_with(SCT_E_HIP);
   c->capacity = cap;
+  c->counted = counted;
   c->idx_bits = sct::mol_idx_bits(nw);
   c->t.nw = nw;
   c->t.kind = kind;
   c->t.umi_bits = umi_bits;
   c->t.mask = (u64)cap - 1;
   if (int rc = alloc_keys(&c->t.keys, cap, hs->stream); rc != SCT_OK) return fail_with(rc);
+  if (counted)
+    if (int rc = alloc_counts(&c->t.cnt, cap, hs->stream); rc != SCT_OK) return fail_with(rc);
   // reads and molecules are one allocation of 2 * nw words, the tally lives in the device words
   e = hipMalloc((void**)&c->t.reads, (size_t)nw * 16);
   if (e == hipSuccess) {
@@ -465,6 +775,16 @@ extern "C" int sct_molecules_create(int64_t nw, int kind, int L, int64_t capacit
   return SCT_OK;
 }
 
+}  // namespace
+
+extern "C" int sct_molecules_create(int64_t nw, int kind, int L, int64_t capacity_hint, sct_molecules** out) {
+  return create(nw, kind, L, capacity_hint, false, out);
+}
+
+extern "C" int sct_molecules_create_counted(int64_t nw, int kind, int L, int64_t capacity_hint, sct_molecules** out) {
+  return create(nw, kind, L, capacity_hint, true, out);
+}
+
 extern "C" int sct_molecules_destroy(sct_molecules* c) {
   if (!c) return SCT_OK;
   if (c->last) {
@@ -472,6 +792,7 @@ extern "C" int sct_molecules_destroy(sct_molecules* c) {
     (void)hipEventDestroy(c->last);
   }
   if (c->t.keys) (void)hipFree(c->t.keys);
+  if (c->t.cnt) (void)hipFree(c->t.cnt);
   if (c->t.reads) (void)hipFree(c->t.reads);
   if (c->t.words) (void)hipFree(c->t.words);
   if (c->h_words) (void)hipHostFree(c->h_words);
@@ -573,6 +894,71 @@ extern "C" int sct_molecules_fetch_host(sct_molecules* c, int32_t* index, uint64
   if (rc == SCT_OK) {
     blk.note(hipMemcpyAsync(umi, b, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
     if (blk.ok()) blk.note(hipMemcpyAsync(index, b + b8, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+  }
+  return blk.finish(rc, "molecule fetch");
+}
+
+extern "C" int sct_molecules_collapse(sct_molecules* c, uint64_t* d_collapsed, uint64_t* d_ncorrected, void* stream) {
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_CHECK(d_collapsed != nullptr, "NULL output");
+  return collapse_device(c, d_collapsed, d_ncorrected, sct::as_stream(stream));
+}
+
+extern "C" int sct_molecules_collapse_host(sct_molecules* c, uint64_t* collapsed, uint64_t* ncorrected) {
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_CHECK(collapsed != nullptr, "NULL output");
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return SCT_E_HIP;
+  hipStream_t s = hs->stream;
+  const size_t nb = (size_t)c->t.nw * 8;
+  sct::PoolBlock blk(s);
+  if (int rc = blk.alloc(nb + 8); rc != SCT_OK) return rc;
+  uint8_t* b = blk.bytes();
+  const int rc = collapse_device(c, (uint64_t*)b, (uint64_t*)(b + nb), s);
+  if (rc == SCT_OK) {
+    blk.note(hipMemcpyAsync(collapsed, b, nb, hipMemcpyDeviceToHost, s));
+    if (blk.ok() && ncorrected) blk.note(hipMemcpyAsync(ncorrected, b + nb, 8, hipMemcpyDeviceToHost, s));
+  }
+  return blk.finish(rc, "molecule collapse");
+}
+
+extern "C" int sct_molecules_fetch_counted(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, uint64_t* d_mreads,
+                                           uint64_t* d_parent, int64_t room, void* stream) {
+  SCT_CHECK(room >= 0, "room must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  hipStream_t s = sct::as_stream(stream);
+  int64_t rows = 0;
+  if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
+  if (rows == 0) return SCT_OK;
+  return fetch_counted_rows(c, d_index, d_umi, d_mreads, d_parent, rows, s);
+}
+
+extern "C" int sct_molecules_fetch_counted_host(sct_molecules* c, int32_t* index, uint64_t* umi, uint64_t* mreads,
+                                                uint64_t* parent, int64_t room) {
+  SCT_CHECK(room >= 0, "room must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_CHECK(room == 0 || (index && umi && mreads), "NULL output");
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return SCT_E_HIP;
+  hipStream_t s = hs->stream;
+  int64_t rows = 0;
+  if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
+  if (rows == 0) return SCT_OK;
+  const size_t b8 = ((size_t)rows * 8 + 255) & ~(size_t)255;
+  sct::PoolBlock blk(s);
+  if (int rc = blk.alloc(3 * b8 + (size_t)rows * 4); rc != SCT_OK) return rc;
+  uint8_t* b = blk.bytes();  // umi, mreads, parent, index
+  const int rc = fetch_counted_rows(c, (int32_t*)(b + 3 * b8), (uint64_t*)b, (uint64_t*)(b + b8),
+                                    parent ? (uint64_t*)(b + 2 * b8) : nullptr, rows, s);
+  if (rc == SCT_OK) {
+    blk.note(hipMemcpyAsync(umi, b, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok()) blk.note(hipMemcpyAsync(mreads, b + b8, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok() && parent) blk.note(hipMemcpyAsync(parent, b + 2 * b8, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok()) blk.note(hipMemcpyAsync(index, b + 3 * b8, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
   }
   return blk.finish(rc, "molecule fetch");
 }

@@ -10,13 +10,16 @@ Counter(codes.tolist()) and np.unique(codes, return_index=True, return_counts=Tr
 n is stated.  Then WhitelistCorrector.count against .nearest() + np.bincount on one batch, with
 the bytes each moves over PCIe.  Then MoleculeCounter.update_device on 100M (index, UMI) reads
 against DeviceCounter on composite keys plus sct_index_tally, with a molecule's reads far apart and
-adjacent (molecules_step; its rounds also go to profiles/ab_molecules_<tag>.jsonl).
+adjacent (molecules_step; its rounds also go to profiles/ab_molecules_<tag>.jsonl).  Then, on the same
+reads, the counted MoleculeCounter and its UMI collapse against the plain one, an earlier library and
+the host (collapse_step; profiles/ab_umi_collapse_<tag>.jsonl).
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends
 the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
 
   python tools/bench_count.py --tag mi355x
   python tools/bench_count.py --tag mi355x --only molecules
+  python tools/bench_count.py --tag mi355x --only collapse --parent-lib /path/to/earlier/libsctools_hip.so
 """
 import argparse
 import json
@@ -28,7 +31,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420}  # seconds
+STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420, "collapse": 600}  # seconds
 MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
 HBM_BYTES_PER_S = 8e12
 
@@ -159,48 +162,13 @@ def molecules_step(args):
 
     import numpy as np
     import torch
-    from sctools_amd import _lib, counting, synthetic
+    from sctools_amd import _lib, counting
 
-    nw, L, seed = synthetic.CONFIGS[4]
-    UL, n = 10, args.n_a
-    wl3 = synthetic.two_to_three(synthetic.whitelist_codes(nw, L, seed), L)
+    nw, UL, n, hint, pool, inputs = _molecules_input(args)
     dev = torch.device("cuda")
-    q, _, _ = synthetic.config4_queries(wl3, n, seed=4, device=dev)
-    d_wl = torch.from_numpy(wl3.view(np.int64)).cuda()
-    d_index = torch.empty(n, dtype=torch.int32, device=dev)
-    d_dist = torch.empty(n, dtype=torch.uint8, device=dev)
-    plan = _lib.NearestPlan(3, d_wl.data_ptr(), nw, 3 * L, 1)
-    plan.query(q.data_ptr(), n, d_index.data_ptr(), d_dist.data_ptr())
-    torch.cuda.synchronize()
-    plan.close()
-    del q, d_dist
-    g = torch.Generator(device=dev).manual_seed(7)
-    # reads per barcode r = (matched reads) / nw; a pool of r / 4 UMIs per barcode gives ~4 reads per molecule
-    matched = int((d_index >= 0).sum())
-    pool = max(1, round(matched / nw / 4))
-    table = torch.zeros(4096, dtype=torch.int64, device=dev)  # 4096 distinct good UMI codes
-    t = torch.randperm(4 ** UL, device=dev, generator=g)[:4096]
-    for p in range(UL):
-        table |= (((t >> (2 * p)) & 3) + 1) << (3 * p)
-    pick = (torch.randint(0, pool, (n,), device=dev, generator=g) + d_index.to(torch.int64) * 31) % 4096
-    d_umi = table[pick]
-    with_n = torch.rand(n, device=dev, generator=g) < 0.01
-    d_umi = torch.where(with_n, d_umi | 6, d_umi)
-    d_keys = (d_index.to(torch.int64) << (3 * UL)) | d_umi  # the yardstick's composite keys
-    del pick, with_n, t
-    torch.cuda.synchronize()
     lib = _lib.lib()
     vp = ctypes.c_void_p
-    hint = 1 << max(6, (n // 2).bit_length())  # at most n / 4 molecules expected: load stays below 1/2
     out = {"n": n, "nw": nw, "umi_length": UL, "umi_pool_per_barcode": pool, "capacity_hint": hint, "inputs": {}}
-    # the same reads in two orders: as drawn (a molecule's reads far apart), and with every molecule's
-    # reads adjacent (molecules in hash order) -- the two ends of how close PCR duplicates can lie
-    # (an odd multiplier permutes the int64 keys: equal keys stay together, their order is scrambled)
-    order = torch.argsort(d_keys * -7046029254386353131)
-    inputs = {"shuffled": (d_index, d_umi, d_keys),
-              "adjacent": (d_index[order].contiguous(), d_umi[order].contiguous(), d_keys[order].contiguous())}
-    del order
-    torch.cuda.synchronize()
 
     def run_molecules(mode, d_index, d_umi):
         with _lib.tuning(count_preagg=mode), counting.MoleculeCounter(nw, UL, capacity_hint=hint) as mc:
@@ -226,6 +194,7 @@ def molecules_step(args):
             nunique = len(dc)
         return ms, nunique
 
+    d_index, d_umi, d_keys = inputs["shuffled"]
     run_molecules(2, d_index, d_umi), run_yardstick(1, d_index, d_keys)  # warm-up: code objects, pool
     facts = None
     lines = []
@@ -263,6 +232,221 @@ def molecules_step(args):
     return out
 
 
+def _molecules_input(args):
+    """(nw, UMI length, n, capacity hint, UMIs per barcode, {order: (d_index, d_umi, d_keys)}): the
+    molecules step's reads, on the device."""
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, synthetic
+
+    nw, L, seed = synthetic.CONFIGS[4]
+    UL, n = 10, args.n_a
+    wl3 = synthetic.two_to_three(synthetic.whitelist_codes(nw, L, seed), L)
+    dev = torch.device("cuda")
+    q, _, _ = synthetic.config4_queries(wl3, n, seed=4, device=dev)
+    d_wl = torch.from_numpy(wl3.view(np.int64)).cuda()
+    d_index = torch.empty(n, dtype=torch.int32, device=dev)
+    d_dist = torch.empty(n, dtype=torch.uint8, device=dev)
+    plan = _lib.NearestPlan(3, d_wl.data_ptr(), nw, 3 * L, 1)
+    plan.query(q.data_ptr(), n, d_index.data_ptr(), d_dist.data_ptr())
+    torch.cuda.synchronize()
+    plan.close()
+    del q, d_dist
+    g = torch.Generator(device=dev).manual_seed(7)
+    # reads per barcode r = (matched reads) / nw; a pool of r / 4 UMIs per barcode gives ~4 reads per molecule
+    matched = int((d_index >= 0).sum())
+    pool = max(1, round(matched / nw / 4))
+    table = torch.zeros(4096, dtype=torch.int64, device=dev)  # 4096 distinct good UMI codes
+    t = torch.randperm(4 ** UL, device=dev, generator=g)[:4096]
+    for p in range(UL):
+        table |= (((t >> (2 * p)) & 3) + 1) << (3 * p)
+    pick = (torch.randint(0, pool, (n,), device=dev, generator=g) + d_index.to(torch.int64) * 31) % 4096
+    d_umi = table[pick]
+    with_n = torch.rand(n, device=dev, generator=g) < 0.01
+    d_umi = torch.where(with_n, d_umi | 6, d_umi)
+    d_keys = (d_index.to(torch.int64) << (3 * UL)) | d_umi  # the yardstick's composite keys
+    del pick, with_n, t
+    torch.cuda.synchronize()
+    hint = 1 << max(6, (n // 2).bit_length())  # at most n / 4 molecules expected: load stays below 1/2
+    # the same reads in two orders: as drawn (a molecule's reads far apart), and with every molecule's
+    # reads adjacent (molecules in hash order) -- the two ends of how close PCR duplicates can lie
+    # (an odd multiplier permutes the int64 keys: equal keys stay together, their order is scrambled)
+    order = torch.argsort(d_keys * -7046029254386353131)
+    inputs = {"shuffled": (d_index, d_umi, d_keys),
+              "adjacent": (d_index[order].contiguous(), d_umi[order].contiguous(), d_keys[order].contiguous())}
+    del order
+    torch.cuda.synchronize()
+    return nw, UL, n, hint, pool, inputs
+
+
+def collapse_step(args):
+    """The counted molecule counter and its UMI collapse on the molecules step's input.  Alternating
+    within every round, per input order and pre-aggregation mode: (a) MoleculeCounter.update_device as
+    it was (no read counts), (a') the same call into the library given by --parent-lib (the commit
+    before the counted counter, loaded beside this one; skipped without it), (b) update_device with
+    read_counts=True, (c) collapse_device on the table (b) left, one lane per slot and then a wave per
+    molecule (SCT_TUNE_COLLAPSE_FORM 0 / 1, the default).  Then, once, the host way to (c)'s
+    answer: pairs(reads=True) to the host, and a Python dict collapse of the first --n-collapse-host
+    molecules (whole barcodes), scaled by molecules / sub-sample; its collapsed counts must equal the
+    device's for those barcodes.  (a) and (a') agree when their medians differ by no more than the
+    min-max spread of (a')'s own rounds; the step fails when they do not.  Every round is one line of
+    profiles/ab_umi_collapse_<tag>.jsonl, the summary its last."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, counting
+
+    nw, UL, n, hint, pool, inputs = _molecules_input(args)
+    dev = torch.device("cuda")
+    vp, i64 = ctypes.c_void_p, ctypes.c_int64
+    old = None
+    if args.parent_lib:
+        old = ctypes.CDLL(os.path.abspath(args.parent_lib))
+        for name in ("sct_tune_set", "sct_molecules_create", "sct_molecules_update", "sct_molecules_counts_host",
+                     "sct_molecules_destroy"):
+            getattr(old, name).argtypes = _lib.SIGNATURES[name]
+    d_collapsed = torch.zeros(nw + 1, dtype=torch.int64, device=dev)
+
+    def facts_of(reads, molecules, tally):
+        return int(reads.sum()), int(molecules.sum()), int(tally[0]), int(tally[1]), int(tally[2])
+
+    def run_update(mode, d_index, d_umi, counted):
+        """(update ms, collapse ms per SCT_TUNE_COLLAPSE_FORM or None, facts)"""
+        mc = counting.MoleculeCounter(nw, UL, capacity_hint=hint, read_counts=counted)
+        with _lib.tuning(count_preagg=mode), mc:
+            def go():
+                mc.update_device(d_index.data_ptr(), d_umi.data_ptr(), n)
+                torch.cuda.synchronize()
+            ms = _time_ms(go)
+            cms = None
+            if counted:
+                def collapse():
+                    mc.collapse_device(d_collapsed.data_ptr(), d_collapsed.data_ptr() + 8 * nw)
+                    torch.cuda.synchronize()
+                cms = []
+                for form in (0, 1):
+                    with _lib.tuning(collapse_form=form):
+                        cms.append(_time_ms(collapse))
+            reads, molecules, n_none, n_amb, n_bad = mc.counts()
+        return ms, cms, facts_of(reads, molecules, (n_none, n_amb, n_bad))
+
+    def run_parent(mode, d_index, d_umi):
+        h = vp()
+        assert old.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], mode) == 0
+        assert old.sct_molecules_create(nw, 3, UL, hint, ctypes.byref(h)) == 0
+        try:
+            def go():
+                assert old.sct_molecules_update(h, vp(d_index.data_ptr()), vp(d_umi.data_ptr()), n, None) == 0
+                torch.cuda.synchronize()
+            ms = _time_ms(go)
+            reads, molecules, tally = np.empty(nw, np.uint64), np.empty(nw, np.uint64), np.empty(3, np.uint64)
+            assert old.sct_molecules_counts_host(h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)) == 0
+        finally:
+            old.sct_molecules_destroy(h)
+        return ms, facts_of(reads, molecules, tally)
+
+    run_update(2, *inputs["shuffled"][:2], True)  # warm-up: code objects, pool
+    if old:
+        run_parent(2, *inputs["shuffled"][:2])
+    facts, lines = None, []
+    out = {"n": n, "nw": nw, "umi_length": UL, "umi_pool_per_barcode": pool, "capacity_hint": hint, "inputs": {},
+           "parent_lib": bool(old)}
+    for which, (di, du, _) in inputs.items():
+        rounds = []
+        for r in range(args.rounds):
+            row = {"input": which, "round": r, "n": n, "nw": nw}
+            for m, name in MODES.items():
+                cell = {}
+                ms, _, f = run_update(m, di, du, False)
+                cell["uncounted_ms"] = round(ms, 3)
+                assert facts is None or f == facts, (f, facts)  # every library, form, order and round: the same numbers
+                facts = f
+                if old:
+                    ms, f = run_parent(m, di, du)
+                    cell["uncounted_parent_ms"] = round(ms, 3)
+                    assert f == facts, (f, facts)
+                ms, cms, f = run_update(m, di, du, True)
+                cell["counted_ms"] = round(ms, 3)
+                cell["collapse_lane_ms"], cell["collapse_wave_ms"] = round(cms[0], 3), round(cms[1], 3)
+                assert f == facts, (f, facts)
+                row[name] = cell
+            rounds.append(row)
+        lines += rounds
+        res = out["inputs"][which] = {}
+        for name in MODES.values():
+            res[name] = {}
+            for key in rounds[0][name]:
+                a = [row[name][key] for row in rounds]
+                res[name][key] = {"median": round(float(np.median(a)), 3), "min": min(a), "max": max(a)}
+            if old:
+                a, b = res[name]["uncounted_ms"], res[name]["uncounted_parent_ms"]
+                res[name]["uncounted_vs_parent"] = {
+                    "median_difference_ms": round(a["median"] - b["median"], 3),
+                    "parent_spread_ms": round(b["max"] - b["min"], 3),
+                    "agree": abs(a["median"] - b["median"]) <= b["max"] - b["min"]}
+    # (d) the host way: the counted rows to the host, and a dict collapse of a prefix of whole barcodes
+    di, du, _ = inputs["shuffled"]
+    with counting.MoleculeCounter(nw, UL, capacity_hint=hint, read_counts=True) as mc:
+        mc.update_device(di.data_ptr(), du.data_ptr(), n)
+        got = {}
+        fetch_ms = _time_ms(lambda: got.update(rows=mc.pairs(reads=True)))
+        collapsed, n_corrected = mc.collapse()
+        index, umi, mreads = got["rows"]
+    nmol = int(index.size)
+    k = min(nmol, args.n_collapse_host)
+    if k < nmol:
+        k = int(np.searchsorted(index, index[k], side="left"))  # whole barcodes only
+    sub_i, sub_u, sub_r = index[:k].tolist(), umi[:k].tolist(), mreads[:k].tolist()
+
+    def host_collapse():
+        table = {(i << (3 * UL)) | u: r for i, u, r in zip(sub_i, sub_u, sub_r)}
+        images, moved = set(), 0
+        for key, r in table.items():
+            best, best_r = key, r
+            for p in range(UL):
+                t = (key >> (3 * p)) & 7
+                for b in (1, 2, 3, 4):
+                    if b != t:
+                        v = key ^ ((t ^ b) << (3 * p))
+                        vr = table.get(v)
+                        if vr is not None and (vr, v) > (best_r, best):
+                            best, best_r = v, vr
+            images.add(best)
+            moved += best != key
+        return np.bincount(np.array([v >> (3 * UL) for v in images], dtype=np.int64), minlength=nw), moved
+
+    host = {}
+    dict_ms = _time_ms(lambda: host.update(res=host_collapse()))
+    nb = int(index[k - 1]) + 1 if k else 0
+    assert np.array_equal(host["res"][0][:nb], collapsed[:nb]), "the device's collapse differs from the host's"
+    scale = nmol / max(1, k)
+    coll = [row[name]["collapse_lane_ms"] for row in lines for name in MODES.values()]
+    wave = [row[name]["collapse_wave_ms"] for row in lines for name in MODES.values()]
+    out["host_yardstick"] = {"fetch_counted_host_ms": round(fetch_ms, 1), "dict_collapse_molecules": k,
+                             "dict_collapse_ms": round(dict_ms, 1), "scale": round(scale, 2),
+                             "dict_collapse_scaled_ms": round(dict_ms * scale, 1),
+                             "total_scaled_ms": round(fetch_ms + dict_ms * scale, 1),
+                             "n_corrected_in_sub_sample": int(host["res"][1])}
+    out["collapse_lane_ms"] = {"median": round(float(np.median(coll)), 3), "min": min(coll), "max": max(coll)}
+    out["collapse_wave_ms"] = {"median": round(float(np.median(wave)), 3), "min": min(wave), "max": max(wave)}
+    reads, molecules, n_none, n_amb, n_bad = facts
+    assert reads + n_none + n_amb + n_bad == n and molecules == nmol
+    out.update(reads=reads, molecules=molecules, collapsed=int(collapsed.sum()), n_corrected=n_corrected,
+               n_none=n_none, n_ambiguous=n_amb, n_bad_umi=n_bad,
+               collapse_ns_per_molecule=round(out["collapse_wave_ms"]["median"] * 1e6 / max(1, nmol), 3))
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "ab_umi_collapse_%s.jsonl" % args.tag), "w") as f:
+        for row in lines:
+            f.write(json.dumps(row, sort_keys=True) + "\n")
+        f.write(json.dumps(out, sort_keys=True) + "\n")
+    # the plain update must be the earlier library's: the step fails (its profile is written) if not
+    apart = ["%s/%s: %s" % (which, name, v["uncounted_vs_parent"]) for which, modes in out["inputs"].items()
+             for name, v in modes.items() if old and not v["uncounted_vs_parent"]["agree"]]
+    assert not apart, "the plain update differs from --parent-lib beyond that library's own spread: " + "; ".join(apart)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tag", default="run")
@@ -272,11 +456,16 @@ def main():
     ap.add_argument("--n-unique", type=int, default=20_000_000, help="codes given to np.unique")
     ap.add_argument("--n-tally", type=int, default=20_000_000, help="queries of the WhitelistCorrector batch")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--n-collapse-host", type=int, default=200_000, help="molecules given to the dict collapse")
+    ap.add_argument("--parent-lib", default="",
+                    help="collapse step: an earlier libsctools_hip.so to time beside this one")
     ap.add_argument("--only", nargs="+", choices=sorted(STEPS), help="launch only these steps")
     args = ap.parse_args()
     if args.step:
         if args.step == "molecules":
             res = molecules_step(args)
+        elif args.step == "collapse":
+            res = collapse_step(args)
         else:
             res = tally_step(args) if args.step == "tally" else counter_step(args.step[-1], args)
         print("RESULT " + json.dumps(res))
@@ -289,7 +478,8 @@ def main():
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step,
                "--tag", args.tag,
                "--n-a", str(args.n_a), "--n-counter", str(args.n_counter), "--n-unique", str(args.n_unique),
-               "--n-tally", str(args.n_tally), "--rounds", str(args.rounds)]
+               "--n-tally", str(args.n_tally), "--rounds", str(args.rounds),
+               "--n-collapse-host", str(args.n_collapse_host), "--parent-lib", args.parent_lib]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not lines:
@@ -307,6 +497,12 @@ def main():
         if "reads_per_molecule" in res:
             short[step] = {"n": res["n"], "molecules": res["molecules"], "reads_per_molecule": res["reads_per_molecule"],
                            "ms": {which: {k: [v["molecules_ms"]["median"], v["counter_plus_tally_ms"]["median"]]
+                                          for k, v in modes.items()} for which, modes in res["inputs"].items()}}
+        elif "collapse_wave_ms" in res:
+            short[step] = {"n": res["n"], "molecules": res["molecules"], "collapsed": res["collapsed"],
+                           "collapse_ms": res["collapse_wave_ms"]["median"],
+                           "host_ms": res["host_yardstick"]["total_scaled_ms"],
+                           "ms": {which: {k: [v[c]["median"] for c in ("uncounted_ms", "counted_ms")]
                                           for k, v in modes.items()} for which, modes in res["inputs"].items()}}
         elif "modes" in res:
             short[step] = {"n": res["n"], "nunique": res["nunique"],
