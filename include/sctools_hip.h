@@ -65,7 +65,10 @@ int sct_set_device(int device);        /* select the device for later calls (hip
                                            counter's insert has the same three forms and default */
 #define SCT_TUNE_COLLAPSE_FORM 18       /* UMI collapse: 0 one lane per table slot probes the molecule's 3 * L
                                            neighbours, 1 a wave shares one molecule's neighbours (default) */
-#define SCT_TUNE_NKEYS 19
+#define SCT_TUNE_MERGE_ROWS 19          /* molecule merge on one device: 0 the kernel reads the source's table in
+                                           place (default), 1 the source's rows are compacted and copied first, as
+                                           they always are between two devices */
+#define SCT_TUNE_NKEYS 20
 int sct_tune_set(int key, int64_t value);
 int sct_tune_get(int key, int64_t* value);  /* -1 when unset */
 
@@ -567,9 +570,21 @@ int sct_nearest_count_host(sct_nearest_plan* plan, const uint64_t* queries, int6
  * slots (each nullable).  counts: nw + nw + 3 words out, each array nullable.  fetch: the distinct
  * molecules in ascending key order (by barcode index, then by UMI code); room < nmolecules is
  * SCT_E_INVALID and leaves the counter as it was.  The counter lives on the device current at
- * create; destroy waits for the work the counter enqueued, and destroy(NULL) is SCT_OK. */
+ * create (create_ex: on the device it names); destroy waits for the work the counter enqueued, and
+ * destroy(NULL) is SCT_OK.
+ * create_ex is the one constructor: flags bit 0 (SCT_MOLECULES_COUNTED) makes a counted counter
+ * (below), any other bit is SCT_E_INVALID; device is a HIP ordinal, or -1 for the current device (an
+ * ordinal that does not exist is SCT_E_INVALID).  sct_molecules_create is create_ex(.., 0, -1, ..)
+ * and sct_molecules_create_counted is create_ex(.., SCT_MOLECULES_COUNTED, -1, ..).
+ * Devices: every sct_molecules_* call works whatever device is current and leaves the current device
+ * as it found it (the call makes the counter's device current for its own duration).  Device
+ * pointers and a non-NULL stream given to a call belong to the counter's device; a NULL stream is
+ * that device's default stream. */
+#define SCT_MOLECULES_COUNTED 1
 typedef struct sct_molecules sct_molecules;
 int sct_molecules_create(int64_t nw, int kind, int L, int64_t capacity_hint, sct_molecules** mol);
+int sct_molecules_create_ex(int64_t nw, int kind, int L, int64_t capacity_hint, int flags, int device,
+                            sct_molecules** mol);
 int sct_molecules_update(sct_molecules* mol, const int32_t* d_index, const uint64_t* d_umi, int64_t n, void* stream);
 int sct_molecules_update_host(sct_molecules* mol, const int32_t* index, const uint64_t* umi, int64_t n);
 int sct_molecules_info(sct_molecules* mol, int64_t* nmolecules, int64_t* total, int64_t* capacity);
@@ -618,6 +633,31 @@ int sct_molecules_fetch_counted(sct_molecules* mol, int32_t* d_index, uint64_t* 
                                 uint64_t* d_parent, int64_t room, void* stream);
 int sct_molecules_fetch_counted_host(sct_molecules* mol, int32_t* index, uint64_t* umi, uint64_t* mreads,
                                      uint64_t* parent, int64_t room);
+
+/* Merging molecule counters: one table from the counters of several files, lanes or devices.  The
+ * two reads of a molecule can land in different counters, so molecules[] of two counters cannot be
+ * added up: the union of the key sets is taken on the device.
+ * After merge(dst, src), dst is the counter that was fed dst's updates followed by src's updates, in
+ * every observable respect: info (nmolecules, total), counts (reads, molecules, the three tallies),
+ * fetch, fetch_counted (mreads and parent) and collapse -- so collapse is valid across shards.
+ * That is: reads[i] += src.reads[i], tally[k] += src.tally[k], total += src.total, every key stored
+ * in src is claimed in dst by the update's own rule (molecules[index] += 1 from the lane whose
+ * compare-and-swap took the slot, and from no other), and for counted counters mreads of the key in
+ * dst += mreads of the key in src.  src is unchanged and stays usable; merging it a second time
+ * doubles reads, mreads, the tallies and total and adds no molecule.  The cost is one update pass
+ * over src's molecules, not over its reads.
+ * Conditions: dst != src, and nw, kind, L and counted-ness equal; a NULL argument or a violated
+ * condition is SCT_E_INVALID (the message names what differs).  A src whose table overflowed is
+ * SCT_E_RANGE, as fetch treats it.  Growth: before any key moves dst is grown by update's rehash so
+ * that dst.nmolecules + src.nmolecules <= capacity / 2 (the smallest such power of two, never less
+ * than dst's capacity); more than 2^31 slots is SCT_E_RANGE.  After any of these errors both
+ * counters are as they were.  The two sizes are read once (each a wait for the stream); the call is
+ * otherwise asynchronous on `stream`, which belongs to dst's device.
+ * The merge orders itself after both counters' earlier work on any stream, and the later work of
+ * both after itself.  The counters may live on different devices: src's occupied rows are then
+ * compacted on its own device and copied into scratch on dst's device (hipMemcpyPeerAsync; peer
+ * access is neither needed nor enabled); on one device the kernel reads src's table in place. */
+int sct_molecules_merge(sct_molecules* dst, sct_molecules* src, void* stream);
 
 /* ---------------------------------------------------------------- FASTQ barcode extraction
  * Replaces the per-record path reader.Reader.__iter__ (src/sctools/reader.py:56-85) ->

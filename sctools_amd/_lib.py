@@ -37,7 +37,8 @@ TUNE_KEYS = {"spectral_chunk": 1, "spectral_min_n": 2, "allpairs_grab": 3, "allp
              "allpairs_grid": 5, "nearest_scheme": 6, "nearest_load": 7, "scalar_server": 8,
              "scalar_idle_ms": 9, "spectral_columns": 10, "plan_cache": 11,
              "encode_grid": 12, "ingest_tiles": 13, "fastq_onepass": 14,
-             "ingest_direct": 15, "ingest_spec": 16, "count_preagg": 17, "collapse_form": 18}
+             "ingest_direct": 15, "ingest_spec": 16, "count_preagg": 17, "collapse_form": 18,
+             "merge_rows": 19}
 NEAREST_AUTO, NEAREST_OA, NEAREST_CSR, NEAREST_HALVES = 0, 1, 2, 3
 
 _i32, _i64, _dbl = ctypes.c_int, ctypes.c_int64, ctypes.c_double
@@ -163,6 +164,8 @@ SIGNATURES = {
     "sct_molecules_collapse_host": [_vp, _vp, _vp],
     "sct_molecules_fetch_counted": [_vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "sct_molecules_fetch_counted_host": [_vp, _vp, _vp, _vp, _vp, _i64],
+    "sct_molecules_create_ex": [_i64, _i32, _i32, _i64, _i32, _i32, ctypes.POINTER(_vp)],
+    "sct_molecules_merge": [_vp, _vp, _vp],
 }
 _RESTYPES = {"sct_last_error": ctypes.c_char_p}
 

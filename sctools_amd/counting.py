@@ -145,9 +145,16 @@ class MoleculeCounter:
     ``read_counts=True`` also keeps the reads of every molecule (8 more bytes per table slot), which
     ``collapse()``, ``pairs(reads=True)`` and ``saturation(collapsed=True)`` need: they merge a UMI
     into the best-supported UMI one base away under the same barcode (include/sctools_hip.h,
-    "collapsing UMIs one base apart")."""
+    "collapsing UMIs one base apart").
 
-    def __init__(self, whitelist_size, umi_length, encoding='ThreeBit', capacity_hint=1 << 20, read_counts=False):
+    ``device`` is the HIP ordinal the counter lives on (default: the device current when it is
+    made).  Every method works whatever device is current and leaves it as it was; device pointers
+    and streams given to the ``*_device`` methods belong to the counter's device.  Counters fed
+    different pieces of the reads -- one per file or lane, or one per GPU -- become one with
+    ``merge``."""
+
+    def __init__(self, whitelist_size, umi_length, encoding='ThreeBit', capacity_hint=1 << 20, read_counts=False,
+                 device=None):
         kinds = {'ThreeBit': 3, 'TwoBit': 2, 3: 3, 2: 2}
         if encoding not in kinds:
             raise ValueError("encoding must be 'ThreeBit' or 'TwoBit'")
@@ -165,8 +172,12 @@ class MoleculeCounter:
         self._lib = _lib.lib()
         self._h = _vp()
         self.read_counts = bool(read_counts)
-        create = self._lib.sct_molecules_create_counted if self.read_counts else self._lib.sct_molecules_create
-        _lib.check(create(nw, kind, L, int(capacity_hint), ctypes.byref(self._h)))
+        self.device = None if device is None else int(device)
+        if self.device is not None and self.device < 0:
+            raise ValueError("device must be a HIP ordinal (or None for the current device)")
+        _lib.check(self._lib.sct_molecules_create_ex(nw, kind, L, int(capacity_hint), int(self.read_counts),
+                                                     -1 if self.device is None else self.device,
+                                                     ctypes.byref(self._h)))
 
     def _need_read_counts(self, what):
         if not self.read_counts:
@@ -249,6 +260,33 @@ class MoleculeCounter:
         self._need_read_counts("collapse_device")
         _lib.check(self._lib.sct_molecules_collapse(self._h, _vp(collapsed_ptr), _vp(ncorrected_ptr or None),
                                                     _vp(stream)))
+
+    def merge_device(self, other, stream=0):
+        """``merge`` enqueued on ``stream`` (of this counter's device; sct_molecules_merge): it waits
+        for the earlier work of both counters on any stream, and their later work waits for it."""
+        if not isinstance(other, MoleculeCounter):
+            raise TypeError("merge needs a MoleculeCounter, not %s" % type(other).__name__)
+        if other is self:
+            raise ValueError("a MoleculeCounter cannot be merged into itself")
+        if not self._h or not other._h:
+            raise ValueError("merge: %s counter is closed" % ("this" if not self._h else "the other"))
+        mine = (self.size, self.kind, self.umi_length, self.read_counts)
+        theirs = (other.size, other.kind, other.umi_length, other.read_counts)
+        for name, a, b in zip(("whitelist_size", "encoding", "umi_length", "read_counts"), mine, theirs):
+            if a != b:
+                raise ValueError("merge: the counters' %s differ (%r and %r)" % (name, a, b))
+        _lib.check(self._lib.sct_molecules_merge(self._h, other._h, _vp(stream)))
+        return self
+
+    def merge(self, other):
+        """Add another counter to this one, on the device: afterwards this counter is what it would
+        be had it been fed its own reads and then ``other``'s -- reads, molecules (the union: a
+        molecule seen by both counts once), tallies, total, per-molecule reads, and so ``collapse()``.
+        ``other`` must have the same whitelist_size, umi_length, encoding and read_counts; it may live
+        on another device, is not changed and stays usable.  The table grows first if it has to.
+        TypeError for anything but a MoleculeCounter; ValueError for this counter itself, a closed
+        counter or differing parameters.  Returns self."""
+        return self.merge_device(other)
 
     def info(self):
         """dict(nmolecules, total, capacity)."""

@@ -43,12 +43,20 @@
 // Every shared write of the pass is an atomic and nothing it reads changes, so there is no
 // inter-workgroup protocol.  fetch_counted sorts (key, slot) pairs and recomputes each row's parent
 // with the same device function.
+//
+// Merging (include/sctools_hip.h, "merging molecule counters"): the rows of another counter -- its
+// table in place when both live on one device, its occupied rows compacted and copied into pool
+// scratch when they do not -- go through the insert's own claim, one row per molecule with the
+// molecule's reads as its count.  The target is grown first (molecules_merge_plan.h) so that every
+// row may be new at a load of at most 1/2; reads[] and the tally are added by a kernel of their own.
+// A counter's calls make its device current for their duration (DeviceGuard).
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 
 #include "mix64.h"
 #include "molecules_key.h"
+#include "molecules_merge_plan.h"
 #include "sct_common.h"
 #include "umi_neighbours.h"
 
@@ -58,8 +66,8 @@ typedef unsigned long long u64;
 
 constexpr int WG = 256;
 constexpr u64 EMPTY = ~0ull;
-constexpr int64_t kMinCapacity = 64;
-constexpr int64_t kMaxCapacity = 1LL << 31;
+constexpr int64_t kMinCapacity = sct::kMolMinCapacity;
+constexpr int64_t kMaxCapacity = sct::kMolMaxCapacity;
 // device words of a molecule counter; W_TALLY .. W_TALLY + 2 = no match, ambiguous, bad UMI
 enum { W_SIZE = 0, W_OVERFLOW = 1, W_ERROR = 2, W_CURSOR = 3, W_TALLY = 4, W_NWORDS = 8 };
 // LDS pre-aggregation: a tile of kTile reads in a table of 2 * kTile slots (load <= 1/2)
@@ -452,6 +460,58 @@ __global__ void __launch_bounds__(WG) molecules_split_kernel(const u64* __restri
   }
 }
 
+// ---- merge (include/sctools_hip.h, "merging molecule counters")
+
+// The rows (keys[], cnt[] or NULL, n) of another counter into the table `t`: its own table as it
+// stands (n = its capacity; a row equal to EMPTY is an empty slot and is skipped) or its occupied
+// rows, dense.  A row is one molecule: the key is claimed in `t` by the insert's rule -- the lane
+// whose CAS took the slot, and only that lane, adds 1 to molecules[index] -- and, COUNTED, the row's
+// reads are added to the slot's.  The source is read once, coalesced and past the caches; the plain
+// instantiation never looks at cnt.  Claims are summed per wave into the size word.  reads, the
+// tally and total are not this kernel's (molecules_add_kernel, the host).
+template <bool COUNTED>
+__global__ void __launch_bounds__(WG) molecules_merge_kernel(Set t, const u64* __restrict__ keys,
+                                                             const u64* __restrict__ cnt, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * WG;
+  const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
+  const int64_t iters = (n + stride - 1) / stride;  // the same for every lane: the wave stays whole
+  int claims = 0;
+  for (int64_t it = 0; it < iters; ++it) {
+    const int64_t i = it * stride + gid;
+    u64 key = EMPTY, count = 0;
+    if (i < n) {
+      key = __builtin_nontemporal_load(&keys[i]);
+      if (COUNTED) count = __builtin_nontemporal_load(&cnt[i]);
+    }
+    if (key == EMPTY) continue;
+    u64 slot = NO_SLOT;
+    const bool claimed = set_claim<COUNTED>(t.keys, t.mask, t.words, key, &slot);
+    if (COUNTED && slot != NO_SLOT) atomicAdd(&t.cnt[slot], count);
+    if (!claimed) continue;
+    atomicAdd(&t.molecules[sct::mol_key_index(key, t.umi_bits)], 1ull);
+    ++claims;
+  }
+  for (int o = 32; o > 0; o >>= 1) claims += __shfl_xor(claims, o);
+  if ((threadIdx.x & 63) == 0 && claims > 0) atomicAdd(&t.words[W_SIZE], (u64)claims);
+}
+
+// reads[nw] += the other counter's, and its three tallies (`words` is its device words or a copy)
+__global__ void __launch_bounds__(WG) molecules_add_kernel(u64* __restrict__ reads, u64* __restrict__ words,
+                                                           const u64* __restrict__ from_reads,
+                                                           const u64* __restrict__ from_words, int64_t nw) {
+  const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
+  for (int64_t i = gid; i < nw; i += (int64_t)gridDim.x * WG) reads[i] += from_reads[i];
+  if (gid < 3) words[W_TALLY + gid] += from_words[W_TALLY + gid];
+}
+
+// the reads of the compacted (key, slot) pairs: the dense rows' cnt[]
+__global__ void __launch_bounds__(WG) molecules_gather_counts_kernel(const u64* __restrict__ cnt,
+                                                                     const uint32_t* __restrict__ slots, int64_t rows,
+                                                                     u64* __restrict__ out) {
+  for (int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WG)
+    out[r] = cnt[slots[r]];
+}
+
 inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap = 256 * 8) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, sct::ceil_div(n, per_block)));
 }
@@ -473,6 +533,34 @@ struct sct_molecules {
 };
 
 namespace {
+
+// A device made current for a scope, and the caller's put back: a counter's calls run on the
+// counter's device (its allocations, the pool, the thread's host stage and every launch follow the
+// current device) whatever device the caller had current.
+struct DeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  hipError_t e;
+  explicit DeviceGuard(int device) {
+    e = hipGetDevice(&prev);
+    if (e == hipSuccess && prev != device) {
+      e = hipSetDevice(device);
+      switched = e == hipSuccess;
+    }
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+  ~DeviceGuard() {
+    if (switched) (void)hipSetDevice(prev);
+  }
+};
+
+// in every call on a counter, after the argument checks and before the counter is used: its device
+// is current until the call returns
+#define SCT_ON_DEVICE_OF(c)                                                                       \
+  DeviceGuard on_device_((c)->device);                                                            \
+  if (on_device_.e != hipSuccess)                                                                 \
+  return sct::fail(SCT_E_HIP, "molecule counter's device %d: %s", (c)->device, hipGetErrorString(on_device_.e))
 
 int alloc_keys(u64** keys, int64_t capacity, hipStream_t s) {
   hipError_t e = hipMalloc((void**)keys, (size_t)capacity * 8);
@@ -721,13 +809,156 @@ int counts_copy(sct_molecules* c, uint64_t* reads, uint64_t* molecules, uint64_t
   return leave(c, s);
 }
 
+// ---- merge
+
+int merge_check(const sct_molecules* dst, const sct_molecules* src) {
+  SCT_CHECK(dst != src, "a molecule counter cannot be merged into itself");
+  SCT_CHECK(dst->t.nw == src->t.nw, "merge: the counters' nw differ (%lld and %lld)", (long long)dst->t.nw,
+            (long long)src->t.nw);
+  SCT_CHECK(dst->t.kind == src->t.kind, "merge: the counters' kind differ (%d and %d)", dst->t.kind, src->t.kind);
+  SCT_CHECK(dst->t.umi_bits == src->t.umi_bits, "merge: the counters' L differ (%d and %d)",
+            dst->t.umi_bits / dst->t.kind, src->t.umi_bits / src->t.kind);
+  SCT_CHECK(dst->counted == src->counted, "merge: one counter keeps read counts and the other does not");
+  return SCT_OK;
+}
+
+inline size_t up256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// src's occupied rows, dense and unsorted, into a pool block on src's device on `ss` (src's device
+// is current): keys[rows], then cnt[rows] for a counted counter (the block's tail holds the slots
+// the counts were gathered through).
+int merge_compact(sct_molecules* src, int64_t rows, hipStream_t ss, void** blk) {
+  const size_t b8 = up256((size_t)rows * 8);
+  SCT_HIP(sct::pool_alloc(blk, src->counted ? 2 * b8 + (size_t)rows * 4 : b8, ss));
+  uint8_t* b = static_cast<uint8_t*>(*blk);
+  u64* keys = reinterpret_cast<u64*>(b);
+  hipError_t e = hipMemsetAsync(&src->t.words[W_CURSOR], 0, 8, ss);
+  if (e == hipSuccess) {
+    const dim3 grid(grid_for(src->capacity, 1024));
+    if (src->counted) {
+      uint32_t* slots = reinterpret_cast<uint32_t*>(b + 2 * b8);
+      hipLaunchKernelGGL(molecules_compact_pairs_kernel, grid, dim3(WG), 0, ss, src->t.keys, src->capacity,
+                         &src->t.words[W_CURSOR], rows, keys, slots);
+      hipLaunchKernelGGL(molecules_gather_counts_kernel, dim3(grid_for(rows, 1024)), dim3(WG), 0, ss, src->t.cnt, slots,
+                         rows, reinterpret_cast<u64*>(b + b8));
+    } else {
+      hipLaunchKernelGGL(molecules_compact_kernel, grid, dim3(WG), 0, ss, src->t.keys, src->capacity,
+                         &src->t.words[W_CURSOR], rows, keys);
+    }
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) {
+    sct::pool_free(*blk, ss);
+    *blk = nullptr;
+    return sct::fail(SCT_E_HIP, "molecule merge, compacting the source: %s", hipGetErrorString(e));
+  }
+  return SCT_OK;
+}
+
+// dst <- dst + src on `s`, a stream of dst's device (the contract: include/sctools_hip.h).  `dense`:
+// src's rows, reads and words travel into scratch on dst's device first, which is the only way
+// between two devices; otherwise the kernels read src's own arrays.
+int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
+  const bool dense = dst->device != src->device || sct::tune(SCT_TUNE_MERGE_ROWS, 0) == 1;
+  // the two sizes, read once; nothing has changed when one of these steps fails
+  hipStream_t ss = s;  // src's side of a dense merge runs on the thread's stage stream of src's device
+  {
+    SCT_ON_DEVICE_OF(src);
+    if (dense) {
+      sct::HostStage* hs = sct::host_stage();
+      if (!hs) return SCT_E_HIP;
+      ss = hs->stream;
+    }
+    SCT_TRY(enter(src, ss));
+    SCT_TRY(read_words(src, ss));  // SCT_E_RANGE for a source that overflowed
+  }
+  const int64_t src_size = src->size_bound;
+  SCT_ON_DEVICE_OF(dst);
+  SCT_TRY(enter(dst, s));
+  SCT_TRY(read_words(dst, s));
+  const int64_t dst_size = dst->size_bound;
+  const int64_t cap = sct::mol_merge_capacity(dst->capacity, dst_size, src_size);
+  if (cap == 0)
+    return sct::fail(SCT_E_RANGE, "merge: %lld + %lld molecules need a table of more than %lld slots",
+                     (long long)dst_size, (long long)src_size, (long long)kMaxCapacity);
+  if (cap > dst->capacity) SCT_TRY(grow(dst, cap / dst->capacity, s));
+
+  const int64_t nw = dst->t.nw;
+  const u64* keys = src->t.keys;
+  const u64* cnt = src->t.cnt;
+  const u64* from_reads = src->t.reads;
+  const u64* from_words = src->t.words;
+  int64_t nrows = src->capacity;
+  void* src_blk = nullptr;
+  void* dst_blk = nullptr;
+  if (dense) {
+    if (src_size > 0) {
+      SCT_ON_DEVICE_OF(src);
+      SCT_TRY(merge_compact(src, src_size, ss, &src_blk));
+    }
+    {  // src's arrays are read by dst's stream from here on: after what src's stream has enqueued
+      SCT_ON_DEVICE_OF(src);
+      SCT_TRY(leave(src, ss));
+    }
+    const size_t b8 = up256((size_t)src_size * 8), bw = up256(W_NWORDS * 8), br = up256((size_t)nw * 8);
+    hipError_t e = sct::pool_alloc(&dst_blk, bw + br + (src->counted ? 2 : 1) * b8, s);
+    uint8_t* b = static_cast<uint8_t*>(dst_blk);
+    const uint8_t* from = static_cast<const uint8_t*>(src_blk);
+    if (e == hipSuccess && ss != s) e = hipStreamWaitEvent(s, src->last, 0);
+    if (e == hipSuccess) e = hipMemcpyPeerAsync(b, dst->device, src->t.words, src->device, W_NWORDS * 8, s);
+    if (e == hipSuccess) e = hipMemcpyPeerAsync(b + bw, dst->device, src->t.reads, src->device, (size_t)nw * 8, s);
+    if (e == hipSuccess && src_size > 0)
+      e = hipMemcpyPeerAsync(b + bw + br, dst->device, from, src->device, (size_t)src_size * 8, s);
+    if (e == hipSuccess && src_size > 0 && src->counted)
+      e = hipMemcpyPeerAsync(b + bw + br + b8, dst->device, from + b8, src->device, (size_t)src_size * 8, s);
+    if (e != hipSuccess) {
+      // nothing of dst has changed; the scratch goes back after what was enqueued
+      if (dst_blk) sct::pool_free(dst_blk, s);
+      (void)hipStreamSynchronize(s);
+      SCT_ON_DEVICE_OF(src);
+      if (src_blk) sct::pool_free(src_blk, ss);
+      return sct::fail(SCT_E_HIP, "molecule merge, copying the source's rows: %s", hipGetErrorString(e));
+    }
+    from_words = reinterpret_cast<const u64*>(b);
+    from_reads = reinterpret_cast<const u64*>(b + bw);
+    keys = reinterpret_cast<const u64*>(b + bw + br);
+    cnt = src->counted ? reinterpret_cast<const u64*>(b + bw + br + b8) : nullptr;
+    nrows = src_size;
+  }
+  if (src_size > 0) {
+    const dim3 grid(grid_for(nrows, 4 * WG));
+    if (dst->counted)
+      hipLaunchKernelGGL(molecules_merge_kernel<true>, grid, dim3(WG), 0, s, dst->t, keys, cnt, nrows);
+    else
+      hipLaunchKernelGGL(molecules_merge_kernel<false>, grid, dim3(WG), 0, s, dst->t, keys, nullptr, nrows);
+  }
+  hipLaunchKernelGGL(molecules_add_kernel, dim3(grid_for(nw, 4 * WG)), dim3(WG), 0, s, dst->t.reads, dst->t.words,
+                     from_reads, from_words, nw);
+  const hipError_t launched = hipGetLastError();
+  if (dst_blk) sct::pool_free(dst_blk, s);
+  dst->total += src->total;
+  dst->size_bound = dst_size + src_size;  // a bound: the next read of the size word makes it exact
+  int rc = launched == hipSuccess ? SCT_OK : sct::fail(SCT_E_HIP, "molecule merge: %s", hipGetErrorString(launched));
+  if (int rl = leave(dst, s); rc == SCT_OK) rc = rl;
+  {  // src's later work, and its scratch going back, wait for the merge that reads them
+    SCT_ON_DEVICE_OF(src);
+    if (ss != s) (void)hipStreamWaitEvent(ss, dst->last, 0);
+    if (src_blk) sct::pool_free(src_blk, ss);
+    if (int rl = leave(src, ss); rc == SCT_OK) rc = rl;
+  }
+  return rc;
+}
+
 }  // namespace
 
 namespace {
 
-int create(int64_t nw, int kind, int L, int64_t capacity_hint, bool counted, sct_molecules** out) {
+int create(int64_t nw, int kind, int L, int64_t capacity_hint, int flags, int device, sct_molecules** out) {
   SCT_CHECK(out != nullptr, "molecule counter is NULL");
   *out = nullptr;
+  SCT_CHECK((flags & ~SCT_MOLECULES_COUNTED) == 0, "unknown flags 0x%x", (unsigned)flags);
+  const bool counted = (flags & SCT_MOLECULES_COUNTED) != 0;
+  SCT_CHECK(device >= -1, "device %d: a HIP ordinal, or -1 for the current device", device);
   SCT_CHECK(nw >= 1 && nw < (1LL << 31), "nw %lld outside [1, 2^31)", (long long)nw);
   SCT_CHECK(kind == 2 || kind == 3, "kind must be 2 (TwoBit) or 3 (ThreeBit)");
   SCT_CHECK(L >= 1, "UMI length L must be >= 1");
@@ -738,13 +969,24 @@ int create(int64_t nw, int kind, int L, int64_t capacity_hint, bool counted, sct
             (long long)capacity_hint);
   int64_t cap = kMinCapacity;
   while (cap < capacity_hint) cap *= 2;
+  hipError_t e = hipSuccess;
+  if (device < 0) {
+    e = hipGetDevice(&device);
+  } else {
+    int ndev = 0;
+    e = hipGetDeviceCount(&ndev);
+    SCT_CHECK(e != hipSuccess || device < ndev, "device %d: %d device(s) are visible", device, ndev);
+  }
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule counter: %s", hipGetErrorString(e));
+  DeviceGuard on_device(device);
+  if (on_device.e != hipSuccess)
+    return sct::fail(SCT_E_HIP, "molecule counter on device %d: %s", device, hipGetErrorString(on_device.e));
   auto* c = new sct_molecules();
+  c->device = device;
   const auto fail_with = [&](int rc) {
     sct_molecules_destroy(c);
     return rc;
   };
-  hipError_t e = hipGetDevice(&c->device);
-  if (e != hipSuccess) return fail_with(sct::fail(SCT_E_HIP, "molecule counter: %s", hipGetErrorString(e)));
   sct::HostStage* hs = sct::host_stage();
   if (!hs) return fail_with(SCT_E_HIP);
   c->capacity = cap;
@@ -777,16 +1019,22 @@ int create(int64_t nw, int kind, int L, int64_t capacity_hint, bool counted, sct
 
 }  // namespace
 
+extern "C" int sct_molecules_create_ex(int64_t nw, int kind, int L, int64_t capacity_hint, int flags, int device,
+                                       sct_molecules** out) {
+  return create(nw, kind, L, capacity_hint, flags, device, out);
+}
+
 extern "C" int sct_molecules_create(int64_t nw, int kind, int L, int64_t capacity_hint, sct_molecules** out) {
-  return create(nw, kind, L, capacity_hint, false, out);
+  return sct_molecules_create_ex(nw, kind, L, capacity_hint, 0, -1, out);
 }
 
 extern "C" int sct_molecules_create_counted(int64_t nw, int kind, int L, int64_t capacity_hint, sct_molecules** out) {
-  return create(nw, kind, L, capacity_hint, true, out);
+  return sct_molecules_create_ex(nw, kind, L, capacity_hint, SCT_MOLECULES_COUNTED, -1, out);
 }
 
 extern "C" int sct_molecules_destroy(sct_molecules* c) {
   if (!c) return SCT_OK;
+  DeviceGuard on_device(c->device);  // (best effort: the frees below name their memory themselves)
   if (c->last) {
     if (c->used) (void)hipEventSynchronize(c->last);  // the work it enqueued reads these arrays
     (void)hipEventDestroy(c->last);
@@ -806,6 +1054,7 @@ extern "C" int sct_molecules_update(sct_molecules* c, const int32_t* d_index, co
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (n == 0) return SCT_OK;
   SCT_CHECK(d_index != nullptr && d_umi != nullptr, "NULL index or umi");
+  SCT_ON_DEVICE_OF(c);
   bool range = false;
   const int rc = update_device(c, d_index, d_umi, n, sct::as_stream(stream), &range);
   return rc == SCT_OK && range ? range_error(c) : rc;
@@ -816,6 +1065,7 @@ extern "C" int sct_molecules_update_host(sct_molecules* c, const int32_t* index,
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (n == 0) return SCT_OK;
   SCT_CHECK(index != nullptr && umi != nullptr, "NULL index or umi");
+  SCT_ON_DEVICE_OF(c);
   sct::HostStage* hs = sct::host_stage();
   if (!hs) return SCT_E_HIP;
   hipStream_t s = hs->stream;
@@ -841,6 +1091,7 @@ extern "C" int sct_molecules_update_host(sct_molecules* c, const int32_t* index,
 extern "C" int sct_molecules_info(sct_molecules* c, int64_t* nmolecules, int64_t* total, int64_t* capacity) {
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (nmolecules) {
+    SCT_ON_DEVICE_OF(c);
     sct::HostStage* hs = sct::host_stage();
     if (!hs) return SCT_E_HIP;
     if (int rc = enter(c, hs->stream); rc != SCT_OK) return rc;
@@ -855,11 +1106,13 @@ extern "C" int sct_molecules_info(sct_molecules* c, int64_t* nmolecules, int64_t
 extern "C" int sct_molecules_counts(sct_molecules* c, uint64_t* d_reads, uint64_t* d_molecules, uint64_t* d_tally,
                                     void* stream) {
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_ON_DEVICE_OF(c);
   return counts_copy(c, d_reads, d_molecules, d_tally, hipMemcpyDeviceToDevice, sct::as_stream(stream));
 }
 
 extern "C" int sct_molecules_counts_host(sct_molecules* c, uint64_t* reads, uint64_t* molecules, uint64_t* tally) {
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_ON_DEVICE_OF(c);
   sct::HostStage* hs = sct::host_stage();
   if (!hs) return SCT_E_HIP;
   const int rc = counts_copy(c, reads, molecules, tally, hipMemcpyDeviceToHost, hs->stream);
@@ -871,6 +1124,7 @@ extern "C" int sct_molecules_counts_host(sct_molecules* c, uint64_t* reads, uint
 extern "C" int sct_molecules_fetch(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, int64_t room, void* stream) {
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_ON_DEVICE_OF(c);
   return fetch_device(c, d_index, d_umi, room, sct::as_stream(stream));
 }
 
@@ -878,6 +1132,7 @@ extern "C" int sct_molecules_fetch_host(sct_molecules* c, int32_t* index, uint64
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   SCT_CHECK(room == 0 || (index && umi), "NULL output");
+  SCT_ON_DEVICE_OF(c);
   sct::HostStage* hs = sct::host_stage();
   if (!hs) return SCT_E_HIP;
   hipStream_t s = hs->stream;
@@ -902,6 +1157,7 @@ extern "C" int sct_molecules_collapse(sct_molecules* c, uint64_t* d_collapsed, u
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (int rc = need_counted(c); rc != SCT_OK) return rc;
   SCT_CHECK(d_collapsed != nullptr, "NULL output");
+  SCT_ON_DEVICE_OF(c);
   return collapse_device(c, d_collapsed, d_ncorrected, sct::as_stream(stream));
 }
 
@@ -909,6 +1165,7 @@ extern "C" int sct_molecules_collapse_host(sct_molecules* c, uint64_t* collapsed
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (int rc = need_counted(c); rc != SCT_OK) return rc;
   SCT_CHECK(collapsed != nullptr, "NULL output");
+  SCT_ON_DEVICE_OF(c);
   sct::HostStage* hs = sct::host_stage();
   if (!hs) return SCT_E_HIP;
   hipStream_t s = hs->stream;
@@ -929,6 +1186,7 @@ extern "C" int sct_molecules_fetch_counted(sct_molecules* c, int32_t* d_index, u
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_ON_DEVICE_OF(c);
   hipStream_t s = sct::as_stream(stream);
   int64_t rows = 0;
   if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
@@ -942,6 +1200,7 @@ extern "C" int sct_molecules_fetch_counted_host(sct_molecules* c, int32_t* index
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (int rc = need_counted(c); rc != SCT_OK) return rc;
   SCT_CHECK(room == 0 || (index && umi && mreads), "NULL output");
+  SCT_ON_DEVICE_OF(c);
   sct::HostStage* hs = sct::host_stage();
   if (!hs) return SCT_E_HIP;
   hipStream_t s = hs->stream;
@@ -961,4 +1220,10 @@ extern "C" int sct_molecules_fetch_counted_host(sct_molecules* c, int32_t* index
     if (blk.ok()) blk.note(hipMemcpyAsync(index, b + 3 * b8, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
   }
   return blk.finish(rc, "molecule fetch");
+}
+
+extern "C" int sct_molecules_merge(sct_molecules* dst, sct_molecules* src, void* stream) {
+  SCT_CHECK(dst != nullptr && src != nullptr, "molecule counter is NULL");
+  if (int rc = merge_check(dst, src); rc != SCT_OK) return rc;
+  return merge(dst, src, sct::as_stream(stream));
 }

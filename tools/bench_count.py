@@ -12,7 +12,10 @@ the bytes each moves over PCIe.  Then MoleculeCounter.update_device on 100M (ind
 against DeviceCounter on composite keys plus sct_index_tally, with a molecule's reads far apart and
 adjacent (molecules_step; its rounds also go to profiles/ab_molecules_<tag>.jsonl).  Then, on the same
 reads, the counted MoleculeCounter and its UMI collapse against the plain one, an earlier library and
-the host (collapse_step; profiles/ab_umi_collapse_<tag>.jsonl).
+the host (collapse_step; profiles/ab_umi_collapse_<tag>.jsonl).  Then MoleculeCounter.merge of the
+second half's counter into the first's against an update of as many reads as the source has molecules
+and against the host route, with the existing molecule rows again beside an earlier library
+(merge_step; profiles/ab_molecules_merge_<tag>.jsonl).
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends
 the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
@@ -20,6 +23,7 @@ the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>
   python tools/bench_count.py --tag mi355x
   python tools/bench_count.py --tag mi355x --only molecules
   python tools/bench_count.py --tag mi355x --only collapse --parent-lib /path/to/earlier/libsctools_hip.so
+  python tools/bench_count.py --tag mi355x --only merge --parent-lib /path/to/earlier/libsctools_hip.so
 """
 import argparse
 import json
@@ -31,7 +35,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420, "collapse": 600}  # seconds
+STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420, "collapse": 600,
+         "merge": 600}  # seconds
 MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
 HBM_BYTES_PER_S = 8e12
 
@@ -447,6 +452,213 @@ def collapse_step(args):
     return out
 
 
+def merge_step(args):
+    """MoleculeCounter.merge on the molecules step's input (as drawn) split in two halves by read
+    position, so that molecules straddle the halves: `a` holds the first half, `b` the second, tables
+    sized up front so that nothing grows.  Alternating within every round, plain and counted: (m) the
+    merge of b into a fresh a, the table read in place; (d) the same merge with b's rows compacted and
+    copied first (SCT_TUNE_MERGE_ROWS 1, the route between two devices, here on one); (x) with two
+    devices visible, b on the second device; (y) the yardstick: sct_molecules_update, form 0, into a
+    fresh a of as many reads as b has molecules -- b's molecules once each in random order, the same
+    claims on the same table.  Then, once, the host route of today: b.pairs(reads=True) to the host and
+    every row replayed mreads times through update.  Then the existing rows of the molecules and
+    collapse steps again (the plain and the counted update of all reads, both orders, the three
+    forms) in this library and, alternating, in --parent-lib; they agree when the medians differ by
+    no more than the parent's own min-max spread, and the step fails (its profile written) when not.
+    Every round is one line of profiles/ab_molecules_merge_<tag>.jsonl, the summary its last."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, counting
+
+    nw, UL, n, hint, pool, inputs = _molecules_input(args)
+    dev = torch.device("cuda")
+    vp = ctypes.c_void_p
+    di, du, _ = inputs["shuffled"]
+    half = n // 2
+    halves = [(di[:half], du[:half]), (di[half:], du[half:])]
+    two_devices = _lib.device_count() >= 2
+
+    def fed(part, counted, capacity, device=None):
+        mc = counting.MoleculeCounter(nw, UL, capacity_hint=capacity, read_counts=counted, device=device)
+        i, u = halves[part]
+        if device not in (None, 0):
+            with torch.cuda.device(device):
+                i, u = i.to("cuda:%d" % device), u.to("cuda:%d" % device)
+                mc.update_device(i.data_ptr(), u.data_ptr(), i.numel())
+                torch.cuda.synchronize()
+        else:
+            mc.update_device(i.data_ptr(), u.data_ptr(), i.numel())
+        torch.cuda.synchronize()
+        return mc
+
+    def facts_of(mc):
+        reads, molecules, n_none, n_amb, n_bad = mc.counts()
+        info = mc.info()
+        return int(reads.sum()), int(molecules.sum()), n_none, n_amb, n_bad, info["nmolecules"], info["total"]
+
+    out = {"n": n, "nw": nw, "umi_length": UL, "two_devices": two_devices, "parent_lib": bool(args.parent_lib)}
+    lines, whole = [], None
+    for counted in (False, True):
+        name = "counted" if counted else "plain"
+        b = fed(1, counted, hint)
+        nb = len(b)
+        probe = fed(0, counted, hint)
+        na = len(probe)
+        probe.close()
+        cap = 64
+        while cap // 2 < na + nb:
+            cap *= 2
+        # the yardstick's reads: b's molecules, once each, in random order
+        y_index = torch.empty(nb, dtype=torch.int32, device=dev)
+        y_umi = torch.empty(nb, dtype=torch.int64, device=dev)
+        b.fetch_device(y_index.data_ptr(), y_umi.data_ptr(), nb)
+        torch.cuda.synchronize()
+        perm = torch.randperm(nb, device=dev, generator=torch.Generator(device=dev).manual_seed(11))
+        y_index, y_umi = y_index[perm].contiguous(), y_umi[perm].contiguous()
+        del perm
+        b_far = fed(1, counted, hint, device=1) if two_devices else None
+        torch.cuda.synchronize()
+
+        def timed_merge(src, rows):
+            a = fed(0, counted, cap)
+            with _lib.tuning(merge_rows=rows), a:
+                def go():
+                    a.merge_device(src)
+                    torch.cuda.synchronize()
+                ms = _time_ms(go)
+                f = facts_of(a)
+                assert a.info()["capacity"] == cap  # sized up front: the merge did not grow it
+            return ms, f
+
+        def timed_yardstick():
+            a = fed(0, counted, cap)
+            with _lib.tuning(count_preagg=0), a:
+                def go():
+                    a.update_device(y_index.data_ptr(), y_umi.data_ptr(), nb)
+                    torch.cuda.synchronize()
+                ms = _time_ms(go)
+                nmol = len(a)
+            return ms, nmol
+
+        timed_merge(b, 0), timed_merge(b, 1), timed_yardstick()  # warm-up: code objects, pool
+        rounds = []
+        for r in range(args.rounds):
+            row = {"what": name, "round": r, "n": n, "src_molecules": nb, "dst_molecules": na, "dst_capacity": cap}
+            ms, f = timed_merge(b, 0)
+            assert whole is None or f == whole, (f, whole)  # every route, form and round: the same numbers
+            whole = f
+            row["merge_ms"] = round(ms, 3)
+            ms, f = timed_merge(b, 1)
+            assert f == whole, (f, whole)
+            row["merge_compacted_ms"] = round(ms, 3)
+            if b_far is not None:
+                ms, f = timed_merge(b_far, 0)
+                assert f == whole, (f, whole)
+                row["merge_other_device_ms"] = round(ms, 3)
+            ms, nmol = timed_yardstick()
+            assert nmol == whole[5], (nmol, whole)
+            row["update_form0_src_molecules_ms"] = round(ms, 3)
+            rounds.append(row)
+        lines += rounds
+        res = out[name] = {"src_molecules": nb, "dst_molecules": na, "merged_molecules": whole[5],
+                           "dst_capacity": cap, "src_capacity": b.info()["capacity"]}
+        for key in rounds[0]:
+            if key.endswith("_ms"):
+                v = [row[key] for row in rounds]
+                res[key] = {"median": round(float(np.median(v)), 3), "min": min(v), "max": max(v)}
+        res["merge_over_yardstick"] = round(res["merge_ms"]["median"] / res["update_form0_src_molecules_ms"]["median"], 3)
+        res["merge_ns_per_src_molecule"] = round(res["merge_ms"]["median"] * 1e6 / nb, 3)
+        if counted:  # the host route a user has today (it loses b's tallies; the molecules and reads are right)
+            a = fed(0, True, cap)
+            got = {}
+            fetch_ms = _time_ms(lambda: got.update(rows=b.pairs(reads=True)))
+            index, umi, mreads = got["rows"]
+
+            def replay():
+                a.update(np.repeat(index, mreads), np.repeat(umi, mreads))
+            replay_ms = _time_ms(replay)
+            assert len(a) == whole[5]
+            a.close()
+            out["host_route"] = {"pairs_reads_ms": round(fetch_ms, 1), "repeat_and_update_ms": round(replay_ms, 1),
+                                 "total_ms": round(fetch_ms + replay_ms, 1), "reads_replayed": int(mreads.sum())}
+            del index, umi, mreads, got
+        if b_far is not None:
+            b_far.close()
+        b.close()
+        del y_index, y_umi
+    reads, molecules, n_none, n_amb, n_bad, nmol, total = whole
+    assert total == n and reads + n_none + n_amb + n_bad == n and molecules == nmol
+    out.update(reads=reads, molecules=molecules, n_none=n_none, n_ambiguous=n_amb, n_bad_umi=n_bad)
+
+    # the existing rows again, this library and the parent's alternating
+    old = None
+    if args.parent_lib:
+        old = ctypes.CDLL(os.path.abspath(args.parent_lib))
+        for fn in ("sct_tune_set", "sct_molecules_create", "sct_molecules_create_counted", "sct_molecules_update",
+                   "sct_molecules_counts_host", "sct_molecules_destroy"):
+            getattr(old, fn).argtypes = _lib.SIGNATURES[fn]
+
+    def full_update(lib, mode, d_index, d_umi, counted):
+        h = vp()
+        assert lib.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], mode) == 0
+        create = lib.sct_molecules_create_counted if counted else lib.sct_molecules_create
+        assert create(nw, 3, UL, hint, ctypes.byref(h)) == 0
+        try:
+            def go():
+                assert lib.sct_molecules_update(h, vp(d_index.data_ptr()), vp(d_umi.data_ptr()), n, None) == 0
+                torch.cuda.synchronize()
+            ms = _time_ms(go)
+            reads, molecules, tally = np.empty(nw, np.uint64), np.empty(nw, np.uint64), np.empty(3, np.uint64)
+            assert lib.sct_molecules_counts_host(h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)) == 0
+        finally:
+            lib.sct_molecules_destroy(h)
+            lib.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], -1)
+        return ms, (int(reads.sum()), int(molecules.sum()), int(tally[0]), int(tally[1]), int(tally[2]))
+
+    libs = {"this": _lib.lib()}
+    if old:
+        libs["parent"] = old
+    out["existing_rows"] = {}
+    for which, (xi, xu, _) in inputs.items():
+        full_update(_lib.lib(), 1, xi, xu, True)
+        rounds = []
+        for r in range(args.rounds):
+            row = {"what": "existing", "input": which, "round": r}
+            for m, mname in MODES.items():
+                cell = {}
+                for counted in (False, True):
+                    for lname, lib in libs.items():
+                        ms, f = full_update(lib, m, xi, xu, counted)
+                        assert f == whole[:5], (f, whole)
+                        cell["%s_%s_ms" % ("counted" if counted else "plain", lname)] = round(ms, 3)
+                row[mname] = cell
+            rounds.append(row)
+        lines += rounds
+        res = out["existing_rows"][which] = {}
+        for mname in MODES.values():
+            res[mname] = {}
+            for key in rounds[0][mname]:
+                v = [row[mname][key] for row in rounds]
+                res[mname][key] = {"median": round(float(np.median(v)), 3), "min": min(v), "max": max(v)}
+            for kind in ("plain", "counted") if old else ():
+                a, b = res[mname][kind + "_this_ms"], res[mname][kind + "_parent_ms"]
+                res[mname][kind + "_vs_parent"] = {"median_difference_ms": round(a["median"] - b["median"], 3),
+                                                   "parent_spread_ms": round(b["max"] - b["min"], 3),
+                                                   "agree": abs(a["median"] - b["median"]) <= b["max"] - b["min"]}
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "ab_molecules_merge_%s.jsonl" % args.tag), "w") as f:
+        for row in lines:
+            f.write(json.dumps(row, sort_keys=True) + "\n")
+        f.write(json.dumps(out, sort_keys=True) + "\n")
+    apart = ["%s/%s/%s: %s" % (which, mname, kind, v[kind + "_vs_parent"])
+             for which, modes in out["existing_rows"].items() for mname, v in modes.items()
+             for kind in ("plain", "counted") if old and not v[kind + "_vs_parent"]["agree"]]
+    assert not apart, "an update differs from --parent-lib beyond that library's own spread: " + "; ".join(apart)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tag", default="run")
@@ -458,7 +670,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--n-collapse-host", type=int, default=200_000, help="molecules given to the dict collapse")
     ap.add_argument("--parent-lib", default="",
-                    help="collapse step: an earlier libsctools_hip.so to time beside this one")
+                    help="collapse and merge steps: an earlier libsctools_hip.so to time beside this one")
     ap.add_argument("--only", nargs="+", choices=sorted(STEPS), help="launch only these steps")
     args = ap.parse_args()
     if args.step:
@@ -466,6 +678,8 @@ def main():
             res = molecules_step(args)
         elif args.step == "collapse":
             res = collapse_step(args)
+        elif args.step == "merge":
+            res = merge_step(args)
         else:
             res = tally_step(args) if args.step == "tally" else counter_step(args.step[-1], args)
         print("RESULT " + json.dumps(res))
@@ -504,6 +718,10 @@ def main():
                            "host_ms": res["host_yardstick"]["total_scaled_ms"],
                            "ms": {which: {k: [v[c]["median"] for c in ("uncounted_ms", "counted_ms")]
                                           for k, v in modes.items()} for which, modes in res["inputs"].items()}}
+        elif "host_route" in res:
+            short[step] = {"n": res["n"], "molecules": res["molecules"], "host_ms": res["host_route"]["total_ms"],
+                           "ms": {k: [res[k]["merge_ms"]["median"], res[k]["update_form0_src_molecules_ms"]["median"]]
+                                  for k in ("plain", "counted")}}
         elif "modes" in res:
             short[step] = {"n": res["n"], "nunique": res["nunique"],
                            "ms": {k: v["median_ms"] for k, v in res["modes"].items()},
