@@ -5,25 +5,16 @@
 // its count and the global position of its first occurrence, so the rows come back in
 // first-occurrence order, which is Counter's iteration order.
 //
-// The table is open addressing over three parallel arrays of `capacity` (a power of two) slots:
-// keys (EMPTY = 2^64 - 1), counts (0) and first (INT64_MAX).  A lane claims a slot with one 64-bit
-// atomicCAS(&keys[s], EMPTY, code); whoever finds EMPTY or its own code there adds to counts[s]
-// and takes the min into first[s].  Counts and first positions are only ever touched by atomics
-// of their own, so nothing is published, no lane waits for another lane's store, and the probe
-// loop is bounded by the capacity (a full table sets the overflow word, never spins).
-// A key is written once and never changes, so a plain load that already shows the lane's own code
-// skips the CAS; a stale load can only show EMPTY, and then the CAS decides.
+// The table is open_table.h's (the claim-by-CAS probe, the bound on the load, the ordering of a
+// counter's calls) over three parallel arrays of `capacity` slots: keys, counts (0) and first
+// (INT64_MAX).  Whoever finds its code in a slot, claimed by itself or not, adds to counts[s] and
+// takes the min into first[s].
 //
 // EMPTY is itself a legal code (the 32-bp all-G TwoBit barcode), so that one key is counted in a
 // side slot outside the table (two words: count, first).  Key 0 needs no special case: the
 // arrays are initialised by a kernel, not by zero fill.
 //
-// The host keeps the load factor bounded: a batch goes in as sub-batches of at most capacity / 4
-// codes; the host tracks an upper bound of the claimed slots (the last size it read plus the
-// codes fed since) and reads the device's size word whenever the bound passes capacity / 2; a
-// true size above capacity / 2 grows the table (x4 while more than capacity / 2 codes of the
-// batch remain, else x2) and a rehash kernel re-inserts every (key, count, first) row by the
-// same claim rule.  The load therefore never passes 3/4.
+// Growth re-inserts every (key, count, first) row into the new table by the same claim rule.
 //
 // Pre-aggregation before the global atomics (SCT_TUNE_COUNT_PREAGG; DESIGN.md has the A/B):
 //   0  none: one claim + add + min per code;
@@ -41,24 +32,15 @@
 #include <algorithm>
 #include <vector>
 
-#include "mix64.h"
-#include "sct_common.h"
+#include "open_table.h"
 
 namespace {
 
-typedef unsigned long long u64;
+using namespace sct::open_table;
 
-constexpr int WG = 256;
-constexpr u64 EMPTY = ~0ull;
 constexpr long long NO_FIRST = LLONG_MAX;
-constexpr int64_t kMinCapacity = 64;
-constexpr int64_t kMaxCapacity = 1LL << 31;  // slot numbers are uint32 in the fetch
-// device words of a counter
-enum { W_SIZE = 0, W_OVERFLOW = 1, W_SIDE_COUNT = 2, W_SIDE_FIRST = 3, W_CURSOR = 4, W_NWORDS = 8 };
-// LDS pre-aggregation: a tile of kTile codes in a table of 2 * kTile slots (load <= 1/2)
-constexpr int kItems = 4;
-constexpr int kTile = WG * kItems;
-constexpr int kLdsSlots = 2 * kTile;
+// the counter's own device words
+enum { W_SIDE_COUNT = W_OWN, W_SIDE_FIRST, W_CURSOR };
 constexpr uint32_t EMPTY32 = 0xFFFFFFFFu;
 
 struct Table {
@@ -69,8 +51,6 @@ struct Table {
   u64 mask;  // capacity - 1
 };
 
-using sct::mix64;
-
 // One (code, count, first) row into the table; true when this call claimed a new slot.
 __device__ __forceinline__ bool table_add(const Table& t, u64 code, u64 count, long long first) {
   if (code == EMPTY) {  // the sentinel's own key: the side slot
@@ -78,30 +58,13 @@ __device__ __forceinline__ bool table_add(const Table& t, u64 code, u64 count, l
     atomicMin(reinterpret_cast<long long*>(&t.words[W_SIDE_FIRST]), first);
     return false;
   }
-  u64 s = mix64(code) & t.mask;
-  for (u64 probe = 0; probe <= t.mask; ++probe) {
-    u64 k = t.keys[s];
-    bool claimed = false;
-    if (k == EMPTY) {
-      k = atomicCAS(&t.keys[s], EMPTY, code);
-      claimed = k == EMPTY;
-      if (claimed) k = code;
-    }
-    if (k == code) {
-      atomicAdd(&t.counts[s], count);
-      atomicMin(&t.first[s], first);
-      return claimed;
-    }
-    s = (s + 1) & t.mask;
+  u64 slot;
+  const bool claimed = claim<true>(t.keys, t.mask, &t.words[W_OVERFLOW], code, &slot);
+  if (slot != NO_SLOT) {
+    atomicAdd(&t.counts[slot], count);
+    atomicMin(&t.first[slot], first);
   }
-  atomicOr(&t.words[W_OVERFLOW], 1ull);  // full table: the host fails with SCT_E_RANGE
-  return false;
-}
-
-// One add of the wave's claimed slots to the size word.
-__device__ __forceinline__ void bump_size(const Table& t, int claims) {
-  for (int o = 32; o > 0; o >>= 1) claims += __shfl_xor(claims, o);
-  if ((threadIdx.x & 63) == 0 && claims > 0) atomicAdd(&t.words[W_SIZE], (u64)claims);
+  return claimed;
 }
 
 __global__ void __launch_bounds__(WG) counter_init_kernel(Table t, int64_t capacity, int init_words) {
@@ -128,23 +91,10 @@ __global__ void __launch_bounds__(WG) counter_insert_kernel(Table t, const u64* 
     const int64_t i = it * stride + gid;
     const bool active = i < n;
     const u64 c = active ? __builtin_nontemporal_load(&codes[i]) : 0ull;
-    u64 count = 1;
-    bool rep = active;
-    if (MERGE) {
-      const int lane = threadIdx.x & 63;
-      u64 todo = __ballot(active);
-      while (todo) {  // wave-uniform: one distinct code leaves per pass
-        const int leader = __ffsll((long long)todo) - 1;
-        const u64 lc = __shfl(c, leader);
-        const u64 m = __ballot(active && c == lc);
-        if (lane == leader) count = (u64)__popcll(m);
-        else if (active && c == lc) rep = false;
-        todo &= ~m;
-      }
-    }
-    if (rep) claims += table_add(t, c, count, base + i) ? 1 : 0;
+    const Merged m = MERGE ? wave_merge(active, c) : Merged{active, 1};
+    if (m.rep) claims += table_add(t, c, m.count, base + i) ? 1 : 0;
   }
-  bump_size(t, claims);
+  add_claims(&t.words[W_SIZE], claims);
 }
 
 // A tile of kTile codes is grouped in an LDS table first (keys, counts, lowest offset in the tile),
@@ -172,25 +122,13 @@ __global__ void __launch_bounds__(WG) counter_insert_lds_kernel(Table t, const u
       const int64_t i = t0 + off;
       if (i >= n) continue;
       const u64 c = __builtin_nontemporal_load(&codes[i]);
-      bool placed = false;
-      if (c != EMPTY) {
-        uint32_t s = (uint32_t)mix64(c) & (kLdsSlots - 1);
-        for (int probe = 0; probe < kLdsSlots; ++probe) {
-          u64 k0 = lkey[s];
-          if (k0 == EMPTY) {
-            k0 = atomicCAS(&lkey[s], EMPTY, c);
-            if (k0 == EMPTY) k0 = c;
-          }
-          if (k0 == c) {
-            atomicAdd(&lcnt[s], 1u);
-            atomicMin(&loff[s], (uint32_t)off);
-            placed = true;
-            break;
-          }
-          s = (s + 1) & (kLdsSlots - 1);
-        }
+      const int s = c != EMPTY ? lds_claim(lkey, (uint32_t)sct::mix64(c) & (kLdsSlots - 1), c) : -1;
+      if (s >= 0) {
+        atomicAdd(&lcnt[s], 1u);
+        atomicMin(&loff[s], (uint32_t)off);
+      } else {
+        claims += table_add(t, c, 1, base + i) ? 1 : 0;
       }
-      if (!placed) claims += table_add(t, c, 1, base + i) ? 1 : 0;
     }
     __syncthreads();
     for (int s = threadIdx.x; s < kLdsSlots; s += WG) {
@@ -203,7 +141,7 @@ __global__ void __launch_bounds__(WG) counter_insert_lds_kernel(Table t, const u
     }
     __syncthreads();
   }
-  bump_size(t, claims);
+  add_claims(&t.words[W_SIZE], claims);
 }
 
 // every row of the old table into the new one (the size word carries over unchanged)
@@ -219,12 +157,11 @@ __global__ void __launch_bounds__(WG) counter_rehash_kernel(Table from, int64_t 
 __global__ void __launch_bounds__(WG) counter_compact_kernel(Table t, int64_t capacity, int64_t room,
                                                              long long* __restrict__ row_first,
                                                              uint32_t* __restrict__ row_slot) {
-  const int lane = threadIdx.x & 63;
   const int64_t stride = (int64_t)gridDim.x * WG;
   const int64_t iters = (capacity + stride - 1) / stride;
   for (int64_t it = 0; it < iters; ++it) {
     const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
-    bool occ = s < capacity && t.keys[s] != EMPTY;
+    const bool occ = s < capacity && t.keys[s] != EMPTY;
     if (s == 0 && t.words[W_SIDE_COUNT] != 0) {  // the thread of slot 0 also writes the side row
       const u64 at = atomicAdd(&t.words[W_CURSOR], 1ull);
       if ((int64_t)at < room) {
@@ -232,12 +169,7 @@ __global__ void __launch_bounds__(WG) counter_compact_kernel(Table t, int64_t ca
         row_slot[at] = EMPTY32;
       }
     }
-    const u64 m = __ballot(occ);
-    if (m == 0) continue;
-    u64 at = 0;
-    const int leader = __ffsll((long long)m) - 1;
-    if (lane == leader) at = atomicAdd(&t.words[W_CURSOR], (u64)__popcll(m));
-    at = __shfl(at, leader) + (u64)__popcll(m & ((1ull << lane) - 1ull));
+    const u64 at = compact_at(occ, &t.words[W_CURSOR]);
     if (occ && (int64_t)at < room) {
       row_first[at] = t.first[s];
       row_slot[at] = (uint32_t)s;
@@ -290,23 +222,10 @@ __global__ void __launch_bounds__(WG) index_tally_kernel(const int32_t* __restri
         if (mt) atomicAdd(&lneg[1], (uint32_t)__popcll(mt));
       }
       if (!valid) continue;
-      bool placed = false;
-      uint32_t s = ((uint32_t)v * 0x9E3779B1u) >> (32 - 11);
       static_assert(kLdsSlots == 1 << 11, "the hash shift assumes 2048 LDS slots");
-      for (int probe = 0; probe < kLdsSlots; ++probe) {
-        uint32_t k0 = lkey[s];
-        if (k0 == EMPTY32) {
-          k0 = atomicCAS(&lkey[s], EMPTY32, (uint32_t)v);
-          if (k0 == EMPTY32) k0 = (uint32_t)v;
-        }
-        if (k0 == (uint32_t)v) {
-          atomicAdd(&lcnt[s], 1u);
-          placed = true;
-          break;
-        }
-        s = (s + 1) & (kLdsSlots - 1);
-      }
-      if (!placed) atomicAdd(&counts[v], 1ull);  // (v < nw was checked above)
+      const int s = lds_claim(lkey, ((uint32_t)v * 0x9E3779B1u) >> (32 - 11), (uint32_t)v);
+      if (s >= 0) atomicAdd(&lcnt[s], 1u);
+      else atomicAdd(&counts[v], 1ull);  // (v < nw was checked above)
     }
     __syncthreads();
     for (int s = threadIdx.x; s < kLdsSlots; s += WG) {
@@ -322,23 +241,12 @@ __global__ void __launch_bounds__(WG) index_tally_kernel(const int32_t* __restri
   if (__ballot(bad) && lane == 0) atomicOr(err, 1ull);
 }
 
-inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap = 256 * 8) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, sct::ceil_div(n, per_block)));
-}
-
 }  // namespace
 
-struct sct_counter {
-  int device = 0;
-  int64_t capacity = 0;
-  Table t{};
-  u64* h_words = nullptr;  // page-locked read-back of the device words
-  int64_t total = 0;       // codes seen
-  int64_t size_bound = 0;  // claimed slots: the last size read plus the codes fed since
+struct sct_counter : Host {
+  sct_counter() : Host("counter") {}
+  Table t{};  // t.words is Host::words
   int64_t grows = 0;
-  hipEvent_t last = nullptr;  // the last work enqueued (another stream's call waits for it)
-  hipStream_t last_stream = nullptr;
-  bool used = false;
 };
 
 namespace {
@@ -364,33 +272,10 @@ int alloc_table(Table& t, int64_t capacity) {
   return SCT_OK;
 }
 
-// work on `s` starts after whatever the counter enqueued last on another stream
-int enter(sct_counter* c, hipStream_t s) {
-  if (c->used && c->last_stream != s) SCT_HIP(hipStreamWaitEvent(s, c->last, 0));
-  return SCT_OK;
-}
-
-int leave(sct_counter* c, hipStream_t s) {
-  SCT_HIP(hipEventRecord(c->last, s));
-  c->last_stream = s;
-  c->used = true;
-  return SCT_OK;
-}
-
-// the device words, read back after everything enqueued on `s`
-int read_words(sct_counter* c, hipStream_t s) {
-  SCT_HIP(hipMemcpyAsync(c->h_words, c->t.words, W_NWORDS * 8, hipMemcpyDeviceToHost, s));
-  SCT_HIP(hipStreamSynchronize(s));
-  if (c->h_words[W_OVERFLOW])
-    return sct::fail(SCT_E_RANGE, "counter table of %lld slots is full", (long long)c->capacity);
-  c->size_bound = (int64_t)c->h_words[W_SIZE];
-  return SCT_OK;
-}
-
 int grow(sct_counter* c, int64_t factor, hipStream_t s) {
-  const int64_t cap = c->capacity * factor;
-  if (cap > kMaxCapacity)
-    return sct::fail(SCT_E_RANGE, "counter cannot grow past %lld slots", (long long)kMaxCapacity);
+  const int64_t cap = sct::table_grown(c->capacity, factor);
+  if (cap == 0)
+    return sct::fail(SCT_E_RANGE, "counter cannot grow past %lld slots", (long long)sct::kTableMaxCapacity);
   Table nt = c->t;
   nt.keys = nt.counts = nullptr;
   nt.first = nullptr;
@@ -413,16 +298,7 @@ int grow(sct_counter* c, int64_t factor, hipStream_t s) {
 int update_device(sct_counter* c, const uint64_t* d_codes, int64_t n, hipStream_t s) {
   if (int rc = enter(c, s); rc != SCT_OK) return rc;
   const int64_t mode = sct::tune(SCT_TUNE_COUNT_PREAGG, 1);
-  int64_t done = 0;
-  while (done < n) {
-    if (c->size_bound > c->capacity / 2) {
-      if (int rc = read_words(c, s); rc != SCT_OK) return rc;
-      if (c->size_bound > c->capacity / 2) {
-        if (int rc = grow(c, n - done > c->capacity / 2 ? 4 : 2, s); rc != SCT_OK) return rc;
-        continue;
-      }
-    }
-    const int64_t m = std::min(n - done, c->capacity / 4);
+  const auto launch = [&](int64_t done, int64_t m) -> int {
     const u64* src = reinterpret_cast<const u64*>(d_codes) + done;
     const long long base = (long long)(c->total + done);
     if (mode == 2)
@@ -432,9 +308,9 @@ int update_device(sct_counter* c, const uint64_t* d_codes, int64_t n, hipStream_
     else
       hipLaunchKernelGGL(counter_insert_kernel<true>, dim3(grid_for(m, 4 * WG)), dim3(WG), 0, s, c->t, src, m, base);
     SCT_LAUNCH_CHECK();
-    c->size_bound += m;
-    done += m;
-  }
+    return SCT_OK;
+  };
+  SCT_TRY(feed(c, n, s, [&](int64_t factor) { return grow(c, factor, s); }, launch));
   c->total += n;
   return leave(c, s);
 }
@@ -453,16 +329,18 @@ int fetch_device(sct_counter* c, uint64_t* d_keys, uint64_t* d_counts, int64_t* 
   size_t sort_bytes = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr,
                                            (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)rows, 0, end_bit, s);
-  const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b8 = al((size_t)rows * 8), b4 = al((size_t)rows * 4);
+  Carve cv;
+  const size_t o_first_in = cv.take((size_t)rows * 8), o_first_out = cv.take((size_t)rows * 8);
+  const size_t o_slot_in = cv.take((size_t)rows * 4), o_slot_out = cv.take((size_t)rows * 4);
+  const size_t o_sort = cv.take(sort_bytes);
   void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, 2 * b8 + 2 * b4 + sort_bytes, s));
+  SCT_HIP(sct::pool_alloc(&blk, cv.size, s));
   uint8_t* b = static_cast<uint8_t*>(blk);
-  long long* first_in = reinterpret_cast<long long*>(b);
-  long long* first_out = reinterpret_cast<long long*>(b + b8);
-  uint32_t* slot_in = reinterpret_cast<uint32_t*>(b + 2 * b8);
-  uint32_t* slot_out = reinterpret_cast<uint32_t*>(b + 2 * b8 + b4);
-  void* sort_tmp = b + 2 * b8 + 2 * b4;
+  long long* first_in = reinterpret_cast<long long*>(b + o_first_in);
+  long long* first_out = reinterpret_cast<long long*>(b + o_first_out);
+  uint32_t* slot_in = reinterpret_cast<uint32_t*>(b + o_slot_in);
+  uint32_t* slot_out = reinterpret_cast<uint32_t*>(b + o_slot_out);
+  void* sort_tmp = b + o_sort;
   hipError_t e = hipMemsetAsync(&c->t.words[W_CURSOR], 0, 8, s);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(counter_compact_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t, c->capacity,
@@ -495,10 +373,9 @@ int sct::tally_launch(const int32_t* d_index, int64_t n, int64_t nw, uint64_t* d
 extern "C" int sct_counter_create(int64_t capacity_hint, sct_counter** out) {
   SCT_CHECK(out != nullptr, "counter is NULL");
   *out = nullptr;
-  SCT_CHECK(capacity_hint >= 0 && capacity_hint <= kMaxCapacity, "capacity hint %lld outside [0, 2^31]",
+  SCT_CHECK(capacity_hint >= 0 && capacity_hint <= sct::kTableMaxCapacity, "capacity hint %lld outside [0, 2^31]",
             (long long)capacity_hint);
-  int64_t cap = kMinCapacity;
-  while (cap < capacity_hint) cap *= 2;
+  const int64_t cap = sct::table_capacity_for(capacity_hint);
   auto* c = new sct_counter();
   const auto fail_with = [&](int rc) {
     sct_counter_destroy(c);
@@ -508,9 +385,8 @@ extern "C" int sct_counter_create(int64_t capacity_hint, sct_counter** out) {
   if (e != hipSuccess) return fail_with(sct::fail(SCT_E_HIP, "counter: %s", hipGetErrorString(e)));
   c->capacity = cap;
   if (int rc = alloc_table(c->t, cap); rc != SCT_OK) return fail_with(rc);
-  e = hipMalloc((void**)&c->t.words, W_NWORDS * 8);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_words, W_NWORDS * 8, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->last, hipEventDisableTiming);
+  e = open_words(c);
+  c->t.words = c->words;
   if (e == hipSuccess) {
     sct::HostStage* hs = sct::host_stage();
     if (!hs) return fail_with(SCT_E_HIP);
@@ -526,13 +402,8 @@ extern "C" int sct_counter_create(int64_t capacity_hint, sct_counter** out) {
 
 extern "C" int sct_counter_destroy(sct_counter* c) {
   if (!c) return SCT_OK;
-  if (c->last) {
-    if (c->used) (void)hipEventSynchronize(c->last);  // the work it enqueued reads these arrays
-    (void)hipEventDestroy(c->last);
-  }
+  close_words(c);
   free_table(c->t);
-  if (c->t.words) (void)hipFree(c->t.words);
-  if (c->h_words) (void)hipHostFree(c->h_words);
   delete c;
   return SCT_OK;
 }
@@ -599,7 +470,7 @@ extern "C" int sct_counter_fetch_host(sct_counter* c, uint64_t* keys, uint64_t* 
   const int64_t rows = c->size_bound + (c->h_words[W_SIDE_COUNT] ? 1 : 0);
   SCT_CHECK(room >= rows, "room for %lld rows, the counter holds %lld", (long long)room, (long long)rows);
   if (rows == 0) return SCT_OK;
-  const size_t b8 = ((size_t)rows * 8 + 255) & ~(size_t)255;
+  const size_t b8 = up256((size_t)rows * 8);
   sct::PoolBlock blk(s);
   if (int rc = blk.alloc(3 * b8); rc != SCT_OK) return rc;
   uint8_t* b = blk.bytes();

@@ -2,14 +2,10 @@
 // kernel: the reference slices the UMI out of the read, fastq.py:181-200, and never counts with it).
 //
 // sct_molecules: a device *set* of molecule keys, key = (index << umi_bits) | umi (molecules_key.h),
-// whose claim event drives a per-barcode tally.  The table is count.hip's open addressing reduced to
-// the keys: one array of `capacity` (a power of two) uint64 slots, EMPTY = 2^64 - 1.  A key's top
-// bit is always 0 (idx_bits + umi_bits <= 63), so EMPTY is never a key and there is no side slot.
-// A lane claims a slot with one 64-bit atomicCAS(&keys[s], EMPTY, key); a plain load that already
-// shows the key skips the CAS (a key is written once and never changes; a stale load can only show
-// EMPTY, and then the CAS decides).  The probe loop is bounded by the capacity: a full table sets the
-// overflow word and never spins.  The lane whose CAS claimed the slot, and only that lane, adds 1 to
-// molecules[index]; claims are summed per wave into the size word.
+// whose claim event drives a per-barcode tally.  The table is open_table.h's (the claim-by-CAS probe,
+// the bound on the load, the ordering of a counter's calls) over the keys alone.  A key's top bit is
+// always 0 (idx_bits + umi_bits <= 63), so EMPTY is never a key and there is no side slot.  The lane
+// whose CAS claimed the slot, and only that lane, adds 1 to molecules[index].
 //
 // Per read the insert loads 12 B once (int32 index, uint64 umi).  The answers -1 / -2 and the bad
 // UMIs are counted by wave ballots into registers and added to the tally once per wave; an index
@@ -23,10 +19,7 @@
 // DESIGN.md §3.10 has the A/B: 1 and 2 are level when a molecule's reads are adjacent (both twice as
 // fast as 0 there), and 1 is ahead of 2 when they are far apart.
 //
-// The host keeps the load factor bounded by the counter's rule: sub-batches of at most capacity / 4
-// reads, the size word read when the bound of claimed slots passes capacity / 2, growth x4 or x2,
-// 2^31 slots at most.  The rehash kernel re-inserts keys only: molecules, reads and the size word are
-// not touched by it.
+// The rehash kernel re-inserts keys only: molecules, reads and the size word are not touched by it.
 //
 // A *counted* counter (sct_molecules_create_counted) keeps a second array cnt[capacity] of uint64
 // beside the keys: the reads of every molecule.  COUNTED is a template parameter of the insert
@@ -54,26 +47,18 @@
 
 #include <algorithm>
 
-#include "mix64.h"
 #include "molecules_key.h"
 #include "molecules_merge_plan.h"
-#include "sct_common.h"
+#include "open_table.h"
 #include "umi_neighbours.h"
 
 namespace {
 
-typedef unsigned long long u64;
+using namespace sct::open_table;
 
-constexpr int WG = 256;
-constexpr u64 EMPTY = ~0ull;
-constexpr int64_t kMinCapacity = sct::kMolMinCapacity;
-constexpr int64_t kMaxCapacity = sct::kMolMaxCapacity;
-// device words of a molecule counter; W_TALLY .. W_TALLY + 2 = no match, ambiguous, bad UMI
-enum { W_SIZE = 0, W_OVERFLOW = 1, W_ERROR = 2, W_CURSOR = 3, W_TALLY = 4, W_NWORDS = 8 };
-// LDS pre-aggregation: a tile of kTile reads in a table of 2 * kTile slots (load <= 1/2)
-constexpr int kItems = 4;
-constexpr int kTile = WG * kItems;
-constexpr int kLdsSlots = 2 * kTile;
+// the molecule counter's own device words; W_TALLY .. W_TALLY + 2 = no match, ambiguous, bad UMI
+enum { W_ERROR = W_OWN, W_CURSOR, W_TALLY };
+static_assert(W_TALLY + 3 <= W_NWORDS, "the tally lives in the device words");
 
 struct Set {
   u64* keys;
@@ -87,32 +72,6 @@ struct Set {
   int umi_bits;
 };
 
-// The key into the table; true when this call claimed a new slot.  SLOT: *slot is the key's slot,
-// or NO_SLOT when the table is full.
-constexpr u64 NO_SLOT = ~0ull;
-template <bool SLOT = false>
-__device__ __forceinline__ bool set_claim(u64* __restrict__ keys, u64 mask, u64* __restrict__ words, u64 key,
-                                          u64* slot = nullptr) {
-  u64 s = sct::mix64(key) & mask;
-  for (u64 probe = 0; probe <= mask; ++probe) {
-    u64 k = keys[s];
-    bool claimed = false;
-    if (k == EMPTY) {
-      k = atomicCAS(&keys[s], EMPTY, key);
-      claimed = k == EMPTY;
-      if (claimed) k = key;
-    }
-    if (k == key) {
-      if (SLOT) *slot = s;
-      return claimed;
-    }
-    s = (s + 1) & mask;
-  }
-  atomicOr(&words[W_OVERFLOW], 1ull);  // full table: the host fails with SCT_E_RANGE
-  if (SLOT) *slot = NO_SLOT;
-  return false;
-}
-
 // `count` reads of one molecule: reads[index] += count, and molecules[index] += 1 from the lane that
 // claimed the key's slot.  The index comes out of a key built from a checked index: index < nw.
 // COUNTED: the carrier of the key also adds its count to the slot's mreads (cnt is zero at every
@@ -121,14 +80,9 @@ template <bool COUNTED>
 __device__ __forceinline__ int set_add(const Set& t, u64 key, u64 count) {
   const uint32_t index = sct::mol_key_index(key, t.umi_bits);
   atomicAdd(&t.reads[index], count);
-  bool claimed;
-  if (COUNTED) {
-    u64 slot;
-    claimed = set_claim<true>(t.keys, t.mask, t.words, key, &slot);
-    if (slot != NO_SLOT) atomicAdd(&t.cnt[slot], count);
-  } else {
-    claimed = set_claim(t.keys, t.mask, t.words, key);
-  }
+  u64 slot = NO_SLOT;
+  const bool claimed = claim<COUNTED>(t.keys, t.mask, &t.words[W_OVERFLOW], key, &slot);
+  if (COUNTED && slot != NO_SLOT) atomicAdd(&t.cnt[slot], count);
   if (!claimed) return 0;
   atomicAdd(&t.molecules[index], 1ull);
   return 1;
@@ -155,14 +109,13 @@ struct WaveTally {
     n[2] += (uint32_t)__popcll(__ballot(what == R_BADUMI));
     error |= what == R_ERROR;
   }
-  // one add per wave and non-zero tally, the claimed slots into the size word, the error word
+  // the claimed slots into the size word, one add per wave and non-zero tally, the error word
   __device__ __forceinline__ void flush(const Set& t, int claims) {
-    for (int o = 32; o > 0; o >>= 1) claims += __shfl_xor(claims, o);
+    add_claims(&t.words[W_SIZE], claims);
     const bool any_error = __ballot(error) != 0;
     if ((threadIdx.x & 63) != 0) return;
     for (int k = 0; k < 3; ++k)
       if (n[k]) atomicAdd(&t.words[W_TALLY + k], (u64)n[k]);
-    if (claims > 0) atomicAdd(&t.words[W_SIZE], (u64)claims);
     if (any_error) atomicOr(&t.words[W_ERROR], 1ull);
   }
 };
@@ -184,21 +137,8 @@ __global__ void __launch_bounds__(WG) molecules_insert_kernel(Set t, const int32
     if (i < n) what = classify(t, __builtin_nontemporal_load(&index[i]), __builtin_nontemporal_load(&umi[i]), &key);
     wt.see(what);
     const bool good = what == R_GOOD;
-    u64 count = 1;
-    bool rep = good;
-    if (MERGE) {
-      const int lane = threadIdx.x & 63;
-      u64 todo = __ballot(good);
-      while (todo) {  // wave-uniform: one distinct key leaves per pass
-        const int leader = __ffsll((long long)todo) - 1;
-        const u64 lk = __shfl(key, leader);
-        const u64 m = __ballot(good && key == lk);
-        if (lane == leader) count = (u64)__popcll(m);
-        else if (good && key == lk) rep = false;
-        todo &= ~m;
-      }
-    }
-    if (rep) claims += set_add<COUNTED>(t, key, count);
+    const Merged m = MERGE ? wave_merge(good, key) : Merged{good, 1};
+    if (m.rep) claims += set_add<COUNTED>(t, key, m.count);
   }
   wt.flush(t, claims);
 }
@@ -229,22 +169,9 @@ __global__ void __launch_bounds__(WG) molecules_insert_lds_kernel(Set t, const i
       if (i < n) what = classify(t, __builtin_nontemporal_load(&index[i]), __builtin_nontemporal_load(&umi[i]), &key);
       wt.see(what);
       if (what != R_GOOD) continue;
-      bool placed = false;
-      uint32_t s = (uint32_t)sct::mix64(key) & (kLdsSlots - 1);
-      for (int probe = 0; probe < kLdsSlots; ++probe) {
-        u64 k0 = lkey[s];
-        if (k0 == EMPTY) {
-          k0 = atomicCAS(&lkey[s], EMPTY, key);
-          if (k0 == EMPTY) k0 = key;
-        }
-        if (k0 == key) {
-          atomicAdd(&lcnt[s], 1u);
-          placed = true;
-          break;
-        }
-        s = (s + 1) & (kLdsSlots - 1);
-      }
-      if (!placed) claims += set_add<COUNTED>(t, key, 1);
+      const int s = lds_claim(lkey, (uint32_t)sct::mix64(key) & (kLdsSlots - 1), key);
+      if (s >= 0) atomicAdd(&lcnt[s], 1u);
+      else claims += set_add<COUNTED>(t, key, 1);
     }
     __syncthreads();
     for (int s = threadIdx.x; s < kLdsSlots; s += WG) {
@@ -265,7 +192,7 @@ __global__ void __launch_bounds__(WG) molecules_rehash_kernel(const u64* __restr
                                                               u64* __restrict__ words) {
   for (int64_t s = (int64_t)blockIdx.x * WG + threadIdx.x; s < from_capacity; s += (int64_t)gridDim.x * WG) {
     const u64 key = from[s];
-    if (key != EMPTY) (void)set_claim(to, to_mask, words, key);
+    if (key != EMPTY) (void)claim(to, to_mask, &words[W_OVERFLOW], key);
   }
 }
 
@@ -280,24 +207,12 @@ __global__ void __launch_bounds__(WG) molecules_rehash_counted_kernel(const u64*
     const u64 key = from[s];
     if (key == EMPTY) continue;
     u64 slot;
-    (void)set_claim<true>(to, to_mask, words, key, &slot);
+    (void)claim<true>(to, to_mask, &words[W_OVERFLOW], key, &slot);
     if (slot != NO_SLOT) to_cnt[slot] = from_cnt[s];
   }
 }
 
 // ---- UMI collapse (the contract's "parent" rule; one implementation for collapse and fetch_counted)
-
-// the slot that holds `key`, or NO_SLOT: a read-only probe, bounded by the capacity
-__device__ __forceinline__ u64 set_find(const u64* __restrict__ keys, u64 mask, u64 key) {
-  u64 s = sct::mix64(key) & mask;
-  for (u64 probe = 0; probe <= mask; ++probe) {
-    const u64 k = keys[s];
-    if (k == key) return s;
-    if (k == EMPTY) return NO_SLOT;
-    s = (s + 1) & mask;
-  }
-  return NO_SLOT;
-}
 
 // The parent rule over the candidates j0, j0 + step, ... of the molecule `key` held in `slot`: the
 // stored key that maximises (mreads, code) over the key itself and those of its 3 * L one-base
@@ -311,7 +226,7 @@ __device__ __forceinline__ Best parent_scan(const Set& t, u64 key, u64 slot, int
   const int n1 = 3 * (t.umi_bits / t.kind);
   for (int j = j0; j < n1; j += step) {
     const u64 nb = sct::umi_neighbour(key, t.kind, j);
-    const u64 s = set_find(t.keys, t.mask, nb);
+    const u64 s = find(t.keys, t.mask, nb);
     if (s == NO_SLOT) continue;
     const u64 r = t.cnt[s];
     if (sct::umi_support_less(b.reads, b.code, r, nb)) b = Best{nb, r, s};
@@ -387,48 +302,23 @@ __global__ void __launch_bounds__(WG) molecules_collapse_wave_kernel(Set t, int6
   if (lane == 0 && moved) atomicAdd(ncorrected, (u64)moved);
 }
 
-// fetch: the occupied slots' keys, in any order (the sort fixes the order); at most `room` are written
+// fetch and merge: the occupied slots' keys and, SLOTS, their slot numbers beside them, in any order
+// (the sort fixes the order); at most `room` are written
+template <bool SLOTS>
 __global__ void __launch_bounds__(WG) molecules_compact_kernel(const u64* __restrict__ keys, int64_t capacity,
                                                                u64* __restrict__ cursor, int64_t room,
-                                                               u64* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
+                                                               u64* __restrict__ out_key,
+                                                               uint32_t* __restrict__ out_slot) {
   const int64_t stride = (int64_t)gridDim.x * WG;
-  const int64_t iters = (capacity + stride - 1) / stride;
+  const int64_t iters = (capacity + stride - 1) / stride;  // the same for every lane: the wave stays whole
   for (int64_t it = 0; it < iters; ++it) {
     const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
     const u64 key = s < capacity ? keys[s] : EMPTY;
     const bool occ = key != EMPTY;
-    const u64 m = __ballot(occ);
-    if (m == 0) continue;
-    u64 at = 0;
-    const int leader = __ffsll((long long)m) - 1;
-    if (lane == leader) at = atomicAdd(cursor, (u64)__popcll(m));
-    at = __shfl(at, leader) + (u64)__popcll(m & ((1ull << lane) - 1ull));
-    if (occ && (int64_t)at < room) out[at] = key;
-  }
-}
-
-// fetch_counted: the occupied slots as (key, slot) pairs, in any order; at most `room` are written
-__global__ void __launch_bounds__(WG) molecules_compact_pairs_kernel(const u64* __restrict__ keys, int64_t capacity,
-                                                                     u64* __restrict__ cursor, int64_t room,
-                                                                     u64* __restrict__ out_key,
-                                                                     uint32_t* __restrict__ out_slot) {
-  const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * WG;
-  const int64_t iters = (capacity + stride - 1) / stride;
-  for (int64_t it = 0; it < iters; ++it) {
-    const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
-    const u64 key = s < capacity ? keys[s] : EMPTY;
-    const bool occ = key != EMPTY;
-    const u64 m = __ballot(occ);
-    if (m == 0) continue;
-    u64 at = 0;
-    const int leader = __ffsll((long long)m) - 1;
-    if (lane == leader) at = atomicAdd(cursor, (u64)__popcll(m));
-    at = __shfl(at, leader) + (u64)__popcll(m & ((1ull << lane) - 1ull));
+    const u64 at = compact_at(occ, cursor);
     if (occ && (int64_t)at < room) {
       out_key[at] = key;
-      out_slot[at] = (uint32_t)s;  // capacity <= 2^31
+      if (SLOTS) out_slot[at] = (uint32_t)s;  // capacity <= 2^31
     }
   }
 }
@@ -485,14 +375,13 @@ __global__ void __launch_bounds__(WG) molecules_merge_kernel(Set t, const u64* _
     }
     if (key == EMPTY) continue;
     u64 slot = NO_SLOT;
-    const bool claimed = set_claim<COUNTED>(t.keys, t.mask, t.words, key, &slot);
+    const bool claimed = claim<COUNTED>(t.keys, t.mask, &t.words[W_OVERFLOW], key, &slot);
     if (COUNTED && slot != NO_SLOT) atomicAdd(&t.cnt[slot], count);
     if (!claimed) continue;
     atomicAdd(&t.molecules[sct::mol_key_index(key, t.umi_bits)], 1ull);
     ++claims;
   }
-  for (int o = 32; o > 0; o >>= 1) claims += __shfl_xor(claims, o);
-  if ((threadIdx.x & 63) == 0 && claims > 0) atomicAdd(&t.words[W_SIZE], (u64)claims);
+  add_claims(&t.words[W_SIZE], claims);
 }
 
 // reads[nw] += the other counter's, and its three tallies (`words` is its device words or a copy)
@@ -512,23 +401,12 @@ __global__ void __launch_bounds__(WG) molecules_gather_counts_kernel(const u64* 
     out[r] = cnt[slots[r]];
 }
 
-inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap = 256 * 8) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, sct::ceil_div(n, per_block)));
-}
-
 }  // namespace
 
-struct sct_molecules {
-  int device = 0;
-  int64_t capacity = 0;
+struct sct_molecules : Host {
+  sct_molecules() : Host("molecule") {}
   int idx_bits = 0;
-  Set t{};
-  u64* h_words = nullptr;  // page-locked read-back of the device words
-  int64_t total = 0;       // reads fed
-  int64_t size_bound = 0;  // claimed slots: the last size read plus the reads fed since
-  hipEvent_t last = nullptr;  // the last work enqueued (another stream's call waits for it)
-  hipStream_t last_stream = nullptr;
-  bool used = false;
+  Set t{};               // t.words is Host::words
   bool counted = false;  // keeps t.cnt beside t.keys
 };
 
@@ -562,63 +440,20 @@ struct DeviceGuard {
   if (on_device_.e != hipSuccess)                                                                 \
   return sct::fail(SCT_E_HIP, "molecule counter's device %d: %s", (c)->device, hipGetErrorString(on_device_.e))
 
-int alloc_keys(u64** keys, int64_t capacity, hipStream_t s) {
-  hipError_t e = hipMalloc((void**)keys, (size_t)capacity * 8);
-  if (e == hipSuccess) e = hipMemsetAsync(*keys, 0xFF, (size_t)capacity * 8, s);  // every slot EMPTY
-  if (e != hipSuccess) {
-    if (*keys) (void)hipFree(*keys);
-    *keys = nullptr;
-    return sct::fail(e == hipErrorOutOfMemory ? SCT_E_NOMEM : SCT_E_HIP, "molecule table of %lld slots: %s",
-                     (long long)capacity, hipGetErrorString(e));
-  }
-  return SCT_OK;
-}
-
-// a counted table's mreads: every slot 0 (an insert adds to it, a rehash stores into it)
-int alloc_counts(u64** cnt, int64_t capacity, hipStream_t s) {
-  hipError_t e = hipMalloc((void**)cnt, (size_t)capacity * 8);
-  if (e == hipSuccess) e = hipMemsetAsync(*cnt, 0, (size_t)capacity * 8, s);
-  if (e != hipSuccess) {
-    if (*cnt) (void)hipFree(*cnt);
-    *cnt = nullptr;
-    return sct::fail(e == hipErrorOutOfMemory ? SCT_E_NOMEM : SCT_E_HIP, "molecule read counts of %lld slots: %s",
-                     (long long)capacity, hipGetErrorString(e));
-  }
-  return SCT_OK;
-}
-
-// work on `s` starts after whatever the counter enqueued last on another stream
-int enter(sct_molecules* c, hipStream_t s) {
-  if (c->used && c->last_stream != s) SCT_HIP(hipStreamWaitEvent(s, c->last, 0));
-  return SCT_OK;
-}
-
-int leave(sct_molecules* c, hipStream_t s) {
-  SCT_HIP(hipEventRecord(c->last, s));
-  c->last_stream = s;
-  c->used = true;
-  return SCT_OK;
-}
-
-// the device words, read back after everything enqueued on `s`
-int read_words(sct_molecules* c, hipStream_t s) {
-  SCT_HIP(hipMemcpyAsync(c->h_words, c->t.words, W_NWORDS * 8, hipMemcpyDeviceToHost, s));
-  SCT_HIP(hipStreamSynchronize(s));
-  if (c->h_words[W_OVERFLOW])
-    return sct::fail(SCT_E_RANGE, "molecule table of %lld slots is full", (long long)c->capacity);
-  c->size_bound = (int64_t)c->h_words[W_SIZE];
-  return SCT_OK;
-}
+// a table's keys are filled with 0xFF, every slot EMPTY; a counted table's mreads with 0 (an insert
+// adds to it, a rehash stores into it)
+constexpr const char* kKeysName = "molecule table";
+constexpr const char* kCountsName = "molecule read counts";
 
 int grow(sct_molecules* c, int64_t factor, hipStream_t s) {
-  const int64_t cap = c->capacity * factor;
-  if (cap > kMaxCapacity)
-    return sct::fail(SCT_E_RANGE, "molecule table cannot grow past %lld slots", (long long)kMaxCapacity);
+  const int64_t cap = sct::table_grown(c->capacity, factor);
+  if (cap == 0)
+    return sct::fail(SCT_E_RANGE, "molecule table cannot grow past %lld slots", (long long)sct::kTableMaxCapacity);
   u64* nk = nullptr;
   u64* nc = nullptr;
-  if (int rc = alloc_keys(&nk, cap, s); rc != SCT_OK) return rc;
+  if (int rc = alloc_filled(&nk, cap, 0xFF, s, kKeysName); rc != SCT_OK) return rc;
   if (c->counted) {
-    if (int rc = alloc_counts(&nc, cap, s); rc != SCT_OK) {
+    if (int rc = alloc_filled(&nc, cap, 0, s, kCountsName); rc != SCT_OK) {
       (void)hipFree(nk);
       return rc;
     }
@@ -655,16 +490,7 @@ int update_device(sct_molecules* c, const int32_t* d_index, const uint64_t* d_um
                   bool* range) {
   if (int rc = enter(c, s); rc != SCT_OK) return rc;
   const int64_t mode = sct::tune(SCT_TUNE_COUNT_PREAGG, 1);
-  int64_t done = 0;
-  while (done < n) {
-    if (c->size_bound > c->capacity / 2) {
-      if (int rc = read_words(c, s); rc != SCT_OK) return rc;
-      if (c->size_bound > c->capacity / 2) {
-        if (int rc = grow(c, n - done > c->capacity / 2 ? 4 : 2, s); rc != SCT_OK) return rc;
-        continue;
-      }
-    }
-    const int64_t m = std::min(n - done, c->capacity / 4);
+  const auto launch_batch = [&](int64_t done, int64_t m) -> int {
     const int32_t* idx = d_index + done;
     const u64* umi = reinterpret_cast<const u64*>(d_umi) + done;
     const dim3 grid(mode <= 1 ? grid_for(m, 4 * WG) : grid_for(m, kTile));
@@ -676,9 +502,9 @@ int update_device(sct_molecules* c, const int32_t* d_index, const uint64_t* d_um
     else
       c->counted ? launch(molecules_insert_lds_kernel<true>) : launch(molecules_insert_lds_kernel<false>);
     SCT_LAUNCH_CHECK();
-    c->size_bound += m;
-    done += m;
-  }
+    return SCT_OK;
+  };
+  SCT_TRY(feed(c, n, s, [&](int64_t factor) { return grow(c, factor, s); }, launch_batch));
   c->total += n;
   // rule 3: the error word of this call's kernels (the read-back also makes the size exact)
   if (int rc = read_words(c, s); rc != SCT_OK) return rc;
@@ -701,17 +527,19 @@ int fetch_device(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, int64_t ro
   size_t sort_bytes = 0;
   (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr, (int)rows, 0,
                                           end_bit, s);
-  const size_t b8 = ((size_t)rows * 8 + 255) & ~(size_t)255;
+  Carve cv;
+  const size_t o_keys_in = cv.take((size_t)rows * 8), o_keys_out = cv.take((size_t)rows * 8);
+  const size_t o_sort = cv.take(sort_bytes);
   void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, 2 * b8 + sort_bytes, s));
+  SCT_HIP(sct::pool_alloc(&blk, cv.size, s));
   uint8_t* b = static_cast<uint8_t*>(blk);
-  u64* keys_in = reinterpret_cast<u64*>(b);
-  u64* keys_out = reinterpret_cast<u64*>(b + b8);
+  u64* keys_in = reinterpret_cast<u64*>(b + o_keys_in);
+  u64* keys_out = reinterpret_cast<u64*>(b + o_keys_out);
   hipError_t e = hipMemsetAsync(&c->t.words[W_CURSOR], 0, 8, s);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(molecules_compact_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
-                       c->capacity, &c->t.words[W_CURSOR], rows, keys_in);
-    e = hipcub::DeviceRadixSort::SortKeys(b + 2 * b8, sort_bytes, keys_in, keys_out, (int)rows, 0, end_bit, s);
+    hipLaunchKernelGGL(molecules_compact_kernel<false>, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
+                       c->capacity, &c->t.words[W_CURSOR], rows, keys_in, nullptr);
+    e = hipcub::DeviceRadixSort::SortKeys(b + o_sort, sort_bytes, keys_in, keys_out, (int)rows, 0, end_bit, s);
   }
   if (e == hipSuccess) {
     hipLaunchKernelGGL(molecules_split_kernel, dim3(grid_for(rows, 1024)), dim3(WG), 0, s, keys_out, rows,
@@ -733,18 +561,19 @@ int need_counted(const sct_molecules* c) {
 int collapse_device(sct_molecules* c, uint64_t* d_collapsed, uint64_t* d_ncorrected, hipStream_t s) {
   if (int rc = enter(c, s); rc != SCT_OK) return rc;
   if (int rc = read_words(c, s); rc != SCT_OK) return rc;
-  const size_t head = 256, bitmap_bytes = (size_t)c->capacity / 8;  // capacity >= 64: whole 32-bit words
+  Carve cv;
+  const size_t o_ncorr = cv.take(8), o_bitmap = cv.take((size_t)c->capacity / 8);  // capacity >= 64: whole 32-bit words
   void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, head + bitmap_bytes, s));
+  SCT_HIP(sct::pool_alloc(&blk, cv.size, s));
   uint8_t* b = static_cast<uint8_t*>(blk);
-  u64* ncorr = reinterpret_cast<u64*>(b);
-  hipError_t e = hipMemsetAsync(b, 0, head + bitmap_bytes, s);
+  u64* ncorr = reinterpret_cast<u64*>(b + o_ncorr);
+  hipError_t e = hipMemsetAsync(b, 0, cv.size, s);
   if (e == hipSuccess) e = hipMemsetAsync(d_collapsed, 0, (size_t)c->t.nw * 8, s);
   if (e == hipSuccess && c->size_bound > 0) {
     const bool wave = sct::tune(SCT_TUNE_COLLAPSE_FORM, 1) == 1;
     const auto kernel = wave ? molecules_collapse_wave_kernel : molecules_collapse_kernel;
     hipLaunchKernelGGL(kernel, dim3(grid_for(c->capacity, WG)), dim3(WG), 0, s, c->t, c->capacity,
-                       reinterpret_cast<uint32_t*>(b + head), reinterpret_cast<u64*>(d_collapsed), ncorr);
+                       reinterpret_cast<uint32_t*>(b + o_bitmap), reinterpret_cast<u64*>(d_collapsed), ncorr);
     e = hipGetLastError();
   }
   if (e == hipSuccess && d_ncorrected) e = hipMemcpyAsync(d_ncorrected, ncorr, 8, hipMemcpyDeviceToDevice, s);
@@ -771,20 +600,22 @@ int fetch_counted_rows(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, uint
   size_t sort_bytes = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr,
                                            (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)rows, 0, end_bit, s);
-  const size_t b8 = ((size_t)rows * 8 + 255) & ~(size_t)255;
-  const size_t b4 = ((size_t)rows * 4 + 255) & ~(size_t)255;
+  Carve cv;
+  const size_t o_keys_in = cv.take((size_t)rows * 8), o_keys_out = cv.take((size_t)rows * 8);
+  const size_t o_slots_in = cv.take((size_t)rows * 4), o_slots_out = cv.take((size_t)rows * 4);
+  const size_t o_sort = cv.take(sort_bytes);
   void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, 2 * b8 + 2 * b4 + sort_bytes, s));
+  SCT_HIP(sct::pool_alloc(&blk, cv.size, s));
   uint8_t* b = static_cast<uint8_t*>(blk);
-  u64* keys_in = reinterpret_cast<u64*>(b);
-  u64* keys_out = reinterpret_cast<u64*>(b + b8);
-  uint32_t* slots_in = reinterpret_cast<uint32_t*>(b + 2 * b8);
-  uint32_t* slots_out = reinterpret_cast<uint32_t*>(b + 2 * b8 + b4);
+  u64* keys_in = reinterpret_cast<u64*>(b + o_keys_in);
+  u64* keys_out = reinterpret_cast<u64*>(b + o_keys_out);
+  uint32_t* slots_in = reinterpret_cast<uint32_t*>(b + o_slots_in);
+  uint32_t* slots_out = reinterpret_cast<uint32_t*>(b + o_slots_out);
   hipError_t e = hipMemsetAsync(&c->t.words[W_CURSOR], 0, 8, s);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(molecules_compact_pairs_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
+    hipLaunchKernelGGL(molecules_compact_kernel<true>, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
                        c->capacity, &c->t.words[W_CURSOR], rows, keys_in, slots_in);
-    e = hipcub::DeviceRadixSort::SortPairs(b + 2 * b8 + 2 * b4, sort_bytes, keys_in, keys_out, slots_in, slots_out,
+    e = hipcub::DeviceRadixSort::SortPairs(b + o_sort, sort_bytes, keys_in, keys_out, slots_in, slots_out,
                                            (int)rows, 0, end_bit, s);
   }
   if (e == hipSuccess) {
@@ -822,28 +653,29 @@ int merge_check(const sct_molecules* dst, const sct_molecules* src) {
   return SCT_OK;
 }
 
-inline size_t up256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 // src's occupied rows, dense and unsorted, into a pool block on src's device on `ss` (src's device
-// is current): keys[rows], then cnt[rows] for a counted counter (the block's tail holds the slots
-// the counts were gathered through).
-int merge_compact(sct_molecules* src, int64_t rows, hipStream_t ss, void** blk) {
-  const size_t b8 = up256((size_t)rows * 8);
-  SCT_HIP(sct::pool_alloc(blk, src->counted ? 2 * b8 + (size_t)rows * 4 : b8, ss));
+// is current): keys[rows] at its head, then *cnt = cnt[rows] for a counted counter (the block's tail
+// holds the slots the counts were gathered through).
+int merge_compact(sct_molecules* src, int64_t rows, hipStream_t ss, void** blk, const u64** cnt) {
+  Carve cv;
+  const size_t o_keys = cv.take((size_t)rows * 8);
+  const size_t o_cnt = src->counted ? cv.take((size_t)rows * 8) : 0, o_slots = src->counted ? cv.take((size_t)rows * 4) : 0;
+  SCT_HIP(sct::pool_alloc(blk, cv.size, ss));
   uint8_t* b = static_cast<uint8_t*>(*blk);
-  u64* keys = reinterpret_cast<u64*>(b);
+  u64* keys = reinterpret_cast<u64*>(b + o_keys);
+  *cnt = src->counted ? reinterpret_cast<const u64*>(b + o_cnt) : nullptr;
   hipError_t e = hipMemsetAsync(&src->t.words[W_CURSOR], 0, 8, ss);
   if (e == hipSuccess) {
     const dim3 grid(grid_for(src->capacity, 1024));
     if (src->counted) {
-      uint32_t* slots = reinterpret_cast<uint32_t*>(b + 2 * b8);
-      hipLaunchKernelGGL(molecules_compact_pairs_kernel, grid, dim3(WG), 0, ss, src->t.keys, src->capacity,
+      uint32_t* slots = reinterpret_cast<uint32_t*>(b + o_slots);
+      hipLaunchKernelGGL(molecules_compact_kernel<true>, grid, dim3(WG), 0, ss, src->t.keys, src->capacity,
                          &src->t.words[W_CURSOR], rows, keys, slots);
       hipLaunchKernelGGL(molecules_gather_counts_kernel, dim3(grid_for(rows, 1024)), dim3(WG), 0, ss, src->t.cnt, slots,
-                         rows, reinterpret_cast<u64*>(b + b8));
+                         rows, reinterpret_cast<u64*>(b + o_cnt));
     } else {
-      hipLaunchKernelGGL(molecules_compact_kernel, grid, dim3(WG), 0, ss, src->t.keys, src->capacity,
-                         &src->t.words[W_CURSOR], rows, keys);
+      hipLaunchKernelGGL(molecules_compact_kernel<false>, grid, dim3(WG), 0, ss, src->t.keys, src->capacity,
+                         &src->t.words[W_CURSOR], rows, keys, nullptr);
     }
     e = hipGetLastError();
   }
@@ -880,7 +712,7 @@ int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
   const int64_t cap = sct::mol_merge_capacity(dst->capacity, dst_size, src_size);
   if (cap == 0)
     return sct::fail(SCT_E_RANGE, "merge: %lld + %lld molecules need a table of more than %lld slots",
-                     (long long)dst_size, (long long)src_size, (long long)kMaxCapacity);
+                     (long long)dst_size, (long long)src_size, (long long)sct::kTableMaxCapacity);
   if (cap > dst->capacity) SCT_TRY(grow(dst, cap / dst->capacity, s));
 
   const int64_t nw = dst->t.nw;
@@ -892,25 +724,27 @@ int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
   void* src_blk = nullptr;
   void* dst_blk = nullptr;
   if (dense) {
+    const u64* src_cnt = nullptr;  // in src_blk, whose head is the keys
     if (src_size > 0) {
       SCT_ON_DEVICE_OF(src);
-      SCT_TRY(merge_compact(src, src_size, ss, &src_blk));
+      SCT_TRY(merge_compact(src, src_size, ss, &src_blk, &src_cnt));
     }
     {  // src's arrays are read by dst's stream from here on: after what src's stream has enqueued
       SCT_ON_DEVICE_OF(src);
       SCT_TRY(leave(src, ss));
     }
-    const size_t b8 = up256((size_t)src_size * 8), bw = up256(W_NWORDS * 8), br = up256((size_t)nw * 8);
-    hipError_t e = sct::pool_alloc(&dst_blk, bw + br + (src->counted ? 2 : 1) * b8, s);
+    Carve cv;
+    const size_t o_words = cv.take(W_NWORDS * 8), o_reads = cv.take((size_t)nw * 8);
+    const size_t o_keys = cv.take((size_t)src_size * 8), o_cnt = src->counted ? cv.take((size_t)src_size * 8) : 0;
+    hipError_t e = sct::pool_alloc(&dst_blk, cv.size, s);
     uint8_t* b = static_cast<uint8_t*>(dst_blk);
-    const uint8_t* from = static_cast<const uint8_t*>(src_blk);
     if (e == hipSuccess && ss != s) e = hipStreamWaitEvent(s, src->last, 0);
-    if (e == hipSuccess) e = hipMemcpyPeerAsync(b, dst->device, src->t.words, src->device, W_NWORDS * 8, s);
-    if (e == hipSuccess) e = hipMemcpyPeerAsync(b + bw, dst->device, src->t.reads, src->device, (size_t)nw * 8, s);
+    if (e == hipSuccess) e = hipMemcpyPeerAsync(b + o_words, dst->device, src->t.words, src->device, W_NWORDS * 8, s);
+    if (e == hipSuccess) e = hipMemcpyPeerAsync(b + o_reads, dst->device, src->t.reads, src->device, (size_t)nw * 8, s);
     if (e == hipSuccess && src_size > 0)
-      e = hipMemcpyPeerAsync(b + bw + br, dst->device, from, src->device, (size_t)src_size * 8, s);
+      e = hipMemcpyPeerAsync(b + o_keys, dst->device, src_blk, src->device, (size_t)src_size * 8, s);
     if (e == hipSuccess && src_size > 0 && src->counted)
-      e = hipMemcpyPeerAsync(b + bw + br + b8, dst->device, from + b8, src->device, (size_t)src_size * 8, s);
+      e = hipMemcpyPeerAsync(b + o_cnt, dst->device, src_cnt, src->device, (size_t)src_size * 8, s);
     if (e != hipSuccess) {
       // nothing of dst has changed; the scratch goes back after what was enqueued
       if (dst_blk) sct::pool_free(dst_blk, s);
@@ -919,10 +753,10 @@ int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
       if (src_blk) sct::pool_free(src_blk, ss);
       return sct::fail(SCT_E_HIP, "molecule merge, copying the source's rows: %s", hipGetErrorString(e));
     }
-    from_words = reinterpret_cast<const u64*>(b);
-    from_reads = reinterpret_cast<const u64*>(b + bw);
-    keys = reinterpret_cast<const u64*>(b + bw + br);
-    cnt = src->counted ? reinterpret_cast<const u64*>(b + bw + br + b8) : nullptr;
+    from_words = reinterpret_cast<const u64*>(b + o_words);
+    from_reads = reinterpret_cast<const u64*>(b + o_reads);
+    keys = reinterpret_cast<const u64*>(b + o_keys);
+    cnt = src->counted ? reinterpret_cast<const u64*>(b + o_cnt) : nullptr;
     nrows = src_size;
   }
   if (src_size > 0) {
@@ -965,10 +799,9 @@ int create(int64_t nw, int kind, int L, int64_t capacity_hint, int flags, int de
   const int umi_bits = sct::mol_umi_bits(nw, kind, L);
   SCT_CHECK(umi_bits > 0, "index bits %d + UMI bits %lld do not fit a 63-bit key", sct::mol_idx_bits(nw),
             (long long)kind * L);
-  SCT_CHECK(capacity_hint >= 0 && capacity_hint <= kMaxCapacity, "capacity hint %lld outside [0, 2^31]",
+  SCT_CHECK(capacity_hint >= 0 && capacity_hint <= sct::kTableMaxCapacity, "capacity hint %lld outside [0, 2^31]",
             (long long)capacity_hint);
-  int64_t cap = kMinCapacity;
-  while (cap < capacity_hint) cap *= 2;
+  const int64_t cap = sct::table_capacity_for(capacity_hint);
   hipError_t e = hipSuccess;
   if (device < 0) {
     e = hipGetDevice(&device);
@@ -996,19 +829,18 @@ int create(int64_t nw, int kind, int L, int64_t capacity_hint, int flags, int de
   c->t.kind = kind;
   c->t.umi_bits = umi_bits;
   c->t.mask = (u64)cap - 1;
-  if (int rc = alloc_keys(&c->t.keys, cap, hs->stream); rc != SCT_OK) return fail_with(rc);
+  if (int rc = alloc_filled(&c->t.keys, cap, 0xFF, hs->stream, kKeysName); rc != SCT_OK) return fail_with(rc);
   if (counted)
-    if (int rc = alloc_counts(&c->t.cnt, cap, hs->stream); rc != SCT_OK) return fail_with(rc);
+    if (int rc = alloc_filled(&c->t.cnt, cap, 0, hs->stream, kCountsName); rc != SCT_OK) return fail_with(rc);
   // reads and molecules are one allocation of 2 * nw words, the tally lives in the device words
   e = hipMalloc((void**)&c->t.reads, (size_t)nw * 16);
   if (e == hipSuccess) {
     c->t.molecules = c->t.reads + nw;
     e = hipMemsetAsync(c->t.reads, 0, (size_t)nw * 16, hs->stream);
   }
-  if (e == hipSuccess) e = hipMalloc((void**)&c->t.words, W_NWORDS * 8);
-  if (e == hipSuccess) e = hipMemsetAsync(c->t.words, 0, W_NWORDS * 8, hs->stream);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_words, W_NWORDS * 8, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->last, hipEventDisableTiming);
+  if (e == hipSuccess) e = open_words(c);
+  c->t.words = c->words;
+  if (e == hipSuccess) e = hipMemsetAsync(c->words, 0, W_NWORDS * 8, hs->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(hs->stream);
   if (e != hipSuccess)
     return fail_with(sct::fail(e == hipErrorOutOfMemory ? SCT_E_NOMEM : SCT_E_HIP, "molecule counter: %s",
@@ -1035,15 +867,10 @@ extern "C" int sct_molecules_create_counted(int64_t nw, int kind, int L, int64_t
 extern "C" int sct_molecules_destroy(sct_molecules* c) {
   if (!c) return SCT_OK;
   DeviceGuard on_device(c->device);  // (best effort: the frees below name their memory themselves)
-  if (c->last) {
-    if (c->used) (void)hipEventSynchronize(c->last);  // the work it enqueued reads these arrays
-    (void)hipEventDestroy(c->last);
-  }
+  close_words(c);
   if (c->t.keys) (void)hipFree(c->t.keys);
   if (c->t.cnt) (void)hipFree(c->t.cnt);
   if (c->t.reads) (void)hipFree(c->t.reads);
-  if (c->t.words) (void)hipFree(c->t.words);
-  if (c->h_words) (void)hipHostFree(c->h_words);
   delete c;
   return SCT_OK;
 }
@@ -1141,7 +968,7 @@ extern "C" int sct_molecules_fetch_host(sct_molecules* c, int32_t* index, uint64
   const int64_t rows = c->size_bound;
   SCT_CHECK(room >= rows, "room for %lld molecules, the counter holds %lld", (long long)room, (long long)rows);
   if (rows == 0) return SCT_OK;
-  const size_t b8 = ((size_t)rows * 8 + 255) & ~(size_t)255;
+  const size_t b8 = up256((size_t)rows * 8);
   sct::PoolBlock blk(s);
   if (int rc = blk.alloc(b8 + (size_t)rows * 4); rc != SCT_OK) return rc;
   uint8_t* b = blk.bytes();
@@ -1207,7 +1034,7 @@ extern "C" int sct_molecules_fetch_counted_host(sct_molecules* c, int32_t* index
   int64_t rows = 0;
   if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
   if (rows == 0) return SCT_OK;
-  const size_t b8 = ((size_t)rows * 8 + 255) & ~(size_t)255;
+  const size_t b8 = up256((size_t)rows * 8);
   sct::PoolBlock blk(s);
   if (int rc = blk.alloc(3 * b8 + (size_t)rows * 4); rc != SCT_OK) return rc;
   uint8_t* b = blk.bytes();  // umi, mreads, parent, index

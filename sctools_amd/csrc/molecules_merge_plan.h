@@ -6,11 +6,12 @@
 #include <stdint.h>
 
 #include "molecules_key.h"
+#include "table_load.h"
 
 namespace sct {
 
-constexpr int64_t kMolMinCapacity = 64;
-constexpr int64_t kMolMaxCapacity = 1LL << 31;
+constexpr int64_t kMolMinCapacity = kTableMinCapacity;
+constexpr int64_t kMolMaxCapacity = kTableMaxCapacity;
 
 // The capacity `dst` must have before the keys of `src` move into it: the smallest power of two that
 // is no smaller than dst_capacity and holds dst_size + src_size keys at a load of at most 1/2 (every
