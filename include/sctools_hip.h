@@ -673,22 +673,26 @@ int sct_molecules_merge(sct_molecules* dst, sct_molecules* src, void* stream);
  * reference raises ValueError('fastq name must start with @') there), or -1.
  */
 typedef struct sct_fastq_index sct_fastq_index;
-/* Pass 1: count every 4 KiB tile's lines (-> nrecords = lines / 4); keeps only per-tile
- * line offsets.  The buffer must stay alive and unchanged until the index is destroyed. */
+/* The count stage, synchronous: every 8 KiB tile's line count and first line end, and the counts
+ * summed over blocks of 32 and 1,024 tiles (-> nrecords = lines / 4); nothing per line is kept.
+ * The buffer must stay alive and unchanged until the index is destroyed.  One launch covers the
+ * buffer, as in sct_fastq_extract_fused: tiles * 256 < 2^32, about 137 GB (SCT_E_INVALID, "buffer
+ * too large", beyond it; the stream form passes a file in pieces). */
 int sct_fastq_index_create(const uint8_t* d_buf, int64_t nbytes, const int64_t* file_ends, int nfiles,
                            int text_mode, void* stream, sct_fastq_index** index);
 int sct_fastq_index_destroy(sct_fastq_index* index);
 /* first_bad_name: from the last sct_fastq_extract_spans (-2 before any). */
 int sct_fastq_index_info(const sct_fastq_index* index, int64_t* nrecords, int64_t* nlines,
                          int64_t* first_bad_name);
-/* Pass 2, synchronous: every record's sequence-line and quality-line slices for all spans
- * (nspans <= 8 host (start, end) pairs, end <= 4096) and the '@' check of every name line.
+/* The range stage on an index, synchronous: every record's sequence-line and quality-line
+ * slices for all spans (nspans <= 8 host (start, end) pairs, end <= 4096) and the '@' check of
+ * every name line.
  * Span k's rows start at d_seq / d_qual + nrecords * sum_{i<k} width_i (zero padded rows of
  * width_k), lengths at d_seq_len / d_qual_len + k * nrecords; every output is nullable. */
 int sct_fastq_extract_spans(sct_fastq_index* index, const uint8_t* d_buf, const int32_t* spans,
                             int nspans, uint8_t* d_seq, uint8_t* d_qual, int32_t* d_seq_len,
                             int32_t* d_qual_len, int64_t* first_bad_name, void* stream);
-/* Index and extraction in one call (a count pass, then the extraction; asynchronous on
+/* Index and extraction in one call (the same count and range stages; asynchronous on
  * `stream`, no host synchronisation): d_file_ends is DEVICE memory; rows are laid out by the
  * caller's capacity (span k's row r at out + cap_records * prefix_k + r * width_k; lengths at
  * len + k * cap + r; records >= cap_records are not written); d_status (3 int64, device): [0]

@@ -20,14 +20,16 @@
 // (tests/fastq_reference.py, tests/test_gpu_fastq_seams.py).
 //
 // Device layout: the files' bytes concatenated in one buffer, read in 8 KiB tiles (32 bytes
-// per thread as two 16-byte loads, SWAR byte compares).  Two passes: count_kernel counts each tile's line
-// terminators and an exclusive scan gives every tile its first line number (the index);
-// extract2_kernel finds the terminators again, numbers them, and for each one that starts a
-// record's name / sequence / quality line checks the '@' or copies that line's slices.
-// No per-line array is ever stored.
-#include <hipcub/hipcub.hpp>
-
-#include <stdlib.h>
+// per thread as two 16-byte loads, SWAR byte compares).  Two stages serve every entry point:
+//   count  fq_count_kernel counts each tile's line terminators and notes its first one, and
+//          tile_sums_reduce_kernel sums the counts over blocks of 32 and 1,024 tiles (tile_prefix.h);
+//   range  fastq_range_kernel gives each workgroup a run of tiles: it takes the run's first line
+//          number from the sums, finds the terminators again, numbers them, and for each one that starts
+//          a record's name / sequence / quality line checks the '@' or copies that line's slices.
+// No per-line array is ever stored.  sct_fastq_extract_fused is the two stages over a pooled scratch;
+// an index keeps the count stage's output, sct_fastq_extract_spans runs the range stage on it, and
+// sct_fastq_extract_host and sct_fastq_stream_chunk are an index and an extraction per buffer or piece.
+// One launch covers a buffer: ntiles * 256 < 2^32, about 137 GB (the stream's pieces are 256 MiB).
 #include <string.h>
 
 #include <algorithm>
@@ -38,6 +40,7 @@
 #include "sct_common.h"
 #include "encode_common.h"
 #include "tile_prefix.h"
+#include "tile_locate.h"
 
 namespace {
 
@@ -187,97 +190,6 @@ struct FileCursor {
   }
 };
 
-// Per tile: its terminator count, and its first terminator (in-tile offset << 2 | 1 if
-// virtual | 2 if "\r\n"; ~0 if none) -- the end of the previous tile's last line.
-// Persistent: a workgroup walks tiles blockIdx.x, + gridDim.x, ... with the next tile's
-// 16 bytes per thread loaded before this tile is reduced (one load in flight per thread
-// while it works: a tile per workgroup left the loads latency-bound).
-__global__ __launch_bounds__(WG) void count_kernel(const uint8_t* __restrict__ buf, int64_t n, Files fs,
-                                                   int text, unsigned long long* __restrict__ counts,
-                                                   uint32_t* __restrict__ first,
-                                                   unsigned* __restrict__ flags, int64_t ntiles) {
-  using BR = hipcub::BlockReduce<uint32_t, WG>;
-  __shared__ typename BR::TempStorage tmp;
-  int64_t tile = blockIdx.x;
-  uint4 cur[SEG], nxt[SEG];
-#pragma unroll
-  for (int k = 0; k < SEG; ++k)
-    cur[k] = tile < ntiles ? load16(buf, n, tile * TILE + (int64_t)threadIdx.x * TB + 16 * k) : make_uint4(0, 0, 0, 0);
-  FileCursor fc;
-  for (; tile < ntiles; tile += gridDim.x) {
-    const int64_t nt = tile + gridDim.x;
-#pragma unroll
-    for (int k = 0; k < SEG; ++k)
-      nxt[k] = nt < ntiles ? load16(buf, n, nt * TILE + (int64_t)threadIdx.x * TB + 16 * k) : make_uint4(0, 0, 0, 0);
-    const int64_t p0 = tile * TILE + (int64_t)threadIdx.x * TB;
-    const bool ends_here = fc.advance(fs, tile * TILE);  // wave-uniform: a file end in this tile
-    uint32_t c = 0, na = 0, f = ~0u;
-    if (p0 < n) {
-      const Span sp = thread_span(buf, n, fs, text, p0, cur, ends_here);
-      na = sp.na;
-      const uint32_t bits = sp.m | sp.vbits;
-      c = __popc(bits);
-      if (bits) {
-        const int j = __ffs(bits) - 1;
-        f = (sp.m >> j & 1u) ? ((uint32_t)(threadIdx.x * TB + j) << 2) | ((sp.crlf >> j & 1u) ? 2u : 0u)
-                             : ((uint32_t)(threadIdx.x * TB + j + 1) << 2) | 1u;
-      }
-    }
-    __syncthreads();  // the previous tile's reductions are done with tmp
-    const uint32_t tot = BR(tmp).Sum(c);
-    __syncthreads();
-    const uint32_t fmin = BR(tmp).Reduce(f, hipcub::Min());
-    if (na) atomicOr(flags, 1u);
-    if (threadIdx.x == 0) {
-      counts[tile] = tot;
-      first[tile] = fmin;
-    }
-#pragma unroll
-    for (int k = 0; k < SEG; ++k) cur[k] = nxt[k];
-  }
-}
-
-// A line as the reference sees it: content [start, content_end), then '\n' when nl.  From a
-// line start, scan at most `need` bytes for its terminator ('\n'; in text mode also '\r',
-// whether of "\r\n" or lone) without crossing the end of the file that holds `start`.
-struct Line {
-  int64_t start, content_end;
-  int nl;
-};
-
-__device__ __forceinline__ Line scan_line(const uint8_t* __restrict__ buf, int64_t n, Files fs,
-                                          int64_t start, int need, int text) {
-  int lo = 0, hi = fs.nfiles;  // the file holding `start`: first end > start
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (fs.ends[mid] <= start) lo = mid + 1; else hi = mid;
-  }
-  const int64_t fe = lo < fs.nfiles ? fs.ends[lo] : n;
-  const int64_t lim = start + need < fe ? start + need : fe;
-  Line L{start, lim, 1};
-  for (int64_t i = start; i < lim; ++i) {
-    const uint8_t c = buf[i];
-    if (c == '\n' || (text && c == '\r')) {
-      L.content_end = i;
-      return L;
-    }
-  }
-  // no terminator in the window: the line is longer than needed (content_end = lim is
-  // enough), or it is the file's unterminated last line
-  if (lim == fe) L.nl = 0;
-  return L;
-}
-
-// One pass over the buffer, a tile per workgroup:
-//  1. each thread finds its 16 bytes' terminators (as count_kernel) and the block scan
-//     numbers them; their in-tile offsets go to LDS in byte order (bit 13 = virtual file
-//     end: the next line starts at the end and the line has no '\n'; bit 14 = "\r\n");
-//  2. the line after terminator t (global number g+1) belongs to record (g+1)/4: a name
-//     line (0) must start with '@' (fastq.py:35-36); for a sequence (1) or quality (3)
-//     line, one item per line finds the line's end at the tile's next terminator
-//     (for the tile's last line: the next tile's first, or a short scan) and copies its
-//     slice (rows inside the tile from the tile's LDS copy).
-// Record 0's name line starts at byte 0, checked by thread 0 of tile 0.
 constexpr int MAX_SPANS = 8;
 struct Spans {
   int n, max_end, width;  // width = sum of the spans' widths
@@ -287,188 +199,25 @@ struct Spans {
 
 constexpr int MAX_TERM = TILE + 16;  // terminators a tile can hold (+ virtual file ends)
 
-// The extraction (round 2: fewer LDS bytes and one barrier fewer per tile than the first
-// version, which kept 32-bit terminators and an action array): terminators as
-// 16-bit tile offsets (bit 13 = virtual file end, bit 14 = "\r\n"; 8 KB), no action array --
-// a copy item (line a) finds its line from the terminators around it (the line after the
-// tile's (te0 + 2a)-th terminator; te0 = 1 when the tile's first terminator number is odd) and
-// copies every span of it in turn -- so the name checks and the copies run in one phase after
-// the terminators are written.  13 KB of LDS: 7 resident workgroups per CU (4 for the first
-// version).  Round 3: one item per line instead of per (line, span), so a line's end is found
-// once for all its spans: 20M records 1.33-1.35 -> 1.16-1.21 ms.
+// A tile's terminators in LDS, in byte order, as 16-bit tile offsets (8 KB): bit 14 = virtual file
+// end (the offset is the file's end: the next line starts there and the line has no '\n'), bit 15 =
+// "\r\n".  No per-line action array: the line after the tile's terminator t (global number g0 + t)
+// is line g0 + t + 1, of record (g0 + t + 1) / 4 -- a name line (0 mod 4) must start with '@'
+// (fastq.py:35-36); a sequence (1) or quality (3) line is one copy item, which finds the line's end
+// at the tile's next terminator (the tile's last line: at the next tile's first, or a short scan)
+// once for all its spans.
 constexpr uint16_t T16_OFF = 0x3FFF, T16_VIRT = 1u << 14, T16_CRLF = 1u << 15;
 static_assert(TILE + 16 <= T16_OFF, "16-bit terminator offsets");
 
-__global__ __launch_bounds__(WG) void extract2_kernel(const uint8_t* __restrict__ buf, int64_t n, Files fs,
-                                                      int text, const unsigned long long* __restrict__ offsets,
-                                                      const uint32_t* __restrict__ first, int64_t ntiles,
-                                                      int64_t nrec, Spans sp, uint8_t* __restrict__ seq_out,
-                                                      uint8_t* __restrict__ qual_out,
-                                                      int32_t* __restrict__ seq_len,
-                                                      int32_t* __restrict__ qual_len,
-                                                      unsigned long long* __restrict__ first_bad) {
-  __shared__ uint16_t term[MAX_TERM];
-  __shared__ uint4 tile_bytes[TILE / 16];  // the tile itself: slices inside it copy from LDS
-  using BS = hipcub::BlockScan<uint32_t, WG>;
-  __shared__ typename BS::TempStorage tmp;
-  int64_t tile = blockIdx.x;
-  uint4 cur[SEG], nxt[SEG];
-#pragma unroll
-  for (int k = 0; k < SEG; ++k)
-    cur[k] = tile < ntiles ? load16(buf, n, tile * TILE + (int64_t)threadIdx.x * TB + 16 * k) : make_uint4(0, 0, 0, 0);
-  unsigned long long g0_cur = tile < ntiles ? offsets[tile] : 0ull;
-  uint32_t nf_cur = tile + 1 < ntiles ? first[tile + 1] : ~0u;
-  FileCursor fc;
-  const uint8_t* tile8 = reinterpret_cast<const uint8_t*>(tile_bytes);
-  const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(tile_bytes);
-  for (; tile < ntiles; tile += gridDim.x) {
-    const int64_t ntl = tile + gridDim.x;
-#pragma unroll
-    for (int k = 0; k < SEG; ++k)
-      nxt[k] = ntl < ntiles ? load16(buf, n, ntl * TILE + (int64_t)threadIdx.x * TB + 16 * k) : make_uint4(0, 0, 0, 0);
-    const unsigned long long g0_nxt = ntl < ntiles ? offsets[ntl] : 0ull;
-    const uint32_t nf_nxt = ntl + 1 < ntiles ? first[ntl + 1] : ~0u;
-    const int64_t t0 = tile * TILE;
-    const int64_t p0 = t0 + (int64_t)threadIdx.x * TB;
-    const bool ends_here = fc.advance(fs, t0);
-    Span spn{0, 0, 0, 0};
-    if (p0 < n) spn = thread_span(buf, n, fs, text, p0, cur, ends_here);
-    __syncthreads();  // the previous tile's readers of tile_bytes / term / tmp are done
-#pragma unroll
-    for (int k = 0; k < SEG; ++k) {
-      tile_bytes[threadIdx.x * SEG + k] = p0 + 16 * k < n ? cur[k] : make_uint4(0, 0, 0, 0);
-      cur[k] = nxt[k];
-    }
-    const uint32_t tbits = spn.m | spn.vbits;
-    uint32_t pre, ntile;
-    BS(tmp).ExclusiveSum((uint32_t)__popc(tbits), pre, ntile);
-    {
-      uint32_t bits = tbits;
-      uint32_t at = pre;
-      while (bits) {
-        const int j = __ffs(bits) - 1;
-        bits &= bits - 1;
-        const uint32_t off = (uint32_t)(threadIdx.x * TB + j);
-        term[at++] = (spn.m >> j & 1u) ? (uint16_t)(off | ((spn.crlf >> j & 1u) ? T16_CRLF : 0u))
-                                       : (uint16_t)((off + 1) | T16_VIRT);  // the file ends after byte off
-      }
-    }
-    __syncthreads();
-    const int64_t g0 = (int64_t)g0_cur;  // global number of the tile's first terminator
-    const uint32_t nf = nf_cur;
-    if (tile == 0 && threadIdx.x == 0 && nrec > 0 && buf[0] != '@') atomicMin(first_bad, 0ull);
-    // terminators of the tile that belong to records < nrec: [0, tmax)
-    const int64_t lim_g = 4 * nrec - 1;  // terminators beyond the last record's line 3 end nothing
-    const int tmax = (int)(g0 + ntile <= lim_g ? ntile : (lim_g > g0 ? lim_g - g0 : 0));
-    // name lines: after terminators g = 3 (mod 4)
-    for (int t = (int)((3 - (g0 & 3)) & 3) + 4 * (int)threadIdx.x; t < tmax; t += 4 * WG) {
-      const uint32_t e = term[t];
-      const int64_t o = (int64_t)(e & T16_OFF) + ((e & T16_VIRT) ? 0 : 1);  // the line's start in the tile
-      const uint8_t ch = o < TILE ? tile8[o] : buf[t0 + o];
-      if (ch != '@') atomicMin(first_bad, (unsigned long long)((g0 + t + 1) >> 2));
-    }
-    // sequence / quality lines: after even terminators; one item per line, its spans in turn
-    // (the line's end is found once for all of them)
-    const int te0 = (int)(g0 & 1);
-    const int nact = tmax > te0 ? (tmax - te0 + 1) / 2 : 0;
-    for (int a = threadIdx.x; a < nact; a += WG) {
-      const int t = te0 + 2 * a;
-      const int64_t line = g0 + t + 1, rec = line >> 2;
-      const bool is_seq = (line & 3) == 1;
-      const uint32_t e = term[t];
-      const int start = (int)(e & T16_OFF) + ((e & T16_VIRT) ? 0 : 1);  // <= TILE
-      int64_t cend;  // content end relative to the tile start
-      int nl;
-      if (t + 1 < (int)ntile) {  // the line ends at the tile's next terminator
-        const uint32_t f = term[t + 1];
-        cend = (int64_t)(f & T16_OFF) - ((f & T16_CRLF) ? 1 : 0);
-        nl = (f & T16_VIRT) ? 0 : 1;
-      } else if (nf != ~0u) {  // the tile's last line ends at the next tile's first terminator
-        cend = TILE + (int64_t)(nf >> 2) - ((nf & 2u) ? 1 : 0);
-        nl = (nf & 1u) ? 0 : 1;
-      } else {  // no terminator in the next tile either: scan (max_end bytes, within its file)
-        const int64_t next = t0 + start;
-        int lo = 0, hi = fs.nfiles;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (fs.ends[mid] <= next) lo = mid + 1; else hi = mid;
-        }
-        const int64_t fe = lo < fs.nfiles ? fs.ends[lo] : n;
-        const int64_t lim = next + sp.max_end < fe ? next + sp.max_end : fe;
-        cend = lim - t0;
-        nl = lim == fe ? 0 : 1;  // longer than the window: its end is irrelevant
-        for (int64_t i = next; i < lim; ++i) {
-          const uint8_t ch = buf[i];
-          if (ch == '\n' || (text && ch == '\r')) {
-            cend = i - t0;
-            nl = 1;
-            break;
-          }
-        }
-      }
-      int32_t* len = is_seq ? seq_len : qual_len;
-      uint8_t* out = is_seq ? seq_out : qual_out;
-      const int64_t clen = cend - start, llen = clen + nl;
-      for (int k = 0; k < sp.n; ++k) {
-        const int64_t sa = sp.start[k] < llen ? sp.start[k] : llen, sb = sp.end[k] < llen ? sp.end[k] : llen;
-        if (len) len[k * nrec + rec] = (int32_t)(sb - sa);
-        if (!out) continue;
-        const int w = sp.end[k] - sp.start[k];
-        uint8_t* o = out + sp.prefix[k] * nrec + rec * w;
-        const uint8_t* src = buf + t0 + start;
-        // fast path: a whole-width slice inside the line's content, a row of whole dwords:
-        // aligned dword loads + byte-align funnel shifts, dword stores
-        const int64_t s0 = t0 + start + sa;
-        const int64_t base = s0 & ~3LL;
-        const int nd = w / 4;
-        if (sb - sa == w && sb <= clen && (w & 3) == 0 && w <= 64 && base + 4 * (nd + 1) <= n &&
-            ((uintptr_t)o & 3) == 0) {
-          // rows inside the tile read its LDS copy; the rest (lines running past it) read L2
-          const uint32_t* d = base + 4 * (nd + 1) <= t0 + TILE ? tile32 + ((base - t0) >> 2)
-                                                               : reinterpret_cast<const uint32_t*>(buf + base);
-          const uint32_t sh = (uint32_t)(s0 & 3);
-          uint32_t* od = reinterpret_cast<uint32_t*>(o);
-          if (nd == 4 && ((uintptr_t)o & 15) == 0) {
-            const uint32_t x0 = d[0], x1 = d[1], x2 = d[2], x3 = d[3], x4 = d[4];
-            *reinterpret_cast<uint4*>(o) =
-                make_uint4(__builtin_amdgcn_alignbyte(x1, x0, sh), __builtin_amdgcn_alignbyte(x2, x1, sh),
-                           __builtin_amdgcn_alignbyte(x3, x2, sh), __builtin_amdgcn_alignbyte(x4, x3, sh));
-            continue;
-          }
-          if (nd == 2 && ((uintptr_t)o & 7) == 0) {
-            const uint32_t x0 = d[0], x1 = d[1], x2 = d[2];
-            *reinterpret_cast<uint2*>(o) =
-                make_uint2(__builtin_amdgcn_alignbyte(x1, x0, sh), __builtin_amdgcn_alignbyte(x2, x1, sh));
-            continue;
-          }
-          uint32_t lo = d[0];
-          for (int q2 = 0; q2 < nd; ++q2) {
-            const uint32_t hi = d[q2 + 1];
-            od[q2] = __builtin_amdgcn_alignbyte(hi, lo, sh);
-            lo = hi;
-          }
-          continue;
-        }
-#pragma unroll 8
-        for (int j = 0; j < w; ++j) {
-          const int64_t i = sa + j;
-          o[j] = i < sb ? (i < clen ? src[i] : (uint8_t)'\n') : (uint8_t)0;
-        }
-      }
-    }
-    g0_cur = g0_nxt;
-    nf_cur = nf_nxt;
-  }
-}
-
-// ---------------------------------------------------------------- without an index (round 4)
-// sct_fastq_extract_fused: fq_count_kernel (one 8 KiB tile per workgroup: a one-pass grid streams
-// the buffer at the copy rate, where the persistent count_kernel loop stayed near 4 TB/s) writes
-// every tile's terminator count and first terminator (count_kernel's encoding) and the non-ASCII
-// flag; tile_sums_reduce_kernel sums the counts into the coarse levels of tile_prefix.h; then
+// ---------------------------------------------------------------- the count and range stages (round 4)
+// Count: fq_count_kernel (one 8 KiB tile per workgroup: a one-pass grid streams the buffer at the
+// copy rate, where a persistent loop over the tiles stayed near 4 TB/s) writes every tile's
+// terminator count, its first terminator -- the end of the previous tile's last line: in-tile
+// offset << 2 | 1 if virtual | 2 if "\r\n"; ~0 if none -- and the non-ASCII flag;
+// tile_sums_reduce_kernel sums the counts into the coarse levels of tile_prefix.h.  Range:
 // fastq_range_kernel gives each workgroup a contiguous range of tiles: it takes its first tile's
 // line number and the total line count from the tile sums once, and walks its range carrying the
-// line number (extract2_kernel's per-tile work, next tile's bytes loaded while this one is worked).
+// line number (the next tile's bytes loaded while this one is worked).
 // No scan launch, no host synchronisation, and no atomics on shared words: publishing into the
 // coarse levels with atomics cost 608 us for 1.38 GB (every tile in flight adds to one word).
 __global__ __launch_bounds__(WG) void fq_count_kernel(const uint8_t* __restrict__ buf, int64_t n, Files fs, int text,
@@ -542,7 +291,7 @@ __global__ __launch_bounds__(WG) void fq_count_kernel(const uint8_t* __restrict_
 // name line and every sequence / quality line's span slices (one item per line, its spans in
 // turn; rows of records >= cap skipped).  Terminators [0, tmax) end lines of records that count
 // (tmax < ntile drops an incomplete trailing record); g0 = the tile's first terminator's global
-// number; nf = the next tile's first terminator (count_kernel's encoding), or ~0u: the tile's last
+// number; nf = the next tile's first terminator (fq_count_kernel's encoding), or ~0u: the tile's last
 // line is then scanned for, in LDS when it ends within the staged head.
 struct TileOut {
   uint8_t* seq_out;
@@ -722,7 +471,6 @@ __device__ __forceinline__ void line_spans(const Spans& sp, const TileOut& to, b
   }
 }
 
-
 __device__ __forceinline__ void tile_items(lds_u16* term, lds_u8* tile8, lds_u32* tile32, const uint8_t* lut,
                                            int ntile, int tmax, int64_t g0, int64_t t0, uint32_t nf, int head,
                                            const uint8_t* __restrict__ buf, int64_t n, Files fs, int text,
@@ -798,7 +546,7 @@ __device__ __forceinline__ void tile_items(lds_u16* term, lds_u8* tile8, lds_u32
 
 // Rows of records >= cap are skipped; span k's row r at out + cap * prefix_k + r * width_k, its
 // length at len + k * cap + r; d_status[0] = the line count, d_status[1] = ~(first bad-name
-// record) or 0 (records < lines / 4 only, as extract2_kernel); optionally span 0's sequence rows
+// record) or 0 (records < lines / 4 only); optionally span 0's sequence rows
 // encoded as they are written (code_kind 2 TwoBit / 3 ThreeBit, one limb: width <= 32 / 21; gc
 // and flags as sct_encode's).
 __global__ __launch_bounds__(WG) void fastq_range_kernel(
@@ -895,7 +643,7 @@ __global__ __launch_bounds__(WG) void fastq_range_kernel(
   }
 }
 
-// grid of the persistent tile kernels: every resident workgroup slot once (at most ntiles)
+// a grid of every resident workgroup slot once (at most ntiles)
 unsigned resident_grid(const void* kernel, int64_t ntiles) {
   sct::scalar_quiesce();
   int dev = 0, cus = 256, per_cu = 0;
@@ -904,18 +652,21 @@ unsigned resident_grid(const void* kernel, int64_t ntiles) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)cus * per_cu));
 }
 
-// The byte just past line `target` (0-based line number; its terminator is terminator
-// number `target` of the buffer): one workgroup finds the tile holding it (binary search of
-// the tile offsets) and recounts that tile's terminators as extract2_kernel does.
+// The byte just past line `target` (0-based line number; its terminator is terminator number
+// `target` of the buffer), or -1 when the buffer has no such line: one workgroup finds the tile
+// holding it from the count stage's sums (tile_locate.h; every thread walks the same few words) and
+// recounts that tile's terminators as fastq_range_kernel numbers them.
 __global__ __launch_bounds__(WG) void line_end_kernel(const uint8_t* __restrict__ buf, int64_t n, Files fs, int text,
-                                                      const unsigned long long* __restrict__ offsets, int64_t ntiles,
-                                                      unsigned long long target, long long* __restrict__ out) {
-  int64_t lo = 0, hi = ntiles - 1;  // last tile k with offsets[k] <= target
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (offsets[mid] <= target) lo = mid; else hi = mid - 1;
+                                                      sct::TileSums ts, int64_t ntiles, unsigned long long target,
+                                                      long long* __restrict__ out) {
+  __shared__ uint32_t w_cnt[WG / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const sct::TileAt at = sct::tile_locate(ts.c0, ts.c1, ts.c2, ntiles, target);
+  if (at.tile < 0) {  // (the whole workgroup)
+    if (tid == 0) *out = -1;
+    return;
   }
-  const int64_t t0 = lo * TILE, p0 = t0 + (int64_t)threadIdx.x * TB;
+  const int64_t p0 = at.tile * TILE + (int64_t)tid * TB;
   uint32_t bits = 0;
   if (p0 < n) {
     uint4 v[SEG];
@@ -924,23 +675,79 @@ __global__ __launch_bounds__(WG) void line_end_kernel(const uint8_t* __restrict_
     const Span sp = thread_span(buf, n, fs, text, p0, v, true);
     bits = sp.m | sp.vbits;
   }
-  using BS = hipcub::BlockScan<uint32_t, WG>;
-  __shared__ typename BS::TempStorage tmp;
-  uint32_t pre;
-  BS(tmp).ExclusiveSum((uint32_t)__popc(bits), pre);
-  const unsigned long long want = target - offsets[lo];
-  uint32_t at = pre;
+  const uint32_t c = __popc(bits);
+  uint32_t ic = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t x = __shfl_up(ic, d);
+    if (lane >= d) ic += x;
+  }
+  if (lane == 63) w_cnt[wave] = ic;
+  __syncthreads();
+  uint32_t nth = ic - c;  // the tile's terminators before this thread's
+  for (int w = 0; w < wave; ++w) nth += w_cnt[w];
+  const unsigned long long want = target - at.before;
   while (bits) {
     const int j = __ffs(bits) - 1;
     bits &= bits - 1;
-    if (at == want) *out = p0 + j + 1;  // a real terminator ends at its byte; a virtual one at the file end
-    ++at;
+    if (nth == want) *out = p0 + j + 1;  // a real terminator ends at its byte; a virtual one at the file end
+    ++nth;
   }
 }
 
-}  // namespace
+// Tiles of a buffer.  fq_count_kernel runs one workgroup per tile and a launch holds < 2^32 threads.
+int tiles_of(int64_t nbytes, int64_t* ntiles) {
+  *ntiles = sct::ceil_div(nbytes, TILE);
+  SCT_CHECK(*ntiles * WG < (1LL << 32), "buffer too large: %lld bytes (one launch covers < %lld bytes; pass the "
+            "files in pieces, sct_fastq_stream_*)", (long long)nbytes, (long long)(((1LL << 32) / WG) * TILE));
+  return SCT_OK;
+}
 
-namespace {
+// The count stage (nbytes > 0): every tile's terminator count into ts.c0 and its first terminator
+// into first[ntiles], bit 0 of *flags set if a byte is not ASCII (the caller zeroes it), then the
+// sums over blocks of 32 and 1,024 tiles into ts.c1 / ts.c2.
+void count_stage(hipStream_t s, const uint8_t* d_buf, int64_t nbytes, Files fs, int text, int64_t ntiles,
+                 sct::TileSums ts, uint32_t* first, unsigned* flags) {
+  hipLaunchKernelGGL(fq_count_kernel, dim3((unsigned)ntiles), dim3(WG), 0, s, d_buf, nbytes, fs, text, ts, first, flags);
+  hipLaunchKernelGGL(sct::tile_sums_reduce_kernel, dim3((unsigned)sct::ceil_div(ntiles, 1024)), dim3(64), 0, s, ts,
+                     ntiles);
+}
+
+// The range stage over the count stage's output: rows laid out by `cap` (fastq_range_kernel), every
+// output nullable; d_status[0] = the line count, d_status[1] |= ~(first bad-name record).
+void range_stage(hipStream_t s, const uint8_t* d_buf, int64_t nbytes, Files fs, int text, int64_t ntiles,
+                 sct::TileSums ts, const uint32_t* first, int64_t cap, const Spans& sp, uint8_t* seq, uint8_t* qual,
+                 int32_t* seq_len, int32_t* qual_len, uint64_t* codes0, uint8_t* gc0, uint8_t* flags0, int code_kind,
+                 unsigned long long* d_status) {
+  // contiguous ranges of 8 tiles (64 KiB) per workgroup: 1.09-1.10 ms per 20M records against
+  // 1.13-1.20 for one range per resident slot and 1.55 for one tile per workgroup (same box,
+  // tools/ingest_tiles_ab.py); SCT_TUNE_INGEST_TILES = 0 sizes the ranges to the resident grid
+  const int64_t knob = sct::tune(SCT_TUNE_INGEST_TILES, -1);
+  const int64_t per_wg = knob > 0   ? knob
+                         : knob < 0 ? 8
+                                    : sct::ceil_div(ntiles, (int64_t)resident_grid((const void*)fastq_range_kernel, ntiles));
+  hipLaunchKernelGGL(fastq_range_kernel, dim3((unsigned)sct::ceil_div(ntiles, per_wg)), dim3(WG), 0, s, d_buf, nbytes,
+                     fs, text, ts, first, ntiles, per_wg, cap, sp, seq, qual, seq_len, qual_len, codes0, gc0, flags0,
+                     code_kind, d_status);
+}
+
+// The kernels' span table from nspans host (start, end) pairs.
+int make_spans(const int32_t* spans, int nspans, Spans* out) {
+  SCT_CHECK(nspans >= 0 && nspans <= MAX_SPANS && (nspans == 0 || spans), "0..%d spans", MAX_SPANS);
+  Spans& sp = *out = Spans{};
+  sp.n = nspans;
+  for (int k = 0; k < nspans; ++k) {
+    SCT_CHECK(0 <= spans[2 * k] && spans[2 * k] <= spans[2 * k + 1] && spans[2 * k + 1] <= 4096,
+              "span %d = [%d, %d) unsupported", k, spans[2 * k], spans[2 * k + 1]);
+    sp.start[k] = spans[2 * k];
+    sp.end[k] = spans[2 * k + 1];
+    sp.prefix[k] = sp.width;  // (at most 8 x 4,096)
+    sp.max_end = std::max(sp.max_end, sp.end[k]);
+    sp.width += sp.end[k] - sp.start[k];
+  }
+  return SCT_OK;
+}
+
 // One spare index allocation per device, kept when an index is destroyed and taken by the
 // next create that fits: a stream of pieces (one index per piece) or repeated extractions pay
 // no hipMalloc / hipFree per call.  Every user of an index synchronises its stream before the
@@ -987,15 +794,14 @@ void ix_release(void* p, size_t bytes) {
 }  // namespace
 
 struct sct_fastq_index {
-  int64_t nbytes = 0, nlines = 0, nrec = 0, first_bad = -2;
+  int64_t nbytes = 0, ntiles = 0, nlines = 0, nrec = 0, first_bad = -2;
   int text = 0, nfiles = 0;
-  int64_t ntiles = 0;
   void* d_mem = nullptr;                    // one allocation holding the arrays below
   size_t mem_bytes = 0;
   int64_t* d_ends = nullptr;                // file ends
-  unsigned long long* d_offsets = nullptr;  // ntiles + 1 line offsets (exclusive scan of tile counts)
-  uint32_t* d_first = nullptr;              // per tile: first terminator (see count_kernel)
-  unsigned long long* d_bad = nullptr;      // first bad-name record of the last extraction
+  sct::TileSums ts{};                       // the count stage's sums (ntiles tiles)
+  uint32_t* d_first = nullptr;              // per tile: first terminator (see fq_count_kernel)
+  unsigned long long* d_status = nullptr;   // sct_fastq_extract_fused's 3 words; [1] of the last extraction
 };
 
 extern "C" int sct_fastq_index_destroy(sct_fastq_index* ix) {
@@ -1004,6 +810,12 @@ extern "C" int sct_fastq_index_destroy(sct_fastq_index* ix) {
   delete ix;
   return SCT_OK;
 }
+namespace {
+struct IndexGuard {  // destroys the index it still holds
+  sct_fastq_index* p;
+  ~IndexGuard() { sct_fastq_index_destroy(p); }
+};
+}  // namespace
 
 extern "C" int sct_fastq_index_create(const uint8_t* d_buf, int64_t nbytes, const int64_t* file_ends,
                                       int nfiles, int text_mode, void* stream, sct_fastq_index** out) {
@@ -1016,53 +828,43 @@ extern "C" int sct_fastq_index_create(const uint8_t* d_buf, int64_t nbytes, cons
               "file_ends must be non-decreasing and <= nbytes");
   SCT_CHECK(file_ends[nfiles - 1] == nbytes, "the last file must end at nbytes");
   hipStream_t s = sct::as_stream(stream);
+  int64_t ntiles = 0;
+  SCT_TRY(tiles_of(nbytes, &ntiles));
   auto* ix = new sct_fastq_index();
-  auto fail_with = [&](int rc) {
-    sct_fastq_index_destroy(ix);
-    return rc;
-  };
+  IndexGuard g{ix};
   ix->nbytes = nbytes;
   ix->text = text_mode ? 1 : 0;
   ix->nfiles = nfiles;
-  ix->ntiles = std::max<int64_t>(1, sct::ceil_div(nbytes, TILE));
-  SCT_CHECK(ix->ntiles < (1LL << 31), "buffer too large");
-  // one allocation: ends | offsets | counts | first | flags, bad | scan scratch
-  size_t tb = 0;
-  SCT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (unsigned long long*)nullptr,
-                                           (unsigned long long*)nullptr, (int)(ix->ntiles + 1), s));
+  ix->ntiles = ntiles;
+  // one allocation: ends | tile sums | first | status
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_ends = 0, o_off = up((size_t)nfiles * 8), o_cnt = o_off + up((ix->ntiles + 1) * 8),
-               o_first = o_cnt + up((ix->ntiles + 1) * 8), o_flags = o_first + up(ix->ntiles * 4),
-               o_tmp = o_flags + 256, total_bytes = o_tmp + up(tb);
-  hipError_t e = ix_alloc(&ix->d_mem, total_bytes, &ix->mem_bytes);
-  if (e != hipSuccess) return fail_with(sct::fail(SCT_E_NOMEM, "fastq index: %s", hipGetErrorString(e)));
+  const size_t o_sums = up((size_t)nfiles * 8), o_first = o_sums + up(sct::tile_sums_bytes(ntiles)),
+               o_status = o_first + up((size_t)ntiles * 4);
+  SCT_HIP(ix_alloc(&ix->d_mem, o_status + 256, &ix->mem_bytes));
   char* base = (char*)ix->d_mem;
-  ix->d_ends = (int64_t*)(base + o_ends);
-  ix->d_offsets = (unsigned long long*)(base + o_off);
+  ix->d_ends = (int64_t*)base;
+  ix->ts = sct::tile_sums_at(base + o_sums, ntiles, false);
   ix->d_first = (uint32_t*)(base + o_first);
-  unsigned long long* d_counts = (unsigned long long*)(base + o_cnt);
-  unsigned* d_flags = (unsigned*)(base + o_flags);
-  ix->d_bad = (unsigned long long*)(base + o_flags + 8);
-  void* d_tmp = base + o_tmp;
+  ix->d_status = (unsigned long long*)(base + o_status);
   SCT_HIP(hipMemcpyAsync(ix->d_ends, file_ends, (size_t)nfiles * 8, hipMemcpyHostToDevice, s));
-  SCT_HIP(hipMemsetAsync(d_flags, 0, 8, s));
-  SCT_HIP(hipMemsetAsync(d_counts, 0, (size_t)(ix->ntiles + 1) * 8, s));
-  const Files fs{ix->d_ends, nfiles};
-  if (nbytes > 0)
-    hipLaunchKernelGGL(count_kernel, dim3(resident_grid((const void*)count_kernel, ix->ntiles)), dim3(WG), 0, s,
-                       d_buf, nbytes, fs, ix->text, d_counts, ix->d_first, d_flags, ix->ntiles);
-  SCT_LAUNCH_CHECK();
-  SCT_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_counts, ix->d_offsets, (int)(ix->ntiles + 1), s));
-  unsigned long long total = 0;
-  unsigned flags = 0;
-  SCT_HIP(hipMemcpyAsync(&total, ix->d_offsets + ix->ntiles, 8, hipMemcpyDeviceToHost, s));
-  SCT_HIP(hipMemcpyAsync(&flags, d_flags, 4, hipMemcpyDeviceToHost, s));
+  SCT_HIP(hipMemsetAsync(ix->d_status, 0, 24, s));
+  // the line count is the sum of the sums over 1,024 tiles: a few words per piece, brought back
+  // with the non-ASCII flag in the one synchronisation
+  std::vector<unsigned long long> c2((size_t)sct::ceil_div(ntiles, 1024));
+  unsigned long long flags = 0;
+  if (nbytes > 0) {
+    count_stage(s, d_buf, nbytes, Files{ix->d_ends, nfiles}, ix->text, ntiles, ix->ts, ix->d_first,
+                reinterpret_cast<unsigned*>(ix->d_status + 2));
+    SCT_LAUNCH_CHECK();
+    SCT_HIP(hipMemcpyAsync(c2.data(), ix->ts.c2, c2.size() * 8, hipMemcpyDeviceToHost, s));
+    SCT_HIP(hipMemcpyAsync(&flags, ix->d_status + 2, 8, hipMemcpyDeviceToHost, s));
+  }
   SCT_HIP(hipStreamSynchronize(s));
   if (ix->text && (flags & 1u))
-    return fail_with(sct::fail(SCT_E_RANGE, "text-mode FASTQ must be ASCII on the device path "
-                                            "(read it in 'rb' mode)"));
-  ix->nlines = (int64_t)total;
-  ix->nrec = (int64_t)total / 4;
+    return sct::fail(SCT_E_RANGE, "text-mode FASTQ must be ASCII on the device path (read it in 'rb' mode)");
+  for (unsigned long long c : c2) ix->nlines += (int64_t)c;
+  ix->nrec = ix->nlines / 4;
+  g.p = nullptr;
   *out = ix;
   return SCT_OK;
 }
@@ -1080,41 +882,27 @@ extern "C" int sct_fastq_extract_spans(sct_fastq_index* ix, const uint8_t* d_buf
                                        int nspans, uint8_t* d_seq, uint8_t* d_qual, int32_t* d_seq_len,
                                        int32_t* d_qual_len, int64_t* first_bad_name, void* stream) {
   SCT_CHECK(ix != nullptr, "index is NULL");
-  SCT_CHECK(nspans >= 0 && nspans <= MAX_SPANS && (nspans == 0 || spans), "0..%d spans", MAX_SPANS);
-  Spans sp{};
-  sp.n = nspans;
-  int64_t pre = 0;
-  for (int k = 0; k < nspans; ++k) {
-    SCT_CHECK(0 <= spans[2 * k] && spans[2 * k] <= spans[2 * k + 1] && spans[2 * k + 1] <= 4096,
-              "span %d = [%d, %d) unsupported", k, spans[2 * k], spans[2 * k + 1]);
-    sp.start[k] = spans[2 * k];
-    sp.end[k] = spans[2 * k + 1];
-    sp.prefix[k] = pre;
-    sp.max_end = std::max(sp.max_end, sp.end[k]);
-    pre += sp.end[k] - sp.start[k];
-  }
-  sp.width = (int)pre;
+  Spans sp;
+  SCT_TRY(make_spans(spans, nspans, &sp));
   hipStream_t s = sct::as_stream(stream);
-  SCT_HIP(hipMemsetAsync(ix->d_bad, 0xFF, 8, s));
+  SCT_HIP(hipMemsetAsync(ix->d_status + 1, 0, 8, s));
   if (ix->nbytes > 0) {
     SCT_CHECK(d_buf != nullptr, "buffer is NULL");
-    const Files fs{ix->d_ends, ix->nfiles};
-    hipLaunchKernelGGL(extract2_kernel, dim3(resident_grid((const void*)extract2_kernel, ix->ntiles)), dim3(WG), 0, s,
-                       d_buf, ix->nbytes, fs,
-                       ix->text, ix->d_offsets, ix->d_first, ix->ntiles, ix->nrec, sp, d_seq, d_qual,
-                       d_seq_len, d_qual_len, ix->d_bad);
+    // cap = nrecords: the range kernel's layout by capacity is the documented one
+    range_stage(s, d_buf, ix->nbytes, Files{ix->d_ends, ix->nfiles}, ix->text, ix->ntiles, ix->ts, ix->d_first,
+                ix->nrec, sp, d_seq, d_qual, d_seq_len, d_qual_len, nullptr, nullptr, nullptr, 2, ix->d_status);
     SCT_LAUNCH_CHECK();
   }
-  unsigned long long bad = ~0ull;
-  SCT_HIP(hipMemcpyAsync(&bad, ix->d_bad, 8, hipMemcpyDeviceToHost, s));
+  unsigned long long bad = 0;  // ~(first bad-name record), or 0
+  SCT_HIP(hipMemcpyAsync(&bad, ix->d_status + 1, 8, hipMemcpyDeviceToHost, s));
   SCT_HIP(hipStreamSynchronize(s));
-  ix->first_bad = bad == ~0ull ? -1 : (int64_t)bad;
+  ix->first_bad = bad ? (int64_t)~bad : -1;
   if (first_bad_name) *first_bad_name = ix->first_bad;
   return SCT_OK;
 }
 
-// Extraction without an index (fq_count_kernel, tile_sums_reduce_kernel, fastq_range_kernel),
-// asynchronous on `stream`: the concatenated files in d_buf, their cumulative ends in d_file_ends
+// The count and range stages back to back over a pooled scratch, nothing kept and nothing brought
+// back, asynchronous on `stream`: the concatenated files in d_buf, their cumulative ends in d_file_ends
 // (DEVICE memory, nfiles entries, the last = nbytes).  Rows are laid out by cap_records (span
 // k's row r at out + cap * prefix_k + r * width_k, its length at len + k * cap + r; rows of
 // records >= cap_records are not written); d_status (3 x int64, device) receives the line count
@@ -1128,52 +916,26 @@ extern "C" int sct_fastq_extract_fused(const uint8_t* d_buf, int64_t nbytes, con
                                        int64_t* d_status, void* stream) {
   SCT_CHECK(d_status != nullptr && nfiles >= 1 && d_file_ends != nullptr, "bad arguments");
   SCT_CHECK(nbytes >= 0 && (nbytes == 0 || d_buf != nullptr) && cap_records >= 0, "bad buffer");
-  SCT_CHECK(nspans >= 0 && nspans <= MAX_SPANS && (nspans == 0 || spans), "0..%d spans", MAX_SPANS);
-  Spans sp{};
-  sp.n = nspans;
-  int64_t pre = 0;
-  for (int k = 0; k < nspans; ++k) {
-    SCT_CHECK(0 <= spans[2 * k] && spans[2 * k] <= spans[2 * k + 1] && spans[2 * k + 1] <= 4096,
-              "span %d = [%d, %d) unsupported", k, spans[2 * k], spans[2 * k + 1]);
-    sp.start[k] = spans[2 * k];
-    sp.end[k] = spans[2 * k + 1];
-    sp.prefix[k] = pre;
-    sp.max_end = std::max(sp.max_end, sp.end[k]);
-    pre += sp.end[k] - sp.start[k];
-  }
-  sp.width = (int)pre;
+  Spans sp;
+  SCT_TRY(make_spans(spans, nspans, &sp));
   SCT_CHECK(code_kind == 2 || code_kind == 3, "code_kind must be 2 or 3");
   SCT_CHECK(!d_codes0 || (nspans >= 1 && code_kind * (sp.end[0] - sp.start[0]) <= 64 && d_seq),
             "span 0 encode needs one limb (width <= %d)", 64 / code_kind);
   hipStream_t s = sct::as_stream(stream);
   SCT_HIP(hipMemsetAsync(d_status, 0, 24, s));
   if (nbytes == 0) return SCT_OK;
-  const int64_t ntiles = sct::ceil_div(nbytes, TILE);
-  // fq_count_kernel runs one workgroup per tile and a launch holds < 2^32 threads
-  SCT_CHECK(ntiles * WG < (1LL << 32), "buffer too large: %lld bytes (one launch covers < %lld bytes; pass the "
-            "files in pieces, sct_fastq_stream_*)", (long long)nbytes, (long long)(((1LL << 32) / WG) * TILE));
+  int64_t ntiles = 0;
+  SCT_TRY(tiles_of(nbytes, &ntiles));
   void* scratch = nullptr;
   const size_t sbytes = sct::tile_sums_bytes(ntiles), fbytes = (size_t)ntiles * 4;
   SCT_HIP(sct::pool_alloc(&scratch, sbytes + fbytes, s));
   const sct::TileSums ts = sct::tile_sums_at(scratch, ntiles, false);
   uint32_t* first = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(scratch) + sbytes);
   const Files fs{d_file_ends, nfiles};
-  hipLaunchKernelGGL(fq_count_kernel, dim3((unsigned)ntiles), dim3(WG), 0, s, d_buf, nbytes, fs, text_mode ? 1 : 0, ts,
-                     first, reinterpret_cast<unsigned*>(d_status + 2));
-  hipLaunchKernelGGL(sct::tile_sums_reduce_kernel, dim3((unsigned)sct::ceil_div(ntiles, 1024)), dim3(64), 0, s, ts,
-                     ntiles);
-  // contiguous tile ranges, one per resident workgroup slot
-  // contiguous ranges of 8 tiles (64 KiB) per workgroup: 1.09-1.10 ms per 20M records against
-  // 1.13-1.20 for one range per resident slot and 1.55 for one tile per workgroup (same box,
-  // tools/ingest_tiles_ab.py); SCT_TUNE_INGEST_TILES = 0 sizes the ranges to the resident grid
-  const int64_t knob = sct::tune(SCT_TUNE_INGEST_TILES, -1);
-  const int64_t per_wg = knob > 0   ? knob
-                         : knob < 0 ? 8
-                                    : sct::ceil_div(ntiles, (int64_t)resident_grid((const void*)fastq_range_kernel, ntiles));
-  hipLaunchKernelGGL(fastq_range_kernel, dim3((unsigned)sct::ceil_div(ntiles, per_wg)), dim3(WG), 0, s, d_buf, nbytes,
-                     fs, text_mode ? 1 : 0, ts, (const uint32_t*)first, ntiles, per_wg, cap_records, sp, d_seq, d_qual,
-                     d_seq_len, d_qual_len, d_codes0, d_gc0, d_flags0, code_kind,
-                     reinterpret_cast<unsigned long long*>(d_status));
+  unsigned long long* status = reinterpret_cast<unsigned long long*>(d_status);
+  count_stage(s, d_buf, nbytes, fs, text_mode ? 1 : 0, ntiles, ts, first, reinterpret_cast<unsigned*>(status + 2));
+  range_stage(s, d_buf, nbytes, fs, text_mode ? 1 : 0, ntiles, ts, first, cap_records, sp, d_seq, d_qual,
+              d_seq_len, d_qual_len, d_codes0, d_gc0, d_flags0, code_kind, status);
   hipError_t e = hipGetLastError();
   sct::pool_free(scratch, s);
   if (e != hipSuccess) return sct::fail(SCT_E_HIP, "fastq fused: %s", hipGetErrorString(e));
@@ -1192,10 +954,7 @@ extern "C" int sct_fastq_extract_host(const uint8_t* buf, int64_t nbytes, const 
   if (nbytes) SCT_HIP(hipMemcpy(d_buf.p, buf, (size_t)nbytes, hipMemcpyHostToDevice));
   sct_fastq_index* ix = nullptr;
   SCT_TRY(sct_fastq_index_create((const uint8_t*)d_buf.p, nbytes, file_ends, nfiles, text_mode, nullptr, &ix));
-  struct Guard {
-    sct_fastq_index* p;
-    ~Guard() { sct_fastq_index_destroy(p); }
-  } g{ix};
+  IndexGuard g{ix};
   *nrecords = ix->nrec;
   if (max_records < ix->nrec) return SCT_OK;  // sizing call: outputs untouched
   // spans laid out back to back: row r of span k at out + nrec * off_k + r * width_k
@@ -1236,7 +995,7 @@ struct sct_fastq_stream {
   void* d_out = nullptr;  // seq | qual | seq_len | qual_len for rec_cap records
   int64_t rec_cap = 0;
   long long* d_end = nullptr;
-  int64_t nrec = 0, first_bad = -1, consumed = 0;
+  int64_t nrec = 0;
   // the next piece copied ahead (sct_fastq_stream_stage): into d_next on copy_stream, `staged`
   // recorded after it; the chunk call for (staged_ptr, staged_n) swaps d_next in
   void* d_next = nullptr;
@@ -1267,20 +1026,14 @@ extern "C" int sct_fastq_stream_create(int text_mode, const int32_t* spans, int 
                                        sct_fastq_stream** out) {
   SCT_CHECK(out != nullptr, "stream is NULL");
   *out = nullptr;
-  SCT_CHECK(nspans >= 0 && nspans <= MAX_SPANS && (nspans == 0 || spans), "0..%d spans", MAX_SPANS);
+  Spans sp;
+  SCT_TRY(make_spans(spans, nspans, &sp));
   auto* s = new sct_fastq_stream();
   s->text = text_mode ? 1 : 0;
   s->nspans = nspans;
   s->qualities = qualities ? 1 : 0;
-  for (int k = 0; k < nspans; ++k) {
-    if (!(0 <= spans[2 * k] && spans[2 * k] <= spans[2 * k + 1] && spans[2 * k + 1] <= 4096)) {
-      delete s;
-      return sct::fail(SCT_E_INVALID, "span %d = [%d, %d) unsupported", k, spans[2 * k], spans[2 * k + 1]);
-    }
-    s->spans[2 * k] = spans[2 * k];
-    s->spans[2 * k + 1] = spans[2 * k + 1];
-    s->width += spans[2 * k + 1] - spans[2 * k];
-  }
+  std::copy(spans, spans + 2 * nspans, s->spans);
+  s->width = sp.width;
   s->st = sct::host_stage();
   if (!s->st || hipMalloc((void**)&s->d_end, 8) != hipSuccess) {
     sct_fastq_stream_destroy(s);
@@ -1335,10 +1088,7 @@ extern "C" int sct_fastq_stream_chunk(sct_fastq_stream* s, const uint8_t* buf, i
   }
   sct_fastq_index* ix = nullptr;
   SCT_TRY(sct_fastq_index_create((const uint8_t*)s->d_buf, nbytes, file_ends, nfiles, s->text, hs, &ix));
-  struct Guard {
-    sct_fastq_index* p;
-    ~Guard() { sct_fastq_index_destroy(p); }
-  } g{ix};
+  IndexGuard g{ix};
   const int64_t nrec = ix->nrec;
   if (nrec > s->rec_cap) {
     if (s->d_out) (void)hipFree(s->d_out);
@@ -1360,7 +1110,7 @@ extern "C" int sct_fastq_stream_chunk(sct_fastq_stream* s, const uint8_t* buf, i
     used = 0;
     if (nrec > 0) {
       hipLaunchKernelGGL(line_end_kernel, dim3(1), dim3(WG), 0, hs, (const uint8_t*)s->d_buf, nbytes,
-                         Files{ix->d_ends, ix->nfiles}, s->text, ix->d_offsets, ix->ntiles,
+                         Files{ix->d_ends, ix->nfiles}, s->text, ix->ts, ix->ntiles,
                          (unsigned long long)(4 * nrec - 1), s->d_end);
       SCT_LAUNCH_CHECK();
       long long e = -1;
@@ -1372,8 +1122,6 @@ extern "C" int sct_fastq_stream_chunk(sct_fastq_stream* s, const uint8_t* buf, i
   }
   if (final) SCT_HIP(hipStreamSynchronize(hs));  // (the piece's buffer is the caller's again)
   s->nrec = nrec;
-  s->first_bad = bad;
-  s->consumed = used;
   *nrecords = nrec;
   *consumed = used;
   *first_bad_name = bad;

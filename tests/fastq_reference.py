@@ -8,6 +8,9 @@ record, line[s:e] slices.  No newline is split here and nothing of the device la
 Part 2, the seam cases: deterministic (contents, description, claims) with one feature -- a
 terminator, a file end, a slice's first byte -- at byte S + d of the concatenated files.  Every
 claim is checked on the CPU (tests/test_fastq_reference_host.py) before a GPU test relies on it.
+
+Part 3, the coarse pieces: whole records up to a tile seam 32 or 1,024 tiles in, then the first
+lines of a record that never ends (their claims are checked on the CPU in the same place).
 """
 
 import io
@@ -498,6 +501,43 @@ def cases(family):
     if family not in _cache:
         _cache[family] = family_high_bytes() if family == HIGH_FAMILY else FAMILIES[family]()
     return _cache[family]
+
+
+# ---------------------------------------------------------------- part 3: pieces past the coarse levels
+# The device code sums its tiles' line counts over blocks of 32 and of 1,024 tiles; a non-final
+# piece's `consumed` is found through those sums.  A coarse piece is P = K * TILE + d bytes of whole
+# records -- so the last complete record's final '\n' is the last byte of tile K - 1 (d = 0) or the
+# first of tile K (d = 1) -- and then 1..3 complete lines of a record that never ends.  Lines of
+# 4,000 bytes keep the Python reference at about a thousand records per 8 MiB.
+COARSE_K = (32, 1024)
+COARSE_LINE, COARSE_LONG = 4000, 20000
+_long = []
+
+
+def _long_records():
+    if not _long:
+        _long.extend(b"".join(record(50 + i, COARSE_LINE)) for i in range(5))
+    return _long
+
+
+def coarse_piece(K, d, tail_lines, long_lines=False):
+    """(buf, P).  long_lines: the last complete record's quality line and the unfinished record's
+    name line are COARSE_LONG bytes each (with their '\\n'), so the tiles before and after the one
+    that holds byte P - 1 hold no terminator."""
+    P = K * TILE + d
+    recs = _long_records()
+    base = len(recs[0])
+    last = record(60, COARSE_LINE)
+    if long_lines:
+        last[3] = qual_of(60, COARSE_LONG - 1) + b"\n"
+    room = len(b"".join(last))
+    n = (P - room) // base
+    body = b"".join(recs[i % len(recs)] for i in range(n))
+    last[0] = b"@" + b"n" * (P - len(body) - room) + b"\n"  # the name line sized to reach P
+    tail = record(61, COARSE_LINE)
+    if long_lines:
+        tail[0] = b"@" + b"m" * (COARSE_LONG - 2) + b"\n"
+    return body + b"".join(last) + b"".join(tail[:tail_lines]), P
 
 
 def check_claims(case):

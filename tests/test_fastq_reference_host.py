@@ -122,6 +122,37 @@ def test_seam_families_cover_the_seams():
     assert two and all(F.fastq_reference(c.contents, c.spans, "r").first_bad >= 0 for c in two)
 
 
+def _tiles_with_a_line_end(buf):
+    a = np.frombuffer(buf, np.uint8)
+    return set((np.flatnonzero((a == 10) | (a == 13)) // F.TILE).tolist())
+
+
+@pytest.mark.parametrize("K", F.COARSE_K)
+def test_coarse_pieces_hold_their_claims(K):
+    """Every coarse piece: P bytes of whole records ending in '\\n' at byte P - 1 -- the last byte of
+    tile K - 1 or the first of tile K -- then exactly the 1..3 complete lines asked for, valid names
+    throughout; the long-line variant leaves the tiles on both sides of that byte's tile without a
+    line end."""
+    for d in (0, 1):
+        for tail_lines in (1, 2, 3):
+            buf, P = F.coarse_piece(K, d, tail_lines)
+            assert P == K * F.TILE + d and (P - 1) // F.TILE == K - 1 + d and (P - 1) % F.TILE == (F.TILE - 1, 0)[d]
+            assert buf[P - 1] == 10 and buf[-1] == 10 and b"\r" not in buf and max(buf) < 128
+            assert buf[P:].count(b"\n") == tail_lines and len(buf) > P + F.COARSE_LINE * (tail_lines > 1)
+            assert buf[:P].count(b"\n") % 4 == 0 and buf[P:P + 1] == b"@"
+            ref, whole = F.fastq_reference([buf[:P]], F.SPANS[0], "rb"), F.fastq_reference([buf], F.SPANS[0], "r")
+            assert ref.nrec == whole.nrec == buf[:P].count(b"\n") // 4 and ref.first_bad == whole.first_bad == -1
+            # records of two lines of COARSE_LINE bytes and little else (the Python reference stays cheap)
+            assert P // (2 * F.COARSE_LINE + 100) - 1 <= ref.nrec <= P // (2 * F.COARSE_LINE)
+    buf, P = F.coarse_piece(K, 0, 2, long_lines=True)
+    assert len(buf) == P + F.COARSE_LONG + F.COARSE_LINE + 1 and buf[P - 1] == 10 and buf[:P].count(b"\n") % 4 == 0
+    assert buf[P - F.COARSE_LONG - 1] == 10 and buf[P + F.COARSE_LONG - 1] == 10  # the two long lines
+    assert b"\n" not in buf[P - F.COARSE_LONG:P - 1] and b"\n" not in buf[P:P + F.COARSE_LONG - 1]
+    t, has = (P - 1) // F.TILE, _tiles_with_a_line_end(buf)
+    assert t == K - 1 and t in has and not {t - 1, t + 1} & has
+    assert F.fastq_reference([buf[:P]], F.SPANS[0], "r").nrec == F.fastq_reference([buf], F.SPANS[0], "rb").nrec > 0
+
+
 def test_last_line_end_text_mode():
     """The piece cut in text mode: also after a '\\r' known to stand alone (a byte other than '\\n'
     follows it inside the piece), never after the piece's last byte when that is a '\\r'."""

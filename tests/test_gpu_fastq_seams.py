@@ -3,10 +3,16 @@ tests/fastq_reference.py -- one terminator, file end or slice at byte S + d of a
 thread's 32 bytes, the 8 KiB tile or the buffer end -- in both modes, through every entry form,
 against Python's own line reading (fastq_reference).  Exact equality throughout.
 
-indexed  _lib.fastq_extract             count_kernel + extract2_kernel
-fused    sct_fastq_extract_fused        fq_count_kernel + fastq_range_kernel (tile_items, line_spans)
-stream   _lib.FastqStream               the indexed kernels per piece + line_end_kernel's `consumed`
+Every form runs one count stage (fq_count_kernel, tile_sums_reduce_kernel) and one range stage
+(fastq_range_kernel: tile_items, line_spans); they differ in what stands around the two:
+
+indexed  _lib.fastq_extract             an index keeps the count stage's sums; rows laid out by the record count
+fused    sct_fastq_extract_fused        both stages in one asynchronous call; rows laid out by a capacity, span 0 encoded
+stream   _lib.FastqStream               an index per piece + line_end_kernel's `consumed` from the same sums
 drop-in  fastq.EmbeddedBarcodeGenerator the files read in pieces of a few bytes
+
+The coarse pieces (fastq_reference part 3) put a non-final piece's last record end 32 and 1,024
+tiles in, where `consumed` and the index's record count come from the sums over blocks of tiles.
 """
 
 import functools
@@ -172,6 +178,54 @@ def test_fastq_high_bytes_text_is_refused():
         finally:
             st.close()
         assert _fused(buf, ends, c.spans, 1)[4] != 0, c.desc
+
+
+# ---------------------------------------------------------------- pieces past the coarse levels
+@functools.lru_cache(maxsize=None)
+def _coarse_ref(K, d, long_lines, mode):
+    """The reference of a coarse piece's first P bytes (the same for every tail)."""
+    buf, P = F.coarse_piece(K, d, 1, long_lines)
+    return F.fastq_reference([buf[:P]], F.SPANS[0], mode)
+
+
+def _check_coarse(K, d, tail_lines, long_lines=False):
+    from sctools_amd import _lib
+    buf, P = F.coarse_piece(K, d, tail_lines, long_lines)
+    spans = F.SPANS[0]
+    for mode, text in MODES:
+        ref = _coarse_ref(K, d, long_lines, mode)
+        what = "K=%d d=%d, %d tail line(s)%s [%s]" % (K, d, tail_lines, ", long lines" if long_lines else "", mode)
+        assert ref.nrec > 0 and ref.first_bad == -1
+        st = _lib.FastqStream(spans, text, True)
+        try:
+            n, used, bad, parts = st.chunk(buf, len(buf), [len(buf)], False)
+        finally:
+            st.close()
+        assert (n, used, bad) == (ref.nrec, P, -1), (what, "records, consumed, first bad", (n, used, bad), (ref.nrec, P, -1))
+        _same(parts, ref, what + " non-final piece")
+        # the whole buffer through the index route: the unfinished record is dropped, the rows are the same
+        whole = F.fastq_reference([buf], spans, mode)
+        assert whole.nrec == ref.nrec
+        n, bad, parts = _lib.fastq_extract(buf, [len(buf)], spans, text)
+        assert (n, bad) == (whole.nrec, whole.first_bad), (what, "indexed: records, first bad name", (n, bad))
+        _same(parts, whole, what + " indexed")
+
+
+@pytest.mark.parametrize("d", (0, 1))
+@pytest.mark.parametrize("K", F.COARSE_K)
+def test_fastq_consumed_past_blocks_of_tiles(K, d):
+    """The last complete record ends on the last byte of tile K - 1 (d = 0) or the first byte of tile
+    K (d = 1), K = one block of the middle level and one of the top level; one to three complete
+    lines of an unfinished record follow.  `consumed` of the non-final piece is exactly P."""
+    for tail_lines in (1, 2, 3):
+        _check_coarse(K, d, tail_lines)
+
+
+@pytest.mark.parametrize("K", F.COARSE_K)
+def test_fastq_consumed_between_tiles_without_a_line_end(K):
+    """The lines on both sides of the last record end are 20,000 bytes: the tiles before and after
+    the tile that holds it count no terminator."""
+    _check_coarse(K, 0, 2, long_lines=True)
 
 
 # ---------------------------------------------------------------- the drop-in, files in tiny pieces

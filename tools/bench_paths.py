@@ -162,8 +162,8 @@ def bench_nearest(nq, max_d=1):
 
 def bench_fastq(n_rec):
     """Device-resident synthetic R1 FASTQ (69-byte records: 12-char name, 26-bp read, '+',
-    26 qualities): index (lines -> records, name check), slice CB 0:16 and UMI 16:24
-    sequences and qualities (TenXV2), TwoBit-encode the CBs with GC."""
+    26 qualities) through the device index: count stage (lines -> records), range stage (name
+    check, CB 0:16 and UMI 16:24 sequences and qualities, TenXV2), then TwoBit-encode the CBs with GC."""
     dev = torch.device("cuda")
     s = torch.cuda.current_stream()
     g = torch.Generator(device=dev).manual_seed(6)
@@ -213,8 +213,9 @@ def bench_fastq(n_rec):
             "fastq_GB_per_s": nbytes / (med * 1e-3) / 1e9,
             "roofline": {"bound": "hbm", "achieved": byts / (med * 1e-3) / 1e9, "peak": HBM_PEAK / 1e9,
                          "unit": "GB/s", "frac": byts / (med * 1e-3) / HBM_PEAK,
-                         "note": "algorithmic bytes: the FASTQ once + slices + codes; the index "
-                                 "reads the buffer twice (count, write) and syncs once for its size"}}
+                         "note": "algorithmic bytes: the FASTQ once + slices + codes; the buffer is read "
+                                 "twice (the index's count stage, which syncs once for the record count, "
+                                 "and the extraction's range stage -- the kernels of sct_fastq_extract_fused)"}}
 
 
 def bench_allpairs5():
