@@ -659,6 +659,75 @@ int sct_molecules_fetch_counted_host(sct_molecules* mol, int32_t* index, uint64_
  * access is neither needed nor enabled); on one device the kernel reads src's table in place. */
 int sct_molecules_merge(sct_molecules* dst, sct_molecules* src, void* stream);
 
+/* Counting molecules per feature: the barcode x feature matrix of a single-cell run -- molecules per
+ * (cell, antibody tag / CRISPR guide / hashtag / gene) -- as CSR on the device.  The contract is
+ * restated in plain Python by tests/count_matrix_reference.py.
+ * A *feature counter* (sct_molecules_create_features) is a molecule counter made for nw barcodes and
+ * nf features, 1 <= nf < 2^31 (else SCT_E_INVALID); flags and device are create_ex's, and create_ex
+ * itself makes what it made before.  With feat_bits = max(1, bit_length(nf - 1)), the rule of
+ * idx_bits, a key is (((index << feat_bits) | feature) << umi_bits) | umi, and
+ * idx_bits + feat_bits + umi_bits <= 63 is required (else SCT_E_INVALID; the message names the three
+ * widths), so the top bit stays 0 and EMPTY is never a key.  In practice: a 737K whitelist (20 bits)
+ * with a ThreeBit 10-base UMI (30 bits) leaves 13 feature bits, enough for tag and guide panels;
+ * gene-sized nf needs TwoBit UMIs -- 3.7M barcodes (22 bits) and 12 TwoBit bases (24 bits) leave 17.
+ * update_features takes feature[i] (int32) beside index[i] and umi[i]: the feature's index as
+ * sct_nearest_correct leaves it for a tag read, or a gene index from any aligner.  For read i, in
+ * this order:
+ *   1-3.  the rules of index, unchanged;
+ *   3b.   feature outside [-2, nf):  not counted, nothing is stored through it, and the call is
+ *                                    SCT_E_RANGE; the rest of the batch is counted;
+ *   4.    a bad UMI, unchanged (tally[2]);
+ *   4b.   feature == -1 or -2 (a tag that could not be placed): n_no_feature += 1, the fourth tally;
+ *                                    the read counts nowhere else;
+ *   5.    otherwise                  reads[index] += 1, and molecules[index] += 1 when the three-part key
+ *                                    is new.
+ * The same UMI under two features of one cell is two molecules (choosing one feature for such a
+ * pair is not done here).  Invariant: reads[nw] and molecules[nw] stay per barcode, and the row sums
+ * of the matrix below equal them (and collapse's collapsed[nw] the row sums of the collapsed values).
+ * The two-array sct_molecules_update(_host) on a feature counter is SCT_E_INVALID, and so is
+ * update_features(_host) on a counter without features; both change nothing.  n == 0 changes nothing
+ * and needs no pointer.  features_info: nf (0 for a counter without features) and n_no_feature, each
+ * nullable; sct_molecules_counts* keeps writing 3 tally words.
+ * Everything else holds for a feature counter unchanged: growth, streams, devices, info, counts,
+ * counted-ness (mreads per three-part key), and
+ *   fetch / fetch_counted   the same rows without the feature column, in ascending key order (so a
+ *                           (index, umi) pair appears once per feature it was seen under);
+ *   collapse                neighbours change UMI bits only, so a molecule's parent lies under its own
+ *                           (index, feature); collapsed[index] is per barcode;
+ *   merge                   nf must be equal too (the message names it).
+ * fetch_features: fetch's rows with the feature column, ascending by barcode, then feature, then UMI
+ * code; d_mreads and d_parent are nullable, and either one non-NULL needs a counted counter (else
+ * SCT_E_INVALID).  The room rule is fetch's.
+ * matrix: the state at the call, written and not accumulated, as CSR over nw rows:
+ *   indptr     int64[nw + 1];
+ *   feature    int32[nnz], ascending within a row;
+ *   molecules  [nnz] the distinct UMIs of entry e;
+ *   reads      [nnz] the sum of their mreads;
+ *   collapsed  [nnz] the distinct parent values over the entry's molecules (a parent always lies in its
+ *              child's entry, so the three value arrays share indptr and feature).
+ * Each value array is nullable; reads or collapsed non-NULL on a counter that is not counted is
+ * SCT_E_INVALID.  nnz (a host word, never NULL) is written whenever the call got as far as counting
+ * the entries: room < nnz is SCT_E_INVALID with nnz reported, nothing else written and the counter
+ * as it was.  nnz <= nmolecules, so room = nmolecules always suffices.  feature may be NULL only
+ * when room == 0.  The call reads the table only: twice gives the same answer.  It waits for the
+ * stream once (to learn nnz), as fetch does to learn nmolecules.  On a counter without features
+ * fetch_features and matrix are SCT_E_INVALID. */
+int sct_molecules_create_features(int64_t nw, int64_t nf, int kind, int L, int64_t capacity_hint, int flags,
+                                  int device, sct_molecules** mol);
+int sct_molecules_update_features(sct_molecules* mol, const int32_t* d_index, const int32_t* d_feature,
+                                  const uint64_t* d_umi, int64_t n, void* stream);
+int sct_molecules_update_features_host(sct_molecules* mol, const int32_t* index, const int32_t* feature,
+                                       const uint64_t* umi, int64_t n);
+int sct_molecules_features_info(sct_molecules* mol, int64_t* nf, int64_t* n_no_feature);
+int sct_molecules_fetch_features(sct_molecules* mol, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi,
+                                 uint64_t* d_mreads, uint64_t* d_parent, int64_t room, void* stream);
+int sct_molecules_fetch_features_host(sct_molecules* mol, int32_t* index, int32_t* feature, uint64_t* umi,
+                                      uint64_t* mreads, uint64_t* parent, int64_t room);
+int sct_molecules_matrix(sct_molecules* mol, int64_t* d_indptr, int32_t* d_feature, uint64_t* d_molecules,
+                         uint64_t* d_reads, uint64_t* d_collapsed, int64_t room, int64_t* nnz, void* stream);
+int sct_molecules_matrix_host(sct_molecules* mol, int64_t* indptr, int32_t* feature, uint64_t* molecules,
+                              uint64_t* reads, uint64_t* collapsed, int64_t room, int64_t* nnz);
+
 /* ---------------------------------------------------------------- FASTQ barcode extraction
  * Replaces the per-record path reader.Reader.__iter__ (src/sctools/reader.py:56-85) ->
  * fastq.Reader.record_grouper (src/sctools/fastq.py:143-150) -> Record name check

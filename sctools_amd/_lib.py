@@ -166,6 +166,14 @@ SIGNATURES = {
     "sct_molecules_fetch_counted_host": [_vp, _vp, _vp, _vp, _vp, _i64],
     "sct_molecules_create_ex": [_i64, _i32, _i32, _i64, _i32, _i32, ctypes.POINTER(_vp)],
     "sct_molecules_merge": [_vp, _vp, _vp],
+    "sct_molecules_create_features": [_i64, _i64, _i32, _i32, _i64, _i32, _i32, ctypes.POINTER(_vp)],
+    "sct_molecules_update_features": [_vp, _vp, _vp, _vp, _i64, _vp],
+    "sct_molecules_update_features_host": [_vp, _vp, _vp, _vp, _i64],
+    "sct_molecules_features_info": [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    "sct_molecules_fetch_features": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "sct_molecules_fetch_features_host": [_vp, _vp, _vp, _vp, _vp, _vp, _i64],
+    "sct_molecules_matrix": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64), _vp],
+    "sct_molecules_matrix_host": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64)],
 }
 _RESTYPES = {"sct_last_error": ctypes.c_char_p}
 

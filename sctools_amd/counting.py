@@ -151,10 +151,16 @@ class MoleculeCounter:
     made).  Every method works whatever device is current and leaves it as it was; device pointers
     and streams given to the ``*_device`` methods belong to the counter's device.  Counters fed
     different pieces of the reads -- one per file or lane, or one per GPU -- become one with
-    ``merge``."""
+    ``merge``.
+
+    ``features=nf`` (1 .. 2**31 - 1) makes a *feature counter*: every read carries a feature index
+    (an antibody tag or guide corrected by ``WhitelistCorrector``, or a gene index) as a third key
+    part, the same UMI under two features of a cell is two molecules, and ``matrix()`` returns the
+    barcode x feature molecules as CSR (include/sctools_hip.h, "counting molecules per feature").
+    Index, feature and UMI bits must fit a 63-bit key together."""
 
     def __init__(self, whitelist_size, umi_length, encoding='ThreeBit', capacity_hint=1 << 20, read_counts=False,
-                 device=None):
+                 device=None, features=None):
         kinds = {'ThreeBit': 3, 'TwoBit': 2, 3: 3, 2: 2}
         if encoding not in kinds:
             raise ValueError("encoding must be 'ThreeBit' or 'TwoBit'")
@@ -166,39 +172,91 @@ class MoleculeCounter:
         idx_bits = max(1, (nw - 1).bit_length())
         if idx_bits + kind * L > 63:
             raise ValueError("index bits %d + UMI bits %d do not fit a 63-bit key" % (idx_bits, kind * L))
+        nf = None if features is None else int(features)
+        if nf is not None:
+            if not 1 <= nf < 2 ** 31:
+                raise ValueError("features %d outside [1, 2**31)" % nf)
+            feat_bits = max(1, (nf - 1).bit_length())
+            if idx_bits + feat_bits + kind * L > 63:
+                raise ValueError("index bits %d + feature bits %d + UMI bits %d do not fit a 63-bit key"
+                                 % (idx_bits, feat_bits, kind * L))
         if not 0 <= int(capacity_hint) <= 2 ** 31:
             raise ValueError("capacity_hint outside [0, 2**31]")
         self.size, self.umi_length, self.kind = nw, L, kind
+        self._nf = nf
         self._lib = _lib.lib()
         self._h = _vp()
         self.read_counts = bool(read_counts)
         self.device = None if device is None else int(device)
         if self.device is not None and self.device < 0:
             raise ValueError("device must be a HIP ordinal (or None for the current device)")
-        _lib.check(self._lib.sct_molecules_create_ex(nw, kind, L, int(capacity_hint), int(self.read_counts),
-                                                     -1 if self.device is None else self.device,
-                                                     ctypes.byref(self._h)))
+        dev = -1 if self.device is None else self.device
+        if nf is None:
+            _lib.check(self._lib.sct_molecules_create_ex(nw, kind, L, int(capacity_hint), int(self.read_counts), dev,
+                                                         ctypes.byref(self._h)))
+        else:
+            _lib.check(self._lib.sct_molecules_create_features(nw, nf, kind, L, int(capacity_hint),
+                                                               int(self.read_counts), dev, ctypes.byref(self._h)))
+
+    @property
+    def features(self):
+        """The number of features of a feature counter, else None."""
+        return self._nf
+
+    @property
+    def n_no_feature(self):
+        """Reads that had a barcode and a good UMI but a feature of -1 or -2 (0 without features)."""
+        n = _i64(0)
+        _lib.check(self._lib.sct_molecules_features_info(self._h, None, ctypes.byref(n)))
+        return n.value
+
+    def _need_features(self, what):
+        if self._nf is None:
+            raise ValueError("%s needs MoleculeCounter(..., features=nf)" % what)
 
     def _need_read_counts(self, what):
         if not self.read_counts:
             raise ValueError("%s needs MoleculeCounter(..., read_counts=True)" % what)
 
-    def update(self, index, umis):
+    def update(self, index, umis, features=None):
         """Count a host batch: ``index`` int32 (-1 no match, -2 ambiguous, else a whitelist index)
         and the reads' uint64 UMI codes.  An index outside [-2, whitelist_size) raises ValueError
-        after the rest of the batch was counted."""
+        after the rest of the batch was counted.  A feature counter needs ``features`` as well, int32
+        of the same length (-1 / -2: no feature; outside [-2, nf) raises like a bad index); any
+        other counter rejects it."""
+        if (features is None) != (self._nf is None):
+            raise ValueError("update: features= is %s" % ("needed by a feature counter" if features is None
+                                                          else "only taken by MoleculeCounter(..., features=nf)"))
         idx = _exact(index, np.int32, "index")
         umi = _exact(umis, np.uint64, "umis")
         if idx.size != umi.size:
             raise ValueError("index and umis differ in length: %d vs %d" % (idx.size, umi.size))
+        if features is None:
+            if idx.size:
+                _lib.check(self._lib.sct_molecules_update_host(self._h, _lib._ptr(idx), _lib._ptr(umi), idx.size))
+            return self
+        feat = _exact(features, np.int32, "features")
+        if feat.size != idx.size:
+            raise ValueError("index and features differ in length: %d vs %d" % (idx.size, feat.size))
         if idx.size:
-            _lib.check(self._lib.sct_molecules_update_host(self._h, _lib._ptr(idx), _lib._ptr(umi), idx.size))
+            _lib.check(self._lib.sct_molecules_update_features_host(self._h, _lib._ptr(idx), _lib._ptr(feat),
+                                                                    _lib._ptr(umi), idx.size))
         return self
 
-    def update_device(self, index_ptr, umi_ptr, n, stream=0):
-        """Count ``n`` reads from device pointers (int32 indices, uint64 UMI codes) on ``stream``."""
-        if n:
+    def update_device(self, index_ptr, umi_ptr, n, stream=0, feature_ptr=None):
+        """Count ``n`` reads from device pointers (int32 indices, uint64 UMI codes and, for a feature
+        counter, int32 features at ``feature_ptr``) on ``stream``."""
+        if (feature_ptr is None) != (self._nf is None):
+            raise ValueError("update_device: feature_ptr= is %s" % (
+                "needed by a feature counter" if feature_ptr is None
+                else "only taken by MoleculeCounter(..., features=nf)"))
+        if not n:
+            return self
+        if feature_ptr is None:
             _lib.check(self._lib.sct_molecules_update(self._h, _vp(index_ptr), _vp(umi_ptr), int(n), _vp(stream)))
+        else:
+            _lib.check(self._lib.sct_molecules_update_features(self._h, _vp(index_ptr), _vp(feature_ptr), _vp(umi_ptr),
+                                                               int(n), _vp(stream)))
         return self
 
     def counts(self):
@@ -211,19 +269,34 @@ class MoleculeCounter:
         _lib.check(self._lib.sct_molecules_counts_host(self._h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)))
         return (reads.view(np.int64), molecules.view(np.int64), int(tally[0]), int(tally[1]), int(tally[2]))
 
-    def pairs(self, room=None, reads=False, parents=False):
+    def pairs(self, room=None, reads=False, parents=False, features=False):
         """(index int32, umi uint64) of the distinct molecules, ascending by index, then by UMI code.
         ``room`` (default: the number of molecules) sizes the output; too little raises ValueError.
         ``reads=True`` (a counter with ``read_counts``) adds each molecule's reads (int64), and
-        ``parents=True`` with it the UMI each molecule collapses into (its own if it stays)."""
+        ``parents=True`` with it the UMI each molecule collapses into (its own if it stays).
+        ``features=True`` (a feature counter): (index, feature int32, umi[, reads][, parents]),
+        ascending by index, then feature, then UMI code."""
         if parents and not reads:
             raise ValueError("parents=True needs reads=True")
         if reads:
             self._need_read_counts("pairs(reads=True)")
+        if features:
+            self._need_features("pairs(features=True)")
         got = len(self)
         n = got if room is None else int(room)
         index = np.empty(n, np.int32)
         umi = np.empty(n, np.uint64)
+        if features:
+            feature = np.empty(n, np.int32)
+            mreads = np.empty(n, np.uint64) if reads else None
+            parent = np.empty(n, np.uint64) if parents else None
+            _lib.check(self._lib.sct_molecules_fetch_features_host(self._h, _lib._ptr(index), _lib._ptr(feature),
+                                                                   _lib._ptr(umi), _lib._ptr(mreads),
+                                                                   _lib._ptr(parent), n))
+            out = (index[:got], feature[:got], umi[:got])
+            if reads:
+                out += (mreads[:got].view(np.int64),)
+            return out + (parent[:got],) if parents else out
         if not reads:
             _lib.check(self._lib.sct_molecules_fetch_host(self._h, _lib._ptr(index), _lib._ptr(umi), n))
             return index[:got], umi[:got]
@@ -244,6 +317,46 @@ class MoleculeCounter:
         self._need_read_counts("fetch_counted_device")
         _lib.check(self._lib.sct_molecules_fetch_counted(self._h, _vp(index_ptr), _vp(umi_ptr), _vp(reads_ptr),
                                                          _vp(parent_ptr or None), int(room), _vp(stream)))
+
+    def matrix(self, reads=False, collapsed=False, room=None):
+        """The barcode x feature count matrix of a feature counter as CSR: (indptr int64
+        [whitelist_size + 1], feature int32 [nnz], molecules int64 [nnz]) and, if asked (a counter
+        with ``read_counts``), reads and collapsed (int64 [nnz]) after them -- the entry's reads and
+        its molecules after the UMI collapse.  Features ascend within a row, and
+        ``scipy.sparse.csr_matrix((molecules, feature, indptr), shape=(whitelist_size, features))``
+        takes the arrays as they are.  ``room`` (default: the number of molecules, which always
+        suffices) sizes the output; fewer than nnz raises ValueError, which names nnz."""
+        self._need_features("matrix")
+        if reads:
+            self._need_read_counts("matrix(reads=True)")
+        if collapsed:
+            self._need_read_counts("matrix(collapsed=True)")
+        n = len(self) if room is None else int(room)
+        if n < 0:
+            raise ValueError("room must be >= 0")
+        indptr = np.empty(self.size + 1, np.int64)
+        feature = np.empty(max(n, 1), np.int32)
+        values = [np.empty(max(n, 1), np.uint64) if want else None for want in (True, reads, collapsed)]
+        nnz = _i64(0)
+        _lib.check(self._lib.sct_molecules_matrix_host(self._h, _lib._ptr(indptr), _lib._ptr(feature),
+                                                       _lib._ptr(values[0]), _lib._ptr(values[1]),
+                                                       _lib._ptr(values[2]), n, ctypes.byref(nnz)))
+        k = nnz.value
+        return (indptr, feature[:k].copy()) + tuple(v[:k].view(np.int64).copy() for v in values if v is not None)
+
+    def matrix_device(self, indptr_ptr, feature_ptr, molecules_ptr, reads_ptr, collapsed_ptr, room, stream=0):
+        """matrix() into device arrays with room for ``room`` entries (sct_molecules_matrix): int64
+        [whitelist_size + 1], int32 [room] and up to three uint64 [room], each of the three 0 / None
+        when not wanted.  Returns nnz; waits for ``stream`` once to learn it."""
+        self._need_features("matrix_device")
+        if reads_ptr or collapsed_ptr:
+            self._need_read_counts("matrix_device with reads or collapsed")
+        nnz = _i64(0)
+        _lib.check(self._lib.sct_molecules_matrix(self._h, _vp(indptr_ptr), _vp(feature_ptr or None),
+                                                  _vp(molecules_ptr or None), _vp(reads_ptr or None),
+                                                  _vp(collapsed_ptr or None), int(room), ctypes.byref(nnz),
+                                                  _vp(stream)))
+        return nnz.value
 
     def collapse(self):
         """(collapsed np.int64[whitelist_size], n_corrected int): the molecules per barcode after every
@@ -270,9 +383,9 @@ class MoleculeCounter:
             raise ValueError("a MoleculeCounter cannot be merged into itself")
         if not self._h or not other._h:
             raise ValueError("merge: %s counter is closed" % ("this" if not self._h else "the other"))
-        mine = (self.size, self.kind, self.umi_length, self.read_counts)
-        theirs = (other.size, other.kind, other.umi_length, other.read_counts)
-        for name, a, b in zip(("whitelist_size", "encoding", "umi_length", "read_counts"), mine, theirs):
+        mine = (self.size, self.kind, self.umi_length, self.read_counts, self._nf)
+        theirs = (other.size, other.kind, other.umi_length, other.read_counts, other._nf)
+        for name, a, b in zip(("whitelist_size", "encoding", "umi_length", "read_counts", "features"), mine, theirs):
             if a != b:
                 raise ValueError("merge: the counters' %s differ (%r and %r)" % (name, a, b))
         _lib.check(self._lib.sct_molecules_merge(self._h, other._h, _vp(stream)))

@@ -43,10 +43,26 @@
 // molecule's reads as its count.  The target is grown first (molecules_merge_plan.h) so that every
 // row may be new at a load of at most 1/2; reads[] and the tally are added by a kernel of their own.
 // A counter's calls make its device current for their duration (DeviceGuard).
+//
+// A *feature counter* (include/sctools_hip.h, "counting molecules per feature") has a third key part
+// between the index and the UMI (molecules_feature_key.h).  FEATURES is a template parameter of the
+// insert kernels as COUNTED is: a counter without features runs the instantiations without it, and
+// the feature insert loads 16 B per read (int32 index, int32 feature, uint64 umi).  Everything that
+// works on whole keys (rehash, merge, compaction, the neighbours of the collapse, which change UMI
+// bits only) is the same code; the barcode of a key is key >> idx_shift in both kinds of counter.
+// The count matrix is built from the sorted (key, slot) rows of fetch_counted by a run pass: a wave
+// takes 64 adjacent rows, a row is a head when its (index, feature) differs from the row before it
+// (lane 0 looks one row back in global memory), the heads of every wave tile are counted, a scan of
+// the tile counts numbers the entries, and a second pass writes feature[e], adds 1 to its barcode's
+// entry count and reduces each entry's rows inside the wave -- run length, cnt[slot], the slot's bit
+// in the collapse pass's bitmap -- to one 64-bit integer atomic add per (wave, entry) and value.
+// A scan of the nw + 1 entry counts is indptr.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <type_traits>
 
+#include "molecules_feature_key.h"
 #include "molecules_key.h"
 #include "molecules_merge_plan.h"
 #include "open_table.h"
@@ -56,9 +72,10 @@ namespace {
 
 using namespace sct::open_table;
 
-// the molecule counter's own device words; W_TALLY .. W_TALLY + 2 = no match, ambiguous, bad UMI
+// the molecule counter's own device words; W_TALLY .. W_TALLY + 3 = no match, ambiguous, bad UMI and
+// (feature counters) no feature
 enum { W_ERROR = W_OWN, W_CURSOR, W_TALLY };
-static_assert(W_TALLY + 3 <= W_NWORDS, "the tally lives in the device words");
+static_assert(W_TALLY + 4 <= W_NWORDS, "the tally lives in the device words");
 
 struct Set {
   u64* keys;
@@ -70,15 +87,19 @@ struct Set {
   int64_t nw;
   int kind;
   int umi_bits;
+  int64_t nf;     // features, 0 in a counter without them
+  int feat_bits;  // 0 in a counter without features
+  int idx_shift;  // feat_bits + umi_bits: a key's barcode is key >> idx_shift
 };
 
 // `count` reads of one molecule: reads[index] += count, and molecules[index] += 1 from the lane that
 // claimed the key's slot.  The index comes out of a key built from a checked index: index < nw.
 // COUNTED: the carrier of the key also adds its count to the slot's mreads (cnt is zero at every
 // empty slot, so it does not matter whether the claiming lane or another one adds first).
-template <bool COUNTED>
+// FEATURES: the barcode lies above the feature bits.
+template <bool COUNTED, bool FEATURES>
 __device__ __forceinline__ int set_add(const Set& t, u64 key, u64 count) {
-  const uint32_t index = sct::mol_key_index(key, t.umi_bits);
+  const uint32_t index = sct::mol_key_index(key, FEATURES ? t.idx_shift : t.umi_bits);
   atomicAdd(&t.reads[index], count);
   u64 slot = NO_SLOT;
   const bool claimed = claim<COUNTED>(t.keys, t.mask, &t.words[W_OVERFLOW], key, &slot);
@@ -88,25 +109,45 @@ __device__ __forceinline__ int set_add(const Set& t, u64 key, u64 count) {
   return 1;
 }
 
-// What one read is: rule 1..5 of the contract.  `key` is set for GOOD only.
-enum { R_SKIP = 0, R_NONE, R_TIE, R_BADUMI, R_ERROR, R_GOOD };
-__device__ __forceinline__ int classify(const Set& t, int32_t v, u64 umi, u64* key) {
+// What one read is: rule 1..5 of the contract (FEATURES: with 3b and 4b).  `key` is set for GOOD only.
+enum { R_SKIP = 0, R_NONE, R_TIE, R_BADUMI, R_ERROR, R_GOOD, R_NOFEATURE };
+template <bool FEATURES>
+__device__ __forceinline__ int classify(const Set& t, int32_t v, int32_t f, u64 umi, u64* key) {
   if (v == -1) return R_NONE;
   if (v == -2) return R_TIE;
   if (v < 0 || (int64_t)v >= t.nw) return R_ERROR;
+  if (FEATURES && (f < -2 || (int64_t)f >= t.nf)) return R_ERROR;
   if (sct::mol_umi_bad(umi, t.kind, t.umi_bits)) return R_BADUMI;
-  *key = sct::mol_key((uint32_t)v, umi, t.umi_bits);
+  if (FEATURES) {
+    if (f < 0) return R_NOFEATURE;
+    *key = sct::mol_fkey((uint32_t)v, (uint32_t)f, umi, t.feat_bits, t.umi_bits);
+  } else {
+    *key = sct::mol_key((uint32_t)v, umi, t.umi_bits);
+  }
   return R_GOOD;
 }
 
-// The three popular non-answers of a wave's reads, summed in registers (the same in every lane).
+// read i of a batch as the insert kernels see it: 12 B, and 4 B more with a feature
+template <bool FEATURES>
+__device__ __forceinline__ int classify_at(const Set& t, const int32_t* __restrict__ index,
+                                           const int32_t* __restrict__ feature, const u64* __restrict__ umi, int64_t i,
+                                           u64* key) {
+  const int32_t f = FEATURES ? __builtin_nontemporal_load(&feature[i]) : 0;
+  return classify<FEATURES>(t, __builtin_nontemporal_load(&index[i]), f, __builtin_nontemporal_load(&umi[i]), key);
+}
+
+// The popular non-answers of a wave's reads, summed in registers (the same in every lane); the
+// fourth, a read with no feature, exists in a feature counter only.
+template <bool FEATURES>
 struct WaveTally {
-  uint32_t n[3] = {0, 0, 0};
+  static constexpr int kN = FEATURES ? 4 : 3;
+  uint32_t n[kN] = {};
   bool error = false;
   __device__ __forceinline__ void see(int what) {
     n[0] += (uint32_t)__popcll(__ballot(what == R_NONE));
     n[1] += (uint32_t)__popcll(__ballot(what == R_TIE));
     n[2] += (uint32_t)__popcll(__ballot(what == R_BADUMI));
+    if (FEATURES) n[kN - 1] += (uint32_t)__popcll(__ballot(what == R_NOFEATURE));
     error |= what == R_ERROR;
   }
   // the claimed slots into the size word, one add per wave and non-zero tally, the error word
@@ -114,7 +155,7 @@ struct WaveTally {
     add_claims(&t.words[W_SIZE], claims);
     const bool any_error = __ballot(error) != 0;
     if ((threadIdx.x & 63) != 0) return;
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < kN; ++k)
       if (n[k]) atomicAdd(&t.words[W_TALLY + k], (u64)n[k]);
     if (any_error) atomicOr(&t.words[W_ERROR], 1ull);
   }
@@ -122,23 +163,24 @@ struct WaveTally {
 
 // MERGE = false: one probe per read.  MERGE = true: equal keys of a wave are merged first -- the
 // lowest lane holding a key carries the count of its copies, the others add nothing.
-template <bool MERGE, bool COUNTED>
+template <bool MERGE, bool COUNTED, bool FEATURES>
 __global__ void __launch_bounds__(WG) molecules_insert_kernel(Set t, const int32_t* __restrict__ index,
+                                                              const int32_t* __restrict__ feature,
                                                               const u64* __restrict__ umi, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * WG;
   const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
   const int64_t iters = (n + stride - 1) / stride;  // the same for every lane: the wave stays whole
-  WaveTally wt;
+  WaveTally<FEATURES> wt;
   int claims = 0;
   for (int64_t it = 0; it < iters; ++it) {
     const int64_t i = it * stride + gid;
     u64 key = 0;
     int what = R_SKIP;
-    if (i < n) what = classify(t, __builtin_nontemporal_load(&index[i]), __builtin_nontemporal_load(&umi[i]), &key);
+    if (i < n) what = classify_at<FEATURES>(t, index, feature, umi, i, &key);
     wt.see(what);
     const bool good = what == R_GOOD;
     const Merged m = MERGE ? wave_merge(good, key) : Merged{good, 1};
-    if (m.rep) claims += set_add<COUNTED>(t, key, m.count);
+    if (m.rep) claims += set_add<COUNTED, FEATURES>(t, key, m.count);
   }
   wt.flush(t, claims);
 }
@@ -146,8 +188,9 @@ __global__ void __launch_bounds__(WG) molecules_insert_kernel(Set t, const int32
 // A tile of kTile reads is grouped in an LDS table first (keys, counts), then every occupied LDS slot
 // becomes one global probe and one reads[index] add.  A key that finds no LDS slot within kLdsSlots
 // probes (the table holds twice a tile's reads, so none does) goes to the global path directly.
-template <bool COUNTED>
+template <bool COUNTED, bool FEATURES>
 __global__ void __launch_bounds__(WG) molecules_insert_lds_kernel(Set t, const int32_t* __restrict__ index,
+                                                                  const int32_t* __restrict__ feature,
                                                                   const u64* __restrict__ umi, int64_t n) {
   __shared__ u64 lkey[kLdsSlots];
   __shared__ uint32_t lcnt[kLdsSlots];
@@ -157,7 +200,7 @@ __global__ void __launch_bounds__(WG) molecules_insert_lds_kernel(Set t, const i
   }
   __syncthreads();
   const int64_t ntiles = (n + kTile - 1) / kTile;
-  WaveTally wt;
+  WaveTally<FEATURES> wt;
   int claims = 0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // block-uniform
     const int64_t t0 = tile * kTile;
@@ -166,18 +209,18 @@ __global__ void __launch_bounds__(WG) molecules_insert_lds_kernel(Set t, const i
       const int64_t i = t0 + k * WG + threadIdx.x;
       u64 key = 0;
       int what = R_SKIP;
-      if (i < n) what = classify(t, __builtin_nontemporal_load(&index[i]), __builtin_nontemporal_load(&umi[i]), &key);
+      if (i < n) what = classify_at<FEATURES>(t, index, feature, umi, i, &key);
       wt.see(what);
       if (what != R_GOOD) continue;
       const int s = lds_claim(lkey, (uint32_t)sct::mix64(key) & (kLdsSlots - 1), key);
       if (s >= 0) atomicAdd(&lcnt[s], 1u);
-      else claims += set_add<COUNTED>(t, key, 1);
+      else claims += set_add<COUNTED, FEATURES>(t, key, 1);
     }
     __syncthreads();
     for (int s = threadIdx.x; s < kLdsSlots; s += WG) {
       const u64 key = lkey[s];
       if (key == EMPTY) continue;
-      claims += set_add<COUNTED>(t, key, (u64)lcnt[s]);
+      claims += set_add<COUNTED, FEATURES>(t, key, (u64)lcnt[s]);
       lkey[s] = EMPTY;
       lcnt[s] = 0;
     }
@@ -263,7 +306,7 @@ __global__ void __launch_bounds__(WG) molecules_collapse_kernel(Set t, int64_t c
       u64 at;
       const u64 parent = parent_of(t, key, (u64)s, &at);
       moves = parent != key;
-      if (bitmap_claim(bitmap, at)) atomicAdd(&collapsed[sct::mol_key_index(key, t.umi_bits)], 1ull);
+      if (bitmap_claim(bitmap, at)) atomicAdd(&collapsed[sct::mol_key_index(key, t.idx_shift)], 1ull);
     }
     moved += (uint32_t)__popcll(__ballot(moves));
   }
@@ -295,7 +338,7 @@ __global__ void __launch_bounds__(WG) molecules_collapse_wave_kernel(Set t, int6
         if (sct::umi_support_less(b.reads, b.code, c.reads, c.code)) b = c;
       }
       if (lane == 0 && bitmap_claim(bitmap, b.slot))
-        atomicAdd(&collapsed[sct::mol_key_index(key, t.umi_bits)], 1ull);
+        atomicAdd(&collapsed[sct::mol_key_index(key, t.idx_shift)], 1ull);
       moved += b.code != key;
     }
   }
@@ -323,17 +366,20 @@ __global__ void __launch_bounds__(WG) molecules_compact_kernel(const u64* __rest
   }
 }
 
-// the sorted (key, slot) pairs as rows: index, UMI, mreads and, if asked, the parent's UMI
+// the sorted (key, slot) pairs as rows: index, UMI and, each if asked, the feature, mreads and the
+// parent's UMI
 __global__ void __launch_bounds__(WG) molecules_emit_kernel(Set t, const u64* __restrict__ keys,
                                                             const uint32_t* __restrict__ slots, int64_t rows,
-                                                            int32_t* __restrict__ index, u64* __restrict__ umi,
-                                                            u64* __restrict__ mreads, u64* __restrict__ parent) {
+                                                            int32_t* __restrict__ index, int32_t* __restrict__ feature,
+                                                            u64* __restrict__ umi, u64* __restrict__ mreads,
+                                                            u64* __restrict__ parent) {
   for (int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WG) {
     const u64 key = keys[r];
     const u64 slot = slots[r];
-    index[r] = (int32_t)sct::mol_key_index(key, t.umi_bits);
+    index[r] = (int32_t)sct::mol_key_index(key, t.idx_shift);
+    if (feature) feature[r] = (int32_t)sct::mol_fkey_feature(key, t.feat_bits, t.umi_bits);
     umi[r] = sct::mol_key_umi(key, t.umi_bits);
-    mreads[r] = t.cnt[slot];
+    if (mreads) mreads[r] = t.cnt[slot];
     if (parent) {
       u64 at;
       parent[r] = sct::mol_key_umi(parent_of(t, key, slot, &at), t.umi_bits);
@@ -342,11 +388,92 @@ __global__ void __launch_bounds__(WG) molecules_emit_kernel(Set t, const u64* __
 }
 
 __global__ void __launch_bounds__(WG) molecules_split_kernel(const u64* __restrict__ keys, int64_t rows, int umi_bits,
-                                                             int32_t* __restrict__ index, u64* __restrict__ umi) {
+                                                             int feat_bits, int32_t* __restrict__ index,
+                                                             int32_t* __restrict__ feature, u64* __restrict__ umi) {
   for (int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WG) {
     const u64 key = keys[r];
-    index[r] = (int32_t)sct::mol_key_index(key, umi_bits);
+    index[r] = (int32_t)sct::mol_key_index(key, feat_bits + umi_bits);
+    if (feature) feature[r] = (int32_t)sct::mol_fkey_feature(key, feat_bits, umi_bits);
     umi[r] = sct::mol_key_umi(key, umi_bits);
+  }
+}
+
+// ---- the count matrix (include/sctools_hip.h, "counting molecules per feature"): the run pass over
+// the rows sorted by key.  A wave tile is 64 adjacent rows, one per lane.
+
+// whether this lane's row opens an entry: its (index, feature) differs from the previous row's.  The
+// previous row is the lane below; lane 0 reads it from global memory.  Called by every lane.
+__device__ __forceinline__ bool row_is_head(const u64* __restrict__ keys, int64_t r, bool in, u64 key, int umi_bits) {
+  u64 prev = __shfl_up(key, 1);
+  if ((threadIdx.x & 63) == 0 && in && r > 0) prev = keys[r - 1];
+  return in && (r == 0 || sct::mol_fkey_head(key, prev, umi_bits));
+}
+
+// heads[tile] = the entries that open in the tile's 64 rows
+__global__ void __launch_bounds__(WG) molecules_matrix_heads_kernel(const u64* __restrict__ keys, int64_t rows,
+                                                                    int umi_bits, u64* __restrict__ heads) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ntiles = (rows + 63) / 64, nwaves = (int64_t)gridDim.x * (WG / 64);
+  for (int64_t tile = ((int64_t)blockIdx.x * WG + threadIdx.x) >> 6; tile < ntiles; tile += nwaves) {  // wave-uniform
+    const int64_t r = tile * 64 + lane;
+    const bool in = r < rows;
+    const u64 key = in ? keys[r] : 0;
+    const u64 m = __ballot(row_is_head(keys, r, in, key, umi_bits));
+    if (lane == 0) heads[tile] = (u64)__popcll(m);
+  }
+}
+
+// base[tile] = the entries that open before the tile (the scan of heads[]).  Row r belongs to entry
+// e = base + (heads of the tile at or below its lane) - 1; a tile whose lane 0 is no head continues
+// entry base - 1.  A head writes feature[e] and adds 1 to its barcode's entry count.  The rows of an
+// entry are adjacent lanes: the lowest of them in this wave (a head, or lane 0) adds the wave's share
+// of each value to the entry, one integer atomic add per (wave, entry) and value -- the run length,
+// the sum of cnt[slot], and the slots whose bit the collapse pass set (the entry's distinct parents:
+// a parent lies in its child's entry).  Each value array is nullable.
+__global__ void __launch_bounds__(WG) molecules_matrix_fill_kernel(Set t, const u64* __restrict__ keys,
+                                                                   const uint32_t* __restrict__ slots, int64_t rows,
+                                                                   const u64* __restrict__ base,
+                                                                   const uint32_t* __restrict__ bitmap,
+                                                                   u64* __restrict__ row_entries,
+                                                                   int32_t* __restrict__ feature,
+                                                                   u64* __restrict__ molecules, u64* __restrict__ reads,
+                                                                   u64* __restrict__ collapsed) {
+  const int lane = threadIdx.x & 63;
+  const u64 at_or_below = ~0ull >> (63 - lane), below = at_or_below >> 1;
+  const int64_t ntiles = (rows + 63) / 64, nwaves = (int64_t)gridDim.x * (WG / 64);
+  for (int64_t tile = ((int64_t)blockIdx.x * WG + threadIdx.x) >> 6; tile < ntiles; tile += nwaves) {  // wave-uniform
+    const int64_t r = tile * 64 + lane;
+    const bool in = r < rows;
+    const u64 key = in ? keys[r] : 0;
+    const bool head = row_is_head(keys, r, in, key, t.umi_bits);
+    const u64 heads = __ballot(head), valid = __ballot(in);
+    const u64 e = base[tile] + (u64)__popcll(heads & at_or_below) - 1;  // lane 0 of tile 0 is a head: e >= 0
+    if (head) {
+      feature[e] = (int32_t)sct::mol_fkey_feature(key, t.feat_bits, t.umi_bits);
+      atomicAdd(&row_entries[sct::mol_key_index(key, t.idx_shift)], 1ull);
+    }
+    // this lane's run: from itself up to the next head, within the tile's rows
+    const bool first = in && (head || lane == 0);
+    const u64 later = heads & ~at_or_below;
+    const u64 run = (later ? (later & (~later + 1)) - 1 : ~0ull) & ~below & valid;
+    if (molecules && first) atomicAdd(&molecules[e], (u64)__popcll(run));
+    if (reads) {
+      const u64 mine = in ? t.cnt[slots[r]] : 0;
+      u64 sum = mine;  // the inclusive prefix sums of the tile's mreads
+      for (int o = 1; o < 64; o <<= 1) {
+        const u64 up = __shfl_up(sum, o);
+        if (lane >= o) sum += up;
+      }
+      const int last = run ? 63 - __clzll((long long)run) : lane;
+      const u64 through = __shfl(sum, last);
+      if (first) atomicAdd(&reads[e], through - sum + mine);
+    }
+    if (collapsed) {
+      const uint32_t s = in ? slots[r] : 0;
+      const u64 images = __ballot(in && ((bitmap[s >> 5] >> (s & 31)) & 1u));
+      const u64 n = (u64)__popcll(images & run);
+      if (first && n) atomicAdd(&collapsed[e], n);
+    }
   }
 }
 
@@ -378,19 +505,19 @@ __global__ void __launch_bounds__(WG) molecules_merge_kernel(Set t, const u64* _
     const bool claimed = claim<COUNTED>(t.keys, t.mask, &t.words[W_OVERFLOW], key, &slot);
     if (COUNTED && slot != NO_SLOT) atomicAdd(&t.cnt[slot], count);
     if (!claimed) continue;
-    atomicAdd(&t.molecules[sct::mol_key_index(key, t.umi_bits)], 1ull);
+    atomicAdd(&t.molecules[sct::mol_key_index(key, t.idx_shift)], 1ull);
     ++claims;
   }
   add_claims(&t.words[W_SIZE], claims);
 }
 
-// reads[nw] += the other counter's, and its three tallies (`words` is its device words or a copy)
+// reads[nw] += the other counter's, and its tallies (the fourth is 0 without features) (`words` is its device words or a copy)
 __global__ void __launch_bounds__(WG) molecules_add_kernel(u64* __restrict__ reads, u64* __restrict__ words,
                                                            const u64* __restrict__ from_reads,
                                                            const u64* __restrict__ from_words, int64_t nw) {
   const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
   for (int64_t i = gid; i < nw; i += (int64_t)gridDim.x * WG) reads[i] += from_reads[i];
-  if (gid < 3) words[W_TALLY + gid] += from_words[W_TALLY + gid];
+  if (gid < 4) words[W_TALLY + gid] += from_words[W_TALLY + gid];
 }
 
 // the reads of the compacted (key, slot) pairs: the dense rows' cnt[]
@@ -482,25 +609,44 @@ int grow(sct_molecules* c, int64_t factor, hipStream_t s) {
 }
 
 int range_error(const sct_molecules* c) {
+  if (c->t.nf)
+    return sct::fail(SCT_E_RANGE, "index outside [-2, %lld) or feature outside [-2, %lld) (not counted)",
+                     (long long)c->t.nw, (long long)c->t.nf);
   return sct::fail(SCT_E_RANGE, "index outside [-2, %lld) (not counted)", (long long)c->t.nw);
 }
 
-// *range is set when the batch held an index outside [-2, nw) (rule 3; the status stays SCT_OK)
-int update_device(sct_molecules* c, const int32_t* d_index, const uint64_t* d_umi, int64_t n, hipStream_t s,
-                  bool* range) {
+// the update form must be the counter's: three arrays for a feature counter, two for any other
+int need_features(const sct_molecules* c, bool features) {
+  if (features) {
+    SCT_CHECK(c->t.nf != 0, "the molecule counter has no features (sct_molecules_create_features makes one that has)");
+  } else {
+    SCT_CHECK(c->t.nf == 0, "a feature counter is updated with a feature per read (sct_molecules_update_features)");
+  }
+  return SCT_OK;
+}
+
+// *range is set when the batch held an index outside [-2, nw) or a feature outside [-2, nf) (rules 3
+// and 3b; the status stays SCT_OK).  d_feature is the third array of a feature counter, else NULL.
+int update_device(sct_molecules* c, const int32_t* d_index, const int32_t* d_feature, const uint64_t* d_umi, int64_t n,
+                  hipStream_t s, bool* range) {
   if (int rc = enter(c, s); rc != SCT_OK) return rc;
   const int64_t mode = sct::tune(SCT_TUNE_COUNT_PREAGG, 1);
   const auto launch_batch = [&](int64_t done, int64_t m) -> int {
     const int32_t* idx = d_index + done;
     const u64* umi = reinterpret_cast<const u64*>(d_umi) + done;
     const dim3 grid(mode <= 1 ? grid_for(m, 4 * WG) : grid_for(m, kTile));
-    const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(WG), 0, s, c->t, idx, umi, m); };
-    if (mode == 0)
-      c->counted ? launch(molecules_insert_kernel<false, true>) : launch(molecules_insert_kernel<false, false>);
-    else if (mode == 1)
-      c->counted ? launch(molecules_insert_kernel<true, true>) : launch(molecules_insert_kernel<true, false>);
-    else
-      c->counted ? launch(molecules_insert_lds_kernel<true>) : launch(molecules_insert_lds_kernel<false>);
+    const int32_t* feat = d_feature ? d_feature + done : nullptr;
+    const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(WG), 0, s, c->t, idx, feat, umi, m); };
+    const auto of_mode = [&](auto counted, auto features) {
+      constexpr bool C = decltype(counted)::value, F = decltype(features)::value;
+      if (mode == 0) launch(molecules_insert_kernel<false, C, F>);
+      else if (mode == 1) launch(molecules_insert_kernel<true, C, F>);
+      else launch(molecules_insert_lds_kernel<C, F>);
+    };
+    const auto of_counted = [&](auto features) {
+      c->counted ? of_mode(std::true_type{}, features) : of_mode(std::false_type{}, features);
+    };
+    d_feature ? of_counted(std::true_type{}) : of_counted(std::false_type{});
     SCT_LAUNCH_CHECK();
     return SCT_OK;
   };
@@ -516,14 +662,15 @@ int update_device(sct_molecules* c, const int32_t* d_index, const uint64_t* d_um
 }
 
 // the distinct molecules in ascending key order into device arrays with room for `room` rows
-int fetch_device(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, int64_t room, hipStream_t s) {
+// (d_feature: the feature column of a feature counter, nullable)
+int fetch_device(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi, int64_t room, hipStream_t s) {
   if (int rc = enter(c, s); rc != SCT_OK) return rc;
   if (int rc = read_words(c, s); rc != SCT_OK) return rc;
   const int64_t rows = c->size_bound;
   SCT_CHECK(room >= rows, "room for %lld molecules, the counter holds %lld", (long long)room, (long long)rows);
   if (rows == 0) return SCT_OK;
   SCT_CHECK(d_index && d_umi, "NULL output");
-  const int end_bit = c->idx_bits + c->t.umi_bits;
+  const int end_bit = c->idx_bits + c->t.idx_shift;
   size_t sort_bytes = 0;
   (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr, (int)rows, 0,
                                           end_bit, s);
@@ -543,7 +690,7 @@ int fetch_device(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, int64_t ro
   }
   if (e == hipSuccess) {
     hipLaunchKernelGGL(molecules_split_kernel, dim3(grid_for(rows, 1024)), dim3(WG), 0, s, keys_out, rows,
-                       c->t.umi_bits, d_index, reinterpret_cast<u64*>(d_umi));
+                       c->t.umi_bits, c->t.feat_bits, d_index, d_feature, reinterpret_cast<u64*>(d_umi));
     e = hipGetLastError();
   }
   sct::pool_free(blk, s);
@@ -592,11 +739,11 @@ int rows_for_fetch(sct_molecules* c, int64_t room, hipStream_t s, int64_t* rows)
 }
 
 // fetch's rows with each row's mreads and, if asked, its parent's UMI beside them: `rows` > 0 rows,
-// as rows_for_fetch gave them on `s`
-int fetch_counted_rows(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, uint64_t* d_mreads, uint64_t* d_parent,
-                       int64_t rows, hipStream_t s) {
-  SCT_CHECK(d_index && d_umi && d_mreads, "NULL output");
-  const int end_bit = c->idx_bits + c->t.umi_bits;
+// as rows_for_fetch gave them on `s` (fetch_features: d_feature is asked for and d_mreads need not be)
+int fetch_counted_rows(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi, uint64_t* d_mreads,
+                       uint64_t* d_parent, int64_t rows, hipStream_t s) {
+  SCT_CHECK(d_index && d_umi && (d_mreads || d_feature), "NULL output");
+  const int end_bit = c->idx_bits + c->t.idx_shift;
   size_t sort_bytes = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr,
                                            (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)rows, 0, end_bit, s);
@@ -620,7 +767,7 @@ int fetch_counted_rows(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, uint
   }
   if (e == hipSuccess) {
     hipLaunchKernelGGL(molecules_emit_kernel, dim3(grid_for(rows, WG)), dim3(WG), 0, s, c->t, keys_out, slots_out, rows,
-                       d_index, reinterpret_cast<u64*>(d_umi), reinterpret_cast<u64*>(d_mreads),
+                       d_index, d_feature, reinterpret_cast<u64*>(d_umi), reinterpret_cast<u64*>(d_mreads),
                        reinterpret_cast<u64*>(d_parent));
     e = hipGetLastError();
   }
@@ -649,6 +796,8 @@ int merge_check(const sct_molecules* dst, const sct_molecules* src) {
   SCT_CHECK(dst->t.kind == src->t.kind, "merge: the counters' kind differ (%d and %d)", dst->t.kind, src->t.kind);
   SCT_CHECK(dst->t.umi_bits == src->t.umi_bits, "merge: the counters' L differ (%d and %d)",
             dst->t.umi_bits / dst->t.kind, src->t.umi_bits / src->t.kind);
+  SCT_CHECK(dst->t.nf == src->t.nf, "merge: the counters' nf differ (%lld and %lld; 0: no features)",
+            (long long)dst->t.nf, (long long)src->t.nf);
   SCT_CHECK(dst->counted == src->counted, "merge: one counter keeps read counts and the other does not");
   return SCT_OK;
 }
@@ -787,7 +936,8 @@ int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
 
 namespace {
 
-int create(int64_t nw, int kind, int L, int64_t capacity_hint, int flags, int device, sct_molecules** out) {
+// nf == 0: a counter without features
+int create(int64_t nw, int64_t nf, int kind, int L, int64_t capacity_hint, int flags, int device, sct_molecules** out) {
   SCT_CHECK(out != nullptr, "molecule counter is NULL");
   *out = nullptr;
   SCT_CHECK((flags & ~SCT_MOLECULES_COUNTED) == 0, "unknown flags 0x%x", (unsigned)flags);
@@ -799,6 +949,10 @@ int create(int64_t nw, int kind, int L, int64_t capacity_hint, int flags, int de
   const int umi_bits = sct::mol_umi_bits(nw, kind, L);
   SCT_CHECK(umi_bits > 0, "index bits %d + UMI bits %lld do not fit a 63-bit key", sct::mol_idx_bits(nw),
             (long long)kind * L);
+  const int feat_bits = nf ? sct::mol_feat_bits(nf) : 0;
+  SCT_CHECK(nf == 0 || sct::mol_feature_umi_bits(nw, nf, kind, L) > 0,
+            "index bits %d + feature bits %d + UMI bits %d do not fit a 63-bit key", sct::mol_idx_bits(nw), feat_bits,
+            umi_bits);
   SCT_CHECK(capacity_hint >= 0 && capacity_hint <= sct::kTableMaxCapacity, "capacity hint %lld outside [0, 2^31]",
             (long long)capacity_hint);
   const int64_t cap = sct::table_capacity_for(capacity_hint);
@@ -828,6 +982,9 @@ int create(int64_t nw, int kind, int L, int64_t capacity_hint, int flags, int de
   c->t.nw = nw;
   c->t.kind = kind;
   c->t.umi_bits = umi_bits;
+  c->t.nf = nf;
+  c->t.feat_bits = feat_bits;
+  c->t.idx_shift = feat_bits + umi_bits;
   c->t.mask = (u64)cap - 1;
   if (int rc = alloc_filled(&c->t.keys, cap, 0xFF, hs->stream, kKeysName); rc != SCT_OK) return fail_with(rc);
   if (counted)
@@ -853,7 +1010,15 @@ int create(int64_t nw, int kind, int L, int64_t capacity_hint, int flags, int de
 
 extern "C" int sct_molecules_create_ex(int64_t nw, int kind, int L, int64_t capacity_hint, int flags, int device,
                                        sct_molecules** out) {
-  return create(nw, kind, L, capacity_hint, flags, device, out);
+  return create(nw, 0, kind, L, capacity_hint, flags, device, out);
+}
+
+extern "C" int sct_molecules_create_features(int64_t nw, int64_t nf, int kind, int L, int64_t capacity_hint, int flags,
+                                             int device, sct_molecules** out) {
+  SCT_CHECK(out != nullptr, "molecule counter is NULL");
+  *out = nullptr;
+  SCT_CHECK(nf >= 1 && nf < (1LL << 31), "nf %lld outside [1, 2^31)", (long long)nf);
+  return create(nw, nf, kind, L, capacity_hint, flags, device, out);
 }
 
 extern "C" int sct_molecules_create(int64_t nw, int kind, int L, int64_t capacity_hint, sct_molecules** out) {
@@ -875,44 +1040,89 @@ extern "C" int sct_molecules_destroy(sct_molecules* c) {
   return SCT_OK;
 }
 
-extern "C" int sct_molecules_update(sct_molecules* c, const int32_t* d_index, const uint64_t* d_umi, int64_t n,
-                                    void* stream) {
+namespace {
+
+// the two update forms' common part: `features` says which form the caller used
+int update_entry(sct_molecules* c, bool features, const int32_t* d_index, const int32_t* d_feature,
+                 const uint64_t* d_umi, int64_t n, void* stream) {
   SCT_CHECK(n >= 0, "n must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (n == 0) return SCT_OK;
-  SCT_CHECK(d_index != nullptr && d_umi != nullptr, "NULL index or umi");
+  if (features) SCT_CHECK(d_index != nullptr && d_feature != nullptr && d_umi != nullptr, "NULL index, feature or umi");
+  else SCT_CHECK(d_index != nullptr && d_umi != nullptr, "NULL index or umi");
+  if (int rc = need_features(c, features); rc != SCT_OK) return rc;
   SCT_ON_DEVICE_OF(c);
   bool range = false;
-  const int rc = update_device(c, d_index, d_umi, n, sct::as_stream(stream), &range);
+  const int rc = update_device(c, d_index, d_feature, d_umi, n, sct::as_stream(stream), &range);
   return rc == SCT_OK && range ? range_error(c) : rc;
 }
 
-extern "C" int sct_molecules_update_host(sct_molecules* c, const int32_t* index, const uint64_t* umi, int64_t n) {
+int update_host_entry(sct_molecules* c, bool features, const int32_t* index, const int32_t* feature,
+                      const uint64_t* umi, int64_t n) {
   SCT_CHECK(n >= 0, "n must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (n == 0) return SCT_OK;
-  SCT_CHECK(index != nullptr && umi != nullptr, "NULL index or umi");
+  if (features) SCT_CHECK(index != nullptr && feature != nullptr && umi != nullptr, "NULL index, feature or umi");
+  else SCT_CHECK(index != nullptr && umi != nullptr, "NULL index or umi");
+  if (int rc = need_features(c, features); rc != SCT_OK) return rc;
   SCT_ON_DEVICE_OF(c);
   sct::HostStage* hs = sct::host_stage();
   if (!hs) return SCT_E_HIP;
   hipStream_t s = hs->stream;
-  // pieces through one pool buffer (umis, then indices): a piece's copies are ordered after the
-  // previous piece's kernels.  An out-of-range index in one piece does not stop the others.
+  // pieces through one pool buffer (umis, then indices, then features): a piece's copies are ordered
+  // after the previous piece's kernels.  An out-of-range index in one piece does not stop the others.
   const int64_t piece = std::min<int64_t>(n, 1LL << 24);
   sct::PoolBlock buf(s);
-  if (int rc = buf.alloc((size_t)piece * 12); rc != SCT_OK) return rc;
+  if (int rc = buf.alloc((size_t)piece * (features ? 16 : 12)); rc != SCT_OK) return rc;
   uint64_t* d_umi = static_cast<uint64_t*>(buf.p);
   int32_t* d_index = reinterpret_cast<int32_t*>(d_umi + piece);
+  int32_t* d_feature = features ? d_index + piece : nullptr;
   int rc = SCT_OK;
   bool range = false;
   for (int64_t b = 0; b < n && rc == SCT_OK && buf.ok(); b += piece) {
     const int64_t m = std::min(piece, n - b);
     buf.note(hipMemcpyAsync(d_umi, umi + b, (size_t)m * 8, hipMemcpyHostToDevice, s));
     if (buf.ok()) buf.note(hipMemcpyAsync(d_index, index + b, (size_t)m * 4, hipMemcpyHostToDevice, s));
-    if (buf.ok()) rc = update_device(c, d_index, d_umi, m, s, &range);
+    if (buf.ok() && features) buf.note(hipMemcpyAsync(d_feature, feature + b, (size_t)m * 4, hipMemcpyHostToDevice, s));
+    if (buf.ok()) rc = update_device(c, d_index, d_feature, d_umi, m, s, &range);
   }
   rc = buf.finish(rc, "molecule update");  // no caller pointer is kept past the return
   return rc == SCT_OK && range ? range_error(c) : rc;
+}
+
+}  // namespace
+
+extern "C" int sct_molecules_update(sct_molecules* c, const int32_t* d_index, const uint64_t* d_umi, int64_t n,
+                                    void* stream) {
+  return update_entry(c, false, d_index, nullptr, d_umi, n, stream);
+}
+
+extern "C" int sct_molecules_update_host(sct_molecules* c, const int32_t* index, const uint64_t* umi, int64_t n) {
+  return update_host_entry(c, false, index, nullptr, umi, n);
+}
+
+extern "C" int sct_molecules_update_features(sct_molecules* c, const int32_t* d_index, const int32_t* d_feature,
+                                             const uint64_t* d_umi, int64_t n, void* stream) {
+  return update_entry(c, true, d_index, d_feature, d_umi, n, stream);
+}
+
+extern "C" int sct_molecules_update_features_host(sct_molecules* c, const int32_t* index, const int32_t* feature,
+                                                  const uint64_t* umi, int64_t n) {
+  return update_host_entry(c, true, index, feature, umi, n);
+}
+
+extern "C" int sct_molecules_features_info(sct_molecules* c, int64_t* nf, int64_t* n_no_feature) {
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (n_no_feature) {
+    SCT_ON_DEVICE_OF(c);
+    sct::HostStage* hs = sct::host_stage();
+    if (!hs) return SCT_E_HIP;
+    if (int rc = enter(c, hs->stream); rc != SCT_OK) return rc;
+    if (int rc = read_words(c, hs->stream); rc != SCT_OK) return rc;
+    *n_no_feature = (int64_t)c->h_words[W_TALLY + 3];
+  }
+  if (nf) *nf = c->t.nf;
+  return SCT_OK;
 }
 
 extern "C" int sct_molecules_info(sct_molecules* c, int64_t* nmolecules, int64_t* total, int64_t* capacity) {
@@ -952,7 +1162,7 @@ extern "C" int sct_molecules_fetch(sct_molecules* c, int32_t* d_index, uint64_t*
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   SCT_ON_DEVICE_OF(c);
-  return fetch_device(c, d_index, d_umi, room, sct::as_stream(stream));
+  return fetch_device(c, d_index, nullptr, d_umi, room, sct::as_stream(stream));
 }
 
 extern "C" int sct_molecules_fetch_host(sct_molecules* c, int32_t* index, uint64_t* umi, int64_t room) {
@@ -972,7 +1182,7 @@ extern "C" int sct_molecules_fetch_host(sct_molecules* c, int32_t* index, uint64
   sct::PoolBlock blk(s);
   if (int rc = blk.alloc(b8 + (size_t)rows * 4); rc != SCT_OK) return rc;
   uint8_t* b = blk.bytes();
-  const int rc = fetch_device(c, (int32_t*)(b + b8), (uint64_t*)b, rows, s);
+  const int rc = fetch_device(c, (int32_t*)(b + b8), nullptr, (uint64_t*)b, rows, s);
   if (rc == SCT_OK) {
     blk.note(hipMemcpyAsync(umi, b, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
     if (blk.ok()) blk.note(hipMemcpyAsync(index, b + b8, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
@@ -1018,7 +1228,8 @@ extern "C" int sct_molecules_fetch_counted(sct_molecules* c, int32_t* d_index, u
   int64_t rows = 0;
   if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
   if (rows == 0) return SCT_OK;
-  return fetch_counted_rows(c, d_index, d_umi, d_mreads, d_parent, rows, s);
+  SCT_CHECK(d_mreads != nullptr, "NULL output");
+  return fetch_counted_rows(c, d_index, nullptr, d_umi, d_mreads, d_parent, rows, s);
 }
 
 extern "C" int sct_molecules_fetch_counted_host(sct_molecules* c, int32_t* index, uint64_t* umi, uint64_t* mreads,
@@ -1038,7 +1249,7 @@ extern "C" int sct_molecules_fetch_counted_host(sct_molecules* c, int32_t* index
   sct::PoolBlock blk(s);
   if (int rc = blk.alloc(3 * b8 + (size_t)rows * 4); rc != SCT_OK) return rc;
   uint8_t* b = blk.bytes();  // umi, mreads, parent, index
-  const int rc = fetch_counted_rows(c, (int32_t*)(b + 3 * b8), (uint64_t*)b, (uint64_t*)(b + b8),
+  const int rc = fetch_counted_rows(c, (int32_t*)(b + 3 * b8), nullptr, (uint64_t*)b, (uint64_t*)(b + b8),
                                     parent ? (uint64_t*)(b + 2 * b8) : nullptr, rows, s);
   if (rc == SCT_OK) {
     blk.note(hipMemcpyAsync(umi, b, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
@@ -1053,4 +1264,216 @@ extern "C" int sct_molecules_merge(sct_molecules* dst, sct_molecules* src, void*
   SCT_CHECK(dst != nullptr && src != nullptr, "molecule counter is NULL");
   if (int rc = merge_check(dst, src); rc != SCT_OK) return rc;
   return merge(dst, src, sct::as_stream(stream));
+}
+
+// ---- counting molecules per feature: the rows with their feature, and the count matrix
+
+namespace {
+
+int need_feature_counter(const sct_molecules* c) {
+  SCT_CHECK(c->t.nf != 0, "the molecule counter has no features (sct_molecules_create_features makes one that has)");
+  return SCT_OK;
+}
+
+// The CSR matrix of the table as it stands, on `s`: d_indptr[nw + 1], d_feature[nnz] and the value
+// arrays asked for, each [nnz].  *nnz is a host word, written in every case that gets as far as
+// counting the entries; room < nnz is SCT_E_INVALID with nothing else written.  All scratch is one
+// carved pool block: the (key, slot) rows twice (the sort's two sides), the tile head counts and their
+// scan, the entry count per barcode, the scratch of the sort and of both scans and, for the collapsed
+// values, what the collapse pass writes (collapsed[nw], n_corrected and its bitmap of a bit per slot).
+int matrix_device(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint64_t* d_molecules, uint64_t* d_reads,
+                  uint64_t* d_collapsed, int64_t room, int64_t* nnz, hipStream_t s) {
+  if (int rc = enter(c, s); rc != SCT_OK) return rc;
+  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  const int64_t rows = c->size_bound, nw = c->t.nw;
+  SCT_CHECK(nw + 1 < (1LL << 31), "matrix: nw + 1 = %lld row offsets are more than one scan takes", (long long)nw + 1);
+  *nnz = 0;
+  if (rows == 0) {
+    SCT_HIP(hipMemsetAsync(d_indptr, 0, (size_t)(nw + 1) * 8, s));
+    return leave(c, s);
+  }
+  const int64_t ntiles = (rows + 63) / 64;
+  const int end_bit = c->idx_bits + c->t.idx_shift;
+  size_t sort_bytes = 0, scan_tiles_bytes = 0, scan_rows_bytes = 0;
+  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr,
+                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)rows, 0, end_bit, s);
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tiles_bytes, (const u64*)nullptr, (u64*)nullptr,
+                                         (int)(ntiles + 1), s);
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_rows_bytes, (const u64*)nullptr, (u64*)nullptr, (int)(nw + 1), s);
+  Carve cv;
+  const size_t o_keys_in = cv.take((size_t)rows * 8), o_keys_out = cv.take((size_t)rows * 8);
+  const size_t o_slots_in = cv.take((size_t)rows * 4), o_slots_out = cv.take((size_t)rows * 4);
+  const size_t o_tmp = cv.take(std::max(sort_bytes, std::max(scan_tiles_bytes, scan_rows_bytes)));
+  const size_t o_heads = cv.take((size_t)(ntiles + 1) * 8), o_base = cv.take((size_t)(ntiles + 1) * 8);
+  const size_t o_row_entries = cv.take((size_t)(nw + 1) * 8);
+  // the collapse pass's outputs, zeroed together: n_corrected, collapsed[nw], the bitmap
+  const size_t o_pass = d_collapsed ? cv.take(8 + (size_t)nw * 8 + (size_t)c->capacity / 8) : 0;
+  void* blk = nullptr;
+  SCT_HIP(sct::pool_alloc(&blk, cv.size, s));
+  uint8_t* b = static_cast<uint8_t*>(blk);
+  u64* keys_in = reinterpret_cast<u64*>(b + o_keys_in);
+  u64* keys_out = reinterpret_cast<u64*>(b + o_keys_out);
+  uint32_t* slots_in = reinterpret_cast<uint32_t*>(b + o_slots_in);
+  uint32_t* slots_out = reinterpret_cast<uint32_t*>(b + o_slots_out);
+  u64* heads = reinterpret_cast<u64*>(b + o_heads);
+  u64* base = reinterpret_cast<u64*>(b + o_base);
+  u64* row_entries = reinterpret_cast<u64*>(b + o_row_entries);
+  const dim3 tiles_grid(grid_for(ntiles, WG / 64));
+  // 1. the rows sorted by key, and the entries that open in every tile; their sum is nnz
+  hipError_t e = hipMemsetAsync(&c->t.words[W_CURSOR], 0, 8, s);
+  if (e == hipSuccess) e = hipMemsetAsync(&heads[ntiles], 0, 8, s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(molecules_compact_kernel<true>, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
+                       c->capacity, &c->t.words[W_CURSOR], rows, keys_in, slots_in);
+    e = hipcub::DeviceRadixSort::SortPairs(b + o_tmp, sort_bytes, keys_in, keys_out, slots_in, slots_out, (int)rows, 0,
+                                           end_bit, s);
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(molecules_matrix_heads_kernel, tiles_grid, dim3(WG), 0, s, keys_out, rows, c->t.umi_bits, heads);
+    e = hipcub::DeviceScan::ExclusiveSum(b + o_tmp, scan_tiles_bytes, heads, base, (int)(ntiles + 1), s);
+  }
+  // (the host word beside the cursor's read-back is free between two read_words)
+  if (e == hipSuccess) e = hipMemcpyAsync(&c->h_words[W_CURSOR], &base[ntiles], 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  const int64_t entries = e == hipSuccess ? (int64_t)c->h_words[W_CURSOR] : 0;
+  if (e == hipSuccess && entries <= room) {
+    // 2. the entries: feature, the values, the entries of every barcode and their scan
+    e = hipMemsetAsync(row_entries, 0, (size_t)(nw + 1) * 8, s);
+    if (e == hipSuccess && d_molecules) e = hipMemsetAsync(d_molecules, 0, (size_t)entries * 8, s);
+    if (e == hipSuccess && d_reads) e = hipMemsetAsync(d_reads, 0, (size_t)entries * 8, s);
+    const uint32_t* bitmap = nullptr;
+    if (e == hipSuccess && d_collapsed) {
+      e = hipMemsetAsync(d_collapsed, 0, (size_t)entries * 8, s);
+      if (e == hipSuccess) e = hipMemsetAsync(b + o_pass, 0, 8 + (size_t)nw * 8 + (size_t)c->capacity / 8, s);
+      u64* pass = reinterpret_cast<u64*>(b + o_pass);
+      bitmap = reinterpret_cast<const uint32_t*>(pass + 1 + nw);
+      if (e == hipSuccess) {
+        const bool wave = sct::tune(SCT_TUNE_COLLAPSE_FORM, 1) == 1;
+        const auto kernel = wave ? molecules_collapse_wave_kernel : molecules_collapse_kernel;
+        hipLaunchKernelGGL(kernel, dim3(grid_for(c->capacity, WG)), dim3(WG), 0, s, c->t, c->capacity,
+                           const_cast<uint32_t*>(bitmap), pass + 1, pass);
+      }
+    }
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(molecules_matrix_fill_kernel, tiles_grid, dim3(WG), 0, s, c->t, keys_out, slots_out, rows, base,
+                         bitmap, row_entries, d_feature, reinterpret_cast<u64*>(d_molecules),
+                         reinterpret_cast<u64*>(d_reads), reinterpret_cast<u64*>(d_collapsed));
+      e = hipcub::DeviceScan::ExclusiveSum(b + o_tmp, scan_rows_bytes, row_entries, reinterpret_cast<u64*>(d_indptr),
+                                           (int)(nw + 1), s);
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+  }
+  sct::pool_free(blk, s);
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule matrix: %s", hipGetErrorString(e));
+  *nnz = entries;
+  if (int rc = leave(c, s); rc != SCT_OK) return rc;
+  SCT_CHECK(room >= entries, "room for %lld matrix entries, the matrix has %lld", (long long)room, (long long)entries);
+  return SCT_OK;
+}
+
+// the checks every matrix call makes before it touches the device
+int matrix_check(const sct_molecules* c, const void* indptr, const void* feature, const void* reads,
+                 const void* collapsed, int64_t room, const int64_t* nnz) {
+  SCT_CHECK(room >= 0, "room must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_CHECK(nnz != nullptr, "NULL nnz");
+  SCT_CHECK(indptr != nullptr && (room == 0 || feature != nullptr), "NULL output");
+  if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
+  if (reads || collapsed)
+    if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  return SCT_OK;
+}
+
+}  // namespace
+
+extern "C" int sct_molecules_fetch_features(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi,
+                                            uint64_t* d_mreads, uint64_t* d_parent, int64_t room, void* stream) {
+  SCT_CHECK(room >= 0, "room must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_CHECK(room == 0 || (d_index && d_feature && d_umi), "NULL output");
+  if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
+  if (d_mreads || d_parent)
+    if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_ON_DEVICE_OF(c);
+  hipStream_t s = sct::as_stream(stream);
+  if (!d_mreads && !d_parent) return fetch_device(c, d_index, d_feature, d_umi, room, s);
+  int64_t rows = 0;
+  if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
+  if (rows == 0) return SCT_OK;
+  return fetch_counted_rows(c, d_index, d_feature, d_umi, d_mreads, d_parent, rows, s);
+}
+
+extern "C" int sct_molecules_fetch_features_host(sct_molecules* c, int32_t* index, int32_t* feature, uint64_t* umi,
+                                                 uint64_t* mreads, uint64_t* parent, int64_t room) {
+  SCT_CHECK(room >= 0, "room must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_CHECK(room == 0 || (index && feature && umi), "NULL output");
+  if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
+  if (mreads || parent)
+    if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_ON_DEVICE_OF(c);
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return SCT_E_HIP;
+  hipStream_t s = hs->stream;
+  int64_t rows = 0;
+  if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
+  if (rows == 0) return SCT_OK;
+  const size_t b8 = up256((size_t)rows * 8), b4 = up256((size_t)rows * 4);
+  sct::PoolBlock blk(s);
+  if (int rc = blk.alloc(3 * b8 + 2 * b4); rc != SCT_OK) return rc;
+  uint8_t* b = blk.bytes();  // umi, mreads, parent, index, feature
+  uint64_t* d_umi = (uint64_t*)b;
+  uint64_t* d_mreads = mreads ? (uint64_t*)(b + b8) : nullptr;
+  uint64_t* d_parent = parent ? (uint64_t*)(b + 2 * b8) : nullptr;
+  int32_t* d_index = (int32_t*)(b + 3 * b8);
+  int32_t* d_feature = (int32_t*)(b + 3 * b8 + b4);
+  const int rc = d_mreads || d_parent ? fetch_counted_rows(c, d_index, d_feature, d_umi, d_mreads, d_parent, rows, s)
+                                      : fetch_device(c, d_index, d_feature, d_umi, rows, s);
+  if (rc == SCT_OK) {
+    blk.note(hipMemcpyAsync(umi, d_umi, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok() && mreads) blk.note(hipMemcpyAsync(mreads, d_mreads, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok() && parent) blk.note(hipMemcpyAsync(parent, d_parent, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok()) blk.note(hipMemcpyAsync(index, d_index, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+    if (blk.ok()) blk.note(hipMemcpyAsync(feature, d_feature, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+  }
+  return blk.finish(rc, "molecule fetch");
+}
+
+extern "C" int sct_molecules_matrix(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint64_t* d_molecules,
+                                    uint64_t* d_reads, uint64_t* d_collapsed, int64_t room, int64_t* nnz, void* stream) {
+  if (int rc = matrix_check(c, d_indptr, d_feature, d_reads, d_collapsed, room, nnz); rc != SCT_OK) return rc;
+  SCT_ON_DEVICE_OF(c);
+  return matrix_device(c, d_indptr, d_feature, d_molecules, d_reads, d_collapsed, room, nnz, sct::as_stream(stream));
+}
+
+extern "C" int sct_molecules_matrix_host(sct_molecules* c, int64_t* indptr, int32_t* feature, uint64_t* molecules,
+                                         uint64_t* reads, uint64_t* collapsed, int64_t room, int64_t* nnz) {
+  if (int rc = matrix_check(c, indptr, feature, reads, collapsed, room, nnz); rc != SCT_OK) return rc;
+  SCT_ON_DEVICE_OF(c);
+  sct::HostStage* hs = sct::host_stage();
+  if (!hs) return SCT_E_HIP;
+  hipStream_t s = hs->stream;
+  if (int rc = enter(c, s); rc != SCT_OK) return rc;
+  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  // nnz <= nmolecules: the device arrays never need more room than that
+  const int64_t r = std::min(room, c->size_bound);
+  const size_t bp = up256((size_t)(c->t.nw + 1) * 8), b8 = up256((size_t)r * 8), b4 = up256((size_t)r * 4);
+  sct::PoolBlock blk(s);
+  if (int rc = blk.alloc(bp + 3 * b8 + b4); rc != SCT_OK) return rc;
+  uint8_t* b = blk.bytes();  // indptr, molecules, reads, collapsed, feature
+  int64_t* d_indptr = (int64_t*)b;
+  uint64_t* d_molecules = molecules ? (uint64_t*)(b + bp) : nullptr;
+  uint64_t* d_reads = reads ? (uint64_t*)(b + bp + b8) : nullptr;
+  uint64_t* d_collapsed = collapsed ? (uint64_t*)(b + bp + 2 * b8) : nullptr;
+  int32_t* d_feature = (int32_t*)(b + bp + 3 * b8);
+  const int rc = matrix_device(c, d_indptr, d_feature, d_molecules, d_reads, d_collapsed, r, nnz, s);
+  if (rc == SCT_OK) {
+    const size_t n = (size_t)*nnz;
+    blk.note(hipMemcpyAsync(indptr, d_indptr, (size_t)(c->t.nw + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok() && n) blk.note(hipMemcpyAsync(feature, d_feature, n * 4, hipMemcpyDeviceToHost, s));
+    if (blk.ok() && n && molecules) blk.note(hipMemcpyAsync(molecules, d_molecules, n * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok() && n && reads) blk.note(hipMemcpyAsync(reads, d_reads, n * 8, hipMemcpyDeviceToHost, s));
+    if (blk.ok() && n && collapsed) blk.note(hipMemcpyAsync(collapsed, d_collapsed, n * 8, hipMemcpyDeviceToHost, s));
+  }
+  return blk.finish(rc, "molecule matrix");
 }

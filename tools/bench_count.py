@@ -15,7 +15,11 @@ reads, the counted MoleculeCounter and its UMI collapse against the plain one, a
 the host (collapse_step; profiles/ab_umi_collapse_<tag>.jsonl).  Then MoleculeCounter.merge of the
 second half's counter into the first's against an update of as many reads as the source has molecules
 and against the host route, with the existing molecule rows again beside an earlier library
-(merge_step; profiles/ab_molecules_merge_<tag>.jsonl).
+(merge_step; profiles/ab_molecules_merge_<tag>.jsonl).  Then the same reads with a feature column
+(nf = 4096): update_features against the plain update, matrix_device in its three forms, the host
+route pairs(features=True) + np.unique, and the plain and counted updates beside an earlier library
+(matrix_step; profiles/ab_count_matrix.jsonl, or ab_count_matrix_<tag>.jsonl for a tag other than
+"run").
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends
 the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
@@ -24,6 +28,7 @@ the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>
   python tools/bench_count.py --tag mi355x --only molecules
   python tools/bench_count.py --tag mi355x --only collapse --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --tag mi355x --only merge --parent-lib /path/to/earlier/libsctools_hip.so
+  python tools/bench_count.py --only matrix --parent-lib /path/to/earlier/libsctools_hip.so
 """
 import argparse
 import json
@@ -36,7 +41,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420, "collapse": 600,
-         "merge": 600}  # seconds
+         "merge": 600, "matrix": 600}  # seconds
 MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
 HBM_BYTES_PER_S = 8e12
 
@@ -659,6 +664,198 @@ def merge_step(args):
     return out
 
 
+def matrix_step(args):
+    """The count matrix on the molecules step's input with a feature column: nf = 4096, ThreeBit, a
+    molecule's feature a hash of its (barcode, UMI) so that the molecules are the plain run's, 2 % of
+    the reads with no feature; `spread` of the 4,096 features are in use (4096: about as many entries
+    as molecules, a gene-like matrix; 16: a tag panel, many molecules per entry).  Alternating within
+    every round, per input order and pre-aggregation mode: the plain update (12 B/read) in this
+    library and in --parent-lib, the counted one likewise, and update_features (16 B/read) plain and
+    counted.  Then per spread, on the table the counted feature update left: matrix_device with the
+    molecules only, with reads, and with reads and collapsed, all outputs device-resident; and once the
+    host route, pairs(features=True) to the host and np.unique over (barcode, feature).  The plain and
+    the counted update agree with the parent when the medians differ by no more than the min-max
+    spread of the parent's own rounds; the step fails (its profile written) when they do not.  Every
+    round is one line of the profile, the summary its last."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, counting
+
+    nw, UL, n, hint, pool, inputs = _molecules_input(args)
+    nf = 4096
+    dev = torch.device("cuda")
+    vp = ctypes.c_void_p
+    old = None
+    if args.parent_lib:
+        old = ctypes.CDLL(os.path.abspath(args.parent_lib))
+        for fn in ("sct_tune_set", "sct_molecules_create", "sct_molecules_create_counted", "sct_molecules_update",
+                   "sct_molecules_counts_host", "sct_molecules_destroy"):
+            getattr(old, fn).argtypes = _lib.SIGNATURES[fn]
+
+    def features_of(d_index, d_umi, spread):
+        g = torch.Generator(device=dev).manual_seed(13)
+        f = (((d_umi * -7046029254386353131) >> 40) ^ d_index.to(torch.int64)) & (spread - 1)
+        f = (f * (nf // spread)).to(torch.int32)  # spread over the whole range of nf
+        none = torch.rand(d_index.numel(), device=dev, generator=g) < 0.02
+        return torch.where(none, torch.full_like(f, -1), f).contiguous()
+
+    def full_update(lib, mode, d_index, d_umi, counted):
+        h = vp()
+        assert lib.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], mode) == 0
+        create = lib.sct_molecules_create_counted if counted else lib.sct_molecules_create
+        assert create(nw, 3, UL, hint, ctypes.byref(h)) == 0
+        try:
+            def go():
+                assert lib.sct_molecules_update(h, vp(d_index.data_ptr()), vp(d_umi.data_ptr()), n, None) == 0
+                torch.cuda.synchronize()
+            ms = _time_ms(go)
+            reads, molecules, tally = np.empty(nw, np.uint64), np.empty(nw, np.uint64), np.empty(3, np.uint64)
+            assert lib.sct_molecules_counts_host(h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)) == 0
+        finally:
+            lib.sct_molecules_destroy(h)
+            lib.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], -1)
+        return ms, (int(reads.sum()), int(molecules.sum()), int(tally[0]), int(tally[1]), int(tally[2]))
+
+    def feature_update(mode, d_index, d_feature, d_umi, counted, keep=False):
+        mc = counting.MoleculeCounter(nw, UL, capacity_hint=hint, read_counts=counted, features=nf)
+        with _lib.tuning(count_preagg=mode):
+            def go():
+                mc.update_device(d_index.data_ptr(), d_umi.data_ptr(), n, feature_ptr=d_feature.data_ptr())
+                torch.cuda.synchronize()
+            ms = _time_ms(go)
+        reads, molecules, n_none, n_amb, n_bad = mc.counts()
+        f = (int(reads.sum()) + mc.n_no_feature, int(molecules.sum()), n_none, n_amb, n_bad)
+        if keep:
+            return ms, f, mc
+        mc.close()
+        return ms, f
+
+    libs = {"this": _lib.lib()}
+    if old:
+        libs["parent"] = old
+    out = {"n": n, "nw": nw, "nf": nf, "umi_length": UL, "capacity_hint": hint, "parent_lib": bool(old),
+           "bytes_per_read": {"plain": 12, "features": 16}, "updates": {}, "matrix": {}}
+    lines, facts = [], None
+    feats = {which: features_of(di, du, nf) for which, (di, du, _) in inputs.items()}
+    for which, (di, du, _) in inputs.items():
+        df = feats[which]
+        full_update(_lib.lib(), 1, di, du, True), feature_update(1, di, df, du, True)  # warm-up
+        rounds = []
+        for r in range(args.rounds):
+            row = {"what": "update", "input": which, "round": r}
+            for m, mname in MODES.items():
+                cell = {}
+                for counted in (False, True):
+                    kind = "counted" if counted else "plain"
+                    for lname, lib in libs.items():
+                        ms, f = full_update(lib, m, di, du, counted)
+                        assert facts is None or f == facts, (f, facts)
+                        facts = f
+                        cell["%s_%s_ms" % (kind, lname)] = round(ms, 3)
+                    ms, f = feature_update(m, di, df, du, counted)
+                    # the reads without a feature are the only ones the plain run counted and this one did not
+                    assert f[0] == facts[0] and f[2:] == facts[2:], (f, facts)
+                    cell["%s_features_ms" % kind] = round(ms, 3)
+                row[mname] = cell
+            rounds.append(row)
+        lines += rounds
+        res = out["updates"][which] = {}
+        for mname in MODES.values():
+            res[mname] = {}
+            for key in rounds[0][mname]:
+                v = [row[mname][key] for row in rounds]
+                res[mname][key] = {"median": round(float(np.median(v)), 3), "min": min(v), "max": max(v)}
+            for kind in ("plain", "counted"):
+                a = res[mname][kind + "_this_ms"]
+                res[mname][kind + "_features_over_plain"] = round(res[mname][kind + "_features_ms"]["median"] / a["median"], 3)
+                if old:
+                    b = res[mname][kind + "_parent_ms"]
+                    res[mname][kind + "_vs_parent"] = {"median_difference_ms": round(a["median"] - b["median"], 3),
+                                                       "parent_spread_ms": round(b["max"] - b["min"], 3),
+                                                       "agree": abs(a["median"] - b["median"]) <= b["max"] - b["min"]}
+    # the matrix, per spread of the features, on the reads as drawn
+    di, du, _ = inputs["shuffled"]
+    for spread in (nf, 16):
+        df = features_of(di, du, spread)
+        _, _, mc = feature_update(1, di, df, du, True, keep=True)
+        nmol = len(mc)
+        o_indptr = torch.empty(nw + 1, dtype=torch.int64, device=dev)
+        o_feat = torch.empty(nmol, dtype=torch.int32, device=dev)
+        o_val = torch.empty((3, nmol), dtype=torch.int64, device=dev)
+        forms = {"molecules": (o_val[0].data_ptr(), None, None),
+                 "molecules_reads": (o_val[0].data_ptr(), o_val[1].data_ptr(), None),
+                 "molecules_reads_collapsed": (o_val[0].data_ptr(), o_val[1].data_ptr(), o_val[2].data_ptr())}
+        got = {}
+
+        def run_matrix(form):
+            def go():
+                got["nnz"] = mc.matrix_device(o_indptr.data_ptr(), o_feat.data_ptr(), *forms[form], nmol)
+                torch.cuda.synchronize()
+            return _time_ms(go)
+
+        d_collapsed = torch.empty(nw + 1, dtype=torch.int64, device=dev)
+
+        def run_collapse():
+            def go():
+                mc.collapse_device(d_collapsed.data_ptr(), d_collapsed.data_ptr() + 8 * nw)
+                torch.cuda.synchronize()
+            return _time_ms(go)
+
+        run_matrix("molecules_reads_collapsed")  # warm-up
+        rounds = []
+        for r in range(args.rounds):
+            row = {"what": "matrix", "spread": spread, "round": r}
+            for form in forms:
+                row[form + "_ms"] = round(run_matrix(form), 3)
+            row["collapse_alone_ms"] = round(run_collapse(), 3)
+            rounds.append(row)
+        lines += rounds
+        nnz = got["nnz"]
+        res = out["matrix"]["spread_%d" % spread] = {"molecules": nmol, "nnz": nnz}
+        for key in rounds[0]:
+            if key.endswith("_ms"):
+                v = [row[key] for row in rounds]
+                res[key] = {"median": round(float(np.median(v)), 3), "min": min(v), "max": max(v)}
+        # the host route: the rows to the host, np.unique over (barcode, feature)
+        rows = {}
+        pairs_ms = _time_ms(lambda: rows.update(r=mc.pairs(features=True, reads=True)))
+        pi, pf, pu, pr = rows["r"]
+
+        def group():
+            cell = pi.astype(np.int64) * nf + pf
+            uniq, start, count = np.unique(cell, return_index=True, return_counts=True)
+            rows["m"] = (uniq, count, np.add.reduceat(pr, start))
+        unique_ms = _time_ms(group)
+        uniq, count, rsum = rows["m"]
+        full = mc.matrix(reads=True, collapsed=True)
+        assert full[1].size == nnz == uniq.size and np.array_equal(uniq % nf, full[1])
+        assert np.array_equal(count, full[2]) and np.array_equal(rsum, full[3])
+        collapsed, _ = mc.collapse()
+        assert int(full[4].sum()) == int(collapsed.sum()) and int(full[2].sum()) == nmol
+        res["host_route"] = {"pairs_features_reads_ms": round(pairs_ms, 1), "np_unique_ms": round(unique_ms, 1),
+                             "total_ms": round(pairs_ms + unique_ms, 1)}
+        res["matrix_host_ms"] = round(_time_ms(lambda: mc.matrix(reads=True, collapsed=True)), 1)
+        res["host_route_over_matrix_device"] = round((pairs_ms + unique_ms) / res["molecules_reads_ms"]["median"], 1)
+        mc.close()
+        del o_indptr, o_feat, o_val, rows, pi, pf, pu, pr, full, df
+    out["matrix_device_ms"] = {k: v["molecules_reads_collapsed_ms"]["median"] for k, v in out["matrix"].items()}
+    reads, molecules, n_none, n_amb, n_bad = facts
+    out.update(reads=reads, n_none=n_none, n_ambiguous=n_amb, n_bad_umi=n_bad)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    name = "ab_count_matrix.jsonl" if args.tag == "run" else "ab_count_matrix_%s.jsonl" % args.tag
+    with open(os.path.join(ROOT, "profiles", name), "w") as f:
+        for row in lines:
+            f.write(json.dumps(row, sort_keys=True) + "\n")
+        f.write(json.dumps(out, sort_keys=True) + "\n")
+    apart = ["%s/%s/%s: %s" % (which, mname, kind, v[kind + "_vs_parent"])
+             for which, modes in out["updates"].items() for mname, v in modes.items()
+             for kind in ("plain", "counted") if old and not v[kind + "_vs_parent"]["agree"]]
+    assert not apart, "an update differs from --parent-lib beyond that library's own spread: " + "; ".join(apart)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tag", default="run")
@@ -670,7 +867,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--n-collapse-host", type=int, default=200_000, help="molecules given to the dict collapse")
     ap.add_argument("--parent-lib", default="",
-                    help="collapse and merge steps: an earlier libsctools_hip.so to time beside this one")
+                    help="collapse, merge and matrix steps: an earlier libsctools_hip.so to time beside this one")
     ap.add_argument("--only", nargs="+", choices=sorted(STEPS), help="launch only these steps")
     args = ap.parse_args()
     if args.step:
@@ -680,6 +877,8 @@ def main():
             res = collapse_step(args)
         elif args.step == "merge":
             res = merge_step(args)
+        elif args.step == "matrix":
+            res = matrix_step(args)
         else:
             res = tally_step(args) if args.step == "tally" else counter_step(args.step[-1], args)
         print("RESULT " + json.dumps(res))
@@ -708,7 +907,14 @@ def main():
         f.write("\n")
     short = {"tag": args.tag, "ok": rc == 0, "detail": os.path.relpath(path, ROOT)}
     for step, res in detail["steps"].items():
-        if "reads_per_molecule" in res:
+        if "matrix_device_ms" in res:
+            short[step] = {"n": res["n"], "nf": res["nf"], "matrix_device_ms": res["matrix_device_ms"],
+                           "nnz": {k: v["nnz"] for k, v in res["matrix"].items()},
+                           "host_route_ms": {k: v["host_route"]["total_ms"] for k, v in res["matrix"].items()},
+                           "update_ms": {which: {k: [v[c]["median"] for c in ("plain_this_ms", "plain_features_ms",
+                                                                               "counted_this_ms", "counted_features_ms")]
+                                                 for k, v in modes.items()} for which, modes in res["updates"].items()}}
+        elif "reads_per_molecule" in res:
             short[step] = {"n": res["n"], "molecules": res["molecules"], "reads_per_molecule": res["reads_per_molecule"],
                            "ms": {which: {k: [v["molecules_ms"]["median"], v["counter_plus_tally_ms"]["median"]]
                                           for k, v in modes.items()} for which, modes in res["inputs"].items()}}
