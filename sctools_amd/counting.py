@@ -284,28 +284,20 @@ class MoleculeCounter:
             self._need_features("pairs(features=True)")
         got = len(self)
         n = got if room is None else int(room)
-        index = np.empty(n, np.int32)
-        umi = np.empty(n, np.uint64)
-        if features:
-            feature = np.empty(n, np.int32)
-            mreads = np.empty(n, np.uint64) if reads else None
-            parent = np.empty(n, np.uint64) if parents else None
-            _lib.check(self._lib.sct_molecules_fetch_features_host(self._h, _lib._ptr(index), _lib._ptr(feature),
-                                                                   _lib._ptr(umi), _lib._ptr(mreads),
-                                                                   _lib._ptr(parent), n))
-            out = (index[:got], feature[:got], umi[:got])
-            if reads:
-                out += (mreads[:got].view(np.int64),)
-            return out + (parent[:got],) if parents else out
-        if not reads:
-            _lib.check(self._lib.sct_molecules_fetch_host(self._h, _lib._ptr(index), _lib._ptr(umi), n))
-            return index[:got], umi[:got]
-        mreads = np.empty(n, np.uint64)
+        index, umi = np.empty(n, np.int32), np.empty(n, np.uint64)
+        feature = np.empty(n, np.int32) if features else None
+        mreads = np.empty(n, np.uint64) if reads else None
         parent = np.empty(n, np.uint64) if parents else None
-        _lib.check(self._lib.sct_molecules_fetch_counted_host(self._h, _lib._ptr(index), _lib._ptr(umi),
-                                                              _lib._ptr(mreads), _lib._ptr(parent), n))
-        out = (index[:got], umi[:got], mreads[:got].view(np.int64))
-        return out + (parent[:got],) if parents else out
+        p = _lib._ptr
+        if features:
+            _lib.check(self._lib.sct_molecules_fetch_features_host(self._h, p(index), p(feature), p(umi), p(mreads),
+                                                                   p(parent), n))
+        elif reads:
+            _lib.check(self._lib.sct_molecules_fetch_counted_host(self._h, p(index), p(umi), p(mreads), p(parent), n))
+        else:
+            _lib.check(self._lib.sct_molecules_fetch_host(self._h, p(index), p(umi), n))
+        columns = (index, feature, umi, mreads.view(np.int64) if reads else None, parent)
+        return tuple(col[:got] for col in columns if col is not None)
 
     def fetch_device(self, index_ptr, umi_ptr, room, stream=0):
         """The same rows into device arrays with room for ``room`` rows (sct_molecules_fetch)."""

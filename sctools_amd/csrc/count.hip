@@ -25,14 +25,12 @@
 // (-1 -> tally[0], -2 -> tally[1]); each tile is pre-aggregated in an LDS table keyed by index, the
 // two negative answers by wave ballots.  An index outside [-2, nw) sets an error word and is never
 // stored through.
-#include <hipcub/hipcub.hpp>
-
 #include <limits.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "open_table.h"
+#include "sorted_rows.h"
 
 namespace {
 
@@ -318,44 +316,26 @@ int update_device(sct_counter* c, const uint64_t* d_codes, int64_t n, hipStream_
 // rows in first-occurrence order into device arrays with room for `room` rows
 int fetch_device(sct_counter* c, uint64_t* d_keys, uint64_t* d_counts, int64_t* d_first, int64_t room,
                  hipStream_t s) {
-  if (int rc = enter(c, s); rc != SCT_OK) return rc;
-  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
   const int64_t rows = c->size_bound + (c->h_words[W_SIDE_COUNT] ? 1 : 0);
   SCT_CHECK(room >= rows, "room for %lld rows, the counter holds %lld", (long long)room, (long long)rows);
   if (rows == 0) return SCT_OK;
   SCT_CHECK(d_keys && d_counts && d_first, "NULL output");
   int end_bit = 1;  // first positions are below the codes seen
   while (end_bit < 64 && (c->total >> end_bit) != 0) ++end_bit;
-  size_t sort_bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr,
-                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)rows, 0, end_bit, s);
-  Carve cv;
-  const size_t o_first_in = cv.take((size_t)rows * 8), o_first_out = cv.take((size_t)rows * 8);
-  const size_t o_slot_in = cv.take((size_t)rows * 4), o_slot_out = cv.take((size_t)rows * 4);
-  const size_t o_sort = cv.take(sort_bytes);
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, cv.size, s));
-  uint8_t* b = static_cast<uint8_t*>(blk);
-  long long* first_in = reinterpret_cast<long long*>(b + o_first_in);
-  long long* first_out = reinterpret_cast<long long*>(b + o_first_out);
-  uint32_t* slot_in = reinterpret_cast<uint32_t*>(b + o_slot_in);
-  uint32_t* slot_out = reinterpret_cast<uint32_t*>(b + o_slot_out);
-  void* sort_tmp = b + o_sort;
-  hipError_t e = hipMemsetAsync(&c->t.words[W_CURSOR], 0, 8, s);
-  if (e == hipSuccess) {
+  // first positions are >= 0 and distinct: an unsigned sort of them is the row order
+  SortedRows<true> sr(rows, end_bit, s);
+  SCT_HIP(sr.alloc());
+  hipError_t e = sr.sort(&c->t.words[W_CURSOR], [&](u64* first, uint32_t* slot) {
     hipLaunchKernelGGL(counter_compact_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t, c->capacity,
-                       rows, first_in, slot_in);
-    // first positions are >= 0 and distinct: an unsigned sort of them is the row order
-    e = hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, reinterpret_cast<const u64*>(first_in),
-                                           reinterpret_cast<u64*>(first_out), slot_in, slot_out, (int)rows, 0, end_bit, s);
-  }
+                       rows, reinterpret_cast<long long*>(first), slot);
+  });
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(counter_gather_kernel, dim3(grid_for(rows, 1024)), dim3(WG), 0, s, c->t, rows, first_out,
-                       slot_out, reinterpret_cast<u64*>(d_keys), reinterpret_cast<u64*>(d_counts),
-                       reinterpret_cast<long long*>(d_first));
+    hipLaunchKernelGGL(counter_gather_kernel, dim3(grid_for(rows, 1024)), dim3(WG), 0, s, c->t, rows,
+                       reinterpret_cast<const long long*>(sr.word()), sr.slot(), reinterpret_cast<u64*>(d_keys),
+                       reinterpret_cast<u64*>(d_counts), reinterpret_cast<long long*>(d_first));
     e = hipGetLastError();
   }
-  sct::pool_free(blk, s);
   if (e != hipSuccess) return sct::fail(SCT_E_HIP, "counter fetch: %s", hipGetErrorString(e));
   return leave(c, s);
 }
@@ -442,8 +422,7 @@ extern "C" int sct_counter_info(sct_counter* c, int64_t* nunique, int64_t* total
   if (nunique) {
     sct::HostStage* hs = sct::host_stage();
     if (!hs) return SCT_E_HIP;
-    if (int rc = enter(c, hs->stream); rc != SCT_OK) return rc;
-    if (int rc = read_words(c, hs->stream); rc != SCT_OK) return rc;
+    if (int rc = enter_read(c, hs->stream); rc != SCT_OK) return rc;
     *nunique = c->size_bound + (c->h_words[W_SIDE_COUNT] ? 1 : 0);
   }
   if (total) *total = c->total;
@@ -465,22 +444,15 @@ extern "C" int sct_counter_fetch_host(sct_counter* c, uint64_t* keys, uint64_t* 
   sct::HostStage* hs = sct::host_stage();
   if (!hs) return SCT_E_HIP;
   hipStream_t s = hs->stream;
-  if (int rc = enter(c, s); rc != SCT_OK) return rc;
-  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
   const int64_t rows = c->size_bound + (c->h_words[W_SIDE_COUNT] ? 1 : 0);
   SCT_CHECK(room >= rows, "room for %lld rows, the counter holds %lld", (long long)room, (long long)rows);
   if (rows == 0) return SCT_OK;
-  const size_t b8 = up256((size_t)rows * 8);
-  sct::PoolBlock blk(s);
-  if (int rc = blk.alloc(3 * b8); rc != SCT_OK) return rc;
-  uint8_t* b = blk.bytes();
-  const int rc = fetch_device(c, (uint64_t*)b, (uint64_t*)(b + b8), (int64_t*)(b + 2 * b8), rows, s);
-  if (rc == SCT_OK) {
-    blk.note(hipMemcpyAsync(keys, b, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok()) blk.note(hipMemcpyAsync(counts, b + b8, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok()) blk.note(hipMemcpyAsync(first, b + 2 * b8, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-  }
-  return blk.finish(rc, "counter fetch");
+  Staged st(s);
+  st.add(keys, 8, rows), st.add(counts, 8, rows), st.add(first, 8, rows);
+  if (int rc = st.alloc(); rc != SCT_OK) return rc;
+  const int rc = fetch_device(c, st.dev<uint64_t>(0), st.dev<uint64_t>(1), st.dev<int64_t>(2), rows, s);
+  return st.finish(rc, "counter fetch");
 }
 
 extern "C" int sct_index_tally(const int32_t* d_index, int64_t n, int64_t nw, uint64_t* d_counts, uint64_t* d_tally,

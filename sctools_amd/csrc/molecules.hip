@@ -19,7 +19,15 @@
 // DESIGN.md §3.10 has the A/B: 1 and 2 are level when a molecule's reads are adjacent (both twice as
 // fast as 0 there), and 1 is ahead of 2 when they are far apart.
 //
-// The rehash kernel re-inserts keys only: molecules, reads and the size word are not touched by it.
+// The rehash kernel re-inserts keys: molecules, reads and the size word are not touched by it.
+//
+// Everything that reads the table back goes through one stage, the table's rows sorted by key
+// (sorted_rows.h): the compaction kernel writes every occupied slot's key and, where a later step
+// needs cnt[slot] or the slot itself, the slot number beside it; a radix sort orders them.  One emit
+// kernel turns the sorted rows into the columns a fetch form asked for (fetch_rows, under the six
+// fetch entry points), and the count matrix runs over the same rows.  The merge between devices uses
+// the compaction alone, with cnt[slot] written beside the key.  The *_host forms stage their outputs
+// in one pool block (open_table.h, Staged) around the device forms.
 //
 // A *counted* counter (sct_molecules_create_counted) keeps a second array cnt[capacity] of uint64
 // beside the keys: the reads of every molecule.  COUNTED is a template parameter of the insert
@@ -57,15 +65,14 @@
 // entry count and reduces each entry's rows inside the wave -- run length, cnt[slot], the slot's bit
 // in the collapse pass's bitmap -- to one 64-bit integer atomic add per (wave, entry) and value.
 // A scan of the nw + 1 entry counts is indptr.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <type_traits>
+
+#include "sorted_rows.h"  // (first: the HIP runtime's qualifiers, which the key headers below use)
 
 #include "molecules_feature_key.h"
 #include "molecules_key.h"
 #include "molecules_merge_plan.h"
-#include "open_table.h"
 #include "umi_neighbours.h"
 
 namespace {
@@ -92,21 +99,27 @@ struct Set {
   int idx_shift;  // feat_bits + umi_bits: a key's barcode is key >> idx_shift
 };
 
-// `count` reads of one molecule: reads[index] += count, and molecules[index] += 1 from the lane that
-// claimed the key's slot.  The index comes out of a key built from a checked index: index < nw.
-// COUNTED: the carrier of the key also adds its count to the slot's mreads (cnt is zero at every
-// empty slot, so it does not matter whether the claiming lane or another one adds first).
-// FEATURES: the barcode lies above the feature bits.
-template <bool COUNTED, bool FEATURES>
-__device__ __forceinline__ int set_add(const Set& t, u64 key, u64 count) {
-  const uint32_t index = sct::mol_key_index(key, FEATURES ? t.idx_shift : t.umi_bits);
-  atomicAdd(&t.reads[index], count);
+// The molecule `key` of barcode `index` claimed: molecules[index] += 1 from the lane that claimed the
+// key's slot (1 is returned there, 0 elsewhere).  COUNTED: the carrier of the key also adds `count` to
+// the slot's mreads (cnt is zero at every empty slot, so it does not matter whether the claiming lane
+// or another one adds first).
+template <bool COUNTED>
+__device__ __forceinline__ int set_claim(const Set& t, u64 key, uint32_t index, u64 count) {
   u64 slot = NO_SLOT;
   const bool claimed = claim<COUNTED>(t.keys, t.mask, &t.words[W_OVERFLOW], key, &slot);
   if (COUNTED && slot != NO_SLOT) atomicAdd(&t.cnt[slot], count);
   if (!claimed) return 0;
   atomicAdd(&t.molecules[index], 1ull);
   return 1;
+}
+
+// `count` reads of one molecule: reads[index] += count, and the claim.  The index comes out of a key
+// built from a checked index: index < nw.  FEATURES: the barcode lies above the feature bits.
+template <bool COUNTED, bool FEATURES>
+__device__ __forceinline__ int set_add(const Set& t, u64 key, u64 count) {
+  const uint32_t index = sct::mol_key_index(key, FEATURES ? t.idx_shift : t.umi_bits);
+  atomicAdd(&t.reads[index], count);
+  return set_claim<COUNTED>(t, key, index, count);
 }
 
 // What one read is: rule 1..5 of the contract (FEATURES: with 3b and 4b).  `key` is set for GOOD only.
@@ -229,29 +242,20 @@ __global__ void __launch_bounds__(WG) molecules_insert_lds_kernel(Set t, const i
   wt.flush(t, claims);
 }
 
-// every key of the old table into the new one: keys only (molecules, reads and the size word stay)
-__global__ void __launch_bounds__(WG) molecules_rehash_kernel(const u64* __restrict__ from, int64_t from_capacity,
-                                                              u64* __restrict__ to, u64 to_mask,
-                                                              u64* __restrict__ words) {
-  for (int64_t s = (int64_t)blockIdx.x * WG + threadIdx.x; s < from_capacity; s += (int64_t)gridDim.x * WG) {
-    const u64 key = from[s];
-    if (key != EMPTY) (void)claim(to, to_mask, &words[W_OVERFLOW], key);
-  }
-}
-
-// the counted table's rehash: the count moves with its key.  A key is unique in the old table, so
-// exactly one lane meets it and that lane's plain store is the only write to the new slot's count.
-__global__ void __launch_bounds__(WG) molecules_rehash_counted_kernel(const u64* __restrict__ from,
-                                                                      const u64* __restrict__ from_cnt,
-                                                                      int64_t from_capacity, u64* __restrict__ to,
-                                                                      u64* __restrict__ to_cnt, u64 to_mask,
-                                                                      u64* __restrict__ words) {
+// every key of the old table into the new one (molecules, reads and the size word stay).  COUNTED:
+// the count moves with its key.  A key is unique in the old table, so exactly one lane meets it and
+// that lane's plain store is the only write to the new slot's count.
+template <bool COUNTED>
+__global__ void __launch_bounds__(WG) molecules_rehash_kernel(const u64* __restrict__ from,
+                                                              const u64* __restrict__ from_cnt, int64_t from_capacity,
+                                                              u64* __restrict__ to, u64* __restrict__ to_cnt,
+                                                              u64 to_mask, u64* __restrict__ words) {
   for (int64_t s = (int64_t)blockIdx.x * WG + threadIdx.x; s < from_capacity; s += (int64_t)gridDim.x * WG) {
     const u64 key = from[s];
     if (key == EMPTY) continue;
-    u64 slot;
-    (void)claim<true>(to, to_mask, &words[W_OVERFLOW], key, &slot);
-    if (slot != NO_SLOT) to_cnt[slot] = from_cnt[s];
+    u64 slot = NO_SLOT;
+    (void)claim<COUNTED>(to, to_mask, &words[W_OVERFLOW], key, &slot);
+    if (COUNTED && slot != NO_SLOT) to_cnt[slot] = from_cnt[s];
   }
 }
 
@@ -345,13 +349,14 @@ __global__ void __launch_bounds__(WG) molecules_collapse_wave_kernel(Set t, int6
   if (lane == 0 && moved) atomicAdd(ncorrected, (u64)moved);
 }
 
-// fetch and merge: the occupied slots' keys and, SLOTS, their slot numbers beside them, in any order
-// (the sort fixes the order); at most `room` are written
-template <bool SLOTS>
-__global__ void __launch_bounds__(WG) molecules_compact_kernel(const u64* __restrict__ keys, int64_t capacity,
+// fetch and merge: the occupied slots' keys in any order (the sort fixes the order) and, beside each,
+// nothing, its slot number (uint32: capacity <= 2^31) or its mreads (u64); at most `room` are written
+enum { BESIDE_NONE, BESIDE_SLOT, BESIDE_COUNT };
+template <int BESIDE>
+__global__ void __launch_bounds__(WG) molecules_compact_kernel(const u64* __restrict__ keys,
+                                                               const u64* __restrict__ cnt, int64_t capacity,
                                                                u64* __restrict__ cursor, int64_t room,
-                                                               u64* __restrict__ out_key,
-                                                               uint32_t* __restrict__ out_slot) {
+                                                               u64* __restrict__ out_key, void* __restrict__ beside) {
   const int64_t stride = (int64_t)gridDim.x * WG;
   const int64_t iters = (capacity + stride - 1) / stride;  // the same for every lane: the wave stays whole
   for (int64_t it = 0; it < iters; ++it) {
@@ -361,13 +366,16 @@ __global__ void __launch_bounds__(WG) molecules_compact_kernel(const u64* __rest
     const u64 at = compact_at(occ, cursor);
     if (occ && (int64_t)at < room) {
       out_key[at] = key;
-      if (SLOTS) out_slot[at] = (uint32_t)s;  // capacity <= 2^31
+      if (BESIDE == BESIDE_SLOT) static_cast<uint32_t*>(beside)[at] = (uint32_t)s;
+      if (BESIDE == BESIDE_COUNT) static_cast<u64*>(beside)[at] = cnt[s];
     }
   }
 }
 
-// the sorted (key, slot) pairs as rows: index, UMI and, each if asked, the feature, mreads and the
-// parent's UMI
+// the sorted keys as rows: index, UMI and, if asked, the feature.  SLOTS: `slots` (the keys' slot
+// numbers, sorted with them; else NULL, as mreads and parent are) also gives, each if asked, mreads
+// and the parent's UMI.
+template <bool SLOTS>
 __global__ void __launch_bounds__(WG) molecules_emit_kernel(Set t, const u64* __restrict__ keys,
                                                             const uint32_t* __restrict__ slots, int64_t rows,
                                                             int32_t* __restrict__ index, int32_t* __restrict__ feature,
@@ -375,26 +383,16 @@ __global__ void __launch_bounds__(WG) molecules_emit_kernel(Set t, const u64* __
                                                             u64* __restrict__ parent) {
   for (int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WG) {
     const u64 key = keys[r];
-    const u64 slot = slots[r];
+    const u64 slot = SLOTS ? slots[r] : 0;  // (loaded with the key, ahead of the stores)
     index[r] = (int32_t)sct::mol_key_index(key, t.idx_shift);
     if (feature) feature[r] = (int32_t)sct::mol_fkey_feature(key, t.feat_bits, t.umi_bits);
     umi[r] = sct::mol_key_umi(key, t.umi_bits);
+    if (!SLOTS) continue;
     if (mreads) mreads[r] = t.cnt[slot];
     if (parent) {
       u64 at;
       parent[r] = sct::mol_key_umi(parent_of(t, key, slot, &at), t.umi_bits);
     }
-  }
-}
-
-__global__ void __launch_bounds__(WG) molecules_split_kernel(const u64* __restrict__ keys, int64_t rows, int umi_bits,
-                                                             int feat_bits, int32_t* __restrict__ index,
-                                                             int32_t* __restrict__ feature, u64* __restrict__ umi) {
-  for (int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WG) {
-    const u64 key = keys[r];
-    index[r] = (int32_t)sct::mol_key_index(key, feat_bits + umi_bits);
-    if (feature) feature[r] = (int32_t)sct::mol_fkey_feature(key, feat_bits, umi_bits);
-    umi[r] = sct::mol_key_umi(key, umi_bits);
   }
 }
 
@@ -500,13 +498,7 @@ __global__ void __launch_bounds__(WG) molecules_merge_kernel(Set t, const u64* _
       key = __builtin_nontemporal_load(&keys[i]);
       if (COUNTED) count = __builtin_nontemporal_load(&cnt[i]);
     }
-    if (key == EMPTY) continue;
-    u64 slot = NO_SLOT;
-    const bool claimed = claim<COUNTED>(t.keys, t.mask, &t.words[W_OVERFLOW], key, &slot);
-    if (COUNTED && slot != NO_SLOT) atomicAdd(&t.cnt[slot], count);
-    if (!claimed) continue;
-    atomicAdd(&t.molecules[sct::mol_key_index(key, t.idx_shift)], 1ull);
-    ++claims;
+    if (key != EMPTY) claims += set_claim<COUNTED>(t, key, sct::mol_key_index(key, t.idx_shift), count);
   }
   add_claims(&t.words[W_SIZE], claims);
 }
@@ -518,14 +510,6 @@ __global__ void __launch_bounds__(WG) molecules_add_kernel(u64* __restrict__ rea
   const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
   for (int64_t i = gid; i < nw; i += (int64_t)gridDim.x * WG) reads[i] += from_reads[i];
   if (gid < 4) words[W_TALLY + gid] += from_words[W_TALLY + gid];
-}
-
-// the reads of the compacted (key, slot) pairs: the dense rows' cnt[]
-__global__ void __launch_bounds__(WG) molecules_gather_counts_kernel(const u64* __restrict__ cnt,
-                                                                     const uint32_t* __restrict__ slots, int64_t rows,
-                                                                     u64* __restrict__ out) {
-  for (int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WG)
-    out[r] = cnt[slots[r]];
 }
 
 }  // namespace
@@ -567,6 +551,13 @@ struct DeviceGuard {
   if (on_device_.e != hipSuccess)                                                                 \
   return sct::fail(SCT_E_HIP, "molecule counter's device %d: %s", (c)->device, hipGetErrorString(on_device_.e))
 
+// the same for a call that works on host arrays: `s` is this thread's stage stream of that device
+#define SCT_ON_STAGE_OF(c, s)                  \
+  SCT_ON_DEVICE_OF(c);                         \
+  sct::HostStage* stage_ = sct::host_stage();  \
+  if (!stage_) return SCT_E_HIP;               \
+  hipStream_t s = stage_->stream
+
 // a table's keys are filled with 0xFF, every slot EMPTY; a counted table's mreads with 0 (an insert
 // adds to it, a rehash stores into it)
 constexpr const char* kKeysName = "molecule table";
@@ -584,12 +575,10 @@ int grow(sct_molecules* c, int64_t factor, hipStream_t s) {
       (void)hipFree(nk);
       return rc;
     }
-    hipLaunchKernelGGL(molecules_rehash_counted_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
-                       c->t.cnt, c->capacity, nk, nc, (u64)cap - 1, c->t.words);
-  } else {
-    hipLaunchKernelGGL(molecules_rehash_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
-                       c->capacity, nk, (u64)cap - 1, c->t.words);
   }
+  const auto rehash = c->counted ? molecules_rehash_kernel<true> : molecules_rehash_kernel<false>;
+  hipLaunchKernelGGL(rehash, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys, c->t.cnt, c->capacity, nk,
+                     nc, (u64)cap - 1, c->t.words);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(s);  // the old arrays are read until here
   if (e != hipSuccess) {
@@ -661,41 +650,82 @@ int update_device(sct_molecules* c, const int32_t* d_index, const int32_t* d_fea
   return leave(c, s);
 }
 
-// the distinct molecules in ascending key order into device arrays with room for `room` rows
-// (d_feature: the feature column of a feature counter, nullable)
-int fetch_device(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi, int64_t room, hipStream_t s) {
-  if (int rc = enter(c, s); rc != SCT_OK) return rc;
-  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
-  const int64_t rows = c->size_bound;
-  SCT_CHECK(room >= rows, "room for %lld molecules, the counter holds %lld", (long long)room, (long long)rows);
-  if (rows == 0) return SCT_OK;
-  SCT_CHECK(d_index && d_umi, "NULL output");
-  const int end_bit = c->idx_bits + c->t.idx_shift;
-  size_t sort_bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr, (int)rows, 0,
-                                          end_bit, s);
-  Carve cv;
-  const size_t o_keys_in = cv.take((size_t)rows * 8), o_keys_out = cv.take((size_t)rows * 8);
-  const size_t o_sort = cv.take(sort_bytes);
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, cv.size, s));
-  uint8_t* b = static_cast<uint8_t*>(blk);
-  u64* keys_in = reinterpret_cast<u64*>(b + o_keys_in);
-  u64* keys_out = reinterpret_cast<u64*>(b + o_keys_out);
-  hipError_t e = hipMemsetAsync(&c->t.words[W_CURSOR], 0, 8, s);
+// the compaction of c's table on `s` (the cursor is zero): at most `rows` keys, and what goes beside them
+void compact(const sct_molecules* c, int beside_what, int64_t rows, u64* out_key, void* beside, hipStream_t s) {
+  const auto kernel = beside_what == BESIDE_NONE   ? molecules_compact_kernel<BESIDE_NONE>
+                      : beside_what == BESIDE_SLOT ? molecules_compact_kernel<BESIDE_SLOT>
+                                                   : molecules_compact_kernel<BESIDE_COUNT>;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys, c->t.cnt, c->capacity,
+                     &c->t.words[W_CURSOR], rows, out_key, beside);
+}
+
+// the table's molecules as rows sorted by key (sorted_rows.h), enqueued into sr's block
+template <bool SLOTS>
+hipError_t sort_rows(const sct_molecules* c, SortedRows<SLOTS>& sr) {
+  return sr.sort(&c->t.words[W_CURSOR], [&](u64* keys, uint32_t* slots) {
+    compact(c, SLOTS ? BESIDE_SLOT : BESIDE_NONE, sr.rows, keys, slots, sr.s);
+  });
+}
+int key_bits(const sct_molecules* c) { return c->idx_bits + c->t.idx_shift; }
+
+// the number of molecules, read on `s` after the counter's earlier work; `room` must hold them
+int rows_for_fetch(sct_molecules* c, int64_t room, hipStream_t s, int64_t* rows) {
+  if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
+  *rows = c->size_bound;
+  SCT_CHECK(room >= *rows, "room for %lld molecules, the counter holds %lld", (long long)room, (long long)*rows);
+  return SCT_OK;
+}
+
+// The distinct molecules in ascending key order into device arrays: `rows` > 0 rows, as rows_for_fetch
+// gave them on `s`.  Beside index and UMI, each if asked: the feature column of a feature counter,
+// each row's mreads and its parent's UMI.  SLOTS: the slots travel through the sort, for the last two.
+template <bool SLOTS>
+int fetch_rows_as(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi, uint64_t* d_mreads,
+                  uint64_t* d_parent, int64_t rows, hipStream_t s) {
+  SortedRows<SLOTS> sr(rows, key_bits(c), s);
+  SCT_HIP(sr.alloc());
+  hipError_t e = sort_rows(c, sr);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(molecules_compact_kernel<false>, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
-                       c->capacity, &c->t.words[W_CURSOR], rows, keys_in, nullptr);
-    e = hipcub::DeviceRadixSort::SortKeys(b + o_sort, sort_bytes, keys_in, keys_out, (int)rows, 0, end_bit, s);
-  }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(molecules_split_kernel, dim3(grid_for(rows, 1024)), dim3(WG), 0, s, keys_out, rows,
-                       c->t.umi_bits, c->t.feat_bits, d_index, d_feature, reinterpret_cast<u64*>(d_umi));
+    // (the grid of each form as it was: a row with a slot may cost a parent's probes)
+    hipLaunchKernelGGL(molecules_emit_kernel<SLOTS>, dim3(grid_for(rows, SLOTS ? WG : 1024)), dim3(WG), 0, s, c->t,
+                       sr.word(), sr.slot(), rows, d_index, d_feature, reinterpret_cast<u64*>(d_umi),
+                       reinterpret_cast<u64*>(d_mreads), reinterpret_cast<u64*>(d_parent));
     e = hipGetLastError();
   }
-  sct::pool_free(blk, s);
   if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule fetch: %s", hipGetErrorString(e));
   return leave(c, s);
+}
+int fetch_rows(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi, uint64_t* d_mreads,
+               uint64_t* d_parent, int64_t rows, hipStream_t s) {
+  const auto as = d_mreads || d_parent ? fetch_rows_as<true> : fetch_rows_as<false>;
+  return as(c, d_index, d_feature, d_umi, d_mreads, d_parent, rows, s);
+}
+
+// the device forms: `given` says whether the form's own columns are there, asked only when rows are
+int fetch_device(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi, uint64_t* d_mreads,
+                 uint64_t* d_parent, bool given, int64_t room, hipStream_t s) {
+  SCT_ON_DEVICE_OF(c);
+  int64_t rows = 0;
+  if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
+  if (rows == 0) return SCT_OK;
+  SCT_CHECK(given, "NULL output");
+  return fetch_rows(c, d_index, d_feature, d_umi, d_mreads, d_parent, rows, s);
+}
+
+// the host forms: the columns asked for, staged
+int fetch_host(sct_molecules* c, int32_t* index, int32_t* feature, uint64_t* umi, uint64_t* mreads, uint64_t* parent,
+               int64_t room) {
+  SCT_ON_STAGE_OF(c, s);
+  int64_t rows = 0;
+  if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
+  if (rows == 0) return SCT_OK;
+  Staged st(s);
+  st.add(umi, 8, rows), st.add(mreads, 8, rows), st.add(parent, 8, rows);
+  st.add(index, 4, rows), st.add(feature, 4, rows);
+  if (int rc = st.alloc(); rc != SCT_OK) return rc;
+  const int rc = fetch_rows(c, st.dev<int32_t>(3), st.dev<int32_t>(4), st.dev<uint64_t>(0), st.dev<uint64_t>(1),
+                            st.dev<uint64_t>(2), rows, s);
+  return st.finish(rc, "molecule fetch");
 }
 
 int need_counted(const sct_molecules* c) {
@@ -703,76 +733,45 @@ int need_counted(const sct_molecules* c) {
   return SCT_OK;
 }
 
-// collapsed[nw] and, if asked, n_corrected, written on `s` from the table as it stands.  Scratch from
-// the pool: one word for n_corrected, then one bit per slot.
-int collapse_device(sct_molecules* c, uint64_t* d_collapsed, uint64_t* d_ncorrected, hipStream_t s) {
-  if (int rc = enter(c, s); rc != SCT_OK) return rc;
-  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
-  Carve cv;
-  const size_t o_ncorr = cv.take(8), o_bitmap = cv.take((size_t)c->capacity / 8);  // capacity >= 64: whole 32-bit words
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, cv.size, s));
-  uint8_t* b = static_cast<uint8_t*>(blk);
-  u64* ncorr = reinterpret_cast<u64*>(b + o_ncorr);
-  hipError_t e = hipMemsetAsync(b, 0, cv.size, s);
-  if (e == hipSuccess) e = hipMemsetAsync(d_collapsed, 0, (size_t)c->t.nw * 8, s);
-  if (e == hipSuccess && c->size_bound > 0) {
-    const bool wave = sct::tune(SCT_TUNE_COLLAPSE_FORM, 1) == 1;
-    const auto kernel = wave ? molecules_collapse_wave_kernel : molecules_collapse_kernel;
-    hipLaunchKernelGGL(kernel, dim3(grid_for(c->capacity, WG)), dim3(WG), 0, s, c->t, c->capacity,
-                       reinterpret_cast<uint32_t*>(b + o_bitmap), reinterpret_cast<u64*>(d_collapsed), ncorr);
-    e = hipGetLastError();
+// The collapse pass's scratch at `b`, in its one layout: the n_corrected word, the bitmap of one bit
+// per slot (capacity >= 64: whole words) and, for a caller that keeps no collapsed[nw] of its own,
+// that array.  The caller zeroes all of it.
+struct CollapseScratch {
+  u64* ncorrected;
+  uint32_t* bitmap;
+  u64* collapsed;
+  static size_t bytes(const sct_molecules* c, bool own_collapsed) {
+    return 8 + (size_t)c->capacity / 8 + (own_collapsed ? (size_t)c->t.nw * 8 : 0);
   }
-  if (e == hipSuccess && d_ncorrected) e = hipMemcpyAsync(d_ncorrected, ncorr, 8, hipMemcpyDeviceToDevice, s);
+  CollapseScratch(const sct_molecules* c, uint8_t* b)
+      : ncorrected(reinterpret_cast<u64*>(b)), bitmap(reinterpret_cast<uint32_t*>(b + 8)),
+        collapsed(reinterpret_cast<u64*>(b + 8 + (size_t)c->capacity / 8)) {}
+};
+
+// the collapse of the table as it stands on `s`, in the form SCT_TUNE_COLLAPSE_FORM names: the parents'
+// bits into `bitmap`, collapsed[nw] and the n_corrected word added to (all zero before)
+hipError_t collapse_pass(const sct_molecules* c, uint32_t* bitmap, u64* collapsed, u64* ncorrected, hipStream_t s) {
+  const bool wave = sct::tune(SCT_TUNE_COLLAPSE_FORM, 1) == 1;
+  const auto kernel = wave ? molecules_collapse_wave_kernel : molecules_collapse_kernel;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(c->capacity, WG)), dim3(WG), 0, s, c->t, c->capacity, bitmap, collapsed,
+                     ncorrected);
+  return hipGetLastError();
+}
+
+// collapsed[nw] and, if asked, n_corrected, written on `s` from the table as it stands
+int collapse_device(sct_molecules* c, uint64_t* d_collapsed, uint64_t* d_ncorrected, hipStream_t s) {
+  if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
+  const size_t bytes = CollapseScratch::bytes(c, false);
+  void* blk = nullptr;
+  SCT_HIP(sct::pool_alloc(&blk, bytes, s));
+  const CollapseScratch cs(c, static_cast<uint8_t*>(blk));
+  hipError_t e = hipMemsetAsync(blk, 0, bytes, s);
+  if (e == hipSuccess) e = hipMemsetAsync(d_collapsed, 0, (size_t)c->t.nw * 8, s);
+  if (e == hipSuccess && c->size_bound > 0)
+    e = collapse_pass(c, cs.bitmap, reinterpret_cast<u64*>(d_collapsed), cs.ncorrected, s);
+  if (e == hipSuccess && d_ncorrected) e = hipMemcpyAsync(d_ncorrected, cs.ncorrected, 8, hipMemcpyDeviceToDevice, s);
   sct::pool_free(blk, s);
   if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule collapse: %s", hipGetErrorString(e));
-  return leave(c, s);
-}
-
-// the number of molecules, read on `s` after the counter's earlier work; `room` must hold them
-int rows_for_fetch(sct_molecules* c, int64_t room, hipStream_t s, int64_t* rows) {
-  if (int rc = enter(c, s); rc != SCT_OK) return rc;
-  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
-  *rows = c->size_bound;
-  SCT_CHECK(room >= *rows, "room for %lld molecules, the counter holds %lld", (long long)room, (long long)*rows);
-  return SCT_OK;
-}
-
-// fetch's rows with each row's mreads and, if asked, its parent's UMI beside them: `rows` > 0 rows,
-// as rows_for_fetch gave them on `s` (fetch_features: d_feature is asked for and d_mreads need not be)
-int fetch_counted_rows(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi, uint64_t* d_mreads,
-                       uint64_t* d_parent, int64_t rows, hipStream_t s) {
-  SCT_CHECK(d_index && d_umi && (d_mreads || d_feature), "NULL output");
-  const int end_bit = c->idx_bits + c->t.idx_shift;
-  size_t sort_bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr,
-                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)rows, 0, end_bit, s);
-  Carve cv;
-  const size_t o_keys_in = cv.take((size_t)rows * 8), o_keys_out = cv.take((size_t)rows * 8);
-  const size_t o_slots_in = cv.take((size_t)rows * 4), o_slots_out = cv.take((size_t)rows * 4);
-  const size_t o_sort = cv.take(sort_bytes);
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, cv.size, s));
-  uint8_t* b = static_cast<uint8_t*>(blk);
-  u64* keys_in = reinterpret_cast<u64*>(b + o_keys_in);
-  u64* keys_out = reinterpret_cast<u64*>(b + o_keys_out);
-  uint32_t* slots_in = reinterpret_cast<uint32_t*>(b + o_slots_in);
-  uint32_t* slots_out = reinterpret_cast<uint32_t*>(b + o_slots_out);
-  hipError_t e = hipMemsetAsync(&c->t.words[W_CURSOR], 0, 8, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(molecules_compact_kernel<true>, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
-                       c->capacity, &c->t.words[W_CURSOR], rows, keys_in, slots_in);
-    e = hipcub::DeviceRadixSort::SortPairs(b + o_sort, sort_bytes, keys_in, keys_out, slots_in, slots_out,
-                                           (int)rows, 0, end_bit, s);
-  }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(molecules_emit_kernel, dim3(grid_for(rows, WG)), dim3(WG), 0, s, c->t, keys_out, slots_out, rows,
-                       d_index, d_feature, reinterpret_cast<u64*>(d_umi), reinterpret_cast<u64*>(d_mreads),
-                       reinterpret_cast<u64*>(d_parent));
-    e = hipGetLastError();
-  }
-  sct::pool_free(blk, s);
-  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule fetch: %s", hipGetErrorString(e));
   return leave(c, s);
 }
 
@@ -803,29 +802,18 @@ int merge_check(const sct_molecules* dst, const sct_molecules* src) {
 }
 
 // src's occupied rows, dense and unsorted, into a pool block on src's device on `ss` (src's device
-// is current): keys[rows] at its head, then *cnt = cnt[rows] for a counted counter (the block's tail
-// holds the slots the counts were gathered through).
+// is current): keys[rows] at its head, then *cnt = cnt[rows] for a counted counter, written by the
+// compaction beside the keys.
 int merge_compact(sct_molecules* src, int64_t rows, hipStream_t ss, void** blk, const u64** cnt) {
   Carve cv;
-  const size_t o_keys = cv.take((size_t)rows * 8);
-  const size_t o_cnt = src->counted ? cv.take((size_t)rows * 8) : 0, o_slots = src->counted ? cv.take((size_t)rows * 4) : 0;
+  const size_t o_keys = cv.take((size_t)rows * 8), o_cnt = src->counted ? cv.take((size_t)rows * 8) : 0;
   SCT_HIP(sct::pool_alloc(blk, cv.size, ss));
   uint8_t* b = static_cast<uint8_t*>(*blk);
-  u64* keys = reinterpret_cast<u64*>(b + o_keys);
-  *cnt = src->counted ? reinterpret_cast<const u64*>(b + o_cnt) : nullptr;
-  hipError_t e = hipMemsetAsync(&src->t.words[W_CURSOR], 0, 8, ss);
+  u64* counts = src->counted ? reinterpret_cast<u64*>(b + o_cnt) : nullptr;
+  *cnt = counts;
+  hipError_t e = zero_cursor(&src->t.words[W_CURSOR], ss);
   if (e == hipSuccess) {
-    const dim3 grid(grid_for(src->capacity, 1024));
-    if (src->counted) {
-      uint32_t* slots = reinterpret_cast<uint32_t*>(b + o_slots);
-      hipLaunchKernelGGL(molecules_compact_kernel<true>, grid, dim3(WG), 0, ss, src->t.keys, src->capacity,
-                         &src->t.words[W_CURSOR], rows, keys, slots);
-      hipLaunchKernelGGL(molecules_gather_counts_kernel, dim3(grid_for(rows, 1024)), dim3(WG), 0, ss, src->t.cnt, slots,
-                         rows, reinterpret_cast<u64*>(b + o_cnt));
-    } else {
-      hipLaunchKernelGGL(molecules_compact_kernel<false>, grid, dim3(WG), 0, ss, src->t.keys, src->capacity,
-                         &src->t.words[W_CURSOR], rows, keys, nullptr);
-    }
+    compact(src, counts ? BESIDE_COUNT : BESIDE_NONE, rows, reinterpret_cast<u64*>(b + o_keys), counts, ss);
     e = hipGetLastError();
   }
   if (e != hipSuccess) {
@@ -850,13 +838,11 @@ int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
       if (!hs) return SCT_E_HIP;
       ss = hs->stream;
     }
-    SCT_TRY(enter(src, ss));
-    SCT_TRY(read_words(src, ss));  // SCT_E_RANGE for a source that overflowed
+    SCT_TRY(enter_read(src, ss));  // SCT_E_RANGE for a source that overflowed
   }
   const int64_t src_size = src->size_bound;
   SCT_ON_DEVICE_OF(dst);
-  SCT_TRY(enter(dst, s));
-  SCT_TRY(read_words(dst, s));
+  SCT_TRY(enter_read(dst, s));
   const int64_t dst_size = dst->size_bound;
   const int64_t cap = sct::mol_merge_capacity(dst->capacity, dst_size, src_size);
   if (cap == 0)
@@ -1065,10 +1051,7 @@ int update_host_entry(sct_molecules* c, bool features, const int32_t* index, con
   if (features) SCT_CHECK(index != nullptr && feature != nullptr && umi != nullptr, "NULL index, feature or umi");
   else SCT_CHECK(index != nullptr && umi != nullptr, "NULL index or umi");
   if (int rc = need_features(c, features); rc != SCT_OK) return rc;
-  SCT_ON_DEVICE_OF(c);
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
+  SCT_ON_STAGE_OF(c, s);
   // pieces through one pool buffer (umis, then indices, then features): a piece's copies are ordered
   // after the previous piece's kernels.  An out-of-range index in one piece does not stop the others.
   const int64_t piece = std::min<int64_t>(n, 1LL << 24);
@@ -1111,14 +1094,16 @@ extern "C" int sct_molecules_update_features_host(sct_molecules* c, const int32_
   return update_host_entry(c, true, index, feature, umi, n);
 }
 
+// the size and the tally words as the counter's work so far leaves them: c->size_bound, c->h_words
+static int read_info(sct_molecules* c) {
+  SCT_ON_STAGE_OF(c, s);
+  return enter_read(c, s);
+}
+
 extern "C" int sct_molecules_features_info(sct_molecules* c, int64_t* nf, int64_t* n_no_feature) {
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (n_no_feature) {
-    SCT_ON_DEVICE_OF(c);
-    sct::HostStage* hs = sct::host_stage();
-    if (!hs) return SCT_E_HIP;
-    if (int rc = enter(c, hs->stream); rc != SCT_OK) return rc;
-    if (int rc = read_words(c, hs->stream); rc != SCT_OK) return rc;
+    if (int rc = read_info(c); rc != SCT_OK) return rc;
     *n_no_feature = (int64_t)c->h_words[W_TALLY + 3];
   }
   if (nf) *nf = c->t.nf;
@@ -1128,11 +1113,7 @@ extern "C" int sct_molecules_features_info(sct_molecules* c, int64_t* nf, int64_
 extern "C" int sct_molecules_info(sct_molecules* c, int64_t* nmolecules, int64_t* total, int64_t* capacity) {
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (nmolecules) {
-    SCT_ON_DEVICE_OF(c);
-    sct::HostStage* hs = sct::host_stage();
-    if (!hs) return SCT_E_HIP;
-    if (int rc = enter(c, hs->stream); rc != SCT_OK) return rc;
-    if (int rc = read_words(c, hs->stream); rc != SCT_OK) return rc;
+    if (int rc = read_info(c); rc != SCT_OK) return rc;
     *nmolecules = c->size_bound;
   }
   if (total) *total = c->total;
@@ -1149,11 +1130,9 @@ extern "C" int sct_molecules_counts(sct_molecules* c, uint64_t* d_reads, uint64_
 
 extern "C" int sct_molecules_counts_host(sct_molecules* c, uint64_t* reads, uint64_t* molecules, uint64_t* tally) {
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
-  SCT_ON_DEVICE_OF(c);
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  const int rc = counts_copy(c, reads, molecules, tally, hipMemcpyDeviceToHost, hs->stream);
-  const hipError_t e = hipStreamSynchronize(hs->stream);  // the caller's arrays are written until here
+  SCT_ON_STAGE_OF(c, s);
+  const int rc = counts_copy(c, reads, molecules, tally, hipMemcpyDeviceToHost, s);
+  const hipError_t e = hipStreamSynchronize(s);  // the caller's arrays are written until here
   if (rc == SCT_OK && e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule counts: %s", hipGetErrorString(e));
   return rc;
 }
@@ -1161,33 +1140,14 @@ extern "C" int sct_molecules_counts_host(sct_molecules* c, uint64_t* reads, uint
 extern "C" int sct_molecules_fetch(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, int64_t room, void* stream) {
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
-  SCT_ON_DEVICE_OF(c);
-  return fetch_device(c, d_index, nullptr, d_umi, room, sct::as_stream(stream));
+  return fetch_device(c, d_index, nullptr, d_umi, nullptr, nullptr, d_index && d_umi, room, sct::as_stream(stream));
 }
 
 extern "C" int sct_molecules_fetch_host(sct_molecules* c, int32_t* index, uint64_t* umi, int64_t room) {
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   SCT_CHECK(room == 0 || (index && umi), "NULL output");
-  SCT_ON_DEVICE_OF(c);
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  if (int rc = enter(c, s); rc != SCT_OK) return rc;
-  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
-  const int64_t rows = c->size_bound;
-  SCT_CHECK(room >= rows, "room for %lld molecules, the counter holds %lld", (long long)room, (long long)rows);
-  if (rows == 0) return SCT_OK;
-  const size_t b8 = up256((size_t)rows * 8);
-  sct::PoolBlock blk(s);
-  if (int rc = blk.alloc(b8 + (size_t)rows * 4); rc != SCT_OK) return rc;
-  uint8_t* b = blk.bytes();
-  const int rc = fetch_device(c, (int32_t*)(b + b8), nullptr, (uint64_t*)b, rows, s);
-  if (rc == SCT_OK) {
-    blk.note(hipMemcpyAsync(umi, b, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok()) blk.note(hipMemcpyAsync(index, b + b8, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-  }
-  return blk.finish(rc, "molecule fetch");
+  return fetch_host(c, index, nullptr, umi, nullptr, nullptr, room);
 }
 
 extern "C" int sct_molecules_collapse(sct_molecules* c, uint64_t* d_collapsed, uint64_t* d_ncorrected, void* stream) {
@@ -1202,20 +1162,11 @@ extern "C" int sct_molecules_collapse_host(sct_molecules* c, uint64_t* collapsed
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (int rc = need_counted(c); rc != SCT_OK) return rc;
   SCT_CHECK(collapsed != nullptr, "NULL output");
-  SCT_ON_DEVICE_OF(c);
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  const size_t nb = (size_t)c->t.nw * 8;
-  sct::PoolBlock blk(s);
-  if (int rc = blk.alloc(nb + 8); rc != SCT_OK) return rc;
-  uint8_t* b = blk.bytes();
-  const int rc = collapse_device(c, (uint64_t*)b, (uint64_t*)(b + nb), s);
-  if (rc == SCT_OK) {
-    blk.note(hipMemcpyAsync(collapsed, b, nb, hipMemcpyDeviceToHost, s));
-    if (blk.ok() && ncorrected) blk.note(hipMemcpyAsync(ncorrected, b + nb, 8, hipMemcpyDeviceToHost, s));
-  }
-  return blk.finish(rc, "molecule collapse");
+  SCT_ON_STAGE_OF(c, s);
+  Staged st(s);
+  st.add(collapsed, 8, (size_t)c->t.nw), st.add(ncorrected, 8, 1);
+  if (int rc = st.alloc(); rc != SCT_OK) return rc;
+  return st.finish(collapse_device(c, st.dev<uint64_t>(0), st.dev<uint64_t>(1), s), "molecule collapse");
 }
 
 extern "C" int sct_molecules_fetch_counted(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, uint64_t* d_mreads,
@@ -1223,13 +1174,8 @@ extern "C" int sct_molecules_fetch_counted(sct_molecules* c, int32_t* d_index, u
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (int rc = need_counted(c); rc != SCT_OK) return rc;
-  SCT_ON_DEVICE_OF(c);
-  hipStream_t s = sct::as_stream(stream);
-  int64_t rows = 0;
-  if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
-  if (rows == 0) return SCT_OK;
-  SCT_CHECK(d_mreads != nullptr, "NULL output");
-  return fetch_counted_rows(c, d_index, nullptr, d_umi, d_mreads, d_parent, rows, s);
+  return fetch_device(c, d_index, nullptr, d_umi, d_mreads, d_parent, d_index && d_umi && d_mreads, room,
+                      sct::as_stream(stream));
 }
 
 extern "C" int sct_molecules_fetch_counted_host(sct_molecules* c, int32_t* index, uint64_t* umi, uint64_t* mreads,
@@ -1238,26 +1184,7 @@ extern "C" int sct_molecules_fetch_counted_host(sct_molecules* c, int32_t* index
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (int rc = need_counted(c); rc != SCT_OK) return rc;
   SCT_CHECK(room == 0 || (index && umi && mreads), "NULL output");
-  SCT_ON_DEVICE_OF(c);
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  int64_t rows = 0;
-  if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
-  if (rows == 0) return SCT_OK;
-  const size_t b8 = up256((size_t)rows * 8);
-  sct::PoolBlock blk(s);
-  if (int rc = blk.alloc(3 * b8 + (size_t)rows * 4); rc != SCT_OK) return rc;
-  uint8_t* b = blk.bytes();  // umi, mreads, parent, index
-  const int rc = fetch_counted_rows(c, (int32_t*)(b + 3 * b8), nullptr, (uint64_t*)b, (uint64_t*)(b + b8),
-                                    parent ? (uint64_t*)(b + 2 * b8) : nullptr, rows, s);
-  if (rc == SCT_OK) {
-    blk.note(hipMemcpyAsync(umi, b, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok()) blk.note(hipMemcpyAsync(mreads, b + b8, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok() && parent) blk.note(hipMemcpyAsync(parent, b + 2 * b8, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok()) blk.note(hipMemcpyAsync(index, b + 3 * b8, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-  }
-  return blk.finish(rc, "molecule fetch");
+  return fetch_host(c, index, nullptr, umi, mreads, parent, room);
 }
 
 extern "C" int sct_molecules_merge(sct_molecules* dst, sct_molecules* src, void* stream) {
@@ -1277,14 +1204,13 @@ int need_feature_counter(const sct_molecules* c) {
 
 // The CSR matrix of the table as it stands, on `s`: d_indptr[nw + 1], d_feature[nnz] and the value
 // arrays asked for, each [nnz].  *nnz is a host word, written in every case that gets as far as
-// counting the entries; room < nnz is SCT_E_INVALID with nothing else written.  All scratch is one
-// carved pool block: the (key, slot) rows twice (the sort's two sides), the tile head counts and their
-// scan, the entry count per barcode, the scratch of the sort and of both scans and, for the collapsed
-// values, what the collapse pass writes (collapsed[nw], n_corrected and its bitmap of a bit per slot).
+// counting the entries; room < nnz is SCT_E_INVALID with nothing else written.  All scratch is the
+// one block of the sorted (key, slot) rows: after them the tile head counts and their scan, the entry
+// count per barcode and, for the collapsed values, the collapse pass's scratch with a collapsed[nw]
+// of its own; both scans run in the sort's scratch.
 int matrix_device(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint64_t* d_molecules, uint64_t* d_reads,
                   uint64_t* d_collapsed, int64_t room, int64_t* nnz, hipStream_t s) {
-  if (int rc = enter(c, s); rc != SCT_OK) return rc;
-  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
   const int64_t rows = c->size_bound, nw = c->t.nw;
   SCT_CHECK(nw + 1 < (1LL << 31), "matrix: nw + 1 = %lld row offsets are more than one scan takes", (long long)nw + 1);
   *nnz = 0;
@@ -1293,44 +1219,27 @@ int matrix_device(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint6
     return leave(c, s);
   }
   const int64_t ntiles = (rows + 63) / 64;
-  const int end_bit = c->idx_bits + c->t.idx_shift;
-  size_t sort_bytes = 0, scan_tiles_bytes = 0, scan_rows_bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const u64*)nullptr, (u64*)nullptr,
-                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)rows, 0, end_bit, s);
+  size_t scan_tiles_bytes = 0, scan_rows_bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tiles_bytes, (const u64*)nullptr, (u64*)nullptr,
                                          (int)(ntiles + 1), s);
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_rows_bytes, (const u64*)nullptr, (u64*)nullptr, (int)(nw + 1), s);
-  Carve cv;
-  const size_t o_keys_in = cv.take((size_t)rows * 8), o_keys_out = cv.take((size_t)rows * 8);
-  const size_t o_slots_in = cv.take((size_t)rows * 4), o_slots_out = cv.take((size_t)rows * 4);
-  const size_t o_tmp = cv.take(std::max(sort_bytes, std::max(scan_tiles_bytes, scan_rows_bytes)));
-  const size_t o_heads = cv.take((size_t)(ntiles + 1) * 8), o_base = cv.take((size_t)(ntiles + 1) * 8);
-  const size_t o_row_entries = cv.take((size_t)(nw + 1) * 8);
-  // the collapse pass's outputs, zeroed together: n_corrected, collapsed[nw], the bitmap
-  const size_t o_pass = d_collapsed ? cv.take(8 + (size_t)nw * 8 + (size_t)c->capacity / 8) : 0;
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, cv.size, s));
-  uint8_t* b = static_cast<uint8_t*>(blk);
-  u64* keys_in = reinterpret_cast<u64*>(b + o_keys_in);
-  u64* keys_out = reinterpret_cast<u64*>(b + o_keys_out);
-  uint32_t* slots_in = reinterpret_cast<uint32_t*>(b + o_slots_in);
-  uint32_t* slots_out = reinterpret_cast<uint32_t*>(b + o_slots_out);
-  u64* heads = reinterpret_cast<u64*>(b + o_heads);
-  u64* base = reinterpret_cast<u64*>(b + o_base);
-  u64* row_entries = reinterpret_cast<u64*>(b + o_row_entries);
+  SortedRows<true> sr(rows, key_bits(c), s, std::max(scan_tiles_bytes, scan_rows_bytes));
+  const size_t o_heads = sr.take((size_t)(ntiles + 1) * 8), o_base = sr.take((size_t)(ntiles + 1) * 8);
+  const size_t o_row_entries = sr.take((size_t)(nw + 1) * 8);
+  const size_t pass_bytes = CollapseScratch::bytes(c, true), o_pass = d_collapsed ? sr.take(pass_bytes) : 0;
+  SCT_HIP(sr.alloc());
+  u64* heads = sr.at<u64>(o_heads);
+  u64* base = sr.at<u64>(o_base);
+  u64* row_entries = sr.at<u64>(o_row_entries);
+  const u64* keys_out = sr.word();
+  const uint32_t* slots_out = sr.slot();
   const dim3 tiles_grid(grid_for(ntiles, WG / 64));
   // 1. the rows sorted by key, and the entries that open in every tile; their sum is nnz
-  hipError_t e = hipMemsetAsync(&c->t.words[W_CURSOR], 0, 8, s);
-  if (e == hipSuccess) e = hipMemsetAsync(&heads[ntiles], 0, 8, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(molecules_compact_kernel<true>, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t.keys,
-                       c->capacity, &c->t.words[W_CURSOR], rows, keys_in, slots_in);
-    e = hipcub::DeviceRadixSort::SortPairs(b + o_tmp, sort_bytes, keys_in, keys_out, slots_in, slots_out, (int)rows, 0,
-                                           end_bit, s);
-  }
+  hipError_t e = hipMemsetAsync(&heads[ntiles], 0, 8, s);
+  if (e == hipSuccess) e = sort_rows(c, sr);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(molecules_matrix_heads_kernel, tiles_grid, dim3(WG), 0, s, keys_out, rows, c->t.umi_bits, heads);
-    e = hipcub::DeviceScan::ExclusiveSum(b + o_tmp, scan_tiles_bytes, heads, base, (int)(ntiles + 1), s);
+    e = hipcub::DeviceScan::ExclusiveSum(sr.tmp(), scan_tiles_bytes, heads, base, (int)(ntiles + 1), s);
   }
   // (the host word beside the cursor's read-back is free between two read_words)
   if (e == hipSuccess) e = hipMemcpyAsync(&c->h_words[W_CURSOR], &base[ntiles], 8, hipMemcpyDeviceToHost, s);
@@ -1344,26 +1253,20 @@ int matrix_device(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint6
     const uint32_t* bitmap = nullptr;
     if (e == hipSuccess && d_collapsed) {
       e = hipMemsetAsync(d_collapsed, 0, (size_t)entries * 8, s);
-      if (e == hipSuccess) e = hipMemsetAsync(b + o_pass, 0, 8 + (size_t)nw * 8 + (size_t)c->capacity / 8, s);
-      u64* pass = reinterpret_cast<u64*>(b + o_pass);
-      bitmap = reinterpret_cast<const uint32_t*>(pass + 1 + nw);
-      if (e == hipSuccess) {
-        const bool wave = sct::tune(SCT_TUNE_COLLAPSE_FORM, 1) == 1;
-        const auto kernel = wave ? molecules_collapse_wave_kernel : molecules_collapse_kernel;
-        hipLaunchKernelGGL(kernel, dim3(grid_for(c->capacity, WG)), dim3(WG), 0, s, c->t, c->capacity,
-                           const_cast<uint32_t*>(bitmap), pass + 1, pass);
-      }
+      if (e == hipSuccess) e = hipMemsetAsync(sr.at<void>(o_pass), 0, pass_bytes, s);
+      const CollapseScratch cs(c, sr.at<uint8_t>(o_pass));
+      bitmap = cs.bitmap;
+      if (e == hipSuccess) e = collapse_pass(c, cs.bitmap, cs.collapsed, cs.ncorrected, s);
     }
     if (e == hipSuccess) {
       hipLaunchKernelGGL(molecules_matrix_fill_kernel, tiles_grid, dim3(WG), 0, s, c->t, keys_out, slots_out, rows, base,
                          bitmap, row_entries, d_feature, reinterpret_cast<u64*>(d_molecules),
                          reinterpret_cast<u64*>(d_reads), reinterpret_cast<u64*>(d_collapsed));
-      e = hipcub::DeviceScan::ExclusiveSum(b + o_tmp, scan_rows_bytes, row_entries, reinterpret_cast<u64*>(d_indptr),
+      e = hipcub::DeviceScan::ExclusiveSum(sr.tmp(), scan_rows_bytes, row_entries, reinterpret_cast<u64*>(d_indptr),
                                            (int)(nw + 1), s);
     }
     if (e == hipSuccess) e = hipGetLastError();
   }
-  sct::pool_free(blk, s);
   if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule matrix: %s", hipGetErrorString(e));
   *nnz = entries;
   if (int rc = leave(c, s); rc != SCT_OK) return rc;
@@ -1394,13 +1297,7 @@ extern "C" int sct_molecules_fetch_features(sct_molecules* c, int32_t* d_index, 
   if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
   if (d_mreads || d_parent)
     if (int rc = need_counted(c); rc != SCT_OK) return rc;
-  SCT_ON_DEVICE_OF(c);
-  hipStream_t s = sct::as_stream(stream);
-  if (!d_mreads && !d_parent) return fetch_device(c, d_index, d_feature, d_umi, room, s);
-  int64_t rows = 0;
-  if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
-  if (rows == 0) return SCT_OK;
-  return fetch_counted_rows(c, d_index, d_feature, d_umi, d_mreads, d_parent, rows, s);
+  return fetch_device(c, d_index, d_feature, d_umi, d_mreads, d_parent, true, room, sct::as_stream(stream));
 }
 
 extern "C" int sct_molecules_fetch_features_host(sct_molecules* c, int32_t* index, int32_t* feature, uint64_t* umi,
@@ -1411,32 +1308,7 @@ extern "C" int sct_molecules_fetch_features_host(sct_molecules* c, int32_t* inde
   if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
   if (mreads || parent)
     if (int rc = need_counted(c); rc != SCT_OK) return rc;
-  SCT_ON_DEVICE_OF(c);
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  int64_t rows = 0;
-  if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
-  if (rows == 0) return SCT_OK;
-  const size_t b8 = up256((size_t)rows * 8), b4 = up256((size_t)rows * 4);
-  sct::PoolBlock blk(s);
-  if (int rc = blk.alloc(3 * b8 + 2 * b4); rc != SCT_OK) return rc;
-  uint8_t* b = blk.bytes();  // umi, mreads, parent, index, feature
-  uint64_t* d_umi = (uint64_t*)b;
-  uint64_t* d_mreads = mreads ? (uint64_t*)(b + b8) : nullptr;
-  uint64_t* d_parent = parent ? (uint64_t*)(b + 2 * b8) : nullptr;
-  int32_t* d_index = (int32_t*)(b + 3 * b8);
-  int32_t* d_feature = (int32_t*)(b + 3 * b8 + b4);
-  const int rc = d_mreads || d_parent ? fetch_counted_rows(c, d_index, d_feature, d_umi, d_mreads, d_parent, rows, s)
-                                      : fetch_device(c, d_index, d_feature, d_umi, rows, s);
-  if (rc == SCT_OK) {
-    blk.note(hipMemcpyAsync(umi, d_umi, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok() && mreads) blk.note(hipMemcpyAsync(mreads, d_mreads, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok() && parent) blk.note(hipMemcpyAsync(parent, d_parent, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok()) blk.note(hipMemcpyAsync(index, d_index, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-    if (blk.ok()) blk.note(hipMemcpyAsync(feature, d_feature, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-  }
-  return blk.finish(rc, "molecule fetch");
+  return fetch_host(c, index, feature, umi, mreads, parent, room);
 }
 
 extern "C" int sct_molecules_matrix(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint64_t* d_molecules,
@@ -1449,31 +1321,16 @@ extern "C" int sct_molecules_matrix(sct_molecules* c, int64_t* d_indptr, int32_t
 extern "C" int sct_molecules_matrix_host(sct_molecules* c, int64_t* indptr, int32_t* feature, uint64_t* molecules,
                                          uint64_t* reads, uint64_t* collapsed, int64_t room, int64_t* nnz) {
   if (int rc = matrix_check(c, indptr, feature, reads, collapsed, room, nnz); rc != SCT_OK) return rc;
-  SCT_ON_DEVICE_OF(c);
-  sct::HostStage* hs = sct::host_stage();
-  if (!hs) return SCT_E_HIP;
-  hipStream_t s = hs->stream;
-  if (int rc = enter(c, s); rc != SCT_OK) return rc;
-  if (int rc = read_words(c, s); rc != SCT_OK) return rc;
+  SCT_ON_STAGE_OF(c, s);
+  if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
   // nnz <= nmolecules: the device arrays never need more room than that
   const int64_t r = std::min(room, c->size_bound);
-  const size_t bp = up256((size_t)(c->t.nw + 1) * 8), b8 = up256((size_t)r * 8), b4 = up256((size_t)r * 4);
-  sct::PoolBlock blk(s);
-  if (int rc = blk.alloc(bp + 3 * b8 + b4); rc != SCT_OK) return rc;
-  uint8_t* b = blk.bytes();  // indptr, molecules, reads, collapsed, feature
-  int64_t* d_indptr = (int64_t*)b;
-  uint64_t* d_molecules = molecules ? (uint64_t*)(b + bp) : nullptr;
-  uint64_t* d_reads = reads ? (uint64_t*)(b + bp + b8) : nullptr;
-  uint64_t* d_collapsed = collapsed ? (uint64_t*)(b + bp + 2 * b8) : nullptr;
-  int32_t* d_feature = (int32_t*)(b + bp + 3 * b8);
-  const int rc = matrix_device(c, d_indptr, d_feature, d_molecules, d_reads, d_collapsed, r, nnz, s);
-  if (rc == SCT_OK) {
-    const size_t n = (size_t)*nnz;
-    blk.note(hipMemcpyAsync(indptr, d_indptr, (size_t)(c->t.nw + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok() && n) blk.note(hipMemcpyAsync(feature, d_feature, n * 4, hipMemcpyDeviceToHost, s));
-    if (blk.ok() && n && molecules) blk.note(hipMemcpyAsync(molecules, d_molecules, n * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok() && n && reads) blk.note(hipMemcpyAsync(reads, d_reads, n * 8, hipMemcpyDeviceToHost, s));
-    if (blk.ok() && n && collapsed) blk.note(hipMemcpyAsync(collapsed, d_collapsed, n * 8, hipMemcpyDeviceToHost, s));
-  }
-  return blk.finish(rc, "molecule matrix");
+  Staged st(s);
+  st.add(indptr, 8, (size_t)c->t.nw + 1), st.add(feature, 4, r);
+  st.add(molecules, 8, r), st.add(reads, 8, r), st.add(collapsed, 8, r);
+  if (int rc = st.alloc(); rc != SCT_OK) return rc;
+  const int rc = matrix_device(c, st.dev<int64_t>(0), st.dev<int32_t>(1), st.dev<uint64_t>(2), st.dev<uint64_t>(3),
+                               st.dev<uint64_t>(4), r, nnz, s);
+  for (int i = 1; i < st.n; ++i) st.cols[i].count = (size_t)*nnz;  // what the matrix wrote of its room
+  return st.finish(rc, "molecule matrix");
 }

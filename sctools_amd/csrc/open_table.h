@@ -227,6 +227,48 @@ inline int read_words(Host* c, hipStream_t s) {
   return SCT_OK;
 }
 
+// how a call that needs the table's size opens: ordered after the counter's earlier work, size exact
+inline int enter_read(Host* c, hipStream_t s) {
+  if (int rc = enter(c, s); rc != SCT_OK) return rc;
+  return read_words(c, s);
+}
+
+// before a compaction (compact_at): the cursor word it counts the rows in
+inline hipError_t zero_cursor(u64* cursor, hipStream_t s) { return hipMemsetAsync(cursor, 0, 8, s); }
+
+// The outputs of a *_host call, staged: columns of `count` elements of `elem` bytes in one pool block,
+// each on a multiple of 256 bytes.  A column whose host pointer is NULL was not asked for: it takes
+// no room and its device pointer is NULL.  add() every column, alloc(), run the device form on
+// dev<T>(i) (i: the order of the add() calls), then finish() copies the columns back -- `count` may be
+// lowered first -- and ends the call as PoolBlock::finish does.
+struct Staged {
+  struct Column {
+    void* host;
+    size_t elem, count, at;
+  };
+  PoolBlock blk;
+  Carve cv;
+  Column cols[6];
+  int n = 0;
+  explicit Staged(hipStream_t s) : blk(s) {}
+  void add(void* host, size_t elem, size_t count) {
+    cols[n++] = Column{host, elem, count, host ? cv.take(elem * count) : 0};
+  }
+  int alloc() { return blk.alloc(std::max<size_t>(cv.size, 1)); }
+  template <class T>
+  T* dev(int i) const {
+    return cols[i].host ? reinterpret_cast<T*>(blk.bytes() + cols[i].at) : nullptr;
+  }
+  int finish(int rc, const char* what) {
+    for (int i = 0; i < n && rc == SCT_OK && blk.ok(); ++i) {
+      const Column& c = cols[i];
+      if (c.host && c.count)
+        blk.note(hipMemcpyAsync(c.host, dev<uint8_t>(i), c.elem * c.count, hipMemcpyDeviceToHost, blk.s));
+    }
+    return blk.finish(rc, what);
+  }
+};
+
 // n items on `s` by table_load.h's policy: grow(factor) re-makes the table at capacity * factor,
 // launch(done, m) enqueues the items [done, done + m); both return a status
 template <class Grow, class Launch>

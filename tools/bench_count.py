@@ -19,7 +19,8 @@ and against the host route, with the existing molecule rows again beside an earl
 (nf = 4096): update_features against the plain update, matrix_device in its three forms, the host
 route pairs(features=True) + np.unique, and the plain and counted updates beside an earlier library
 (matrix_step; profiles/ab_count_matrix.jsonl, or ab_count_matrix_<tag>.jsonl for a tag other than
-"run").
+"run").  Then the calls that read a table back, merge two and grow one, each beside an earlier library,
+timings and outputs (calls_step; profiles/ab_molecules_calls_<tag>.jsonl).
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends
 the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
@@ -29,8 +30,10 @@ the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>
   python tools/bench_count.py --tag mi355x --only collapse --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --tag mi355x --only merge --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only matrix --parent-lib /path/to/earlier/libsctools_hip.so
+  python tools/bench_count.py --only calls --parent-lib /path/to/earlier/libsctools_hip.so
 """
 import argparse
+import functools
 import json
 import os
 import subprocess
@@ -41,7 +44,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420, "collapse": 600,
-         "merge": 600, "matrix": 600}  # seconds
+         "merge": 600, "matrix": 600, "calls": 600}  # seconds
 MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
 HBM_BYTES_PER_S = 8e12
 
@@ -289,6 +292,67 @@ def _molecules_input(args):
     return nw, UL, n, hint, pool, inputs
 
 
+UPDATE_CALLS = ("sct_tune_set", "sct_molecules_create", "sct_molecules_create_counted", "sct_molecules_update",
+                "sct_molecules_counts_host", "sct_molecules_destroy")
+
+
+def _parent_lib(args, names=UPDATE_CALLS):
+    """--parent-lib loaded beside this library, with the signatures of the calls in `names`; None without it."""
+    import ctypes
+
+    from sctools_amd import _lib
+    if not args.parent_lib:
+        return None
+    old = ctypes.CDLL(os.path.abspath(args.parent_lib))
+    for name in names:
+        getattr(old, name).argtypes = _lib.SIGNATURES[name]
+    return old
+
+
+def _full_update(lib, mode, d_index, d_umi, counted, shape):
+    """(ms, facts): sct_molecules_update of all n reads into a fresh counter of `lib`, through the C ABI;
+    shape = (nw, UL, n, hint)."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib
+    nw, UL, n, hint = shape
+    vp, h = ctypes.c_void_p, ctypes.c_void_p()
+    assert lib.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], mode) == 0
+    create = lib.sct_molecules_create_counted if counted else lib.sct_molecules_create
+    assert create(nw, 3, UL, hint, ctypes.byref(h)) == 0
+    try:
+        def go():
+            assert lib.sct_molecules_update(h, vp(d_index.data_ptr()), vp(d_umi.data_ptr()), n, None) == 0
+            torch.cuda.synchronize()
+        ms = _time_ms(go)
+        reads, molecules, tally = np.empty(nw, np.uint64), np.empty(nw, np.uint64), np.empty(3, np.uint64)
+        assert lib.sct_molecules_counts_host(h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)) == 0
+    finally:
+        lib.sct_molecules_destroy(h)
+        lib.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], -1)
+    return ms, (int(reads.sum()), int(molecules.sum()), int(tally[0]), int(tally[1]), int(tally[2]))
+
+
+def _vs_parent(a, b):
+    """This library's {median, min, max} beside the parent's: they agree when the medians differ by no
+    more than the min-max spread of the parent's own rounds."""
+    return {"median_difference_ms": round(a["median"] - b["median"], 3),
+            "parent_spread_ms": round(b["max"] - b["min"], 3),
+            "agree": abs(a["median"] - b["median"]) <= b["max"] - b["min"]}
+
+
+def _features_of(d_index, d_umi, spread, nf):
+    """A molecule's feature: a hash of its (barcode, UMI) over `spread` of the nf features, 2 % none."""
+    import torch
+    g = torch.Generator(device=d_index.device).manual_seed(13)
+    f = (((d_umi * -7046029254386353131) >> 40) ^ d_index.to(torch.int64)) & (spread - 1)
+    f = (f * (nf // spread)).to(torch.int32)  # spread over the whole range of nf
+    none = torch.rand(d_index.numel(), device=d_index.device, generator=g) < 0.02
+    return torch.where(none, torch.full_like(f, -1), f).contiguous()
+
+
 def collapse_step(args):
     """The counted molecule counter and its UMI collapse on the molecules step's input.  Alternating
     within every round, per input order and pre-aggregation mode: (a) MoleculeCounter.update_device as
@@ -301,21 +365,14 @@ def collapse_step(args):
     device's for those barcodes.  (a) and (a') agree when their medians differ by no more than the
     min-max spread of (a')'s own rounds; the step fails when they do not.  Every round is one line of
     profiles/ab_umi_collapse_<tag>.jsonl, the summary its last."""
-    import ctypes
-
     import numpy as np
     import torch
     from sctools_amd import _lib, counting
 
     nw, UL, n, hint, pool, inputs = _molecules_input(args)
     dev = torch.device("cuda")
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    old = None
-    if args.parent_lib:
-        old = ctypes.CDLL(os.path.abspath(args.parent_lib))
-        for name in ("sct_tune_set", "sct_molecules_create", "sct_molecules_update", "sct_molecules_counts_host",
-                     "sct_molecules_destroy"):
-            getattr(old, name).argtypes = _lib.SIGNATURES[name]
+    # (a library from before the counted counter will do: only the plain update is asked of it)
+    old = _parent_lib(args, [name for name in UPDATE_CALLS if name != "sct_molecules_create_counted"])
     d_collapsed = torch.zeros(nw + 1, dtype=torch.int64, device=dev)
 
     def facts_of(reads, molecules, tally):
@@ -342,19 +399,7 @@ def collapse_step(args):
         return ms, cms, facts_of(reads, molecules, (n_none, n_amb, n_bad))
 
     def run_parent(mode, d_index, d_umi):
-        h = vp()
-        assert old.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], mode) == 0
-        assert old.sct_molecules_create(nw, 3, UL, hint, ctypes.byref(h)) == 0
-        try:
-            def go():
-                assert old.sct_molecules_update(h, vp(d_index.data_ptr()), vp(d_umi.data_ptr()), n, None) == 0
-                torch.cuda.synchronize()
-            ms = _time_ms(go)
-            reads, molecules, tally = np.empty(nw, np.uint64), np.empty(nw, np.uint64), np.empty(3, np.uint64)
-            assert old.sct_molecules_counts_host(h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)) == 0
-        finally:
-            old.sct_molecules_destroy(h)
-        return ms, facts_of(reads, molecules, tally)
+        return _full_update(old, mode, d_index, d_umi, False, (nw, UL, n, hint))
 
     run_update(2, *inputs["shuffled"][:2], True)  # warm-up: code objects, pool
     if old:
@@ -390,11 +435,7 @@ def collapse_step(args):
                 a = [row[name][key] for row in rounds]
                 res[name][key] = {"median": round(float(np.median(a)), 3), "min": min(a), "max": max(a)}
             if old:
-                a, b = res[name]["uncounted_ms"], res[name]["uncounted_parent_ms"]
-                res[name]["uncounted_vs_parent"] = {
-                    "median_difference_ms": round(a["median"] - b["median"], 3),
-                    "parent_spread_ms": round(b["max"] - b["min"], 3),
-                    "agree": abs(a["median"] - b["median"]) <= b["max"] - b["min"]}
+                res[name]["uncounted_vs_parent"] = _vs_parent(res[name]["uncounted_ms"], res[name]["uncounted_parent_ms"])
     # (d) the host way: the counted rows to the host, and a dict collapse of a prefix of whole barcodes
     di, du, _ = inputs["shuffled"]
     with counting.MoleculeCounter(nw, UL, capacity_hint=hint, read_counts=True) as mc:
@@ -471,15 +512,12 @@ def merge_step(args):
     forms) in this library and, alternating, in --parent-lib; they agree when the medians differ by
     no more than the parent's own min-max spread, and the step fails (its profile written) when not.
     Every round is one line of profiles/ab_molecules_merge_<tag>.jsonl, the summary its last."""
-    import ctypes
-
     import numpy as np
     import torch
     from sctools_amd import _lib, counting
 
     nw, UL, n, hint, pool, inputs = _molecules_input(args)
     dev = torch.device("cuda")
-    vp = ctypes.c_void_p
     di, du, _ = inputs["shuffled"]
     half = n // 2
     halves = [(di[:half], du[:half]), (di[half:], du[half:])]
@@ -598,30 +636,8 @@ def merge_step(args):
     out.update(reads=reads, molecules=molecules, n_none=n_none, n_ambiguous=n_amb, n_bad_umi=n_bad)
 
     # the existing rows again, this library and the parent's alternating
-    old = None
-    if args.parent_lib:
-        old = ctypes.CDLL(os.path.abspath(args.parent_lib))
-        for fn in ("sct_tune_set", "sct_molecules_create", "sct_molecules_create_counted", "sct_molecules_update",
-                   "sct_molecules_counts_host", "sct_molecules_destroy"):
-            getattr(old, fn).argtypes = _lib.SIGNATURES[fn]
-
-    def full_update(lib, mode, d_index, d_umi, counted):
-        h = vp()
-        assert lib.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], mode) == 0
-        create = lib.sct_molecules_create_counted if counted else lib.sct_molecules_create
-        assert create(nw, 3, UL, hint, ctypes.byref(h)) == 0
-        try:
-            def go():
-                assert lib.sct_molecules_update(h, vp(d_index.data_ptr()), vp(d_umi.data_ptr()), n, None) == 0
-                torch.cuda.synchronize()
-            ms = _time_ms(go)
-            reads, molecules, tally = np.empty(nw, np.uint64), np.empty(nw, np.uint64), np.empty(3, np.uint64)
-            assert lib.sct_molecules_counts_host(h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)) == 0
-        finally:
-            lib.sct_molecules_destroy(h)
-            lib.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], -1)
-        return ms, (int(reads.sum()), int(molecules.sum()), int(tally[0]), int(tally[1]), int(tally[2]))
-
+    old = _parent_lib(args)
+    full_update = functools.partial(_full_update, shape=(nw, UL, n, hint))
     libs = {"this": _lib.lib()}
     if old:
         libs["parent"] = old
@@ -648,10 +664,7 @@ def merge_step(args):
                 v = [row[mname][key] for row in rounds]
                 res[mname][key] = {"median": round(float(np.median(v)), 3), "min": min(v), "max": max(v)}
             for kind in ("plain", "counted") if old else ():
-                a, b = res[mname][kind + "_this_ms"], res[mname][kind + "_parent_ms"]
-                res[mname][kind + "_vs_parent"] = {"median_difference_ms": round(a["median"] - b["median"], 3),
-                                                   "parent_spread_ms": round(b["max"] - b["min"], 3),
-                                                   "agree": abs(a["median"] - b["median"]) <= b["max"] - b["min"]}
+                res[mname][kind + "_vs_parent"] = _vs_parent(res[mname][kind + "_this_ms"], res[mname][kind + "_parent_ms"])
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     with open(os.path.join(ROOT, "profiles", "ab_molecules_merge_%s.jsonl" % args.tag), "w") as f:
         for row in lines:
@@ -677,8 +690,6 @@ def matrix_step(args):
     the counted update agree with the parent when the medians differ by no more than the min-max
     spread of the parent's own rounds; the step fails (its profile written) when they do not.  Every
     round is one line of the profile, the summary its last."""
-    import ctypes
-
     import numpy as np
     import torch
     from sctools_amd import _lib, counting
@@ -686,37 +697,10 @@ def matrix_step(args):
     nw, UL, n, hint, pool, inputs = _molecules_input(args)
     nf = 4096
     dev = torch.device("cuda")
-    vp = ctypes.c_void_p
-    old = None
-    if args.parent_lib:
-        old = ctypes.CDLL(os.path.abspath(args.parent_lib))
-        for fn in ("sct_tune_set", "sct_molecules_create", "sct_molecules_create_counted", "sct_molecules_update",
-                   "sct_molecules_counts_host", "sct_molecules_destroy"):
-            getattr(old, fn).argtypes = _lib.SIGNATURES[fn]
+    old = _parent_lib(args)
+    full_update = functools.partial(_full_update, shape=(nw, UL, n, hint))
 
-    def features_of(d_index, d_umi, spread):
-        g = torch.Generator(device=dev).manual_seed(13)
-        f = (((d_umi * -7046029254386353131) >> 40) ^ d_index.to(torch.int64)) & (spread - 1)
-        f = (f * (nf // spread)).to(torch.int32)  # spread over the whole range of nf
-        none = torch.rand(d_index.numel(), device=dev, generator=g) < 0.02
-        return torch.where(none, torch.full_like(f, -1), f).contiguous()
-
-    def full_update(lib, mode, d_index, d_umi, counted):
-        h = vp()
-        assert lib.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], mode) == 0
-        create = lib.sct_molecules_create_counted if counted else lib.sct_molecules_create
-        assert create(nw, 3, UL, hint, ctypes.byref(h)) == 0
-        try:
-            def go():
-                assert lib.sct_molecules_update(h, vp(d_index.data_ptr()), vp(d_umi.data_ptr()), n, None) == 0
-                torch.cuda.synchronize()
-            ms = _time_ms(go)
-            reads, molecules, tally = np.empty(nw, np.uint64), np.empty(nw, np.uint64), np.empty(3, np.uint64)
-            assert lib.sct_molecules_counts_host(h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)) == 0
-        finally:
-            lib.sct_molecules_destroy(h)
-            lib.sct_tune_set(_lib.TUNE_KEYS["count_preagg"], -1)
-        return ms, (int(reads.sum()), int(molecules.sum()), int(tally[0]), int(tally[1]), int(tally[2]))
+    features_of = functools.partial(_features_of, nf=nf)
 
     def feature_update(mode, d_index, d_feature, d_umi, counted, keep=False):
         mc = counting.MoleculeCounter(nw, UL, capacity_hint=hint, read_counts=counted, features=nf)
@@ -771,10 +755,7 @@ def matrix_step(args):
                 a = res[mname][kind + "_this_ms"]
                 res[mname][kind + "_features_over_plain"] = round(res[mname][kind + "_features_ms"]["median"] / a["median"], 3)
                 if old:
-                    b = res[mname][kind + "_parent_ms"]
-                    res[mname][kind + "_vs_parent"] = {"median_difference_ms": round(a["median"] - b["median"], 3),
-                                                       "parent_spread_ms": round(b["max"] - b["min"], 3),
-                                                       "agree": abs(a["median"] - b["median"]) <= b["max"] - b["min"]}
+                    res[mname][kind + "_vs_parent"] = _vs_parent(a, res[mname][kind + "_parent_ms"])
     # the matrix, per spread of the features, on the reads as drawn
     di, du, _ = inputs["shuffled"]
     for spread in (nf, 16):
@@ -856,6 +837,217 @@ def matrix_step(args):
     return out
 
 
+CALLS_ABI = UPDATE_CALLS + (
+    "sct_molecules_create_features", "sct_molecules_update_features", "sct_molecules_info", "sct_molecules_fetch",
+    "sct_molecules_fetch_counted", "sct_molecules_fetch_features", "sct_molecules_collapse", "sct_molecules_matrix",
+    "sct_molecules_merge", "sct_counter_create", "sct_counter_update", "sct_counter_info", "sct_counter_fetch",
+    "sct_counter_destroy")
+
+
+def calls_step(args):
+    """The calls that read a table back, merge two and grow one, in this library and in --parent-lib
+    (without it: this library alone, nothing compared), through the C ABI with device-resident outputs
+    and a stream synchronise inside the timed window.  On the molecules step's input as drawn, per
+    library, filled once: a counted feature counter (nf = 4096), a counted plain counter and a barcode
+    counter of the composite keys.  Timed, alternating between the libraries within every round (each
+    goes first in every other round, and every timed call follows an untimed one of its own kind):
+    sct_molecules_fetch; sct_molecules_fetch_counted without and with parents;
+    sct_molecules_fetch_features with every column; sct_molecules_collapse; sct_molecules_matrix with
+    the molecules, with reads, with reads and collapsed; sct_molecules_merge of the plain counter into
+    an empty counter sized up front, the table in place and compacted first (SCT_TUNE_MERGE_ROWS 1);
+    sct_molecules_update of all reads from capacity_hint 0 (the growth path), plain and counted;
+    sct_counter_fetch.  Before the rounds every call runs once in each library and every output
+    array must be equal element for element.  A call agrees when the medians differ by no more than
+    the min-max spread of the parent's own rounds; the step fails (its profile written) when a call is
+    slower than the parent beyond that spread; one that is faster beyond it is reported.  Every round
+    is one line of profiles/ab_molecules_calls_<tag>.jsonl, the summary its last."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib
+
+    nw, UL, n, hint, pool, inputs = _molecules_input(args)
+    nf = 4096
+    di, du, dk = inputs["shuffled"]
+    df = _features_of(di, du, nf, nf)
+    dev = torch.device("cuda")
+    vp, i64, ref = ctypes.c_void_p, ctypes.c_int64, ctypes.byref
+    libs = {"this": _lib.lib()}
+    old = _parent_lib(args, CALLS_ABI)
+    if old:
+        libs["parent"] = old
+    ptr = lambda t: vp(t.data_ptr())  # noqa: E731
+
+    class Side:
+        """One library's counters and output arrays."""
+        def __init__(self, lib):
+            self.lib = lib
+            self.feat, self.plain, self.counter = vp(), vp(), vp()
+            assert lib.sct_molecules_create_features(nw, nf, 3, UL, hint, 1, -1, ref(self.feat)) == 0
+            assert lib.sct_molecules_update_features(self.feat, ptr(di), ptr(df), ptr(du), n, None) == 0
+            assert lib.sct_molecules_create_counted(nw, 3, UL, hint, ref(self.plain)) == 0
+            assert lib.sct_molecules_update(self.plain, ptr(di), ptr(du), n, None) == 0
+            assert lib.sct_counter_create(hint, ref(self.counter)) == 0
+            assert lib.sct_counter_update(self.counter, ptr(dk), n, None) == 0
+            torch.cuda.synchronize()
+            self.nfeat, self.nplain, self.ncodes = self.size(self.feat), self.size(self.plain), i64(0)
+            assert lib.sct_counter_info(self.counter, ref(self.ncodes), None, None) == 0
+            self.ncodes = self.ncodes.value
+            rows = max(self.nfeat, self.nplain, self.ncodes, nw + 1)
+            self.i32 = torch.zeros((2, rows), dtype=torch.int32, device=dev)
+            self.i64 = torch.zeros((4, rows), dtype=torch.int64, device=dev)
+            self.cap = 64
+            while self.cap // 2 < self.nplain:
+                self.cap *= 2
+            self.made = None  # the counter a merge or an update made, kept until its rows are compared
+
+        def size(self, h):
+            v = i64(0)
+            assert self.lib.sct_molecules_info(h, ref(v), None, None) == 0
+            return v.value
+
+        def drop(self):
+            if self.made is not None:
+                self.lib.sct_molecules_destroy(self.made)
+                self.made = None
+
+        def close(self):
+            self.drop()
+            self.lib.sct_molecules_destroy(self.feat), self.lib.sct_molecules_destroy(self.plain)
+            self.lib.sct_counter_destroy(self.counter)
+
+    def timed(call):
+        def go():
+            assert call() == 0
+            torch.cuda.synchronize()
+        return _time_ms(go)
+
+    def rows_of(s, h):
+        """A made counter's table as arrays: its counted (or plain) rows, reads, molecules and tally."""
+        m = s.size(h)
+        if counted_of[h.value]:
+            assert s.lib.sct_molecules_fetch_counted(h, ptr(s.i32[0]), ptr(s.i64[0]), ptr(s.i64[1]), None, m, None) == 0
+        else:
+            assert s.lib.sct_molecules_fetch(h, ptr(s.i32[0]), ptr(s.i64[0]), m, None) == 0
+        torch.cuda.synchronize()
+        reads, molecules, tally = np.empty(nw, np.uint64), np.empty(nw, np.uint64), np.empty(3, np.uint64)
+        assert s.lib.sct_molecules_counts_host(h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)) == 0
+        return [s.i32[0, :m].clone(), s.i64[:2, :m].clone() if counted_of[h.value] else s.i64[0, :m].clone(),
+                torch.from_numpy(np.concatenate([reads, molecules, tally]).view(np.int64))]
+
+    counted_of = {}
+
+    def make(s, counted, capacity):
+        s.drop()
+        h = vp()
+        create = s.lib.sct_molecules_create_counted if counted else s.lib.sct_molecules_create
+        assert create(nw, 3, UL, capacity, ref(h)) == 0
+        counted_of[h.value] = counted
+        s.made = h
+        return h
+
+    def fetch(s):
+        ms = timed(lambda: s.lib.sct_molecules_fetch(s.plain, ptr(s.i32[0]), ptr(s.i64[0]), s.nplain, None))
+        return ms, [s.i32[0, :s.nplain], s.i64[0, :s.nplain]]
+
+    def fetch_counted(s, parents):
+        par = ptr(s.i64[2]) if parents else None
+        ms = timed(lambda: s.lib.sct_molecules_fetch_counted(s.plain, ptr(s.i32[0]), ptr(s.i64[0]), ptr(s.i64[1]), par,
+                                                             s.nplain, None))
+        return ms, [s.i32[0, :s.nplain], s.i64[:3 if parents else 2, :s.nplain]]
+
+    def fetch_features(s):
+        ms = timed(lambda: s.lib.sct_molecules_fetch_features(s.feat, ptr(s.i32[0]), ptr(s.i32[1]), ptr(s.i64[0]),
+                                                              ptr(s.i64[1]), ptr(s.i64[2]), s.nfeat, None))
+        return ms, [s.i32[:, :s.nfeat], s.i64[:3, :s.nfeat]]
+
+    def collapse(s):
+        ms = timed(lambda: s.lib.sct_molecules_collapse(s.plain, ptr(s.i64[0]), ptr(s.i64[1]), None))
+        return ms, [s.i64[0, :nw], s.i64[1, :1]]
+
+    def matrix(s, values):
+        nnz = i64(0)
+        val = [ptr(s.i64[1 + k]) if k < values else None for k in range(3)]
+        ms = timed(lambda: s.lib.sct_molecules_matrix(s.feat, ptr(s.i64[0]), ptr(s.i32[0]), val[0], val[1], val[2],
+                                                      s.nfeat, ref(nnz), None))
+        return ms, [s.i64[0, :nw + 1], s.i32[0, :nnz.value], s.i64[1:1 + values, :nnz.value]]
+
+    def merge(s, rows):
+        h = make(s, True, s.cap)
+        assert s.lib.sct_tune_set(_lib.TUNE_KEYS["merge_rows"], rows) == 0
+        try:
+            ms = timed(lambda: s.lib.sct_molecules_merge(h, s.plain, None))
+        finally:
+            s.lib.sct_tune_set(_lib.TUNE_KEYS["merge_rows"], -1)
+        return ms, functools.partial(rows_of, s, h)
+
+    def update(s, counted):
+        h = make(s, counted, 0)
+        ms = timed(lambda: s.lib.sct_molecules_update(h, ptr(di), ptr(du), n, None))
+        return ms, functools.partial(rows_of, s, h)
+
+    def counter_fetch(s):
+        ms = timed(lambda: s.lib.sct_counter_fetch(s.counter, ptr(s.i64[0]), ptr(s.i64[1]), ptr(s.i64[2]), s.ncodes,
+                                                   None))
+        return ms, [s.i64[:3, :s.ncodes]]
+
+    calls = {"fetch": fetch, "fetch_counted": functools.partial(fetch_counted, parents=False),
+             "fetch_counted_parents": functools.partial(fetch_counted, parents=True), "fetch_features": fetch_features,
+             "collapse": collapse, "matrix_molecules": functools.partial(matrix, values=1),
+             "matrix_molecules_reads": functools.partial(matrix, values=2),
+             "matrix_molecules_reads_collapsed": functools.partial(matrix, values=3),
+             "merge": functools.partial(merge, rows=0), "merge_compacted": functools.partial(merge, rows=1),
+             "update_growing": functools.partial(update, counted=False),
+             "update_growing_counted": functools.partial(update, counted=True), "counter_fetch": counter_fetch}
+    sides = {name: Side(lib) for name, lib in libs.items()}
+    out = {"n": n, "nw": nw, "nf": nf, "umi_length": UL, "capacity_hint": hint, "parent_lib": bool(old),
+           "molecules": sides["this"].nplain, "feature_molecules": sides["this"].nfeat, "codes": sides["this"].ncodes,
+           "outputs_equal": {}, "calls": {}}
+    # every call once in each library (the warm-up as well): the outputs, element for element
+    for name, call in calls.items():
+        got = {}
+        for lname, s in sides.items():
+            arrays = call(s)[1]
+            got[lname] = [a.clone() for a in (arrays() if callable(arrays) else arrays)]
+        if old:
+            same = len(got["this"]) == len(got["parent"]) and all(
+                a.shape == b.shape and bool((a == b).all()) for a, b in zip(got["this"], got["parent"]))
+            out["outputs_equal"][name] = same
+        del got
+    lines = []
+    for r in range(args.rounds):
+        row = {"round": r}
+        order = list(sides.items())[::-1 if r % 2 else 1]  # each library goes first in every other round
+        for name, call in calls.items():
+            row[name] = {}
+            for lname, s in order:
+                call(s)  # untimed: the timed call follows one of its own kind, not the other library's or another call
+                row[name][lname + "_ms"] = round(call(s)[0], 3)
+        lines.append(row)
+    for s in sides.values():
+        s.close()
+    for name in calls:
+        res = out["calls"][name] = {}
+        for key in lines[0][name]:
+            v = [row[name][key] for row in lines]
+            res[key] = {"median": round(float(np.median(v)), 3), "min": min(v), "max": max(v)}
+        if old:
+            res["vs_parent"] = _vs_parent(res["this_ms"], res["parent_ms"])
+    apart = {name: res["vs_parent"] for name, res in out["calls"].items() if old and not res["vs_parent"]["agree"]}
+    slower = ["%s: %s" % (name, v) for name, v in apart.items() if v["median_difference_ms"] > 0]
+    out["faster_than_parent"] = sorted(name for name, v in apart.items() if v["median_difference_ms"] < 0)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "ab_molecules_calls_%s.jsonl" % args.tag), "w") as f:
+        for row in lines:
+            f.write(json.dumps(row, sort_keys=True) + "\n")
+        f.write(json.dumps(out, sort_keys=True) + "\n")
+    unequal = [name for name, same in out["outputs_equal"].items() if not same]
+    assert not unequal, "outputs differ from --parent-lib: " + ", ".join(unequal)
+    assert not slower, "a call is slower than --parent-lib beyond that library's own spread: " + "; ".join(slower)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tag", default="run")
@@ -867,18 +1059,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--n-collapse-host", type=int, default=200_000, help="molecules given to the dict collapse")
     ap.add_argument("--parent-lib", default="",
-                    help="collapse, merge and matrix steps: an earlier libsctools_hip.so to time beside this one")
+                    help="collapse, merge, matrix and calls steps: an earlier libsctools_hip.so to time beside this one")
     ap.add_argument("--only", nargs="+", choices=sorted(STEPS), help="launch only these steps")
     args = ap.parse_args()
     if args.step:
-        if args.step == "molecules":
-            res = molecules_step(args)
-        elif args.step == "collapse":
-            res = collapse_step(args)
-        elif args.step == "merge":
-            res = merge_step(args)
-        elif args.step == "matrix":
-            res = matrix_step(args)
+        whole = {"molecules": molecules_step, "collapse": collapse_step, "merge": merge_step, "matrix": matrix_step,
+                 "calls": calls_step}
+        if args.step in whole:
+            res = whole[args.step](args)
         else:
             res = tally_step(args) if args.step == "tally" else counter_step(args.step[-1], args)
         print("RESULT " + json.dumps(res))
@@ -914,6 +1102,11 @@ def main():
                            "update_ms": {which: {k: [v[c]["median"] for c in ("plain_this_ms", "plain_features_ms",
                                                                                "counted_this_ms", "counted_features_ms")]
                                                  for k, v in modes.items()} for which, modes in res["updates"].items()}}
+        elif "outputs_equal" in res:
+            short[step] = {"n": res["n"], "outputs_equal": all(res["outputs_equal"].values()),
+                           "faster_than_parent": res["faster_than_parent"],
+                           "ms": {k: [t["median"] for t in (v["this_ms"], v.get("parent_ms")) if t]
+                                  for k, v in res["calls"].items()}}
         elif "reads_per_molecule" in res:
             short[step] = {"n": res["n"], "molecules": res["molecules"], "reads_per_molecule": res["reads_per_molecule"],
                            "ms": {which: {k: [v["molecules_ms"]["median"], v["counter_plus_tally_ms"]["median"]]
