@@ -68,7 +68,9 @@ int sct_set_device(int device);        /* select the device for later calls (hip
 #define SCT_TUNE_MERGE_ROWS 19          /* molecule merge on one device: 0 the kernel reads the source's table in
                                            place (default), 1 the source's rows are compacted and copied first, as
                                            they always are between two devices */
-#define SCT_TUNE_NKEYS 20
+#define SCT_TUNE_TILE_CHAIN 20          /* SPECTRAL int8 tile, densest column <= 125 codes: 1 stage 2 as one MFMA
+                                           chain per tile (default), 0 the shift form (read at plan creation) */
+#define SCT_TUNE_NKEYS 21
 int sct_tune_set(int key, int64_t value);
 int sct_tune_get(int key, int64_t* value);  /* -1 when unset */
 

@@ -146,6 +146,7 @@ struct State {
   int elem_bytes = 1;            // seed -> tile intermediate: int8 / int16 / int32
   uint16_t* d_order = nullptr;   // [2^17]: at [L, 2L) the offsets [0, L) sorted by digit weight
   int tile_wgs = 2;              // resident register-tile workgroups per CU
+  bool tile_chain = false;       // int8 seeds and max_m <= 125: stage 2 as one MFMA chain per tile
   void* d_buf = nullptr;         // chunk slices x 2^14 seed values
   size_t buf_bytes = 0;
   int64_t chunk = 0;             // slices per pass

@@ -485,7 +485,16 @@ typedef short v2s_t __attribute__((ext_vector_type(2)));
 // the slice's + [R' != 0].  Each wave of the grid takes a contiguous run
 // of slice positions; position u is slice order[u] (a whole aligned chunk sorted by digit
 // weight, so the run's weight changes rarely and F^2 is binned in registers) or u.
+//   Chain (plans whose densest column holds <= kChainMaxM codes): the per-plane stage 2 without
+//     the shift.  |v| <= 64 m <= 8000, so y = v + 128 is in [-7872, 8128], h in [-31, 31] and 4 h
+//     fits a byte: H v = (64 H) (4 h) + H (l' - 128), the high K-steps on A = 64 H (bytes 0x40 /
+//     0xC0) against B = 4 h = (Bh << 2) & 0xFCFCFCFC (the mask drops the two bits the dword shift
+//     carries into each byte from its neighbour), all K-steps one MFMA chain into one accumulator
+//     with no vector instruction between them.  (m = 126: y reaches 8192, 4 h = 128.)  The
+//     plane sums (|h| up to 127) keep the shift form.
 typedef int v16i_t __attribute__((ext_vector_type(16)));
+constexpr unsigned kChainMaxM = 125;
+template <bool Chain>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void tile_reg_kernel(
     const int8_t* __restrict__ buf, const uint16_t* __restrict__ order, int z0, int nslices,
     unsigned long long* __restrict__ counts, unsigned long long add_n, const unsigned long long* __restrict__ sumsq) {
@@ -513,13 +522,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
     H[0][0][d] = H[0][1][d] = H[1][0][d] = (int)v;
     H[1][1][d] = (int)(v ^ 0xFEFEFEFEu);  // bytes 0x01 <-> 0xFF
   }
+  // 64 H (Chain): bytes 0x01 -> 0x40, 0xFF -> 0xC0; the block of t = ks = 1 negated likewise
+  v4i_t H64[2][2];
+  if constexpr (Chain) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const uint32_t v = ((uint32_t)H[0][0][d] << 6) & 0xC0C0C0C0u;
+      H64[0][0][d] = H64[0][1][d] = H64[1][0][d] = (int)v;
+      H64[1][1][d] = (int)(v ^ 0x80808080u);
+    }
+  }
   const int wt_thread = digit_weight((uint32_t)lane);
   const int lane_off = 16 * (lane >> 5) + 32 * ((lane >> 3) & 1) + 64 * (lane & 3) + 256 * ((lane >> 4) & 1) +
                        512 * ((lane >> 2) & 1);
   const int gw = blockIdx.x * 4 + wave, GW = gridDim.x * 4;
   const int ub = (int)((int64_t)nslices * gw / GW), ue = (int)((int64_t)nslices * (gw + 1) / GW);
   // the squares of the two interleaved M-tiles go to separate sums (two dependency chains per
-  // weight instead of one), added at the flush
+  // weight instead of one), added at the flush.  Chain: both go to accB -- accB2's 8 VGPRs are
+  // what the two 64 H blocks take, and the kernel stays at 168 without scratch
   unsigned long long accA[4] = {0, 0, 0, 0}, accB[4] = {0, 0, 0, 0}, accB2[4] = {0, 0, 0, 0};
   int cur_w = -1;
   auto flush = [&]() {
@@ -541,8 +561,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
       dst[k] = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(p + 1024 * k));
   };
   // stage 2 of N-tile nt from its byte splits (Bl / Bh [K-step]), both M-tiles' chains
-  // interleaved, then their squares (M-tile 0 into acc, 1 into acc2)
-  auto stage2 = [&](const v4i_t* Bl, const v4i_t* Bh, auto nt_c, unsigned long long* acc,
+  // interleaved, then their squares (M-tile 0 into acc, 1 into acc2); chain_c: the high bytes
+  // as 64 H against 4 h instead of the shift (the caller's |v| <= 64 kChainMaxM)
+  auto stage2 = [&](const v4i_t* Bl, const v4i_t* Bh, auto nt_c, auto chain_c, unsigned long long* acc,
                     unsigned long long* acc2) {
     constexpr int nt = decltype(nt_c)::value;
     v16i_t c[2];
@@ -550,14 +571,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int i = 0; i < 16; ++i) c[t][i] = 0;
+    if constexpr (decltype(chain_c)::value) {
+      v4i_t Bh4[2];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+      for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int t = 0; t < 2; ++t) c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(H[t][ks], Bh[ks], c[t], 0, 0, 0);
+        for (int d = 0; d < 4; ++d) Bh4[ks][d] = (int)(((uint32_t)Bh[ks][d] << 2) & 0xFCFCFCFCu);
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+      for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) c[t][i] <<= 8;
+        for (int t = 0; t < 2; ++t)
+          c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(H64[t][ks], Bh4[ks], c[t], 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(H[t][ks], Bh[ks], c[t], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) c[t][i] <<= 8;
+    }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -645,7 +679,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
                                                               __builtin_bit_cast(v2s_t, pr[k]));
           split16(pr, Bl[mt], Bh[mt]);
         }
-        stage2(Bl, Bh, nt_c, accB, accB2);
+        stage2(Bl, Bh, nt_c, std::bool_constant<Chain>(), accB, Chain ? accB : accB2);
         __builtin_amdgcn_sched_barrier(0);
       };
       ntile(std::integral_constant<int, 0>());
@@ -654,10 +688,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
     v4i_t Bl[2], Bh[2];
     split16(csp[0][0], Bl[0], Bh[0]);
     split16(csp[0][1], Bl[1], Bh[1]);
-    stage2(Bl, Bh, std::integral_constant<int, 0>(), accA, accA);
+    stage2(Bl, Bh, std::integral_constant<int, 0>(), std::false_type(), accA, accA);
     split16(csp[1][0], Bl[0], Bh[0]);
     split16(csp[1][1], Bl[1], Bh[1]);
-    stage2(Bl, Bh, std::integral_constant<int, 1>(), accA, accA);
+    stage2(Bl, Bh, std::integral_constant<int, 1>(), std::false_type(), accA, accA);
   }
   if (cur_w >= 0) flush();
   __syncthreads();
@@ -792,8 +826,8 @@ int launch_tile(State& st, int z0, int z1, unsigned long long* counts, hipStream
     const int ns = z1 - z0;
     const uint16_t* order = ((ns & (ns - 1)) == 0 && z0 % ns == 0) ? st.d_order + std::min(ns, kMaxOrder) : nullptr;
     const dim3 rgrid((unsigned)std::max(1, std::min(st.grid * st.tile_wgs, (z1 - z0 + 3) / 4)));
-    hipLaunchKernelGGL(tile_reg_kernel, rgrid, dim3(256), 0, s, buf, order, z0, z1 - z0, counts, add_n,
-                       st.sumsq_ptr());
+    hipLaunchKernelGGL(st.tile_chain ? tile_reg_kernel<true> : tile_reg_kernel<false>, rgrid, dim3(256), 0, s, buf,
+                       order, z0, z1 - z0, counts, add_n, st.sumsq_ptr());
   } else {
     const dim3 grid((unsigned)std::min(st.grid * 2, z1 - z0));
     hipLaunchKernelGGL(tile_kernel<T>, grid, dim3(256), 0, s, buf, z0, z1 - z0, counts, add_n,
@@ -1044,6 +1078,14 @@ int alloc_buf(State& st, int64_t* chunk, int64_t min_chunk, size_t bytes_per_sli
   }
 }
 
+// resident register-tile workgroups per CU (VGPR bound: 3)
+template <typename K>
+static int tile_wgs_per_cu(K kernel) {
+  int v = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kernel, 256, 0) != hipSuccess || v <= 0) v = 2;
+  return v;
+}
+
 int create(State& st, const uint64_t* d_codes, int64_t n, int64_t chunk, int cus, unsigned max14, unsigned max16) {
   st.n = n;
   st.chunk = std::max<int64_t>(kWalk, std::min<int64_t>(chunk, kSlices));
@@ -1064,12 +1106,11 @@ int create(State& st, const uint64_t* d_codes, int64_t n, int64_t chunk, int cus
   // the intermediate holds one chunk: at most 4 GiB (all 2^18 slices at int8: one seed and one
   // tile launch per count; int16 / int32 seeds take 2 / 4 passes)
   st.chunk = std::min<int64_t>(st.chunk, (int64_t(4) << 30) / ((int64_t)kLo * st.elem_bytes));
-  static const int per_cu = [] {  // resident register-tile workgroups per CU (VGPR bound: 3)
-    int v = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, tile_reg_kernel, 256, 0) != hipSuccess || v <= 0) v = 2;
-    return v;
-  }();
-  st.tile_wgs = per_cu;
+  // the unbroken stage-2 chain needs 4 h in a byte: |v| <= 64 * 125 (tile_reg_kernel);
+  // SCT_TUNE_TILE_CHAIN = 0 keeps the shift form for every plan
+  st.tile_chain = st.elem_bytes == 1 && maxm <= kChainMaxM && sct::tune(SCT_TUNE_TILE_CHAIN, 1) != 0;
+  static const int per_cu[2] = {tile_wgs_per_cu(tile_reg_kernel<false>), tile_wgs_per_cu(tile_reg_kernel<true>)};
+  st.tile_wgs = per_cu[st.tile_chain];
   if (int rc = make_order_table(st); rc != SCT_OK) return rc;
   st.max_groups = sct::ceil_div(n, 32) + kLo;
   if (int rc = get_slot(st, W_GOFS, (size_t)(kLo + 1) * 4, &st.d_gofs); rc != SCT_OK) return rc;
