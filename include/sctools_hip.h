@@ -30,6 +30,7 @@ extern "C" {
 #define SCT_E_HIP (-2)       /* HIP runtime failure / no device (RuntimeError) */
 #define SCT_E_NOMEM (-3)     /* device allocation failed (MemoryError)         */
 #define SCT_E_RANGE (-4)     /* value outside what the kernel supports         */
+#define SCT_E_INTERNAL (-5)  /* a bound the library's own code guarantees was passed (RuntimeError) */
 
 /* ---------------------------------------------------------------- library */
 int sct_version(void);                 /* ABI version, currently 1 */
@@ -70,7 +71,9 @@ int sct_set_device(int device);        /* select the device for later calls (hip
                                            they always are between two devices */
 #define SCT_TUNE_TILE_CHAIN 20          /* SPECTRAL int8 tile, densest column <= 125 codes: 1 stage 2 as one MFMA
                                            chain per tile (default), 0 the shift form (read at plan creation) */
-#define SCT_TUNE_NKEYS 21
+#define SCT_TUNE_DIRECTIONAL_FORM 21    /* directional clusters: 1 the sweeps run over the worklist of molecules
+                                           with an in-edge (default), 0 every sweep runs over the whole table */
+#define SCT_TUNE_NKEYS 22
 int sct_tune_set(int key, int64_t value);
 int sct_tune_get(int key, int64_t* value);  /* -1 when unset */
 
@@ -636,6 +639,56 @@ int sct_molecules_fetch_counted(sct_molecules* mol, int32_t* d_index, uint64_t* 
 int sct_molecules_fetch_counted_host(sct_molecules* mol, int32_t* index, uint64_t* umi, uint64_t* mreads,
                                      uint64_t* parent, int64_t room);
 
+/* Directional clusters: the transitive collapse, UMI-tools' *directional* method, on a counted
+ * counter.  The one-step rule above counts images and has no support threshold; here a molecule is
+ * merged into whatever reaches it through better-supported UMIs, and the clusters are the molecules.
+ * The contract is restated in plain Python by tests/umi_directional_reference.py.
+ * Edge: for u, v stored under the same index (and the same feature, on a feature counter: neighbours
+ * change UMI bits only) there is an edge u -> v when v is in N1(u) and
+ * mreads[u] >= 2 * mreads[v] - 1, evaluated without overflow for any counts >= 1 as
+ * mreads[u] >= mreads[v] && mreads[u] - mreads[v] >= mreads[v] - 1.  Two UMIs are joined in both
+ * directions exactly when both have 1 read; UMIs with equal reads >= 2 are not joined.
+ * Root: order the molecules by (mreads, code), the parent rule's order.  root(v) is the largest
+ * molecule, in that order, among v and everything that reaches v along edges; v is a root when
+ * root(v) == v, and a cluster is a root with everything whose root it is.
+ * This is UMI-tools' sequential procedure -- molecules taken in descending (mreads, code) order, each
+ * one not yet claimed becomes a root and claims every unclaimed molecule reachable from it: the
+ * largest ancestor w of v has no larger ancestor of its own (that would be an ancestor of v), so
+ * nothing claims w before its turn, and v is still unclaimed then because only a larger ancestor
+ * could have claimed it.  UMI-tools breaks ties in mreads by insertion order, this contract by code:
+ * only the name of the root of mutually joined 1-read UMIs can differ, never the number of clusters,
+ * which is the number of strongly connected components with no edge coming in from outside.
+ * The entry points below take `method` after the handle: SCT_COLLAPSE_ONE_STEP gives exactly what
+ * the entry point without _by gives (which is that call), any value but the two is SCT_E_INVALID,
+ * and with SCT_COLLAPSE_DIRECTIONAL
+ *   collapse_by        collapsed[i] is the number of roots under barcode i, n_corrected the number of
+ *                      molecules with root != self.  ThreeBit L = 2 under one barcode, AA x 1, AC x 2,
+ *                      GC x 5: AC -> AA (2 >= 1) and GC -> AC (5 >= 3), so collapsed = 1 and
+ *                      n_corrected = 2;
+ *   fetch_counted_by,
+ *   fetch_features_by  the parent column carries the root's UMI;
+ *   matrix_by          collapsed[e] is the number of roots in entry e (a root lies in its cluster's entry).
+ * Every other argument, check and result is the sibling's.  The pass reads the table and mreads only:
+ * it is repeatable, later updates are unaffected, and it is valid after merge.  On a counter that is
+ * not counted it is SCT_E_INVALID and changes nothing.  It orders itself after the counter's earlier
+ * work on other streams and checks the overflow word first, as collapse does.  The labels settle in
+ * sweeps, one launch each, and the device forms wait for `stream` between them (matrix already waits
+ * once); there is no device-side barrier.  More than nmolecules + 2 sweeps is SCT_E_INTERNAL, which
+ * correct code never returns.  Scratch: 4 B per slot and 8 B per molecule from the library's pool.
+ * directional_info: of the counter's last directional pass, the sweeps, the molecules with an
+ * in-edge (the first sweep's worklist) and the molecules all sweeps looked at together (each
+ * nullable; a bench aid). */
+#define SCT_COLLAPSE_ONE_STEP 0
+#define SCT_COLLAPSE_DIRECTIONAL 1
+int sct_molecules_collapse_by(sct_molecules* mol, int method, uint64_t* d_collapsed, uint64_t* d_ncorrected,
+                              void* stream);
+int sct_molecules_collapse_by_host(sct_molecules* mol, int method, uint64_t* collapsed, uint64_t* ncorrected);
+int sct_molecules_fetch_counted_by(sct_molecules* mol, int method, int32_t* d_index, uint64_t* d_umi,
+                                   uint64_t* d_mreads, uint64_t* d_parent, int64_t room, void* stream);
+int sct_molecules_fetch_counted_by_host(sct_molecules* mol, int method, int32_t* index, uint64_t* umi,
+                                        uint64_t* mreads, uint64_t* parent, int64_t room);
+int sct_molecules_directional_info(sct_molecules* mol, int64_t* sweeps, int64_t* worklist, int64_t* swept);
+
 /* Merging molecule counters: one table from the counters of several files, lanes or devices.  The
  * two reads of a molecule can land in different counters, so molecules[] of two counters cannot be
  * added up: the union of the key sets is taken on the device.
@@ -729,6 +782,18 @@ int sct_molecules_matrix(sct_molecules* mol, int64_t* d_indptr, int32_t* d_featu
                          uint64_t* d_reads, uint64_t* d_collapsed, int64_t room, int64_t* nnz, void* stream);
 int sct_molecules_matrix_host(sct_molecules* mol, int64_t* indptr, int32_t* feature, uint64_t* molecules,
                               uint64_t* reads, uint64_t* collapsed, int64_t room, int64_t* nnz);
+/* the same with a collapse method ("directional clusters" above) */
+int sct_molecules_fetch_features_by(sct_molecules* mol, int method, int32_t* d_index, int32_t* d_feature,
+                                    uint64_t* d_umi, uint64_t* d_mreads, uint64_t* d_parent, int64_t room,
+                                    void* stream);
+int sct_molecules_fetch_features_by_host(sct_molecules* mol, int method, int32_t* index, int32_t* feature,
+                                         uint64_t* umi, uint64_t* mreads, uint64_t* parent, int64_t room);
+int sct_molecules_matrix_by(sct_molecules* mol, int method, int64_t* d_indptr, int32_t* d_feature,
+                            uint64_t* d_molecules, uint64_t* d_reads, uint64_t* d_collapsed, int64_t room,
+                            int64_t* nnz, void* stream);
+int sct_molecules_matrix_by_host(sct_molecules* mol, int method, int64_t* indptr, int32_t* feature,
+                                 uint64_t* molecules, uint64_t* reads, uint64_t* collapsed, int64_t room,
+                                 int64_t* nnz);
 
 /* ---------------------------------------------------------------- FASTQ barcode extraction
  * Replaces the per-record path reader.Reader.__iter__ (src/sctools/reader.py:56-85) ->

@@ -25,6 +25,7 @@ SCT_E_INVALID = -1
 SCT_E_HIP = -2
 SCT_E_NOMEM = -3
 SCT_E_RANGE = -4
+SCT_E_INTERNAL = -5
 
 # all-pairs count schemes (include/sctools_hip.h)
 SCHEME_AUTO = -1
@@ -38,7 +39,8 @@ TUNE_KEYS = {"spectral_chunk": 1, "spectral_min_n": 2, "allpairs_grab": 3, "allp
              "scalar_idle_ms": 9, "spectral_columns": 10, "plan_cache": 11,
              "encode_grid": 12, "ingest_tiles": 13, "fastq_onepass": 14,
              "ingest_direct": 15, "ingest_spec": 16, "count_preagg": 17, "collapse_form": 18,
-             "merge_rows": 19, "tile_chain": 20}
+             "merge_rows": 19, "tile_chain": 20, "directional_form": 21}
+COLLAPSE_ONE_STEP, COLLAPSE_DIRECTIONAL = 0, 1
 NEAREST_AUTO, NEAREST_OA, NEAREST_CSR, NEAREST_HALVES = 0, 1, 2, 3
 
 _i32, _i64, _dbl = ctypes.c_int, ctypes.c_int64, ctypes.c_double
@@ -174,6 +176,15 @@ SIGNATURES = {
     "sct_molecules_fetch_features_host": [_vp, _vp, _vp, _vp, _vp, _vp, _i64],
     "sct_molecules_matrix": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64), _vp],
     "sct_molecules_matrix_host": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64)],
+    "sct_molecules_collapse_by": [_vp, _i32, _vp, _vp, _vp],
+    "sct_molecules_collapse_by_host": [_vp, _i32, _vp, _vp],
+    "sct_molecules_fetch_counted_by": [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
+    "sct_molecules_fetch_counted_by_host": [_vp, _i32, _vp, _vp, _vp, _vp, _i64],
+    "sct_molecules_fetch_features_by": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "sct_molecules_fetch_features_by_host": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64],
+    "sct_molecules_matrix_by": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64), _vp],
+    "sct_molecules_matrix_by_host": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64)],
+    "sct_molecules_directional_info": [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
 }
 _RESTYPES = {"sct_last_error": ctypes.c_char_p}
 

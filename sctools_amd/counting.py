@@ -132,6 +132,18 @@ def _exact(values, dtype, what):
     return np.ascontiguousarray(src.astype(dtype)).reshape(-1)
 
 
+COLLAPSE_METHODS = {"one_step": _lib.COLLAPSE_ONE_STEP, "directional": _lib.COLLAPSE_DIRECTIONAL}
+
+
+def collapse_method(name):
+    """The SCT_COLLAPSE_* number of a collapse method's name: 'one_step' (every UMI to its best
+    neighbour, once) or 'directional' (UMI-tools' directional clusters).  Anything else raises
+    ValueError."""
+    if not isinstance(name, str) or name not in COLLAPSE_METHODS:
+        raise ValueError("method must be 'one_step' or 'directional', not %r" % (name,))
+    return COLLAPSE_METHODS[name]
+
+
 class MoleculeCounter:
     """Molecules per whitelist barcode on the device (sct_molecules_*): the distinct
     (corrected barcode index, UMI code) pairs, which removes PCR duplicates.
@@ -269,13 +281,15 @@ class MoleculeCounter:
         _lib.check(self._lib.sct_molecules_counts_host(self._h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)))
         return (reads.view(np.int64), molecules.view(np.int64), int(tally[0]), int(tally[1]), int(tally[2]))
 
-    def pairs(self, room=None, reads=False, parents=False, features=False):
+    def pairs(self, room=None, reads=False, parents=False, features=False, method='one_step'):
         """(index int32, umi uint64) of the distinct molecules, ascending by index, then by UMI code.
         ``room`` (default: the number of molecules) sizes the output; too little raises ValueError.
         ``reads=True`` (a counter with ``read_counts``) adds each molecule's reads (int64), and
         ``parents=True`` with it the UMI each molecule collapses into (its own if it stays).
         ``features=True`` (a feature counter): (index, feature int32, umi[, reads][, parents]),
-        ascending by index, then feature, then UMI code."""
+        ascending by index, then feature, then UMI code.  ``method='directional'``: the parents column
+        carries each molecule's root (``collapse``)."""
+        by = collapse_method(method)
         if parents and not reads:
             raise ValueError("parents=True needs reads=True")
         if reads:
@@ -290,10 +304,11 @@ class MoleculeCounter:
         parent = np.empty(n, np.uint64) if parents else None
         p = _lib._ptr
         if features:
-            _lib.check(self._lib.sct_molecules_fetch_features_host(self._h, p(index), p(feature), p(umi), p(mreads),
-                                                                   p(parent), n))
+            _lib.check(self._lib.sct_molecules_fetch_features_by_host(self._h, by, p(index), p(feature), p(umi),
+                                                                      p(mreads), p(parent), n))
         elif reads:
-            _lib.check(self._lib.sct_molecules_fetch_counted_host(self._h, p(index), p(umi), p(mreads), p(parent), n))
+            _lib.check(self._lib.sct_molecules_fetch_counted_by_host(self._h, by, p(index), p(umi), p(mreads),
+                                                                     p(parent), n))
         else:
             _lib.check(self._lib.sct_molecules_fetch_host(self._h, p(index), p(umi), n))
         columns = (index, feature, umi, mreads.view(np.int64) if reads else None, parent)
@@ -303,21 +318,25 @@ class MoleculeCounter:
         """The same rows into device arrays with room for ``room`` rows (sct_molecules_fetch)."""
         _lib.check(self._lib.sct_molecules_fetch(self._h, _vp(index_ptr), _vp(umi_ptr), int(room), _vp(stream)))
 
-    def fetch_counted_device(self, index_ptr, umi_ptr, reads_ptr, parent_ptr, room, stream=0):
+    def fetch_counted_device(self, index_ptr, umi_ptr, reads_ptr, parent_ptr, room, stream=0, method='one_step'):
         """fetch_device's rows with uint64 reads and, unless ``parent_ptr`` is 0 / None, uint64 parent
-        UMIs beside them (sct_molecules_fetch_counted)."""
+        UMIs beside them (sct_molecules_fetch_counted_by); ``method='directional'`` writes the roots
+        there and may wait for ``stream``."""
+        by = collapse_method(method)
         self._need_read_counts("fetch_counted_device")
-        _lib.check(self._lib.sct_molecules_fetch_counted(self._h, _vp(index_ptr), _vp(umi_ptr), _vp(reads_ptr),
-                                                         _vp(parent_ptr or None), int(room), _vp(stream)))
+        _lib.check(self._lib.sct_molecules_fetch_counted_by(self._h, by, _vp(index_ptr), _vp(umi_ptr), _vp(reads_ptr),
+                                                            _vp(parent_ptr or None), int(room), _vp(stream)))
 
-    def matrix(self, reads=False, collapsed=False, room=None):
+    def matrix(self, reads=False, collapsed=False, room=None, method='one_step'):
         """The barcode x feature count matrix of a feature counter as CSR: (indptr int64
         [whitelist_size + 1], feature int32 [nnz], molecules int64 [nnz]) and, if asked (a counter
         with ``read_counts``), reads and collapsed (int64 [nnz]) after them -- the entry's reads and
         its molecules after the UMI collapse.  Features ascend within a row, and
         ``scipy.sparse.csr_matrix((molecules, feature, indptr), shape=(whitelist_size, features))``
         takes the arrays as they are.  ``room`` (default: the number of molecules, which always
-        suffices) sizes the output; fewer than nnz raises ValueError, which names nnz."""
+        suffices) sizes the output; fewer than nnz raises ValueError, which names nnz.
+        ``method='directional'``: collapsed is the entry's directional clusters (``collapse``)."""
+        by = collapse_method(method)
         self._need_features("matrix")
         if reads:
             self._need_read_counts("matrix(reads=True)")
@@ -330,41 +349,49 @@ class MoleculeCounter:
         feature = np.empty(max(n, 1), np.int32)
         values = [np.empty(max(n, 1), np.uint64) if want else None for want in (True, reads, collapsed)]
         nnz = _i64(0)
-        _lib.check(self._lib.sct_molecules_matrix_host(self._h, _lib._ptr(indptr), _lib._ptr(feature),
-                                                       _lib._ptr(values[0]), _lib._ptr(values[1]),
-                                                       _lib._ptr(values[2]), n, ctypes.byref(nnz)))
+        _lib.check(self._lib.sct_molecules_matrix_by_host(self._h, by, _lib._ptr(indptr), _lib._ptr(feature),
+                                                          _lib._ptr(values[0]), _lib._ptr(values[1]),
+                                                          _lib._ptr(values[2]), n, ctypes.byref(nnz)))
         k = nnz.value
         return (indptr, feature[:k].copy()) + tuple(v[:k].view(np.int64).copy() for v in values if v is not None)
 
-    def matrix_device(self, indptr_ptr, feature_ptr, molecules_ptr, reads_ptr, collapsed_ptr, room, stream=0):
-        """matrix() into device arrays with room for ``room`` entries (sct_molecules_matrix): int64
+    def matrix_device(self, indptr_ptr, feature_ptr, molecules_ptr, reads_ptr, collapsed_ptr, room, stream=0,
+                      method='one_step'):
+        """matrix() into device arrays with room for ``room`` entries (sct_molecules_matrix_by): int64
         [whitelist_size + 1], int32 [room] and up to three uint64 [room], each of the three 0 / None
         when not wanted.  Returns nnz; waits for ``stream`` once to learn it."""
+        by = collapse_method(method)
         self._need_features("matrix_device")
         if reads_ptr or collapsed_ptr:
             self._need_read_counts("matrix_device with reads or collapsed")
         nnz = _i64(0)
-        _lib.check(self._lib.sct_molecules_matrix(self._h, _vp(indptr_ptr), _vp(feature_ptr or None),
-                                                  _vp(molecules_ptr or None), _vp(reads_ptr or None),
-                                                  _vp(collapsed_ptr or None), int(room), ctypes.byref(nnz),
-                                                  _vp(stream)))
+        _lib.check(self._lib.sct_molecules_matrix_by(self._h, by, _vp(indptr_ptr), _vp(feature_ptr or None),
+                                                     _vp(molecules_ptr or None), _vp(reads_ptr or None),
+                                                     _vp(collapsed_ptr or None), int(room), ctypes.byref(nnz),
+                                                     _vp(stream)))
         return nnz.value
 
-    def collapse(self):
+    def collapse(self, method='one_step'):
         """(collapsed np.int64[whitelist_size], n_corrected int): the molecules per barcode after every
-        UMI went to the best-supported UMI one base away (ties to the larger code), and how many moved."""
+        UMI went to the best-supported UMI one base away (ties to the larger code), and how many moved.
+        ``method='directional'`` is UMI-tools' directional method instead: a UMI with a reads joins a
+        UMI one base away with b reads when b >= 2 * a - 1, transitively; collapsed counts the
+        clusters per barcode and n_corrected the molecules that are not their cluster's root
+        (include/sctools_hip.h, "directional clusters")."""
+        by = collapse_method(method)
         self._need_read_counts("collapse")
         collapsed = np.empty(self.size, np.uint64)
         ncorr = np.zeros(1, np.uint64)
-        _lib.check(self._lib.sct_molecules_collapse_host(self._h, _lib._ptr(collapsed), _lib._ptr(ncorr)))
+        _lib.check(self._lib.sct_molecules_collapse_by_host(self._h, by, _lib._ptr(collapsed), _lib._ptr(ncorr)))
         return collapsed.view(np.int64), int(ncorr[0])
 
-    def collapse_device(self, collapsed_ptr, ncorrected_ptr=None, stream=0):
+    def collapse_device(self, collapsed_ptr, ncorrected_ptr=None, stream=0, method='one_step'):
         """collapse() into device memory: uint64[whitelist_size] and, unless 0 / None, one uint64
-        (sct_molecules_collapse), on ``stream``."""
+        (sct_molecules_collapse_by), on ``stream``; ``method='directional'`` may wait for it."""
+        by = collapse_method(method)
         self._need_read_counts("collapse_device")
-        _lib.check(self._lib.sct_molecules_collapse(self._h, _vp(collapsed_ptr), _vp(ncorrected_ptr or None),
-                                                    _vp(stream)))
+        _lib.check(self._lib.sct_molecules_collapse_by(self._h, by, _vp(collapsed_ptr), _vp(ncorrected_ptr or None),
+                                                       _vp(stream)))
 
     def merge_device(self, other, stream=0):
         """``merge`` enqueued on ``stream`` (of this counter's device; sct_molecules_merge): it waits
@@ -402,12 +429,13 @@ class MoleculeCounter:
     def __len__(self):
         return self.info()["nmolecules"]
 
-    def saturation(self, collapsed=False):
+    def saturation(self, collapsed=False, method='one_step'):
         """Sequencing saturation 1 - molecules / reads over the counted reads (nan when none);
-        ``collapsed=True`` takes the molecules of ``collapse()``."""
+        ``collapsed=True`` takes the molecules of ``collapse(method)``."""
+        collapse_method(method)
         reads, molecules = self.counts()[:2]
         if collapsed:
-            molecules = self.collapse()[0]
+            molecules = self.collapse(method=method)[0]
         total = int(reads.sum())
         return 1.0 - int(molecules.sum()) / total if total else float("nan")
 

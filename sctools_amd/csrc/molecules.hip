@@ -43,7 +43,11 @@
 // molecules[index] idiom again and counts every distinct parent once however many children it has.
 // Every shared write of the pass is an atomic and nothing it reads changes, so there is no
 // inter-workgroup protocol.  fetch_counted sorts (key, slot) pairs and recomputes each row's parent
-// with the same device function.
+// with the same device function.  The directional clusters (include/sctools_hip.h, "directional
+// clusters") are the transitive form of that pass: a label per slot in scratch,
+// the same probes in a discovery pass, then one launch per sweep over the molecules whose label may
+// still grow until a sweep moves nothing; the host reads two words between sweeps, and no kernel
+// waits for another.
 //
 // Merging (include/sctools_hip.h, "merging molecule counters"): the rows of another counter -- its
 // table in place when both live on one device, its occupied rows compacted and copied into pool
@@ -73,6 +77,7 @@
 #include "molecules_feature_key.h"
 #include "molecules_key.h"
 #include "molecules_merge_plan.h"
+#include "umi_directional.h"
 #include "umi_neighbours.h"
 
 namespace {
@@ -349,6 +354,121 @@ __global__ void __launch_bounds__(WG) molecules_collapse_wave_kernel(Set t, int6
   if (lane == 0 && moved) atomicAdd(ncorrected, (u64)moved);
 }
 
+// ---- directional clusters (include/sctools_hip.h, "directional clusters"): the low 31 bits of
+// lab[slot] are the slot of the best ancestor of the slot's molecule known so far (capacity <= 2^31),
+// meaningful where keys is occupied.  A label names a stored molecule, so it is compared by
+// (cnt[label], keys[label]).  The top bit says that the label may still grow: the molecule has an
+// in-neighbour whose own word has the bit.  A word without it is final.
+
+constexpr uint32_t kLabelOpen = 1u << 31, kLabelSlot = kLabelOpen - 1;
+
+struct Label {
+  u64 reads, code;
+  uint32_t slot;
+};
+__device__ __forceinline__ Label label_at(const Set& t, uint32_t slot) { return Label{t.cnt[slot], t.keys[slot], slot}; }
+__device__ __forceinline__ Label label_max(const Label& a, const Label& b) {
+  return sct::umi_label_less(a.reads, a.code, b.reads, b.code) ? b : a;
+}
+// a word is read and written while other waves do the same: whole words, in any order
+__device__ __forceinline__ uint32_t label_load(const uint32_t* lab, u64 slot) {
+  return __atomic_load_n(&lab[slot], __ATOMIC_RELAXED);
+}
+
+// A wave per 64 items, the shape of molecules_collapse_wave_kernel: an item is a table slot (n = the
+// capacity, a multiple of 64) or, LISTED, an entry of list[n].  The occupied items are taken one
+// after the other; lane j probes neighbour j (and j + 64) of the molecule v, applies the edge test
+// neighbour -> v to what it finds, and the wave reduces the lanes' candidates by the labels' order.
+//   DISCOVER: the candidates are the in-neighbours themselves, lab[v] becomes the best of them and v,
+//     open when v has any in-edge.  A v without an in-edge is a root and final.
+//   otherwise, a sweep: the candidates are lab[v], lab[lab[v]] and lab[a] of every in-neighbour a --
+//     ancestors of v all -- and a label that moves sets *changed.  v stays open while an in-neighbour's
+//     word is open; when none is, this sweep read their final labels and lab[v] is final too (label
+//     and bit are one word).  Only v's own wave writes lab[v] and a label only ever grows, so
+//     updating in place reaches the fixpoint of the plain iteration; a sweep that changes nothing
+//     read final labels only.
+// The open molecules are appended to worklist[room] (if not NULL), one add on the cursor per wave and
+// 64 items: the next sweep's list.  Molecules that only feed each other (1-read sets) stay open until
+// no label moves.
+template <bool DISCOVER, bool LISTED>
+__global__ void __launch_bounds__(WG) molecules_directional_kernel(Set t, int64_t n, const uint32_t* __restrict__ list,
+                                                                   uint32_t* lab, uint32_t* __restrict__ worklist,
+                                                                   int64_t room, u64* __restrict__ cursor,
+                                                                   u64* __restrict__ changed) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (WG / 64);
+  const int n1 = 3 * (t.umi_bits / t.kind);
+  bool moved = false;  // the same in every lane
+  for (int64_t base = (((int64_t)blockIdx.x * WG + threadIdx.x) >> 6) * 64; base < n; base += nwaves * 64) {  // wave-uniform
+    const int64_t i = base + lane;
+    uint32_t slot = 0;
+    u64 mine = EMPTY;
+    if (i < n) {
+      slot = LISTED ? list[i] : (uint32_t)i;
+      mine = t.keys[slot];
+    }
+    u64 todo = __ballot(mine != EMPTY);
+    u64 still_open = 0;
+    while (todo) {
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const u64 key = __shfl(mine, src);
+      const uint32_t v = __shfl(slot, src);
+      const u64 v_reads = t.cnt[v];
+      const uint32_t word = DISCOVER ? v : label_load(lab, v);
+      const uint32_t was = word & kLabelSlot;
+      // (lab[x] is never below x)
+      Label b = DISCOVER ? Label{v_reads, key, v} : label_at(t, label_load(lab, was) & kLabelSlot);
+      bool open = false;
+      for (int j = lane; j < n1; j += 64) {
+        const u64 nb = sct::umi_neighbour(key, t.kind, j);
+        const u64 s = find(t.keys, t.mask, nb);
+        if (s == NO_SLOT) continue;
+        const u64 r = t.cnt[s];
+        if (!sct::umi_directional_edge(r, v_reads)) continue;
+        const uint32_t theirs = DISCOVER ? kLabelOpen : label_load(lab, s);
+        open |= (theirs & kLabelOpen) != 0;
+        b = label_max(b, DISCOVER ? Label{r, nb, (uint32_t)s} : label_at(t, theirs & kLabelSlot));
+      }
+      for (int o = 32; o > 0; o >>= 1)
+        b = label_max(b, Label{__shfl_xor(b.reads, o), __shfl_xor(b.code, o), __shfl_xor(b.slot, o)});
+      const bool any_open = __ballot(open) != 0;
+      const uint32_t now = b.slot | (any_open ? kLabelOpen : 0);
+      if (lane == 0 && (DISCOVER || now != word)) __atomic_store_n(&lab[v], now, __ATOMIC_RELAXED);
+      still_open |= any_open ? 1ull << src : 0;
+      moved |= b.slot != was;
+    }
+    if (worklist) {
+      const bool listed = (still_open >> lane) & 1;
+      const u64 at = compact_at(listed, cursor);
+      if (listed && (int64_t)at < room) worklist[at] = slot;
+    }
+  }
+  if (!DISCOVER && lane == 0 && moved) atomicOr(changed, 1ull);
+}
+
+// collapsed[index] += the molecules of the barcode that are their own label, one add per (wave,
+// index); the others are summed per wave into *ncorrected.
+__global__ void __launch_bounds__(WG) molecules_directional_count_kernel(Set t, int64_t capacity,
+                                                                         const uint32_t* __restrict__ lab,
+                                                                         u64* __restrict__ collapsed,
+                                                                         u64* __restrict__ ncorrected) {
+  const int64_t stride = (int64_t)gridDim.x * WG;
+  const int64_t iters = (capacity + stride - 1) / stride;  // the same for every lane: the wave stays whole
+  uint32_t moved = 0;
+  for (int64_t it = 0; it < iters; ++it) {
+    const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
+    const u64 key = s < capacity ? t.keys[s] : EMPTY;
+    const bool occ = key != EMPTY;
+    const bool root = occ && (lab[s] & kLabelSlot) == (uint32_t)s;
+    const u64 index = occ ? sct::mol_key_index(key, t.idx_shift) : 0;
+    const Merged m = wave_merge(root, index);
+    if (m.rep) atomicAdd(&collapsed[index], m.count);
+    moved += (uint32_t)__popcll(__ballot(occ && !root));
+  }
+  if ((threadIdx.x & 63) == 0 && moved) atomicAdd(ncorrected, (u64)moved);
+}
+
 // fetch and merge: the occupied slots' keys in any order (the sort fixes the order) and, beside each,
 // nothing, its slot number (uint32: capacity <= 2^31) or its mreads (u64); at most `room` are written
 enum { BESIDE_NONE, BESIDE_SLOT, BESIDE_COUNT };
@@ -374,13 +494,13 @@ __global__ void __launch_bounds__(WG) molecules_compact_kernel(const u64* __rest
 
 // the sorted keys as rows: index, UMI and, if asked, the feature.  SLOTS: `slots` (the keys' slot
 // numbers, sorted with them; else NULL, as mreads and parent are) also gives, each if asked, mreads
-// and the parent's UMI.
+// and the parent's UMI: the one-step parent, or with `lab` (the directional labels) the root.
 template <bool SLOTS>
 __global__ void __launch_bounds__(WG) molecules_emit_kernel(Set t, const u64* __restrict__ keys,
                                                             const uint32_t* __restrict__ slots, int64_t rows,
                                                             int32_t* __restrict__ index, int32_t* __restrict__ feature,
                                                             u64* __restrict__ umi, u64* __restrict__ mreads,
-                                                            u64* __restrict__ parent) {
+                                                            u64* __restrict__ parent, const uint32_t* __restrict__ lab) {
   for (int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WG) {
     const u64 key = keys[r];
     const u64 slot = SLOTS ? slots[r] : 0;  // (loaded with the key, ahead of the stores)
@@ -391,7 +511,7 @@ __global__ void __launch_bounds__(WG) molecules_emit_kernel(Set t, const u64* __
     if (mreads) mreads[r] = t.cnt[slot];
     if (parent) {
       u64 at;
-      parent[r] = sct::mol_key_umi(parent_of(t, key, slot, &at), t.umi_bits);
+      parent[r] = sct::mol_key_umi(lab ? t.keys[lab[slot] & kLabelSlot] : parent_of(t, key, slot, &at), t.umi_bits);
     }
   }
 }
@@ -427,11 +547,13 @@ __global__ void __launch_bounds__(WG) molecules_matrix_heads_kernel(const u64* _
 // entry are adjacent lanes: the lowest of them in this wave (a head, or lane 0) adds the wave's share
 // of each value to the entry, one integer atomic add per (wave, entry) and value -- the run length,
 // the sum of cnt[slot], and the slots whose bit the collapse pass set (the entry's distinct parents:
-// a parent lies in its child's entry).  Each value array is nullable.
+// a parent lies in its child's entry) or, with `lab` in place of the bitmap, the slots that are their
+// own directional label (the entry's roots).  Each value array is nullable.
 __global__ void __launch_bounds__(WG) molecules_matrix_fill_kernel(Set t, const u64* __restrict__ keys,
                                                                    const uint32_t* __restrict__ slots, int64_t rows,
                                                                    const u64* __restrict__ base,
                                                                    const uint32_t* __restrict__ bitmap,
+                                                                   const uint32_t* __restrict__ lab,
                                                                    u64* __restrict__ row_entries,
                                                                    int32_t* __restrict__ feature,
                                                                    u64* __restrict__ molecules, u64* __restrict__ reads,
@@ -468,7 +590,7 @@ __global__ void __launch_bounds__(WG) molecules_matrix_fill_kernel(Set t, const 
     }
     if (collapsed) {
       const uint32_t s = in ? slots[r] : 0;
-      const u64 images = __ballot(in && ((bitmap[s >> 5] >> (s & 31)) & 1u));
+      const u64 images = __ballot(in && (lab ? (lab[s] & kLabelSlot) == s : (bitmap[s >> 5] >> (s & 31)) & 1u));
       const u64 n = (u64)__popcll(images & run);
       if (first && n) atomicAdd(&collapsed[e], n);
     }
@@ -519,6 +641,8 @@ struct sct_molecules : Host {
   int idx_bits = 0;
   Set t{};               // t.words is Host::words
   bool counted = false;  // keeps t.cnt beside t.keys
+  // what the last directional pass took (sct_molecules_directional_info)
+  int64_t dir_sweeps = 0, dir_listed = 0, dir_swept = 0;
 };
 
 namespace {
@@ -668,6 +792,77 @@ hipError_t sort_rows(const sct_molecules* c, SortedRows<SLOTS>& sr) {
 }
 int key_bits(const sct_molecules* c) { return c->idx_bits + c->t.idx_shift; }
 
+int method_check(int method) {
+  SCT_CHECK(method == SCT_COLLAPSE_ONE_STEP || method == SCT_COLLAPSE_DIRECTIONAL,
+            "unknown collapse method %d (SCT_COLLAPSE_ONE_STEP or SCT_COLLAPSE_DIRECTIONAL)", method);
+  return SCT_OK;
+}
+
+// The directional pass's scratch at `b`, in its one layout: three words (the worklist's cursor and the
+// sweep's changed word, read back together, and n_corrected), a word per slot and two worklists of an
+// entry per molecule, a sweep's own and the one it writes.  The size is exact when it is planned
+// (enter_read).
+struct DirectionalScratch {
+  u64* words;
+  uint32_t* lab;
+  uint32_t* worklist[2];
+  enum { D_CURSOR = 0, D_CHANGED, D_NCORRECTED, D_NWORDS };
+  static size_t bytes(const sct_molecules* c) { return 256 + (size_t)c->capacity * 4 + (size_t)c->size_bound * 8; }
+  DirectionalScratch(const sct_molecules* c, uint8_t* b)
+      : words(reinterpret_cast<u64*>(b)), lab(reinterpret_cast<uint32_t*>(b + 256)),
+        worklist{lab + c->capacity, lab + c->capacity + c->size_bound} {}
+};
+
+// lab[] of the table as it stands on `s`, which is waited for between the sweeps: the discovery pass,
+// then sweeps until one changes nothing -- each over the molecules the pass before it left open
+// (SCT_TUNE_DIRECTIONAL_FORM 1, the default; an empty list ends them too) or over the whole table (0).
+// The three words are zeroed here.  After k sweeps a label is at least the best ancestor within k + 1
+// edges (a sweep reads nothing older than the sweep before it left), so `molecules` sweeps settle any
+// table and the cap of molecules + 2 is never met.
+int directional_labels(sct_molecules* c, const DirectionalScratch& ds, hipStream_t s) {
+  const bool listed = sct::tune(SCT_TUNE_DIRECTIONAL_FORM, 1) != 0;
+  const int64_t rows = c->size_bound;
+  u64* h_words = &c->h_words[W_CURSOR];  // cursor and changed (free between two read_words)
+  const auto read_words = [&]() -> int {
+    SCT_HIP(hipMemcpyAsync(h_words, ds.words, 16, hipMemcpyDeviceToHost, s));
+    SCT_HIP(hipStreamSynchronize(s));
+    return SCT_OK;
+  };
+  const auto open_left = [&]() { return std::min<int64_t>((int64_t)h_words[DirectionalScratch::D_CURSOR], rows); };
+  SCT_HIP(hipMemsetAsync(ds.words, 0, DirectionalScratch::D_NWORDS * 8, s));
+  hipLaunchKernelGGL((molecules_directional_kernel<true, false>), dim3(grid_for(c->capacity, WG)), dim3(WG), 0, s, c->t,
+                     c->capacity, nullptr, ds.lab, listed ? ds.worklist[0] : nullptr, rows,
+                     &ds.words[DirectionalScratch::D_CURSOR], nullptr);
+  SCT_LAUNCH_CHECK();
+  int64_t n = c->capacity;
+  if (listed) {
+    SCT_TRY(read_words());
+    n = open_left();
+  }
+  c->dir_listed = listed ? n : rows;
+  c->dir_sweeps = c->dir_swept = 0;
+  for (int from = 0; n > 0; from ^= 1) {
+    if (c->dir_sweeps >= rows + 2)
+      return sct::fail(SCT_E_INTERNAL, "directional clusters: %lld sweeps over %lld molecules did not settle",
+                       (long long)c->dir_sweeps, (long long)rows);
+    SCT_HIP(hipMemsetAsync(ds.words, 0, 16, s));
+    if (listed)
+      hipLaunchKernelGGL((molecules_directional_kernel<false, true>), dim3(grid_for(n, WG)), dim3(WG), 0, s, c->t, n,
+                         ds.worklist[from], ds.lab, ds.worklist[from ^ 1], rows,
+                         &ds.words[DirectionalScratch::D_CURSOR], &ds.words[DirectionalScratch::D_CHANGED]);
+    else
+      hipLaunchKernelGGL((molecules_directional_kernel<false, false>), dim3(grid_for(n, WG)), dim3(WG), 0, s, c->t, n,
+                         nullptr, ds.lab, nullptr, 0, nullptr, &ds.words[DirectionalScratch::D_CHANGED]);
+    SCT_LAUNCH_CHECK();
+    c->dir_sweeps += 1;
+    c->dir_swept += listed ? n : rows;
+    SCT_TRY(read_words());
+    if (h_words[DirectionalScratch::D_CHANGED] == 0) break;
+    if (listed) n = open_left();
+  }
+  return SCT_OK;
+}
+
 // the number of molecules, read on `s` after the counter's earlier work; `room` must hold them
 int rows_for_fetch(sct_molecules* c, int64_t room, hipStream_t s, int64_t* rows) {
   if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
@@ -679,42 +874,51 @@ int rows_for_fetch(sct_molecules* c, int64_t room, hipStream_t s, int64_t* rows)
 // The distinct molecules in ascending key order into device arrays: `rows` > 0 rows, as rows_for_fetch
 // gave them on `s`.  Beside index and UMI, each if asked: the feature column of a feature counter,
 // each row's mreads and its parent's UMI.  SLOTS: the slots travel through the sort, for the last two.
+// The parent of SCT_COLLAPSE_DIRECTIONAL is the root: the labels are made first, in the rows' block.
 template <bool SLOTS>
-int fetch_rows_as(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi, uint64_t* d_mreads,
-                  uint64_t* d_parent, int64_t rows, hipStream_t s) {
+int fetch_rows_as(sct_molecules* c, int method, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi,
+                  uint64_t* d_mreads, uint64_t* d_parent, int64_t rows, hipStream_t s) {
   SortedRows<SLOTS> sr(rows, key_bits(c), s);
+  const bool roots = SLOTS && d_parent && method == SCT_COLLAPSE_DIRECTIONAL;
+  const size_t o_labels = roots ? sr.take(DirectionalScratch::bytes(c)) : 0;
   SCT_HIP(sr.alloc());
+  const uint32_t* lab = nullptr;
+  if (roots) {
+    const DirectionalScratch ds(c, sr.template at<uint8_t>(o_labels));
+    SCT_TRY(directional_labels(c, ds, s));
+    lab = ds.lab;
+  }
   hipError_t e = sort_rows(c, sr);
   if (e == hipSuccess) {
     // (the grid of each form as it was: a row with a slot may cost a parent's probes)
     hipLaunchKernelGGL(molecules_emit_kernel<SLOTS>, dim3(grid_for(rows, SLOTS ? WG : 1024)), dim3(WG), 0, s, c->t,
                        sr.word(), sr.slot(), rows, d_index, d_feature, reinterpret_cast<u64*>(d_umi),
-                       reinterpret_cast<u64*>(d_mreads), reinterpret_cast<u64*>(d_parent));
+                       reinterpret_cast<u64*>(d_mreads), reinterpret_cast<u64*>(d_parent), lab);
     e = hipGetLastError();
   }
   if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule fetch: %s", hipGetErrorString(e));
   return leave(c, s);
 }
-int fetch_rows(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi, uint64_t* d_mreads,
-               uint64_t* d_parent, int64_t rows, hipStream_t s) {
+int fetch_rows(sct_molecules* c, int method, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi,
+               uint64_t* d_mreads, uint64_t* d_parent, int64_t rows, hipStream_t s) {
   const auto as = d_mreads || d_parent ? fetch_rows_as<true> : fetch_rows_as<false>;
-  return as(c, d_index, d_feature, d_umi, d_mreads, d_parent, rows, s);
+  return as(c, method, d_index, d_feature, d_umi, d_mreads, d_parent, rows, s);
 }
 
 // the device forms: `given` says whether the form's own columns are there, asked only when rows are
-int fetch_device(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi, uint64_t* d_mreads,
-                 uint64_t* d_parent, bool given, int64_t room, hipStream_t s) {
+int fetch_device(sct_molecules* c, int method, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi,
+                 uint64_t* d_mreads, uint64_t* d_parent, bool given, int64_t room, hipStream_t s) {
   SCT_ON_DEVICE_OF(c);
   int64_t rows = 0;
   if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
   if (rows == 0) return SCT_OK;
   SCT_CHECK(given, "NULL output");
-  return fetch_rows(c, d_index, d_feature, d_umi, d_mreads, d_parent, rows, s);
+  return fetch_rows(c, method, d_index, d_feature, d_umi, d_mreads, d_parent, rows, s);
 }
 
 // the host forms: the columns asked for, staged
-int fetch_host(sct_molecules* c, int32_t* index, int32_t* feature, uint64_t* umi, uint64_t* mreads, uint64_t* parent,
-               int64_t room) {
+int fetch_host(sct_molecules* c, int method, int32_t* index, int32_t* feature, uint64_t* umi, uint64_t* mreads,
+               uint64_t* parent, int64_t room) {
   SCT_ON_STAGE_OF(c, s);
   int64_t rows = 0;
   if (int rc = rows_for_fetch(c, room, s, &rows); rc != SCT_OK) return rc;
@@ -723,8 +927,8 @@ int fetch_host(sct_molecules* c, int32_t* index, int32_t* feature, uint64_t* umi
   st.add(umi, 8, rows), st.add(mreads, 8, rows), st.add(parent, 8, rows);
   st.add(index, 4, rows), st.add(feature, 4, rows);
   if (int rc = st.alloc(); rc != SCT_OK) return rc;
-  const int rc = fetch_rows(c, st.dev<int32_t>(3), st.dev<int32_t>(4), st.dev<uint64_t>(0), st.dev<uint64_t>(1),
-                            st.dev<uint64_t>(2), rows, s);
+  const int rc = fetch_rows(c, method, st.dev<int32_t>(3), st.dev<int32_t>(4), st.dev<uint64_t>(0),
+                            st.dev<uint64_t>(1), st.dev<uint64_t>(2), rows, s);
   return st.finish(rc, "molecule fetch");
 }
 
@@ -758,8 +962,36 @@ hipError_t collapse_pass(const sct_molecules* c, uint32_t* bitmap, u64* collapse
   return hipGetLastError();
 }
 
+// the directional clusters of the table as it stands on `s`: its labels, then collapsed[nw] and the
+// n_corrected word of `ds` added to (collapsed zero before)
+int directional_pass(sct_molecules* c, const DirectionalScratch& ds, u64* collapsed, hipStream_t s) {
+  SCT_TRY(directional_labels(c, ds, s));
+  hipLaunchKernelGGL(molecules_directional_count_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t,
+                     c->capacity, ds.lab, collapsed, &ds.words[DirectionalScratch::D_NCORRECTED]);
+  SCT_LAUNCH_CHECK();
+  return SCT_OK;
+}
+
+// collapsed[nw] and, if asked, n_corrected of the directional clusters
+int collapse_directional_device(sct_molecules* c, uint64_t* d_collapsed, uint64_t* d_ncorrected, hipStream_t s) {
+  if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
+  SCT_HIP(hipMemsetAsync(d_collapsed, 0, (size_t)c->t.nw * 8, s));
+  if (d_ncorrected) SCT_HIP(hipMemsetAsync(d_ncorrected, 0, 8, s));
+  if (c->size_bound > 0) {
+    sct::PoolBlock blk(s);
+    SCT_TRY(blk.alloc(DirectionalScratch::bytes(c)));
+    const DirectionalScratch ds(c, blk.bytes());
+    int rc = directional_pass(c, ds, reinterpret_cast<u64*>(d_collapsed), s);
+    if (rc == SCT_OK && d_ncorrected)
+      blk.note(hipMemcpyAsync(d_ncorrected, &ds.words[DirectionalScratch::D_NCORRECTED], 8, hipMemcpyDeviceToDevice, s));
+    SCT_TRY(blk.finish(rc, "directional clusters"));
+  }
+  return leave(c, s);
+}
+
 // collapsed[nw] and, if asked, n_corrected, written on `s` from the table as it stands
-int collapse_device(sct_molecules* c, uint64_t* d_collapsed, uint64_t* d_ncorrected, hipStream_t s) {
+int collapse_device(sct_molecules* c, int method, uint64_t* d_collapsed, uint64_t* d_ncorrected, hipStream_t s) {
+  if (method == SCT_COLLAPSE_DIRECTIONAL) return collapse_directional_device(c, d_collapsed, d_ncorrected, s);
   if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
   const size_t bytes = CollapseScratch::bytes(c, false);
   void* blk = nullptr;
@@ -1140,51 +1372,86 @@ extern "C" int sct_molecules_counts_host(sct_molecules* c, uint64_t* reads, uint
 extern "C" int sct_molecules_fetch(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, int64_t room, void* stream) {
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
-  return fetch_device(c, d_index, nullptr, d_umi, nullptr, nullptr, d_index && d_umi, room, sct::as_stream(stream));
+  return fetch_device(c, SCT_COLLAPSE_ONE_STEP, d_index, nullptr, d_umi, nullptr, nullptr, d_index && d_umi, room,
+                      sct::as_stream(stream));
 }
 
 extern "C" int sct_molecules_fetch_host(sct_molecules* c, int32_t* index, uint64_t* umi, int64_t room) {
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   SCT_CHECK(room == 0 || (index && umi), "NULL output");
-  return fetch_host(c, index, nullptr, umi, nullptr, nullptr, room);
+  return fetch_host(c, SCT_COLLAPSE_ONE_STEP, index, nullptr, umi, nullptr, nullptr, room);
 }
 
-extern "C" int sct_molecules_collapse(sct_molecules* c, uint64_t* d_collapsed, uint64_t* d_ncorrected, void* stream) {
+// The entry points that take a collapse method (include/sctools_hip.h, "directional clusters"); the
+// ones without are these with SCT_COLLAPSE_ONE_STEP.
+extern "C" int sct_molecules_collapse_by(sct_molecules* c, int method, uint64_t* d_collapsed, uint64_t* d_ncorrected,
+                                         void* stream) {
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
   if (int rc = need_counted(c); rc != SCT_OK) return rc;
   SCT_CHECK(d_collapsed != nullptr, "NULL output");
   SCT_ON_DEVICE_OF(c);
-  return collapse_device(c, d_collapsed, d_ncorrected, sct::as_stream(stream));
+  return collapse_device(c, method, d_collapsed, d_ncorrected, sct::as_stream(stream));
 }
 
-extern "C" int sct_molecules_collapse_host(sct_molecules* c, uint64_t* collapsed, uint64_t* ncorrected) {
+extern "C" int sct_molecules_collapse(sct_molecules* c, uint64_t* d_collapsed, uint64_t* d_ncorrected, void* stream) {
+  return sct_molecules_collapse_by(c, SCT_COLLAPSE_ONE_STEP, d_collapsed, d_ncorrected, stream);
+}
+
+extern "C" int sct_molecules_collapse_by_host(sct_molecules* c, int method, uint64_t* collapsed,
+                                              uint64_t* ncorrected) {
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
   if (int rc = need_counted(c); rc != SCT_OK) return rc;
   SCT_CHECK(collapsed != nullptr, "NULL output");
   SCT_ON_STAGE_OF(c, s);
   Staged st(s);
   st.add(collapsed, 8, (size_t)c->t.nw), st.add(ncorrected, 8, 1);
   if (int rc = st.alloc(); rc != SCT_OK) return rc;
-  return st.finish(collapse_device(c, st.dev<uint64_t>(0), st.dev<uint64_t>(1), s), "molecule collapse");
+  return st.finish(collapse_device(c, method, st.dev<uint64_t>(0), st.dev<uint64_t>(1), s), "molecule collapse");
+}
+
+extern "C" int sct_molecules_collapse_host(sct_molecules* c, uint64_t* collapsed, uint64_t* ncorrected) {
+  return sct_molecules_collapse_by_host(c, SCT_COLLAPSE_ONE_STEP, collapsed, ncorrected);
+}
+
+extern "C" int sct_molecules_directional_info(sct_molecules* c, int64_t* sweeps, int64_t* worklist, int64_t* swept) {
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (sweeps) *sweeps = c->dir_sweeps;
+  if (worklist) *worklist = c->dir_listed;
+  if (swept) *swept = c->dir_swept;
+  return SCT_OK;
+}
+
+extern "C" int sct_molecules_fetch_counted_by(sct_molecules* c, int method, int32_t* d_index, uint64_t* d_umi,
+                                              uint64_t* d_mreads, uint64_t* d_parent, int64_t room, void* stream) {
+  SCT_CHECK(room >= 0, "room must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
+  if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  return fetch_device(c, method, d_index, nullptr, d_umi, d_mreads, d_parent, d_index && d_umi && d_mreads, room,
+                      sct::as_stream(stream));
 }
 
 extern "C" int sct_molecules_fetch_counted(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, uint64_t* d_mreads,
                                            uint64_t* d_parent, int64_t room, void* stream) {
+  return sct_molecules_fetch_counted_by(c, SCT_COLLAPSE_ONE_STEP, d_index, d_umi, d_mreads, d_parent, room, stream);
+}
+
+extern "C" int sct_molecules_fetch_counted_by_host(sct_molecules* c, int method, int32_t* index, uint64_t* umi,
+                                                   uint64_t* mreads, uint64_t* parent, int64_t room) {
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
   if (int rc = need_counted(c); rc != SCT_OK) return rc;
-  return fetch_device(c, d_index, nullptr, d_umi, d_mreads, d_parent, d_index && d_umi && d_mreads, room,
-                      sct::as_stream(stream));
+  SCT_CHECK(room == 0 || (index && umi && mreads), "NULL output");
+  return fetch_host(c, method, index, nullptr, umi, mreads, parent, room);
 }
 
 extern "C" int sct_molecules_fetch_counted_host(sct_molecules* c, int32_t* index, uint64_t* umi, uint64_t* mreads,
                                                 uint64_t* parent, int64_t room) {
-  SCT_CHECK(room >= 0, "room must be >= 0");
-  SCT_CHECK(c != nullptr, "molecule counter is NULL");
-  if (int rc = need_counted(c); rc != SCT_OK) return rc;
-  SCT_CHECK(room == 0 || (index && umi && mreads), "NULL output");
-  return fetch_host(c, index, nullptr, umi, mreads, parent, room);
+  return sct_molecules_fetch_counted_by_host(c, SCT_COLLAPSE_ONE_STEP, index, umi, mreads, parent, room);
 }
 
 extern "C" int sct_molecules_merge(sct_molecules* dst, sct_molecules* src, void* stream) {
@@ -1208,8 +1475,8 @@ int need_feature_counter(const sct_molecules* c) {
 // one block of the sorted (key, slot) rows: after them the tile head counts and their scan, the entry
 // count per barcode and, for the collapsed values, the collapse pass's scratch with a collapsed[nw]
 // of its own; both scans run in the sort's scratch.
-int matrix_device(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint64_t* d_molecules, uint64_t* d_reads,
-                  uint64_t* d_collapsed, int64_t room, int64_t* nnz, hipStream_t s) {
+int matrix_device(sct_molecules* c, int method, int64_t* d_indptr, int32_t* d_feature, uint64_t* d_molecules,
+                  uint64_t* d_reads, uint64_t* d_collapsed, int64_t room, int64_t* nnz, hipStream_t s) {
   if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
   const int64_t rows = c->size_bound, nw = c->t.nw;
   SCT_CHECK(nw + 1 < (1LL << 31), "matrix: nw + 1 = %lld row offsets are more than one scan takes", (long long)nw + 1);
@@ -1226,7 +1493,9 @@ int matrix_device(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint6
   SortedRows<true> sr(rows, key_bits(c), s, std::max(scan_tiles_bytes, scan_rows_bytes));
   const size_t o_heads = sr.take((size_t)(ntiles + 1) * 8), o_base = sr.take((size_t)(ntiles + 1) * 8);
   const size_t o_row_entries = sr.take((size_t)(nw + 1) * 8);
-  const size_t pass_bytes = CollapseScratch::bytes(c, true), o_pass = d_collapsed ? sr.take(pass_bytes) : 0;
+  const bool directional = method == SCT_COLLAPSE_DIRECTIONAL;
+  const size_t pass_bytes = directional ? DirectionalScratch::bytes(c) : CollapseScratch::bytes(c, true);
+  const size_t o_pass = d_collapsed ? sr.take(pass_bytes) : 0;
   SCT_HIP(sr.alloc());
   u64* heads = sr.at<u64>(o_heads);
   u64* base = sr.at<u64>(o_base);
@@ -1251,7 +1520,14 @@ int matrix_device(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint6
     if (e == hipSuccess && d_molecules) e = hipMemsetAsync(d_molecules, 0, (size_t)entries * 8, s);
     if (e == hipSuccess && d_reads) e = hipMemsetAsync(d_reads, 0, (size_t)entries * 8, s);
     const uint32_t* bitmap = nullptr;
-    if (e == hipSuccess && d_collapsed) {
+    const uint32_t* lab = nullptr;
+    if (e == hipSuccess && d_collapsed && directional) {
+      // the entry's roots: the labels alone (the sweeps wait for the stream)
+      e = hipMemsetAsync(d_collapsed, 0, (size_t)entries * 8, s);
+      const DirectionalScratch ds(c, sr.at<uint8_t>(o_pass));
+      if (e == hipSuccess) SCT_TRY(directional_labels(c, ds, s));
+      lab = ds.lab;
+    } else if (e == hipSuccess && d_collapsed) {
       e = hipMemsetAsync(d_collapsed, 0, (size_t)entries * 8, s);
       if (e == hipSuccess) e = hipMemsetAsync(sr.at<void>(o_pass), 0, pass_bytes, s);
       const CollapseScratch cs(c, sr.at<uint8_t>(o_pass));
@@ -1260,7 +1536,7 @@ int matrix_device(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint6
     }
     if (e == hipSuccess) {
       hipLaunchKernelGGL(molecules_matrix_fill_kernel, tiles_grid, dim3(WG), 0, s, c->t, keys_out, slots_out, rows, base,
-                         bitmap, row_entries, d_feature, reinterpret_cast<u64*>(d_molecules),
+                         bitmap, lab, row_entries, d_feature, reinterpret_cast<u64*>(d_molecules),
                          reinterpret_cast<u64*>(d_reads), reinterpret_cast<u64*>(d_collapsed));
       e = hipcub::DeviceScan::ExclusiveSum(sr.tmp(), scan_rows_bytes, row_entries, reinterpret_cast<u64*>(d_indptr),
                                            (int)(nw + 1), s);
@@ -1289,37 +1565,62 @@ int matrix_check(const sct_molecules* c, const void* indptr, const void* feature
 
 }  // namespace
 
-extern "C" int sct_molecules_fetch_features(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi,
-                                            uint64_t* d_mreads, uint64_t* d_parent, int64_t room, void* stream) {
+extern "C" int sct_molecules_fetch_features_by(sct_molecules* c, int method, int32_t* d_index, int32_t* d_feature,
+                                               uint64_t* d_umi, uint64_t* d_mreads, uint64_t* d_parent, int64_t room,
+                                               void* stream) {
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
   SCT_CHECK(room == 0 || (d_index && d_feature && d_umi), "NULL output");
   if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
   if (d_mreads || d_parent)
     if (int rc = need_counted(c); rc != SCT_OK) return rc;
-  return fetch_device(c, d_index, d_feature, d_umi, d_mreads, d_parent, true, room, sct::as_stream(stream));
+  return fetch_device(c, method, d_index, d_feature, d_umi, d_mreads, d_parent, true, room, sct::as_stream(stream));
 }
 
-extern "C" int sct_molecules_fetch_features_host(sct_molecules* c, int32_t* index, int32_t* feature, uint64_t* umi,
-                                                 uint64_t* mreads, uint64_t* parent, int64_t room) {
+extern "C" int sct_molecules_fetch_features(sct_molecules* c, int32_t* d_index, int32_t* d_feature, uint64_t* d_umi,
+                                            uint64_t* d_mreads, uint64_t* d_parent, int64_t room, void* stream) {
+  return sct_molecules_fetch_features_by(c, SCT_COLLAPSE_ONE_STEP, d_index, d_feature, d_umi, d_mreads, d_parent, room,
+                                         stream);
+}
+
+extern "C" int sct_molecules_fetch_features_by_host(sct_molecules* c, int method, int32_t* index, int32_t* feature,
+                                                    uint64_t* umi, uint64_t* mreads, uint64_t* parent, int64_t room) {
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
   SCT_CHECK(room == 0 || (index && feature && umi), "NULL output");
   if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
   if (mreads || parent)
     if (int rc = need_counted(c); rc != SCT_OK) return rc;
-  return fetch_host(c, index, feature, umi, mreads, parent, room);
+  return fetch_host(c, method, index, feature, umi, mreads, parent, room);
+}
+
+extern "C" int sct_molecules_fetch_features_host(sct_molecules* c, int32_t* index, int32_t* feature, uint64_t* umi,
+                                                 uint64_t* mreads, uint64_t* parent, int64_t room) {
+  return sct_molecules_fetch_features_by_host(c, SCT_COLLAPSE_ONE_STEP, index, feature, umi, mreads, parent, room);
+}
+
+extern "C" int sct_molecules_matrix_by(sct_molecules* c, int method, int64_t* d_indptr, int32_t* d_feature,
+                                       uint64_t* d_molecules, uint64_t* d_reads, uint64_t* d_collapsed, int64_t room,
+                                       int64_t* nnz, void* stream) {
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
+  if (int rc = matrix_check(c, d_indptr, d_feature, d_reads, d_collapsed, room, nnz); rc != SCT_OK) return rc;
+  SCT_ON_DEVICE_OF(c);
+  return matrix_device(c, method, d_indptr, d_feature, d_molecules, d_reads, d_collapsed, room, nnz,
+                       sct::as_stream(stream));
 }
 
 extern "C" int sct_molecules_matrix(sct_molecules* c, int64_t* d_indptr, int32_t* d_feature, uint64_t* d_molecules,
                                     uint64_t* d_reads, uint64_t* d_collapsed, int64_t room, int64_t* nnz, void* stream) {
-  if (int rc = matrix_check(c, d_indptr, d_feature, d_reads, d_collapsed, room, nnz); rc != SCT_OK) return rc;
-  SCT_ON_DEVICE_OF(c);
-  return matrix_device(c, d_indptr, d_feature, d_molecules, d_reads, d_collapsed, room, nnz, sct::as_stream(stream));
+  return sct_molecules_matrix_by(c, SCT_COLLAPSE_ONE_STEP, d_indptr, d_feature, d_molecules, d_reads, d_collapsed, room,
+                                 nnz, stream);
 }
 
-extern "C" int sct_molecules_matrix_host(sct_molecules* c, int64_t* indptr, int32_t* feature, uint64_t* molecules,
-                                         uint64_t* reads, uint64_t* collapsed, int64_t room, int64_t* nnz) {
+extern "C" int sct_molecules_matrix_by_host(sct_molecules* c, int method, int64_t* indptr, int32_t* feature,
+                                            uint64_t* molecules, uint64_t* reads, uint64_t* collapsed, int64_t room,
+                                            int64_t* nnz) {
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
   if (int rc = matrix_check(c, indptr, feature, reads, collapsed, room, nnz); rc != SCT_OK) return rc;
   SCT_ON_STAGE_OF(c, s);
   if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
@@ -1329,8 +1630,13 @@ extern "C" int sct_molecules_matrix_host(sct_molecules* c, int64_t* indptr, int3
   st.add(indptr, 8, (size_t)c->t.nw + 1), st.add(feature, 4, r);
   st.add(molecules, 8, r), st.add(reads, 8, r), st.add(collapsed, 8, r);
   if (int rc = st.alloc(); rc != SCT_OK) return rc;
-  const int rc = matrix_device(c, st.dev<int64_t>(0), st.dev<int32_t>(1), st.dev<uint64_t>(2), st.dev<uint64_t>(3),
-                               st.dev<uint64_t>(4), r, nnz, s);
+  const int rc = matrix_device(c, method, st.dev<int64_t>(0), st.dev<int32_t>(1), st.dev<uint64_t>(2),
+                               st.dev<uint64_t>(3), st.dev<uint64_t>(4), r, nnz, s);
   for (int i = 1; i < st.n; ++i) st.cols[i].count = (size_t)*nnz;  // what the matrix wrote of its room
   return st.finish(rc, "molecule matrix");
+}
+
+extern "C" int sct_molecules_matrix_host(sct_molecules* c, int64_t* indptr, int32_t* feature, uint64_t* molecules,
+                                         uint64_t* reads, uint64_t* collapsed, int64_t room, int64_t* nnz) {
+  return sct_molecules_matrix_by_host(c, SCT_COLLAPSE_ONE_STEP, indptr, feature, molecules, reads, collapsed, room, nnz);
 }

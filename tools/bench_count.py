@@ -20,7 +20,10 @@ and against the host route, with the existing molecule rows again beside an earl
 route pairs(features=True) + np.unique, and the plain and counted updates beside an earlier library
 (matrix_step; profiles/ab_count_matrix.jsonl, or ab_count_matrix_<tag>.jsonl for a tag other than
 "run").  Then the calls that read a table back, merge two and grow one, each beside an earlier library,
-timings and outputs (calls_step; profiles/ab_molecules_calls_<tag>.jsonl).
+timings and outputs (calls_step; profiles/ab_molecules_calls_<tag>.jsonl).  Then the directional
+clusters in both forms beside the one-step collapse, on the same reads with --umi-error substitutions
+per UMI base, and the updates and the one-step collapse beside an earlier library (directional_step;
+profiles/ab_umi_directional.jsonl).
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends
 the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
@@ -31,6 +34,7 @@ the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>
   python tools/bench_count.py --tag mi355x --only merge --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only matrix --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only calls --parent-lib /path/to/earlier/libsctools_hip.so
+  python tools/bench_count.py --only directional --umi-error 0.01 --parent-lib /path/to/earlier/libsctools_hip.so
 """
 import argparse
 import functools
@@ -44,7 +48,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420, "collapse": 600,
-         "merge": 600, "matrix": 600, "calls": 600}  # seconds
+         "merge": 600, "matrix": 600, "calls": 600, "directional": 600}  # seconds
 MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
 HBM_BYTES_PER_S = 8e12
 
@@ -1048,6 +1052,148 @@ def calls_step(args):
     return out
 
 
+def _with_umi_errors(d_umi, UL, rate, seed=17):
+    """The reads' ThreeBit UMIs with every base of every read replaced by one of the three other bases
+    with probability `rate` (a triplet that is no base, the N of a bad UMI, stays as it is)."""
+    import torch
+    g = torch.Generator(device=d_umi.device).manual_seed(seed)
+    out = d_umi.clone()
+    n = out.numel()
+    for p in range(UL):
+        t = (out >> (3 * p)) & 7
+        hit = (torch.rand(n, device=out.device, generator=g) < rate) & (t >= 1) & (t <= 4)
+        other = ((t - 1 + torch.randint(1, 4, (n,), device=out.device, generator=g)) & 3) + 1
+        out ^= torch.where(hit, (t ^ other) << (3 * p), torch.zeros_like(t))
+    return out.contiguous()
+
+
+DIRECTIONAL_CALLS = UPDATE_CALLS + ("sct_molecules_collapse",)
+
+
+def directional_step(args):
+    """The directional clusters (collapse_device(method='directional')) on the molecules step's reads
+    as drawn, with every UMI base of every read substituted with probability --umi-error, so that
+    stored UMIs have neighbours.  Alternating within every round, through the C ABI, for this library
+    and for the one given by --parent-lib (skipped without it): (a) the plain update, (b) the counted
+    update, (c) the one-step collapse on the table (b) left; then, this library only, on the same
+    table: (d) the directional call with the sweeps over the worklist (SCT_TUNE_DIRECTIONAL_FORM 1, the
+    default) and (e) over the whole table (0), each with its sweeps and worklist entries.  Medians with
+    min-max over --rounds; the clusters beside the one-step collapsed.  (a), (b) and (c) must not be
+    slower than the parent's by more than the min-max spread of the parent's own rounds: the step
+    fails, its profile written, when one is.  Every round is one line of
+    profiles/ab_umi_directional.jsonl (ab_umi_directional_<tag>.jsonl for a tag other than "run"), the
+    summary its last."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib
+
+    nw, UL, n, hint, pool, inputs = _molecules_input(args)
+    d_index, d_umi, _ = inputs["shuffled"]
+    d_umi = _with_umi_errors(d_umi, UL, args.umi_error)
+    del inputs
+    torch.cuda.empty_cache()
+    this, old = _lib.lib(), _parent_lib(args, DIRECTIONAL_CALLS)
+    vp = ctypes.c_void_p
+    d_out = torch.zeros(nw + 1, dtype=torch.int64, device=d_index.device)
+
+    def synced(call):
+        def go():
+            assert call() == 0
+            torch.cuda.synchronize()
+        return _time_ms(go)
+
+    def answer():
+        got = d_out.cpu().tolist()
+        return sum(got[:nw]), got[nw]
+
+    def run(lib, counted, directional=False):
+        """{what: ms} and {what: numbers} of one fresh counter of `lib`"""
+        h = vp()
+        create = lib.sct_molecules_create_counted if counted else lib.sct_molecules_create
+        assert create(nw, 3, UL, hint, ctypes.byref(h)) == 0
+        ms, facts = {}, {}
+        try:
+            ms["update"] = synced(lambda: lib.sct_molecules_update(h, vp(d_index.data_ptr()), vp(d_umi.data_ptr()), n, None))
+            if counted:
+                ms["collapse"] = synced(lambda: lib.sct_molecules_collapse(h, vp(d_out.data_ptr()),
+                                                                           vp(d_out.data_ptr() + 8 * nw), None))
+                facts["one_step"] = answer()
+            for form in (1, 0) if directional else ():
+                with _lib.tuning(directional_form=form):
+                    ms["directional_form%d" % form] = synced(lambda: lib.sct_molecules_collapse_by(
+                        h, _lib.COLLAPSE_DIRECTIONAL, vp(d_out.data_ptr()), vp(d_out.data_ptr() + 8 * nw), None))
+                sweeps, listed, swept = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+                assert lib.sct_molecules_directional_info(h, ctypes.byref(sweeps), ctypes.byref(listed),
+                                                          ctypes.byref(swept)) == 0
+                facts["directional_form%d" % form] = answer() + (listed.value,)
+                # (how far a sweep sees the labels other waves write in it is not fixed: these may differ by round)
+                ms["sweeps_form%d" % form], ms["swept_form%d" % form] = sweeps.value, swept.value
+            if directional:
+                capacity = ctypes.c_int64()
+                assert lib.sct_molecules_info(h, None, None, ctypes.byref(capacity)) == 0
+                facts["capacity"] = capacity.value
+            reads, molecules, tally = np.empty(nw, np.uint64), np.empty(nw, np.uint64), np.empty(3, np.uint64)
+            assert lib.sct_molecules_counts_host(h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)) == 0
+            facts["counts"] = (int(reads.sum()), int(molecules.sum())) + tuple(int(t) for t in tally)
+        finally:
+            lib.sct_molecules_destroy(h)
+        return ms, facts
+
+    run(this, True, True)  # warm-up: code objects, pool
+    if old:
+        run(old, True)
+    lines, facts = [], None
+    for r in range(args.rounds):
+        row = {"round": r, "n": n, "nw": nw, "umi_error": args.umi_error}
+        for name, lib in (("this", this), ("parent", old))[::-1 if r % 2 else 1]:  # (who goes first alternates)
+            if lib is None:
+                continue
+            plain, f_plain = run(lib, False)
+            counted, f = run(lib, True, directional=lib is this)
+            assert f["counts"] == f_plain["counts"], (f, f_plain)
+            if lib is this:
+                assert f["directional_form1"][:2] == f["directional_form0"][:2], f  # both forms: the same numbers
+                row[name + "_sweeps"] = {k: v for k, v in counted.items() if k.startswith("sw")}
+            known = {k: v for k, v in (facts or f).items() if k in f}
+            assert f == known, (f, facts)  # every library and round: the same numbers
+            facts = facts or f
+            row[name] = {"plain_update_ms": round(plain["update"], 3), "counted_update_ms": round(counted["update"], 3),
+                         "collapse_ms": round(counted["collapse"], 3)}
+            row[name].update({k + "_ms": round(v, 3) for k, v in counted.items() if k.startswith("directional")})
+        lines.append(row)
+    out = {"n": n, "nw": nw, "umi_length": UL, "umi_error": args.umi_error, "capacity_hint": hint,
+           "parent_lib": bool(old), "rounds": args.rounds}
+    for name in ("this", "parent"):
+        if name in lines[0]:
+            out[name] = {}
+            for key in lines[0][name]:
+                a = [row[name][key] for row in lines]
+                out[name][key] = {"median": round(float(np.median(a)), 3), "min": min(a), "max": max(a)}
+    reads, molecules = facts["counts"][:2]
+    clusters, moved, listed = facts["directional_form1"]
+    out["sweeps"] = {k: {"median": float(np.median(a)), "min": min(a), "max": max(a)}
+                     for k in lines[0]["this_sweeps"] for a in [[row["this_sweeps"][k] for row in lines]]}
+    out.update(reads=reads, molecules=molecules, one_step_collapsed=facts["one_step"][0],
+               one_step_n_corrected=facts["one_step"][1], clusters=clusters, directional_n_corrected=moved,
+               worklist=listed,
+               capacity=facts["capacity"], scratch_bytes=4 * facts["capacity"] + 8 * molecules + 256)
+    slower = []
+    if old:
+        out["vs_parent"] = {k: _vs_parent(out["this"][k], out["parent"][k]) for k in out["parent"]}
+        slower = ["%s: %s" % (k, v) for k, v in out["vs_parent"].items()
+                  if not v["agree"] and v["median_difference_ms"] > 0]
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    name = "ab_umi_directional.jsonl" if args.tag == "run" else "ab_umi_directional_%s.jsonl" % args.tag
+    with open(os.path.join(ROOT, "profiles", name), "w") as f:
+        for row in lines:
+            f.write(json.dumps(row, sort_keys=True) + "\n")
+        f.write(json.dumps(out, sort_keys=True) + "\n")
+    assert not slower, "slower than --parent-lib beyond that library's own spread: " + "; ".join(slower)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tag", default="run")
@@ -1059,12 +1205,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--n-collapse-host", type=int, default=200_000, help="molecules given to the dict collapse")
     ap.add_argument("--parent-lib", default="",
-                    help="collapse, merge, matrix and calls steps: an earlier libsctools_hip.so to time beside this one")
+                    help="collapse, merge, matrix, calls and directional steps: an earlier libsctools_hip.so to time "
+                         "beside this one")
+    ap.add_argument("--umi-error", type=float, default=0.01,
+                    help="directional step: the probability that a UMI base of a read is substituted")
     ap.add_argument("--only", nargs="+", choices=sorted(STEPS), help="launch only these steps")
     args = ap.parse_args()
     if args.step:
         whole = {"molecules": molecules_step, "collapse": collapse_step, "merge": merge_step, "matrix": matrix_step,
-                 "calls": calls_step}
+                 "calls": calls_step, "directional": directional_step}
         if args.step in whole:
             res = whole[args.step](args)
         else:
@@ -1080,7 +1229,8 @@ def main():
                "--tag", args.tag,
                "--n-a", str(args.n_a), "--n-counter", str(args.n_counter), "--n-unique", str(args.n_unique),
                "--n-tally", str(args.n_tally), "--rounds", str(args.rounds),
-               "--n-collapse-host", str(args.n_collapse_host), "--parent-lib", args.parent_lib]
+               "--n-collapse-host", str(args.n_collapse_host), "--parent-lib", args.parent_lib,
+               "--umi-error", str(args.umi_error)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not lines:
@@ -1102,6 +1252,12 @@ def main():
                            "update_ms": {which: {k: [v[c]["median"] for c in ("plain_this_ms", "plain_features_ms",
                                                                                "counted_this_ms", "counted_features_ms")]
                                                  for k, v in modes.items()} for which, modes in res["updates"].items()}}
+        elif "clusters" in res:
+            short[step] = {"n": res["n"], "molecules": res["molecules"], "clusters": res["clusters"],
+                           "one_step_collapsed": res["one_step_collapsed"],
+                           "sweeps": res["sweeps"]["sweeps_form1"]["median"],
+                           "worklist": res["worklist"],
+                           "ms": {k: v["median"] for k, v in res["this"].items()}}
         elif "outputs_equal" in res:
             short[step] = {"n": res["n"], "outputs_equal": all(res["outputs_equal"].values()),
                            "faster_than_parent": res["faster_than_parent"],
