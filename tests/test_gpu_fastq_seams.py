@@ -146,6 +146,24 @@ def test_fastq_seams(family, form):
     assert count == 2 * len(F.cases(family))  # every case, both modes
 
 
+@pytest.mark.parametrize("tiles", (1, 2, 0))
+@pytest.mark.parametrize("family", sorted(F.FAMILIES))
+def test_fastq_seams_range_sizes(family, tiles):
+    """The fused form with fastq_range_kernel's range fixed by ingest_tiles (unset: 8 tiles, under
+    which the 8 KiB and 16 KiB seams lie inside a workgroup's range): 1, every 8 KiB seam starts a
+    range (line number and file cursor from the tile sums, not carried); 2, the 16 KiB seam starts
+    one and the 8 KiB seam is carried; 0, the ranges are sized to the resident grid."""
+    from sctools_amd import _lib
+    count = 0
+    with _lib.tuning(ingest_tiles=tiles):
+        assert _lib.tune_get("ingest_tiles") == tiles
+        for args in _each(family):
+            _check_fused(*args)
+            count += 1
+    assert _lib.tune_get("ingest_tiles") == -1
+    assert count == 2 * len(F.cases(family))  # every case, both modes
+
+
 @pytest.mark.parametrize("form", sorted(FORMS))
 def test_fastq_high_bytes_binary(form):
     """0x80 / 0xFF in sequence and quality lines at the seams, mode 'rb': the bytes arrive in the
