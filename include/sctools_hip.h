@@ -73,7 +73,9 @@ int sct_set_device(int device);        /* select the device for later calls (hip
                                            chain per tile (default), 0 the shift form (read at plan creation) */
 #define SCT_TUNE_DIRECTIONAL_FORM 21    /* directional clusters: 1 the sweeps run over the worklist of molecules
                                            with an in-edge (default), 0 every sweep runs over the whole table */
-#define SCT_TUNE_NKEYS 22
+#define SCT_TUNE_DOWNSAMPLE_WAVE_READS 22 /* downsampling: a molecule of at least this many reads is thinned by its
+                                           whole wave, 64 draws at a time (default 64); below it by its own lane */
+#define SCT_TUNE_NKEYS 23
 int sct_tune_set(int key, int64_t value);
 int sct_tune_get(int key, int64_t* value);  /* -1 when unset */
 
@@ -713,6 +715,56 @@ int sct_molecules_directional_info(sct_molecules* mol, int64_t* sweeps, int64_t*
  * compacted on its own device and copied into scratch on dst's device (hipMemcpyPeerAsync; peer
  * access is neither needed nor enabled); on one device the kernel reads src's table in place. */
 int sct_molecules_merge(sct_molecules* dst, sct_molecules* src, void* stream);
+
+/* Downsampling reads: what the library would have shown at a fraction of its reads -- the saturation
+ * curve of a QC report -- and a library thinned to the depth of a shallower one before they are
+ * merged (binomial thinning of every molecule's reads).  On counted counters.  The contract is
+ * restated in plain Python by tests/downsample_reference.py; mix64 is csrc/mix64.h and the draw is
+ * csrc/downsample_draw.h.  All arithmetic is exact, unsigned 64-bit and modulo 2^64.
+ *   G = 0x9e3779b97f4a7c15
+ *   stream(seed, key)  = mix64(key ^ mix64(seed ^ G))                  seed: any uint64
+ *   draw(seed, key, j) = mix64(stream(seed, key) + (j + 1) * G) >> 32  j = 0, 1, ...: the j-th read
+ * Read j of a molecule is kept at threshold T (0 <= T <= 2^32) exactly when draw < T;
+ * thin(seed, key, r, T) is the number of j < r that are kept.  T = 0 keeps nothing, T = 2^32
+ * everything, and a fraction f is the threshold round(f * 2^32).  The draw depends on (seed, key, j)
+ * only -- not on a slot, the capacity or the order of updates and merges -- so two counters with the
+ * same contents thin to the same table, and for one seed what is kept at T1 <= T2 is a subset of what
+ * is kept at T2: a curve is monotone by construction.
+ * Reads that never became molecules are thinned by the same rule under keys no molecule can have: the
+ * n reads of tally k (0 no match, 1 ambiguous, 2 bad UMI, 3 no feature) use key 2^63 | k, and
+ * thin_tally(seed, k, n, T) is the number of j < n with draw(seed, 2^63 | k, j) < T.
+ * downsample(dst, src, T, seed) is merge's sibling: afterwards dst is the counter that was fed dst's
+ * updates followed by the thinned src.  For every key stored in src, m = thin(seed, key, mreads, T);
+ * if m > 0 the key is claimed in dst by the update's own rule (molecules[index] += 1 from the lane
+ * whose compare-and-swap took the slot, and from no other), mreads of the key in dst += m and
+ * reads[index] += m; a molecule with m == 0 leaves no trace.  tally[k] += thin_tally(seed, k,
+ * src.tally[k], T) for each of the four tallies, and total grows by the kept molecule reads plus the
+ * kept tallies: reads of src that rule 3 refused (an index out of range) are in src.total only and
+ * are not carried.  src is unchanged and stays usable; the same call twice adds the same reads again
+ * and no molecule.  The result is an ordinary counter: collapse, the directional clusters, matrix,
+ * merge and a further downsample work on it.
+ * Conditions: dst != src; both counted; nw, kind, L and nf equal (merge's messages); T <= 2^32; both
+ * on one device (for two, downsample on the source's device and then merge: the message says so).
+ * A NULL counter or a violated condition is SCT_E_INVALID, a src whose table overflowed SCT_E_RANGE;
+ * after any of these both counters are as they were.  Growth: the surviving molecules are counted
+ * first (the curve pass below at the one threshold) and dst is grown by update's rehash so that
+ * dst.nmolecules + survivors <= capacity / 2, merge's rule on the survivors and not on src's size: a
+ * 10 % sample of a large table gets a small one.  More than 2^31 slots is SCT_E_RANGE.  The call
+ * orders itself after both counters' earlier work on any stream and their later work after itself,
+ * and waits for `stream` to learn the sizes and the kept reads (total is a host word).
+ * downsample_curve: the whole curve in one pass over the table, nothing is built.  thresholds is a
+ * host array of k integers, 1 <= k <= 64, none above 2^32 and none below the one before it (else
+ * SCT_E_INVALID).  reads[t] = the sum of thin(seed, key, mreads, thresholds[t]) over the stored
+ * molecules, molecules[t] = the stored molecules with thin > 0 there; both uint64[k], each nullable,
+ * written and not accumulated; tallies are no part of the curve.  reads[t] and molecules[t] equal the
+ * sums of reads[] and molecules[] after downsample(thresholds[t]) into an empty counter.  It needs a
+ * counted counter (else SCT_E_INVALID), reads the table only (twice gives the same answer) and is
+ * asynchronous on `stream` after one wait for the size; the _host form stages its outputs. */
+int sct_molecules_downsample(sct_molecules* dst, sct_molecules* src, uint64_t threshold, uint64_t seed, void* stream);
+int sct_molecules_downsample_curve(sct_molecules* mol, const uint64_t* thresholds, int64_t k, uint64_t seed,
+                                   uint64_t* d_reads, uint64_t* d_molecules, void* stream);
+int sct_molecules_downsample_curve_host(sct_molecules* mol, const uint64_t* thresholds, int64_t k, uint64_t seed,
+                                        uint64_t* reads, uint64_t* molecules);
 
 /* Counting molecules per feature: the barcode x feature matrix of a single-cell run -- molecules per
  * (cell, antibody tag / CRISPR guide / hashtag / gene) -- as CSR on the device.  The contract is

@@ -39,7 +39,8 @@ TUNE_KEYS = {"spectral_chunk": 1, "spectral_min_n": 2, "allpairs_grab": 3, "allp
              "scalar_idle_ms": 9, "spectral_columns": 10, "plan_cache": 11,
              "encode_grid": 12, "ingest_tiles": 13, "fastq_onepass": 14,
              "ingest_direct": 15, "ingest_spec": 16, "count_preagg": 17, "collapse_form": 18,
-             "merge_rows": 19, "tile_chain": 20, "directional_form": 21}
+             "merge_rows": 19, "tile_chain": 20, "directional_form": 21,
+             "downsample_wave_reads": 22}
 COLLAPSE_ONE_STEP, COLLAPSE_DIRECTIONAL = 0, 1
 NEAREST_AUTO, NEAREST_OA, NEAREST_CSR, NEAREST_HALVES = 0, 1, 2, 3
 
@@ -168,6 +169,9 @@ SIGNATURES = {
     "sct_molecules_fetch_counted_host": [_vp, _vp, _vp, _vp, _vp, _i64],
     "sct_molecules_create_ex": [_i64, _i32, _i32, _i64, _i32, _i32, ctypes.POINTER(_vp)],
     "sct_molecules_merge": [_vp, _vp, _vp],
+    "sct_molecules_downsample": [_vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp],
+    "sct_molecules_downsample_curve": [_vp, _vp, _i64, ctypes.c_uint64, _vp, _vp, _vp],
+    "sct_molecules_downsample_curve_host": [_vp, _vp, _i64, ctypes.c_uint64, _vp, _vp],
     "sct_molecules_create_features": [_i64, _i64, _i32, _i32, _i64, _i32, _i32, ctypes.POINTER(_vp)],
     "sct_molecules_update_features": [_vp, _vp, _vp, _vp, _i64, _vp],
     "sct_molecules_update_features_host": [_vp, _vp, _vp, _vp, _i64],

@@ -144,6 +144,23 @@ def collapse_method(name):
     return COLLAPSE_METHODS[name]
 
 
+def downsample_threshold(fraction):
+    """The integer threshold in [0, 2**32] of a fraction of the reads in [0, 1]:
+    ``int(round(fraction * 2**32))``.  The scaling by a power of two is exact, so a fraction always
+    maps to the same threshold.  Anything outside [0, 1] (nan included) raises ValueError."""
+    f = float(fraction)
+    if not 0.0 <= f <= 1.0:
+        raise ValueError("fraction must lie in [0, 1], not %r" % (fraction,))
+    return int(round(f * 4294967296))
+
+
+def _seed(value, what="seed"):
+    """``value`` as a ctypes uint64; ValueError unless it is an int in [0, 2**64)."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) < 2 ** 64:
+        raise ValueError("%s must be an int in [0, 2**64), not %r" % (what, value))
+    return ctypes.c_uint64(int(value))
+
+
 class MoleculeCounter:
     """Molecules per whitelist barcode on the device (sct_molecules_*): the distinct
     (corrected barcode index, UMI code) pairs, which removes PCR duplicates.
@@ -163,7 +180,9 @@ class MoleculeCounter:
     made).  Every method works whatever device is current and leaves it as it was; device pointers
     and streams given to the ``*_device`` methods belong to the counter's device.  Counters fed
     different pieces of the reads -- one per file or lane, or one per GPU -- become one with
-    ``merge``.
+    ``merge``.  With ``read_counts``, ``downsample(fraction)`` gives the counter a fraction of the
+    reads would have made, and ``saturation_curve(fractions)`` the reads and molecules at every depth
+    in one pass (include/sctools_hip.h, "downsampling reads").
 
     ``features=nf`` (1 .. 2**31 - 1) makes a *feature counter*: every read carries a feature index
     (an antibody tag or guide corrected by ``WhitelistCorrector``, or a gene index) as a third key
@@ -419,6 +438,71 @@ class MoleculeCounter:
         TypeError for anything but a MoleculeCounter; ValueError for this counter itself, a closed
         counter or differing parameters.  Returns self."""
         return self.merge_device(other)
+
+    def downsample_device(self, into, threshold, seed=0, stream=0):
+        """``downsample`` enqueued on ``stream`` with the threshold as an integer in [0, 2**32]
+        (sct_molecules_downsample): read j of a molecule is kept when its draw lies below it.  Waits
+        for ``stream`` to learn how many molecules survive.  Returns ``into``."""
+        self._need_read_counts("downsample")
+        if not isinstance(into, MoleculeCounter):
+            raise TypeError("downsample needs a MoleculeCounter to thin into, not %s" % type(into).__name__)
+        if into is self:
+            raise ValueError("a MoleculeCounter cannot be downsampled into itself")
+        if not self._h or not into._h:
+            raise ValueError("downsample: %s counter is closed" % ("this" if not self._h else "the target"))
+        into._need_read_counts("downsample(into=...)")
+        mine = (self.size, self.kind, self.umi_length, self._nf)
+        theirs = (into.size, into.kind, into.umi_length, into._nf)
+        for name, a, b in zip(("whitelist_size", "encoding", "umi_length", "features"), mine, theirs):
+            if a != b:
+                raise ValueError("downsample: the counters' %s differ (%r and %r)" % (name, a, b))
+        _lib.check(self._lib.sct_molecules_downsample(into._h, self._h, _seed(threshold, "threshold"), _seed(seed),
+                                                      _vp(stream)))
+        return into
+
+    def downsample(self, fraction, seed=0, into=None):
+        """This counter with every read kept with probability ``fraction``, added to ``into`` (default:
+        a new counter of the same whitelist_size, umi_length, encoding, features and device, with
+        ``read_counts``) and returned: binomial thinning of each molecule's reads, the molecules that
+        keep none dropped, the tallies thinned alike (include/sctools_hip.h, "downsampling reads").
+        The result is an ordinary counter -- ``collapse``, ``matrix``, ``merge`` work on it -- sized for
+        what survives.  What is kept depends on ``seed`` (an int in [0, 2**64)), the molecule and the
+        read's number only: equal counters thin to equal tables whatever their history, and a smaller
+        fraction keeps a subset of a larger one's reads.  This counter is not changed."""
+        self._need_read_counts("downsample")
+        threshold = downsample_threshold(fraction)
+        made = into is None
+        if made:
+            into = MoleculeCounter(self.size, self.umi_length, encoding={3: 'ThreeBit', 2: 'TwoBit'}[self.kind],
+                                   read_counts=True, device=self.device, features=self._nf)
+        try:
+            return self.downsample_device(into, threshold, seed)
+        except Exception:
+            if made:
+                into.close()
+            raise
+
+    def saturation_curve_device(self, thresholds, reads_ptr, molecules_ptr, seed=0, stream=0):
+        """``saturation_curve`` into device memory, on ``stream``: ``thresholds`` is a non-decreasing
+        sequence of 1 to 64 integers in [0, 2**32], and uint64[len(thresholds)] is written at each
+        pointer that is not 0 / None (sct_molecules_downsample_curve)."""
+        self._need_read_counts("saturation_curve")
+        th = np.array([_seed(t, "threshold").value for t in thresholds], dtype=np.uint64)
+        _lib.check(self._lib.sct_molecules_downsample_curve(self._h, _lib._ptr(th), th.size, _seed(seed),
+                                                            _vp(reads_ptr or None), _vp(molecules_ptr or None),
+                                                            _vp(stream)))
+
+    def saturation_curve(self, fractions, seed=0):
+        """(reads, molecules), each np.int64[len(fractions)]: the reads kept and the molecules still
+        seen at every one of 1 to 64 non-decreasing ``fractions`` of the reads, in one pass over the
+        table -- ``counts()[0].sum()`` and ``counts()[1].sum()`` of ``downsample(f, seed)`` for each f.
+        Sequencing saturation at depth f is ``1 - molecules / reads``."""
+        self._need_read_counts("saturation_curve")
+        th = np.array([downsample_threshold(f) for f in fractions], dtype=np.uint64)
+        reads, molecules = np.empty(th.size, np.uint64), np.empty(th.size, np.uint64)
+        _lib.check(self._lib.sct_molecules_downsample_curve_host(self._h, _lib._ptr(th), th.size, _seed(seed),
+                                                                 _lib._ptr(reads), _lib._ptr(molecules)))
+        return reads.view(np.int64), molecules.view(np.int64)
 
     def info(self):
         """dict(nmolecules, total, capacity)."""

@@ -56,6 +56,13 @@
 // row may be new at a load of at most 1/2; reads[] and the tally are added by a kernel of their own.
 // A counter's calls make its device current for their duration (DeviceGuard).
 //
+// Downsampling (include/sctools_hip.h, "downsampling reads") is the merge on one
+// device with a draw per read in front of it (downsample_draw.h): a walk over the source's table in
+// place that keeps m of a molecule's reads and claims the molecule with m as its count when m > 0.
+// The survivors are counted first, by the one-threshold form of the curve pass, so the target grows
+// to what survives; the curve itself is the same walk into a per-workgroup LDS histogram.  A molecule
+// with many reads is thinned by its whole wave, as the collapse shares a molecule's neighbours.
+//
 // A *feature counter* (include/sctools_hip.h, "counting molecules per feature") has a third key part
 // between the index and the UMI (molecules_feature_key.h).  FEATURES is a template parameter of the
 // insert kernels as COUNTED is: a counter without features runs the instantiations without it, and
@@ -74,6 +81,7 @@
 
 #include "sorted_rows.h"  // (first: the HIP runtime's qualifiers, which the key headers below use)
 
+#include "downsample_draw.h"
 #include "molecules_feature_key.h"
 #include "molecules_key.h"
 #include "molecules_merge_plan.h"
@@ -634,6 +642,162 @@ __global__ void __launch_bounds__(WG) molecules_add_kernel(u64* __restrict__ rea
   if (gid < 4) words[W_TALLY + gid] += from_words[W_TALLY + gid];
 }
 
+// ---- downsampling (include/sctools_hip.h, "downsampling reads"; the draw: downsample_draw.h)
+
+// what a share of a molecule's reads gives: the reads kept (at the last threshold) and the lowest
+// bucket among them (any value at or above the number of thresholds when none is kept)
+struct Thinned {
+  u64 kept;
+  int first;
+};
+
+// The walk of the three kernels below over a counted table in place (n = its capacity): a grid stride
+// with the wave kept whole, keys and mreads loaded once and past the caches.  A molecule of fewer than
+// `wave_reads` reads is thinned by its own lane, share(stream, 0, 1, r).  The others are taken one
+// after the other by the whole wave, the shape of molecules_collapse_wave_kernel: lane l takes the
+// reads j = l, l + 64, ..., the shares are summed (and the lowest bucket taken) across the wave, and
+// the molecule's own lane goes on.  molecule(key, thinned) runs once per stored molecule, in its lane.
+template <class Share, class Molecule>
+__device__ __forceinline__ void downsample_walk(const u64* __restrict__ keys, const u64* __restrict__ cnt, int64_t n,
+                                                u64 seed, u64 wave_reads, Share share, Molecule molecule) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * WG;
+  const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
+  const int64_t iters = (n + stride - 1) / stride;  // the same for every lane: the wave stays whole
+  for (int64_t it = 0; it < iters; ++it) {
+    const int64_t i = it * stride + gid;
+    u64 key = EMPTY, r = 0;
+    if (i < n) {
+      key = __builtin_nontemporal_load(&keys[i]);
+      r = __builtin_nontemporal_load(&cnt[i]);
+    }
+    const bool occ = key != EMPTY;
+    const u64 stream = sct::downsample_stream(seed, key);
+    const bool heavy = occ && r >= wave_reads;
+    if (occ && !heavy) molecule(key, share(stream, 0, 1, r));
+    u64 todo = __ballot(heavy);
+    while (todo) {  // wave-uniform
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      Thinned m = share(__shfl(stream, src), (u64)lane, 64, __shfl(r, src));
+      for (int o = 32; o > 0; o >>= 1) {
+        m.kept += __shfl_xor(m.kept, o);
+        m.first = min(m.first, __shfl_xor(m.first, o));
+      }
+      if (lane == src) molecule(key, m);
+    }
+  }
+}
+
+// Thin-and-claim, molecules_merge_kernel<true> with the draw in front: a molecule of `src` that keeps
+// m > 0 of its reads at `threshold` is claimed in `t` by the insert's rule, with m as its count, and
+// reads[index] += m.  A molecule that keeps none leaves no trace.  Claims are summed per wave into the
+// size word; the tally and total are not this kernel's.
+__global__ void __launch_bounds__(WG) molecules_downsample_kernel(Set t, const u64* __restrict__ keys,
+                                                                  const u64* __restrict__ cnt, int64_t n,
+                                                                  u64 threshold, u64 seed, u64 wave_reads) {
+  int claims = 0;
+  downsample_walk(
+      keys, cnt, n, seed, wave_reads,
+      [&](u64 stream, u64 j0, u64 step, u64 r) {
+        return Thinned{sct::downsample_thin_stride(stream, j0, step, r, threshold), 0};
+      },
+      [&](u64 key, const Thinned& m) {
+        if (m.kept == 0) return;
+        const uint32_t index = sct::mol_key_index(key, t.idx_shift);
+        atomicAdd(&t.reads[index], m.kept);
+        claims += set_claim<true>(t, key, index, m.kept);
+      });
+  add_claims(&t.words[W_SIZE], claims);
+}
+
+// The curve at one threshold: *reads += the reads kept, *molecules += the molecules that keep any.
+// The sums stay in lane registers and are reduced once per wave: one add per wave and word.
+__global__ void __launch_bounds__(WG) molecules_downsample_count_kernel(const u64* __restrict__ keys,
+                                                                        const u64* __restrict__ cnt, int64_t n,
+                                                                        u64 threshold, u64 seed, u64 wave_reads,
+                                                                        u64* __restrict__ reads,
+                                                                        u64* __restrict__ molecules) {
+  u64 kept = 0, alive = 0;
+  downsample_walk(
+      keys, cnt, n, seed, wave_reads,
+      [&](u64 stream, u64 j0, u64 step, u64 r) {
+        return Thinned{sct::downsample_thin_stride(stream, j0, step, r, threshold), 0};
+      },
+      [&](u64, const Thinned& m) {
+        kept += m.kept;
+        alive += m.kept != 0;
+      });
+  for (int o = 32; o > 0; o >>= 1) {
+    kept += __shfl_xor(kept, o);
+    alive += __shfl_xor(alive, o);
+  }
+  if ((threadIdx.x & 63) != 0) return;
+  if (kept) atomicAdd(reads, kept);
+  if (alive) atomicAdd(molecules, alive);
+}
+
+// The whole curve in one walk.  The k ascending thresholds lie in LDS; a read's bucket is the first
+// threshold that keeps it (a binary search), a molecule's bucket the lowest of its reads'.  Both are
+// counted into a per-workgroup LDS histogram -- a read or molecule that no threshold keeps counts
+// nowhere -- and at the end of the workgroup the inclusive prefix over the buckets turns "first kept
+// at t" into "kept at t": one 64-bit add per non-zero word.  reads[k] and molecules[k] are added to.
+struct CurvePoints {
+  u64 threshold[sct::kDownsampleMaxPoints];
+};
+__global__ void __launch_bounds__(WG) molecules_downsample_curve_kernel(const u64* __restrict__ keys,
+                                                                        const u64* __restrict__ cnt, int64_t n,
+                                                                        CurvePoints points, int k, u64 seed,
+                                                                        u64 wave_reads, u64* __restrict__ reads,
+                                                                        u64* __restrict__ molecules) {
+  constexpr int K = sct::kDownsampleMaxPoints;
+  __shared__ uint64_t threshold[K];
+  __shared__ u64 first_kept[2][K];  // [0] reads, [1] molecules, by bucket
+  for (int t = threadIdx.x; t < K; t += WG) {
+    threshold[t] = points.threshold[t < k ? t : k - 1];
+    first_kept[0][t] = first_kept[1][t] = 0;
+  }
+  __syncthreads();
+  downsample_walk(
+      keys, cnt, n, seed, wave_reads,
+      [&](u64 stream, u64 j0, u64 step, u64 r) {
+        Thinned m{0, k};
+        for (u64 j = j0; j < r; j += step) {
+          const int b = sct::downsample_bucket(sct::downsample_draw_at(stream, j), threshold, k);
+          if (b >= k) continue;
+          atomicAdd(&first_kept[0][b], 1ull);
+          m.kept += 1;
+          m.first = min(m.first, b);
+        }
+        return m;
+      },
+      [&](u64, const Thinned& m) {
+        if (m.first < k) atomicAdd(&first_kept[1][m.first], 1ull);
+      });
+  __syncthreads();
+  if ((int)threadIdx.x >= 2 * k) return;
+  const int what = (int)threadIdx.x / k, t = (int)threadIdx.x % k;
+  u64 sum = 0;
+  for (int b = 0; b <= t; ++b) sum += first_kept[what][b];
+  if (sum) atomicAdd(what == 0 ? &reads[t] : &molecules[t], sum);
+}
+
+// words[W_TALLY + k] += the reads of tally k kept at `threshold`: read j < from.n[k] draws under the
+// key no molecule can have (downsample_tally_key).  A grid stride over j, one add per wave and tally.
+struct TallyReads {
+  u64 n[4];
+};
+__global__ void __launch_bounds__(WG) molecules_downsample_tally_kernel(TallyReads from, u64 threshold, u64 seed,
+                                                                        u64* __restrict__ words) {
+  const u64 gid = (u64)blockIdx.x * WG + threadIdx.x, stride = (u64)gridDim.x * WG;
+  for (int k = 0; k < 4; ++k) {
+    const u64 stream = sct::downsample_stream(seed, sct::downsample_tally_key(k));
+    u64 kept = sct::downsample_thin_stride(stream, gid, stride, from.n[k], threshold);
+    for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);
+    if ((threadIdx.x & 63) == 0 && kept) atomicAdd(&words[W_TALLY + k], kept);
+  }
+}
+
 }  // namespace
 
 struct sct_molecules : Host {
@@ -1150,6 +1314,134 @@ int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
   return rc;
 }
 
+// ---- downsample
+
+// a molecule of at least this many reads is thinned by its whole wave (SCT_TUNE_DOWNSAMPLE_WAVE_READS;
+// DESIGN.md §3.10.7 has the sweep: 64 ahead of 256, 1024 and 4096 where few molecules carry half the reads)
+constexpr int64_t kDownsampleWaveReads = 64;
+u64 downsample_wave_reads() { return (u64)sct::tune(SCT_TUNE_DOWNSAMPLE_WAVE_READS, kDownsampleWaveReads); }
+
+// The curve of c's table as it stands, enqueued on `s`: reads[k] and molecules[k] (device words, zero
+// before) are added to.  One threshold runs the register form, more the LDS histogram.
+hipError_t curve_pass(const sct_molecules* c, const uint64_t* thresholds, int k, u64 seed, u64* reads, u64* molecules,
+                      hipStream_t s) {
+  const dim3 grid(grid_for(c->capacity, 4 * WG));
+  if (k == 1) {
+    hipLaunchKernelGGL(molecules_downsample_count_kernel, grid, dim3(WG), 0, s, c->t.keys, c->t.cnt, c->capacity,
+                       (u64)thresholds[0], seed, downsample_wave_reads(), reads, molecules);
+  } else {
+    CurvePoints points{};
+    for (int t = 0; t < k; ++t) points.threshold[t] = thresholds[t];
+    hipLaunchKernelGGL(molecules_downsample_curve_kernel, grid, dim3(WG), 0, s, c->t.keys, c->t.cnt, c->capacity,
+                       points, k, seed, downsample_wave_reads(), reads, molecules);
+  }
+  return hipGetLastError();
+}
+
+// reads[k] and molecules[k] (each nullable) written on `s` from the table as it stands
+int curve_device(sct_molecules* c, const uint64_t* thresholds, int k, u64 seed, uint64_t* d_reads,
+                 uint64_t* d_molecules, hipStream_t s) {
+  if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
+  void* blk = nullptr;
+  const size_t bytes = (size_t)k * 8;
+  SCT_HIP(sct::pool_alloc(&blk, 2 * bytes, s));
+  u64* sums = static_cast<u64*>(blk);
+  hipError_t e = hipMemsetAsync(blk, 0, 2 * bytes, s);
+  if (e == hipSuccess && c->size_bound > 0) e = curve_pass(c, thresholds, k, seed, sums, sums + k, s);
+  if (e == hipSuccess && d_reads) e = hipMemcpyAsync(d_reads, sums, bytes, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess && d_molecules) e = hipMemcpyAsync(d_molecules, sums + k, bytes, hipMemcpyDeviceToDevice, s);
+  sct::pool_free(blk, s);
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule downsample curve: %s", hipGetErrorString(e));
+  return leave(c, s);
+}
+
+int curve_check(const sct_molecules* c, const uint64_t* thresholds, int64_t k) {
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_CHECK(k >= 1 && k <= sct::kDownsampleMaxPoints, "downsample curve: %lld thresholds, outside [1, %d]",
+            (long long)k, sct::kDownsampleMaxPoints);
+  SCT_CHECK(thresholds != nullptr, "NULL thresholds");
+  SCT_CHECK(sct::downsample_thresholds_ok(thresholds, k),
+            "downsample curve: the thresholds must not decrease and none may be above 2^32");
+  return need_counted(c);
+}
+
+int downsample_check(const sct_molecules* dst, const sct_molecules* src, uint64_t threshold) {
+  SCT_CHECK(dst != nullptr && src != nullptr, "molecule counter is NULL");
+  SCT_CHECK(dst != src, "a molecule counter cannot be downsampled into itself");
+  if (int rc = need_counted(src); rc != SCT_OK) return rc;
+  if (int rc = need_counted(dst); rc != SCT_OK) return rc;
+  if (int rc = merge_check(dst, src); rc != SCT_OK) return rc;
+  SCT_CHECK(threshold <= sct::kDownsampleKeepAll, "downsample: threshold %llu is above 2^32",
+            (unsigned long long)threshold);
+  SCT_CHECK(dst->device == src->device,
+            "downsample: the counters live on devices %d and %d (downsample on the source's device, then merge)",
+            dst->device, src->device);
+  return SCT_OK;
+}
+
+// dst <- dst + src thinned at `threshold`, on `s` (the contract: include/sctools_hip.h).  Both counters
+// are counted and live on the device that is current.  The kept reads, molecules and tallies are
+// counted into scratch first and read back once; until then nothing of dst has changed.
+int downsample(sct_molecules* dst, sct_molecules* src, u64 threshold, u64 seed, hipStream_t s) {
+  SCT_TRY(enter_read(src, s));  // SCT_E_RANGE for a source that overflowed
+  const int64_t src_size = src->size_bound;
+  TallyReads tally{};
+  u64 tally_most = 0;
+  for (int k = 0; k < 4; ++k) {
+    tally.n[k] = src->h_words[W_TALLY + k];
+    tally_most = std::max(tally_most, tally.n[k]);
+  }
+  SCT_TRY(enter_read(dst, s));
+  const int64_t dst_size = dst->size_bound;
+  // the scratch has the layout of a counter's device words: the kept tallies where molecules_add_kernel
+  // looks for them, the kept reads and molecules in the two words before the counter's own
+  void* blk = nullptr;
+  SCT_HIP(sct::pool_alloc(&blk, W_NWORDS * 8, s));
+  u64* kept = static_cast<u64*>(blk);
+  enum { K_READS = 0, K_MOLECULES = 1 };
+  static_assert(K_MOLECULES < W_TALLY, "the kept sums lie below the tally");
+  const auto fail_with = [&](int rc) {
+    sct::pool_free(blk, s);
+    return rc;
+  };
+  hipError_t e = hipMemsetAsync(blk, 0, W_NWORDS * 8, s);
+  const uint64_t point = threshold;
+  if (e == hipSuccess && src_size > 0) e = curve_pass(src, &point, 1, seed, &kept[K_READS], &kept[K_MOLECULES], s);
+  if (e == hipSuccess && tally_most > 0) {
+    const int64_t most = (int64_t)std::min<u64>(tally_most, 1ull << 62);
+    hipLaunchKernelGGL(molecules_downsample_tally_kernel, dim3(grid_for(most, 64 * WG)), dim3(WG), 0, s, tally,
+                       threshold, seed, kept);
+    e = hipGetLastError();
+  }
+  // (dst's read-back words are free between two read_words)
+  if (e == hipSuccess) e = hipMemcpyAsync(dst->h_words, kept, W_NWORDS * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess)
+    return fail_with(sct::fail(SCT_E_HIP, "molecule downsample, counting the kept reads: %s", hipGetErrorString(e)));
+  const int64_t survivors = (int64_t)dst->h_words[K_MOLECULES];
+  u64 kept_total = dst->h_words[K_READS];
+  for (int k = 0; k < 4; ++k) kept_total += dst->h_words[W_TALLY + k];
+  const int64_t cap = sct::mol_merge_capacity(dst->capacity, dst_size, survivors);
+  if (cap == 0)
+    return fail_with(sct::fail(SCT_E_RANGE, "downsample: %lld + %lld molecules need a table of more than %lld slots",
+                               (long long)dst_size, (long long)survivors, (long long)sct::kTableMaxCapacity));
+  if (cap > dst->capacity)
+    if (int rc = grow(dst, cap / dst->capacity, s); rc != SCT_OK) return fail_with(rc);
+  if (survivors > 0)
+    hipLaunchKernelGGL(molecules_downsample_kernel, dim3(grid_for(src->capacity, 4 * WG)), dim3(WG), 0, s, dst->t,
+                       src->t.keys, src->t.cnt, src->capacity, threshold, seed, downsample_wave_reads());
+  // the kept tallies (reads[] was the thinning kernel's: nw = 0 here)
+  hipLaunchKernelGGL(molecules_add_kernel, dim3(1), dim3(WG), 0, s, dst->t.reads, dst->t.words, kept, kept, (int64_t)0);
+  const hipError_t launched = hipGetLastError();
+  sct::pool_free(blk, s);
+  dst->total += (int64_t)kept_total;
+  dst->size_bound = dst_size + survivors;  // a bound: the next read of the size word makes it exact
+  int rc = launched == hipSuccess ? SCT_OK : sct::fail(SCT_E_HIP, "molecule downsample: %s", hipGetErrorString(launched));
+  if (int rl = leave(dst, s); rc == SCT_OK) rc = rl;
+  if (int rl = leave(src, s); rc == SCT_OK) rc = rl;
+  return rc;
+}
+
 }  // namespace
 
 namespace {
@@ -1458,6 +1750,31 @@ extern "C" int sct_molecules_merge(sct_molecules* dst, sct_molecules* src, void*
   SCT_CHECK(dst != nullptr && src != nullptr, "molecule counter is NULL");
   if (int rc = merge_check(dst, src); rc != SCT_OK) return rc;
   return merge(dst, src, sct::as_stream(stream));
+}
+
+extern "C" int sct_molecules_downsample(sct_molecules* dst, sct_molecules* src, uint64_t threshold, uint64_t seed,
+                                        void* stream) {
+  if (int rc = downsample_check(dst, src, threshold); rc != SCT_OK) return rc;
+  SCT_ON_DEVICE_OF(dst);
+  return downsample(dst, src, (u64)threshold, (u64)seed, sct::as_stream(stream));
+}
+
+extern "C" int sct_molecules_downsample_curve(sct_molecules* c, const uint64_t* thresholds, int64_t k, uint64_t seed,
+                                              uint64_t* d_reads, uint64_t* d_molecules, void* stream) {
+  if (int rc = curve_check(c, thresholds, k); rc != SCT_OK) return rc;
+  SCT_ON_DEVICE_OF(c);
+  return curve_device(c, thresholds, (int)k, (u64)seed, d_reads, d_molecules, sct::as_stream(stream));
+}
+
+extern "C" int sct_molecules_downsample_curve_host(sct_molecules* c, const uint64_t* thresholds, int64_t k,
+                                                   uint64_t seed, uint64_t* reads, uint64_t* molecules) {
+  if (int rc = curve_check(c, thresholds, k); rc != SCT_OK) return rc;
+  SCT_ON_STAGE_OF(c, s);
+  Staged st(s);
+  st.add(reads, 8, (size_t)k), st.add(molecules, 8, (size_t)k);
+  if (int rc = st.alloc(); rc != SCT_OK) return rc;
+  return st.finish(curve_device(c, thresholds, (int)k, (u64)seed, st.dev<uint64_t>(0), st.dev<uint64_t>(1), s),
+                   "molecule downsample curve");
 }
 
 // ---- counting molecules per feature: the rows with their feature, and the count matrix

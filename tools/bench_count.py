@@ -23,7 +23,10 @@ route pairs(features=True) + np.unique, and the plain and counted updates beside
 timings and outputs (calls_step; profiles/ab_molecules_calls_<tag>.jsonl).  Then the directional
 clusters in both forms beside the one-step collapse, on the same reads with --umi-error substitutions
 per UMI base, and the updates and the one-step collapse beside an earlier library (directional_step;
-profiles/ab_umi_directional.jsonl).
+profiles/ab_umi_directional.jsonl).  Then downsampling on the same reads: downsample at two fractions,
+the saturation curve, merge and the host route beside them, SCT_TUNE_DOWNSAMPLE_WAVE_READS swept on a
+skewed table, and the updates, the collapse and the merge beside an earlier library (downsample_step;
+profiles/ab_downsample.jsonl).
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends
 the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
@@ -35,6 +38,7 @@ the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>
   python tools/bench_count.py --only matrix --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only calls --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only directional --umi-error 0.01 --parent-lib /path/to/earlier/libsctools_hip.so
+  python tools/bench_count.py --only downsample --parent-lib /path/to/earlier/libsctools_hip.so
 """
 import argparse
 import functools
@@ -48,7 +52,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420, "collapse": 600,
-         "merge": 600, "matrix": 600, "calls": 600, "directional": 600}  # seconds
+         "merge": 600, "matrix": 600, "calls": 600, "directional": 600, "downsample": 600}  # seconds
 MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
 HBM_BYTES_PER_S = 8e12
 
@@ -1194,6 +1198,203 @@ def directional_step(args):
     return out
 
 
+DOWNSAMPLE_CALLS = UPDATE_CALLS + ("sct_molecules_collapse", "sct_molecules_merge")
+DOWNSAMPLE_WAVE_READS = (64, 256, 1024, 4096)
+
+
+def _skewed_counter(nw, UL, device):
+    """A counted MoleculeCounter in which 0.1 % of the molecules carry half the reads: 2,000,000
+    molecules of 4 reads and 2,000 of 250, 1,000, 4,000 or 16,000 (a quarter each).  (counter, reads)."""
+    import torch
+    from sctools_amd import counting
+    light, heavy = 2_000_000, 2_000
+    g = torch.Generator(device=device).manual_seed(23)
+    table = torch.zeros(4096, dtype=torch.int64, device=device)  # 4096 distinct good UMI codes
+    t = torch.randperm(4 ** UL, device=device, generator=g)[:4096]
+    for p in range(UL):
+        table |= (((t >> (2 * p)) & 3) + 1) << (3 * p)
+    mol = torch.arange(light + heavy, device=device)
+    per = torch.full((light + heavy,), 4, dtype=torch.int64, device=device)
+    per[light:] = torch.tensor([250, 1000, 4000, 16000], device=device).repeat(heavy // 4)
+    row = torch.repeat_interleave(mol, per)
+    row = row[torch.randperm(row.numel(), device=device, generator=g)]
+    d_index = (row % nw).to(torch.int32).contiguous()
+    d_umi = table[row // nw].contiguous()
+    mc = counting.MoleculeCounter(nw, UL, capacity_hint=1 << 23, read_counts=True)
+    mc.update_device(d_index.data_ptr(), d_umi.data_ptr(), row.numel())
+    torch.cuda.synchronize()
+    assert len(mc) == light + heavy
+    return mc, int(row.numel())
+
+
+def downsample_step(args):
+    """Downsampling on the molecules step's reads as drawn: a counted table of all n reads, then, per
+    round and on that table, downsample at fractions 0.1 and 0.5 into an empty 64-slot counter (the
+    whole call, and the counting pass alone as the one-threshold curve; the insert pass is the rest),
+    saturation_curve at k = 16, the one-threshold curve in the register form beside the LDS form (the
+    same threshold given twice), and merge of the table into an empty counter, whose claim path is
+    downsample's.  Once: the host route pairs(reads=True) + numpy binomial + update at 0.5.  Then
+    SCT_TUNE_DOWNSAMPLE_WAVE_READS 64, 256, 1024 and 4096, interleaved, on a second table in which
+    0.1 % of the molecules carry half the reads.  And, alternating within every round through the C
+    ABI, this library and --parent-lib (skipped without it): the plain update, the counted update,
+    the one-step collapse and the merge into an empty counter, which must not be slower than the
+    parent's by more than the min-max spread of the parent's own rounds: the step fails, its profile
+    written, when one is.  Medians with min-max over --rounds; every round is one line of
+    profiles/ab_downsample.jsonl (ab_downsample_<tag>.jsonl for a tag other than "run"), the summary
+    its last."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, counting
+
+    nw, UL, n, hint, pool, inputs = _molecules_input(args)
+    d_index, d_umi, _ = inputs["shuffled"]
+    del inputs
+    torch.cuda.empty_cache()
+    this, old = _lib.lib(), _parent_lib(args, DOWNSAMPLE_CALLS)
+    vp = ctypes.c_void_p
+    d_out = torch.zeros(nw + 1, dtype=torch.int64, device=d_index.device)
+    d_curve = torch.zeros(2 * 64, dtype=torch.int64, device=d_index.device)
+
+    def synced(call):
+        def go():
+            assert call() in (0, None)
+            torch.cuda.synchronize()
+        return _time_ms(go)
+
+    def run(lib, counted):
+        """{what: ms} and the counts of one fresh counter of `lib`, through the C ABI"""
+        h, e = vp(), vp()
+        create = lib.sct_molecules_create_counted if counted else lib.sct_molecules_create
+        assert create(nw, 3, UL, hint, ctypes.byref(h)) == 0
+        assert create(nw, 3, UL, 64, ctypes.byref(e)) == 0
+        ms = {}
+        try:
+            ms["update"] = synced(lambda: lib.sct_molecules_update(h, vp(d_index.data_ptr()), vp(d_umi.data_ptr()), n, None))
+            if counted:
+                ms["collapse"] = synced(lambda: lib.sct_molecules_collapse(h, vp(d_out.data_ptr()),
+                                                                           vp(d_out.data_ptr() + 8 * nw), None))
+                ms["merge"] = synced(lambda: lib.sct_molecules_merge(e, h, None))
+            reads, molecules, tally = np.empty(nw, np.uint64), np.empty(nw, np.uint64), np.empty(3, np.uint64)
+            assert lib.sct_molecules_counts_host(h, _lib._ptr(reads), _lib._ptr(molecules), _lib._ptr(tally)) == 0
+        finally:
+            lib.sct_molecules_destroy(h)
+            lib.sct_molecules_destroy(e)
+        return ms, (int(reads.sum()), int(molecules.sum())) + tuple(int(t) for t in tally)
+
+    def curve_ms(mc, thresholds):
+        return synced(lambda: mc.saturation_curve_device(thresholds, d_curve.data_ptr(), d_curve.data_ptr() + 8 * 64))
+
+    def thin_ms(mc, threshold):
+        """(ms, (molecules, total, capacity)) of downsample into an empty 64-slot counter"""
+        with counting.MoleculeCounter(nw, UL, capacity_hint=64, read_counts=True) as into:
+            ms = synced(lambda: (mc.downsample_device(into, threshold), None)[1])
+            info = into.info()
+        return ms, (info["nmolecules"], info["total"], info["capacity"])
+
+    table = counting.MoleculeCounter(nw, UL, capacity_hint=hint, read_counts=True)
+    table.update_device(d_index.data_ptr(), d_umi.data_ptr(), n)
+    torch.cuda.synchronize()
+    fractions = {"0.1": counting.downsample_threshold(0.1), "0.5": counting.downsample_threshold(0.5)}
+    points = [counting.downsample_threshold((t + 1) / 16) for t in range(16)]
+    skewed, skewed_reads = _skewed_counter(nw, UL, d_index.device)
+
+    def this_only():
+        ms, facts = {}, {}
+        for name, threshold in fractions.items():
+            ms["downsample_%s" % name], facts["downsample_%s" % name] = thin_ms(table, threshold)
+            ms["count_pass_%s" % name] = curve_ms(table, [threshold])
+            ms["insert_pass_%s" % name] = ms["downsample_%s" % name] - ms["count_pass_%s" % name]
+            facts["curve_%s" % name] = (int(d_curve[0]), int(d_curve[64]))
+            ms["count_pass_lds_form_%s" % name] = curve_ms(table, [threshold, threshold])
+            assert facts["curve_%s" % name] == (int(d_curve[0]), int(d_curve[64])) == (int(d_curve[1]), int(d_curve[65]))
+        ms["curve_k16"] = curve_ms(table, points)
+        facts["curve_k16"] = (d_curve[:16].tolist(), d_curve[64:80].tolist())
+        for w in DOWNSAMPLE_WAVE_READS:
+            with _lib.tuning(downsample_wave_reads=w):
+                ms["skewed_downsample_0.5_w%d" % w], f = thin_ms(skewed, fractions["0.5"])
+                ms["skewed_curve_k16_w%d" % w] = curve_ms(skewed, points)
+            f = (f, d_curve[:16].tolist(), d_curve[64:80].tolist())
+            assert facts.setdefault("skewed", f) == f, (w, f)  # every W: the same numbers
+        return ms, facts
+
+    def host_route(threshold):
+        """the rows fetched, thinned by numpy and replayed through update: {part: ms}"""
+        out = {}
+        t = time.perf_counter()
+        index, umi, reads = table.pairs(reads=True)
+        out["pairs_ms"] = (time.perf_counter() - t) * 1e3
+        t = time.perf_counter()
+        kept = np.random.default_rng(0).binomial(reads, threshold / 2 ** 32)
+        index, umi = np.repeat(index, kept), np.repeat(umi, kept)
+        out["numpy_ms"] = (time.perf_counter() - t) * 1e3
+        t = time.perf_counter()
+        with counting.MoleculeCounter(nw, UL, capacity_hint=64, read_counts=True) as into:
+            into.update(index, umi)
+            out["molecules"] = len(into)
+        out["update_ms"] = (time.perf_counter() - t) * 1e3
+        out["total_ms"] = out["pairs_ms"] + out["numpy_ms"] + out["update_ms"]
+        return {k: round(v, 3) for k, v in out.items()}
+
+    run(this, True)  # warm-up: code objects, pool
+    this_only()
+    if old:
+        run(old, True)
+    lines, facts, counts = [], None, None
+    for r in range(args.rounds):
+        row = {"round": r, "n": n, "nw": nw}
+        for name, lib in (("this", this), ("parent", old))[::-1 if r % 2 else 1]:  # (who goes first alternates)
+            if lib is None:
+                continue
+            plain, c_plain = run(lib, False)
+            counted, c = run(lib, True)
+            assert c == c_plain == (counts or c), (c, c_plain, counts)  # every library and round: the same numbers
+            counts = c
+            row[name] = {"plain_update_ms": round(plain["update"], 3), "counted_update_ms": round(counted["update"], 3),
+                         "collapse_ms": round(counted["collapse"], 3), "merge_ms": round(counted["merge"], 3)}
+        ms, f = this_only()
+        assert f == (facts or f), (f, facts)
+        facts = f
+        row["downsample"] = {k + "_ms": round(v, 3) for k, v in ms.items()}
+        lines.append(row)
+    host = host_route(fractions["0.5"])
+    out = {"n": n, "nw": nw, "umi_length": UL, "capacity_hint": hint, "parent_lib": bool(old), "rounds": args.rounds,
+           "reads": counts[0], "molecules": counts[1], "table_capacity": table.info()["capacity"],
+           "skewed": {"reads": skewed_reads, "molecules": len(skewed), "capacity": skewed.info()["capacity"]},
+           "host_route_0.5": host}
+    table.close()
+    skewed.close()
+    for name in ("this", "parent", "downsample"):
+        if name in lines[0]:
+            out[name] = {}
+            for key in lines[0][name]:
+                a = [row[name][key] for row in lines]
+                out[name][key] = {"median": round(float(np.median(a)), 3), "min": min(a), "max": max(a)}
+    for name in fractions:
+        molecules, total, capacity = facts["downsample_%s" % name]
+        out["kept_%s" % name] = {"molecules": molecules, "total": total, "capacity": capacity,
+                                 "curve": facts["curve_%s" % name]}
+    out["curve_k16"] = {"reads": facts["curve_k16"][0], "molecules": facts["curve_k16"][1]}
+    sweep = {w: out["downsample"]["skewed_downsample_0.5_w%d_ms" % w]["median"]
+             + out["downsample"]["skewed_curve_k16_w%d_ms" % w]["median"] for w in DOWNSAMPLE_WAVE_READS}
+    out["wave_reads_sweep_ms"] = {str(w): round(v, 3) for w, v in sweep.items()}
+    out["wave_reads_best"] = min(sweep, key=sweep.get)
+    slower = []
+    if old:
+        out["vs_parent"] = {k: _vs_parent(out["this"][k], out["parent"][k]) for k in out["parent"]}
+        slower = ["%s: %s" % (k, v) for k, v in out["vs_parent"].items()
+                  if not v["agree"] and v["median_difference_ms"] > 0]
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    name = "ab_downsample.jsonl" if args.tag == "run" else "ab_downsample_%s.jsonl" % args.tag
+    with open(os.path.join(ROOT, "profiles", name), "w") as f:
+        for row in lines:
+            f.write(json.dumps(row, sort_keys=True) + "\n")
+        f.write(json.dumps(out, sort_keys=True) + "\n")
+    assert not slower, "slower than --parent-lib beyond that library's own spread: " + "; ".join(slower)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tag", default="run")
@@ -1205,7 +1406,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--n-collapse-host", type=int, default=200_000, help="molecules given to the dict collapse")
     ap.add_argument("--parent-lib", default="",
-                    help="collapse, merge, matrix, calls and directional steps: an earlier libsctools_hip.so to time "
+                    help="collapse, merge, matrix, calls, directional and downsample steps: an earlier libsctools_hip.so to time "
                          "beside this one")
     ap.add_argument("--umi-error", type=float, default=0.01,
                     help="directional step: the probability that a UMI base of a read is substituted")
@@ -1213,7 +1414,7 @@ def main():
     args = ap.parse_args()
     if args.step:
         whole = {"molecules": molecules_step, "collapse": collapse_step, "merge": merge_step, "matrix": matrix_step,
-                 "calls": calls_step, "directional": directional_step}
+                 "calls": calls_step, "directional": directional_step, "downsample": downsample_step}
         if args.step in whole:
             res = whole[args.step](args)
         else:
@@ -1258,6 +1459,12 @@ def main():
                            "sweeps": res["sweeps"]["sweeps_form1"]["median"],
                            "worklist": res["worklist"],
                            "ms": {k: v["median"] for k, v in res["this"].items()}}
+        elif "wave_reads_sweep_ms" in res:
+            short[step] = {"n": res["n"], "molecules": res["molecules"],
+                           "kept": {k: res["kept_%s" % k]["molecules"] for k in ("0.1", "0.5")},
+                           "wave_reads_sweep_ms": res["wave_reads_sweep_ms"], "host_ms": res["host_route_0.5"]["total_ms"],
+                           "ms": {k: v["median"] for k, v in res["downsample"].items() if "skewed" not in k},
+                           "merge_ms": res["this"]["merge_ms"]["median"]}
         elif "outputs_equal" in res:
             short[step] = {"n": res["n"], "outputs_equal": all(res["outputs_equal"].values()),
                            "faster_than_parent": res["faster_than_parent"],
