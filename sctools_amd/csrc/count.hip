@@ -81,17 +81,12 @@ __global__ void __launch_bounds__(WG) counter_init_kernel(Table t, int64_t capac
 template <bool MERGE>
 __global__ void __launch_bounds__(WG) counter_insert_kernel(Table t, const u64* __restrict__ codes, int64_t n,
                                                             long long base) {
-  const int64_t stride = (int64_t)gridDim.x * WG;
-  const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
-  const int64_t iters = (n + stride - 1) / stride;  // the same for every lane: the wave stays whole
   int claims = 0;
-  for (int64_t it = 0; it < iters; ++it) {
-    const int64_t i = it * stride + gid;
-    const bool active = i < n;
+  for_each_item(n, [&](int64_t i, bool active) {
     const u64 c = active ? __builtin_nontemporal_load(&codes[i]) : 0ull;
     const Merged m = MERGE ? wave_merge(active, c) : Merged{active, 1};
     if (m.rep) claims += table_add(t, c, m.count, base + i) ? 1 : 0;
-  }
+  });
   add_claims(&t.words[W_SIZE], claims);
 }
 
@@ -155,11 +150,8 @@ __global__ void __launch_bounds__(WG) counter_rehash_kernel(Table from, int64_t 
 __global__ void __launch_bounds__(WG) counter_compact_kernel(Table t, int64_t capacity, int64_t room,
                                                              long long* __restrict__ row_first,
                                                              uint32_t* __restrict__ row_slot) {
-  const int64_t stride = (int64_t)gridDim.x * WG;
-  const int64_t iters = (capacity + stride - 1) / stride;
-  for (int64_t it = 0; it < iters; ++it) {
-    const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
-    const bool occ = s < capacity && t.keys[s] != EMPTY;
+  for_each_item(capacity, [&](int64_t s, bool in) {
+    const bool occ = in && t.keys[s] != EMPTY;
     if (s == 0 && t.words[W_SIDE_COUNT] != 0) {  // the thread of slot 0 also writes the side row
       const u64 at = atomicAdd(&t.words[W_CURSOR], 1ull);
       if ((int64_t)at < room) {
@@ -172,7 +164,7 @@ __global__ void __launch_bounds__(WG) counter_compact_kernel(Table t, int64_t ca
       row_first[at] = t.first[s];
       row_slot[at] = (uint32_t)s;
     }
-  }
+  });
 }
 
 __global__ void __launch_bounds__(WG) counter_gather_kernel(Table t, int64_t rows,

@@ -47,7 +47,9 @@
 // clusters") are the transitive form of that pass: a label per slot in scratch,
 // the same probes in a discovery pass, then one launch per sweep over the molecules whose label may
 // still grow until a sweep moves nothing; the host reads two words between sweeps, and no kernel
-// waits for another.
+// waits for another.  Both passes probe through one neighbour_scan and compare one Candidate (reads,
+// code, slot) by one wave_max, and every kernel's loop over slots, rows or reads is one of
+// open_table.h's walks: for_each_item, for_each_wave_tile, wave_serial.
 //
 // Merging (include/sctools_hip.h, "merging molecule counters"): the rows of another counter -- its
 // table in place when both live on one device, its occupied rows compacted and copied into pool
@@ -62,6 +64,9 @@
 // The survivors are counted first, by the one-threshold form of the curve pass, so the target grows
 // to what survives; the curve itself is the same walk into a per-workgroup LDS histogram.  A molecule
 // with many reads is thinned by its whole wave, as the collapse shares a molecule's neighbours.
+// Merge and downsample share the growth in front of the claim kernel (make_room) and what follows
+// it (absorbed); the scratch of every device form is a sct::StreamBlock, given back stream-ordered
+// on every path out of its scope.
 //
 // A *feature counter* (include/sctools_hip.h, "counting molecules per feature") has a third key part
 // between the index and the UMI (molecules_feature_key.h).  FEATURES is a template parameter of the
@@ -193,21 +198,17 @@ template <bool MERGE, bool COUNTED, bool FEATURES>
 __global__ void __launch_bounds__(WG) molecules_insert_kernel(Set t, const int32_t* __restrict__ index,
                                                               const int32_t* __restrict__ feature,
                                                               const u64* __restrict__ umi, int64_t n) {
-  const int64_t stride = (int64_t)gridDim.x * WG;
-  const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
-  const int64_t iters = (n + stride - 1) / stride;  // the same for every lane: the wave stays whole
   WaveTally<FEATURES> wt;
   int claims = 0;
-  for (int64_t it = 0; it < iters; ++it) {
-    const int64_t i = it * stride + gid;
+  for_each_item(n, [&](int64_t i, bool in) {
     u64 key = 0;
     int what = R_SKIP;
-    if (i < n) what = classify_at<FEATURES>(t, index, feature, umi, i, &key);
+    if (in) what = classify_at<FEATURES>(t, index, feature, umi, i, &key);
     wt.see(what);
     const bool good = what == R_GOOD;
     const Merged m = MERGE ? wave_merge(good, key) : Merged{good, 1};
     if (m.rep) claims += set_add<COUNTED, FEATURES>(t, key, m.count);
-  }
+  });
   wt.flush(t, claims);
 }
 
@@ -274,34 +275,45 @@ __global__ void __launch_bounds__(WG) molecules_rehash_kernel(const u64* __restr
 
 // ---- UMI collapse (the contract's "parent" rule; one implementation for collapse and fetch_counted)
 
-// The parent rule over the candidates j0, j0 + step, ... of the molecule `key` held in `slot`: the
-// stored key that maximises (mreads, code) over the key itself and those of its 3 * L one-base
-// neighbours under the same index.  (0, 1) is the whole rule in one lane; (lane, 64) is a wave's
-// share of it, to be reduced by the same order.
-struct Best {
-  u64 code, reads, slot;
+// A stored molecule as a candidate for parent or label: ordered by (mreads, code), umi_support_less.
+struct Candidate {
+  u64 reads, code;
+  uint32_t slot;  // (capacity <= 2^31)
 };
-__device__ __forceinline__ Best parent_scan(const Set& t, u64 key, u64 slot, int j0, int step) {
-  Best b{key, t.cnt[slot], slot};
+__device__ __forceinline__ Candidate candidate_max(const Candidate& a, const Candidate& b) {
+  return sct::umi_support_less(a.reads, a.code, b.reads, b.code) ? b : a;
+}
+// the best of the 64 lanes' candidates, in every lane
+__device__ __forceinline__ Candidate wave_max(Candidate b) {
+  for (int o = 32; o > 0; o >>= 1)
+    b = candidate_max(b, Candidate{__shfl_xor(b.reads, o), __shfl_xor(b.code, o), __shfl_xor(b.slot, o)});
+  return b;
+}
+
+// visit(neighbour, slot, mreads) for every stored one among the neighbours j0, j0 + step, ... of `key`
+template <class Visit>
+__device__ __forceinline__ void neighbour_scan(const Set& t, u64 key, int j0, int step, Visit visit) {
   const int n1 = 3 * (t.umi_bits / t.kind);
   for (int j = j0; j < n1; j += step) {
     const u64 nb = sct::umi_neighbour(key, t.kind, j);
     const u64 s = find(t.keys, t.mask, nb);
-    if (s == NO_SLOT) continue;
-    const u64 r = t.cnt[s];
-    if (sct::umi_support_less(b.reads, b.code, r, nb)) b = Best{nb, r, s};
+    if (s != NO_SLOT) visit(nb, (uint32_t)s, t.cnt[s]);
   }
+}
+
+// The parent rule over the candidates j0, j0 + step, ... of the molecule `key` held in `slot`: the
+// stored key that maximises (mreads, code) over the key itself and those of its 3 * L one-base
+// neighbours under the same index.  (0, 1) is the whole rule in one lane; (lane, 64) is a wave's
+// share of it, to be reduced by wave_max.
+__device__ __forceinline__ Candidate parent_scan(const Set& t, u64 key, uint32_t slot, int j0, int step) {
+  Candidate b{t.cnt[slot], key, slot};
+  neighbour_scan(t, key, j0, step,
+                 [&](u64 nb, uint32_t s, u64 r) { b = candidate_max(b, Candidate{r, nb, s}); });
   return b;
 }
 
-__device__ __forceinline__ u64 parent_of(const Set& t, u64 key, u64 slot, u64* at) {
-  const Best b = parent_scan(t, key, slot, 0, 1);
-  *at = b.slot;
-  return b.code;
-}
-
 // the claim of a parent's slot: true in the one lane that flips its bit 0 -> 1
-__device__ __forceinline__ bool bitmap_claim(uint32_t* __restrict__ bitmap, u64 at) {
+__device__ __forceinline__ bool bitmap_claim(uint32_t* __restrict__ bitmap, uint32_t at) {
   const uint32_t bit = 1u << (at & 31);
   return (atomicOr(&bitmap[at >> 5], bit) & bit) == 0;
 }
@@ -312,21 +324,17 @@ __device__ __forceinline__ bool bitmap_claim(uint32_t* __restrict__ bitmap, u64 
 __global__ void __launch_bounds__(WG) molecules_collapse_kernel(Set t, int64_t capacity, uint32_t* __restrict__ bitmap,
                                                                 u64* __restrict__ collapsed,
                                                                 u64* __restrict__ ncorrected) {
-  const int64_t stride = (int64_t)gridDim.x * WG;
-  const int64_t iters = (capacity + stride - 1) / stride;  // the same for every lane: the wave stays whole
   uint32_t moved = 0;
-  for (int64_t it = 0; it < iters; ++it) {
-    const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
-    const u64 key = s < capacity ? t.keys[s] : EMPTY;
+  for_each_item(capacity, [&](int64_t s, bool in) {
+    const u64 key = in ? t.keys[s] : EMPTY;
     bool moves = false;
     if (key != EMPTY) {
-      u64 at;
-      const u64 parent = parent_of(t, key, (u64)s, &at);
-      moves = parent != key;
-      if (bitmap_claim(bitmap, at)) atomicAdd(&collapsed[sct::mol_key_index(key, t.idx_shift)], 1ull);
+      const Candidate parent = parent_scan(t, key, (uint32_t)s, 0, 1);
+      moves = parent.code != key;
+      if (bitmap_claim(bitmap, parent.slot)) atomicAdd(&collapsed[sct::mol_key_index(key, t.idx_shift)], 1ull);
     }
     moved += (uint32_t)__popcll(__ballot(moves));
-  }
+  });
   if ((threadIdx.x & 63) == 0 && moved) atomicAdd(ncorrected, (u64)moved);
 }
 
@@ -339,26 +347,17 @@ __global__ void __launch_bounds__(WG) molecules_collapse_wave_kernel(Set t, int6
                                                                      u64* __restrict__ collapsed,
                                                                      u64* __restrict__ ncorrected) {
   const int lane = threadIdx.x & 63;
-  const int64_t nwaves = (int64_t)gridDim.x * (WG / 64);
   uint32_t moved = 0;  // the same in every lane
-  // capacity is a multiple of 64, so base + lane < capacity and the loop is wave-uniform
-  for (int64_t base = (((int64_t)blockIdx.x * WG + threadIdx.x) >> 6) * 64; base < capacity; base += nwaves * 64) {
+  for_each_wave_tile(capacity, [&](int64_t base) {  // (capacity is a multiple of 64: base + lane < capacity)
     const u64 mine = t.keys[base + lane];
-    u64 todo = __ballot(mine != EMPTY);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
+    wave_serial(__ballot(mine != EMPTY), [&](int src) {
       const u64 key = __shfl(mine, src);
-      Best b = parent_scan(t, key, (u64)(base + src), lane, 64);
-      for (int o = 32; o > 0; o >>= 1) {
-        const Best c{__shfl_xor(b.code, o), __shfl_xor(b.reads, o), __shfl_xor(b.slot, o)};
-        if (sct::umi_support_less(b.reads, b.code, c.reads, c.code)) b = c;
-      }
+      const Candidate b = wave_max(parent_scan(t, key, (uint32_t)(base + src), lane, 64));
       if (lane == 0 && bitmap_claim(bitmap, b.slot))
         atomicAdd(&collapsed[sct::mol_key_index(key, t.idx_shift)], 1ull);
       moved += b.code != key;
-    }
-  }
+    });
+  });
   if (lane == 0 && moved) atomicAdd(ncorrected, (u64)moved);
 }
 
@@ -366,17 +365,13 @@ __global__ void __launch_bounds__(WG) molecules_collapse_wave_kernel(Set t, int6
 // lab[slot] are the slot of the best ancestor of the slot's molecule known so far (capacity <= 2^31),
 // meaningful where keys is occupied.  A label names a stored molecule, so it is compared by
 // (cnt[label], keys[label]).  The top bit says that the label may still grow: the molecule has an
-// in-neighbour whose own word has the bit.  A word without it is final.
+// in-neighbour whose own word has the bit.  A word without it is final.  Two molecules of a cluster
+// share index and feature bits, so the labels' order (umi_label_less) is the candidates'.
 
 constexpr uint32_t kLabelOpen = 1u << 31, kLabelSlot = kLabelOpen - 1;
 
-struct Label {
-  u64 reads, code;
-  uint32_t slot;
-};
-__device__ __forceinline__ Label label_at(const Set& t, uint32_t slot) { return Label{t.cnt[slot], t.keys[slot], slot}; }
-__device__ __forceinline__ Label label_max(const Label& a, const Label& b) {
-  return sct::umi_label_less(a.reads, a.code, b.reads, b.code) ? b : a;
+__device__ __forceinline__ Candidate label_at(const Set& t, uint32_t slot) {
+  return Candidate{t.cnt[slot], t.keys[slot], slot};
 }
 // a word is read and written while other waves do the same: whole words, in any order
 __device__ __forceinline__ uint32_t label_load(const uint32_t* lab, u64 slot) {
@@ -404,10 +399,8 @@ __global__ void __launch_bounds__(WG) molecules_directional_kernel(Set t, int64_
                                                                    int64_t room, u64* __restrict__ cursor,
                                                                    u64* __restrict__ changed) {
   const int lane = threadIdx.x & 63;
-  const int64_t nwaves = (int64_t)gridDim.x * (WG / 64);
-  const int n1 = 3 * (t.umi_bits / t.kind);
   bool moved = false;  // the same in every lane
-  for (int64_t base = (((int64_t)blockIdx.x * WG + threadIdx.x) >> 6) * 64; base < n; base += nwaves * 64) {  // wave-uniform
+  for_each_wave_tile(n, [&](int64_t base) {
     const int64_t i = base + lane;
     uint32_t slot = 0;
     u64 mine = EMPTY;
@@ -415,43 +408,35 @@ __global__ void __launch_bounds__(WG) molecules_directional_kernel(Set t, int64_
       slot = LISTED ? list[i] : (uint32_t)i;
       mine = t.keys[slot];
     }
-    u64 todo = __ballot(mine != EMPTY);
     u64 still_open = 0;
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
+    wave_serial(__ballot(mine != EMPTY), [&](int src) {
       const u64 key = __shfl(mine, src);
       const uint32_t v = __shfl(slot, src);
       const u64 v_reads = t.cnt[v];
       const uint32_t word = DISCOVER ? v : label_load(lab, v);
       const uint32_t was = word & kLabelSlot;
       // (lab[x] is never below x)
-      Label b = DISCOVER ? Label{v_reads, key, v} : label_at(t, label_load(lab, was) & kLabelSlot);
+      Candidate b = DISCOVER ? Candidate{v_reads, key, v} : label_at(t, label_load(lab, was) & kLabelSlot);
       bool open = false;
-      for (int j = lane; j < n1; j += 64) {
-        const u64 nb = sct::umi_neighbour(key, t.kind, j);
-        const u64 s = find(t.keys, t.mask, nb);
-        if (s == NO_SLOT) continue;
-        const u64 r = t.cnt[s];
-        if (!sct::umi_directional_edge(r, v_reads)) continue;
+      neighbour_scan(t, key, lane, 64, [&](u64 nb, uint32_t s, u64 r) {
+        if (!sct::umi_directional_edge(r, v_reads)) return;
         const uint32_t theirs = DISCOVER ? kLabelOpen : label_load(lab, s);
         open |= (theirs & kLabelOpen) != 0;
-        b = label_max(b, DISCOVER ? Label{r, nb, (uint32_t)s} : label_at(t, theirs & kLabelSlot));
-      }
-      for (int o = 32; o > 0; o >>= 1)
-        b = label_max(b, Label{__shfl_xor(b.reads, o), __shfl_xor(b.code, o), __shfl_xor(b.slot, o)});
+        b = candidate_max(b, DISCOVER ? Candidate{r, nb, s} : label_at(t, theirs & kLabelSlot));
+      });
+      b = wave_max(b);
       const bool any_open = __ballot(open) != 0;
       const uint32_t now = b.slot | (any_open ? kLabelOpen : 0);
       if (lane == 0 && (DISCOVER || now != word)) __atomic_store_n(&lab[v], now, __ATOMIC_RELAXED);
       still_open |= any_open ? 1ull << src : 0;
       moved |= b.slot != was;
-    }
+    });
     if (worklist) {
       const bool listed = (still_open >> lane) & 1;
       const u64 at = compact_at(listed, cursor);
       if (listed && (int64_t)at < room) worklist[at] = slot;
     }
-  }
+  });
   if (!DISCOVER && lane == 0 && moved) atomicOr(changed, 1ull);
 }
 
@@ -461,19 +446,16 @@ __global__ void __launch_bounds__(WG) molecules_directional_count_kernel(Set t, 
                                                                          const uint32_t* __restrict__ lab,
                                                                          u64* __restrict__ collapsed,
                                                                          u64* __restrict__ ncorrected) {
-  const int64_t stride = (int64_t)gridDim.x * WG;
-  const int64_t iters = (capacity + stride - 1) / stride;  // the same for every lane: the wave stays whole
   uint32_t moved = 0;
-  for (int64_t it = 0; it < iters; ++it) {
-    const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
-    const u64 key = s < capacity ? t.keys[s] : EMPTY;
+  for_each_item(capacity, [&](int64_t s, bool in) {
+    const u64 key = in ? t.keys[s] : EMPTY;
     const bool occ = key != EMPTY;
     const bool root = occ && (lab[s] & kLabelSlot) == (uint32_t)s;
     const u64 index = occ ? sct::mol_key_index(key, t.idx_shift) : 0;
     const Merged m = wave_merge(root, index);
     if (m.rep) atomicAdd(&collapsed[index], m.count);
     moved += (uint32_t)__popcll(__ballot(occ && !root));
-  }
+  });
   if ((threadIdx.x & 63) == 0 && moved) atomicAdd(ncorrected, (u64)moved);
 }
 
@@ -485,11 +467,8 @@ __global__ void __launch_bounds__(WG) molecules_compact_kernel(const u64* __rest
                                                                const u64* __restrict__ cnt, int64_t capacity,
                                                                u64* __restrict__ cursor, int64_t room,
                                                                u64* __restrict__ out_key, void* __restrict__ beside) {
-  const int64_t stride = (int64_t)gridDim.x * WG;
-  const int64_t iters = (capacity + stride - 1) / stride;  // the same for every lane: the wave stays whole
-  for (int64_t it = 0; it < iters; ++it) {
-    const int64_t s = it * stride + (int64_t)blockIdx.x * WG + threadIdx.x;
-    const u64 key = s < capacity ? keys[s] : EMPTY;
+  for_each_item(capacity, [&](int64_t s, bool in) {
+    const u64 key = in ? keys[s] : EMPTY;
     const bool occ = key != EMPTY;
     const u64 at = compact_at(occ, cursor);
     if (occ && (int64_t)at < room) {
@@ -497,7 +476,7 @@ __global__ void __launch_bounds__(WG) molecules_compact_kernel(const u64* __rest
       if (BESIDE == BESIDE_SLOT) static_cast<uint32_t*>(beside)[at] = (uint32_t)s;
       if (BESIDE == BESIDE_COUNT) static_cast<u64*>(beside)[at] = cnt[s];
     }
-  }
+  });
 }
 
 // the sorted keys as rows: index, UMI and, if asked, the feature.  SLOTS: `slots` (the keys' slot
@@ -511,16 +490,14 @@ __global__ void __launch_bounds__(WG) molecules_emit_kernel(Set t, const u64* __
                                                             u64* __restrict__ parent, const uint32_t* __restrict__ lab) {
   for (int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WG) {
     const u64 key = keys[r];
-    const u64 slot = SLOTS ? slots[r] : 0;  // (loaded with the key, ahead of the stores)
+    const uint32_t slot = SLOTS ? slots[r] : 0;  // (loaded with the key, ahead of the stores)
     index[r] = (int32_t)sct::mol_key_index(key, t.idx_shift);
     if (feature) feature[r] = (int32_t)sct::mol_fkey_feature(key, t.feat_bits, t.umi_bits);
     umi[r] = sct::mol_key_umi(key, t.umi_bits);
     if (!SLOTS) continue;
     if (mreads) mreads[r] = t.cnt[slot];
-    if (parent) {
-      u64 at;
-      parent[r] = sct::mol_key_umi(lab ? t.keys[lab[slot] & kLabelSlot] : parent_of(t, key, slot, &at), t.umi_bits);
-    }
+    if (parent)
+      parent[r] = sct::mol_key_umi(lab ? t.keys[lab[slot] & kLabelSlot] : parent_scan(t, key, slot, 0, 1).code, t.umi_bits);
   }
 }
 
@@ -539,14 +516,13 @@ __device__ __forceinline__ bool row_is_head(const u64* __restrict__ keys, int64_
 __global__ void __launch_bounds__(WG) molecules_matrix_heads_kernel(const u64* __restrict__ keys, int64_t rows,
                                                                     int umi_bits, u64* __restrict__ heads) {
   const int lane = threadIdx.x & 63;
-  const int64_t ntiles = (rows + 63) / 64, nwaves = (int64_t)gridDim.x * (WG / 64);
-  for (int64_t tile = ((int64_t)blockIdx.x * WG + threadIdx.x) >> 6; tile < ntiles; tile += nwaves) {  // wave-uniform
-    const int64_t r = tile * 64 + lane;
+  for_each_wave_tile(rows, [&](int64_t base) {
+    const int64_t r = base + lane;
     const bool in = r < rows;
     const u64 key = in ? keys[r] : 0;
     const u64 m = __ballot(row_is_head(keys, r, in, key, umi_bits));
-    if (lane == 0) heads[tile] = (u64)__popcll(m);
-  }
+    if (lane == 0) heads[base >> 6] = (u64)__popcll(m);
+  });
 }
 
 // base[tile] = the entries that open before the tile (the scan of heads[]).  Row r belongs to entry
@@ -568,14 +544,13 @@ __global__ void __launch_bounds__(WG) molecules_matrix_fill_kernel(Set t, const 
                                                                    u64* __restrict__ collapsed) {
   const int lane = threadIdx.x & 63;
   const u64 at_or_below = ~0ull >> (63 - lane), below = at_or_below >> 1;
-  const int64_t ntiles = (rows + 63) / 64, nwaves = (int64_t)gridDim.x * (WG / 64);
-  for (int64_t tile = ((int64_t)blockIdx.x * WG + threadIdx.x) >> 6; tile < ntiles; tile += nwaves) {  // wave-uniform
-    const int64_t r = tile * 64 + lane;
+  for_each_wave_tile(rows, [&](int64_t row0) {
+    const int64_t r = row0 + lane;
     const bool in = r < rows;
     const u64 key = in ? keys[r] : 0;
     const bool head = row_is_head(keys, r, in, key, t.umi_bits);
     const u64 heads = __ballot(head), valid = __ballot(in);
-    const u64 e = base[tile] + (u64)__popcll(heads & at_or_below) - 1;  // lane 0 of tile 0 is a head: e >= 0
+    const u64 e = base[row0 >> 6] + (u64)__popcll(heads & at_or_below) - 1;  // lane 0 of tile 0 is a head: e >= 0
     if (head) {
       feature[e] = (int32_t)sct::mol_fkey_feature(key, t.feat_bits, t.umi_bits);
       atomicAdd(&row_entries[sct::mol_key_index(key, t.idx_shift)], 1ull);
@@ -602,7 +577,7 @@ __global__ void __launch_bounds__(WG) molecules_matrix_fill_kernel(Set t, const 
       const u64 n = (u64)__popcll(images & run);
       if (first && n) atomicAdd(&collapsed[e], n);
     }
-  }
+  });
 }
 
 // ---- merge (include/sctools_hip.h, "merging molecule counters")
@@ -617,19 +592,15 @@ __global__ void __launch_bounds__(WG) molecules_matrix_fill_kernel(Set t, const 
 template <bool COUNTED>
 __global__ void __launch_bounds__(WG) molecules_merge_kernel(Set t, const u64* __restrict__ keys,
                                                              const u64* __restrict__ cnt, int64_t n) {
-  const int64_t stride = (int64_t)gridDim.x * WG;
-  const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
-  const int64_t iters = (n + stride - 1) / stride;  // the same for every lane: the wave stays whole
   int claims = 0;
-  for (int64_t it = 0; it < iters; ++it) {
-    const int64_t i = it * stride + gid;
+  for_each_item(n, [&](int64_t i, bool in) {
     u64 key = EMPTY, count = 0;
-    if (i < n) {
+    if (in) {
       key = __builtin_nontemporal_load(&keys[i]);
       if (COUNTED) count = __builtin_nontemporal_load(&cnt[i]);
     }
     if (key != EMPTY) claims += set_claim<COUNTED>(t, key, sct::mol_key_index(key, t.idx_shift), count);
-  }
+  });
   add_claims(&t.words[W_SIZE], claims);
 }
 
@@ -661,13 +632,9 @@ template <class Share, class Molecule>
 __device__ __forceinline__ void downsample_walk(const u64* __restrict__ keys, const u64* __restrict__ cnt, int64_t n,
                                                 u64 seed, u64 wave_reads, Share share, Molecule molecule) {
   const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * WG;
-  const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
-  const int64_t iters = (n + stride - 1) / stride;  // the same for every lane: the wave stays whole
-  for (int64_t it = 0; it < iters; ++it) {
-    const int64_t i = it * stride + gid;
+  for_each_item(n, [&](int64_t i, bool in) {
     u64 key = EMPTY, r = 0;
-    if (i < n) {
+    if (in) {
       key = __builtin_nontemporal_load(&keys[i]);
       r = __builtin_nontemporal_load(&cnt[i]);
     }
@@ -675,18 +642,15 @@ __device__ __forceinline__ void downsample_walk(const u64* __restrict__ keys, co
     const u64 stream = sct::downsample_stream(seed, key);
     const bool heavy = occ && r >= wave_reads;
     if (occ && !heavy) molecule(key, share(stream, 0, 1, r));
-    u64 todo = __ballot(heavy);
-    while (todo) {  // wave-uniform
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
+    wave_serial(__ballot(heavy), [&](int src) {
       Thinned m = share(__shfl(stream, src), (u64)lane, 64, __shfl(r, src));
       for (int o = 32; o > 0; o >>= 1) {
         m.kept += __shfl_xor(m.kept, o);
         m.first = min(m.first, __shfl_xor(m.first, o));
       }
       if (lane == src) molecule(key, m);
-    }
-  }
+    });
+  });
 }
 
 // Thin-and-claim, molecules_merge_kernel<true> with the draw in front: a molecule of `src` that keeps
@@ -1158,15 +1122,14 @@ int collapse_device(sct_molecules* c, int method, uint64_t* d_collapsed, uint64_
   if (method == SCT_COLLAPSE_DIRECTIONAL) return collapse_directional_device(c, d_collapsed, d_ncorrected, s);
   if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
   const size_t bytes = CollapseScratch::bytes(c, false);
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, bytes, s));
-  const CollapseScratch cs(c, static_cast<uint8_t*>(blk));
-  hipError_t e = hipMemsetAsync(blk, 0, bytes, s);
+  sct::StreamBlock blk(s);
+  SCT_HIP(blk.alloc(bytes));
+  const CollapseScratch cs(c, blk.bytes());
+  hipError_t e = hipMemsetAsync(blk.p, 0, bytes, s);
   if (e == hipSuccess) e = hipMemsetAsync(d_collapsed, 0, (size_t)c->t.nw * 8, s);
   if (e == hipSuccess && c->size_bound > 0)
     e = collapse_pass(c, cs.bitmap, reinterpret_cast<u64*>(d_collapsed), cs.ncorrected, s);
   if (e == hipSuccess && d_ncorrected) e = hipMemcpyAsync(d_ncorrected, cs.ncorrected, 8, hipMemcpyDeviceToDevice, s);
-  sct::pool_free(blk, s);
   if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule collapse: %s", hipGetErrorString(e));
   return leave(c, s);
 }
@@ -1197,26 +1160,53 @@ int merge_check(const sct_molecules* dst, const sct_molecules* src) {
   return SCT_OK;
 }
 
-// src's occupied rows, dense and unsorted, into a pool block on src's device on `ss` (src's device
-// is current): keys[rows] at its head, then *cnt = cnt[rows] for a counted counter, written by the
-// compaction beside the keys.
-int merge_compact(sct_molecules* src, int64_t rows, hipStream_t ss, void** blk, const u64** cnt) {
+// Room in dst, which holds `size` molecules, for `incoming` more, every one of which may be new
+// (molecules_merge_plan.h): the table is grown on `s` if it must be.  `what` names the operation.
+int make_room(sct_molecules* dst, int64_t size, int64_t incoming, const char* what, hipStream_t s) {
+  const int64_t cap = sct::mol_merge_capacity(dst->capacity, size, incoming);
+  if (cap == 0)
+    return sct::fail(SCT_E_RANGE, "%s: %lld + %lld molecules need a table of more than %lld slots", what,
+                     (long long)size, (long long)incoming, (long long)sct::kTableMaxCapacity);
+  return cap > dst->capacity ? grow(dst, cap / dst->capacity, s) : SCT_OK;
+}
+
+// What follows the claim kernel of a merge or a downsample on `s`: from_reads[nw] and the tallies of
+// from_words added to dst's, `total` reads and `incoming` molecules more in dst's books (the size a
+// bound: the next read of the size word makes it exact), and the work recorded in both counters, the
+// first failure kept.  src's later work on `ss`, and src_rows (its scratch, if any) going back there
+// with src's device current, wait for the kernels that read them.
+int absorbed(sct_molecules* dst, sct_molecules* src, const u64* from_reads, const u64* from_words, int64_t nw,
+             int64_t total, int64_t incoming, const char* what, hipStream_t s, hipStream_t ss,
+             sct::StreamBlock* src_rows = nullptr) {
+  hipLaunchKernelGGL(molecules_add_kernel, dim3(grid_for(nw, 4 * WG)), dim3(WG), 0, s, dst->t.reads, dst->t.words,
+                     from_reads, from_words, nw);
+  const hipError_t launched = hipGetLastError();
+  dst->total += total;
+  dst->size_bound += incoming;
+  int rc = launched == hipSuccess ? SCT_OK : sct::fail(SCT_E_HIP, "molecule %s: %s", what, hipGetErrorString(launched));
+  if (int rl = leave(dst, s); rc == SCT_OK) rc = rl;
+  SCT_ON_DEVICE_OF(src);
+  if (ss != s) (void)hipStreamWaitEvent(ss, dst->last, 0);
+  if (src_rows) src_rows->free();
+  if (int rl = leave(src, ss); rc == SCT_OK) rc = rl;
+  return rc;
+}
+
+// src's occupied rows, dense and unsorted, into `blk`, a pool block on src's device and stream (src's
+// device is current): keys[rows] at its head, then *cnt = cnt[rows] for a counted counter, written by
+// the compaction beside the keys.
+int merge_compact(sct_molecules* src, int64_t rows, sct::StreamBlock& blk, const u64** cnt) {
   Carve cv;
   const size_t o_keys = cv.take((size_t)rows * 8), o_cnt = src->counted ? cv.take((size_t)rows * 8) : 0;
-  SCT_HIP(sct::pool_alloc(blk, cv.size, ss));
-  uint8_t* b = static_cast<uint8_t*>(*blk);
-  u64* counts = src->counted ? reinterpret_cast<u64*>(b + o_cnt) : nullptr;
+  SCT_HIP(blk.alloc(cv.size));
+  u64* counts = src->counted ? reinterpret_cast<u64*>(blk.bytes() + o_cnt) : nullptr;
   *cnt = counts;
-  hipError_t e = zero_cursor(&src->t.words[W_CURSOR], ss);
+  hipError_t e = zero_cursor(&src->t.words[W_CURSOR], blk.s);
   if (e == hipSuccess) {
-    compact(src, counts ? BESIDE_COUNT : BESIDE_NONE, rows, reinterpret_cast<u64*>(b + o_keys), counts, ss);
+    compact(src, counts ? BESIDE_COUNT : BESIDE_NONE, rows, reinterpret_cast<u64*>(blk.bytes() + o_keys), counts, blk.s);
     e = hipGetLastError();
   }
-  if (e != hipSuccess) {
-    sct::pool_free(*blk, ss);
-    *blk = nullptr;
-    return sct::fail(SCT_E_HIP, "molecule merge, compacting the source: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule merge, compacting the source: %s", hipGetErrorString(e));
   return SCT_OK;
 }
 
@@ -1239,12 +1229,7 @@ int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
   const int64_t src_size = src->size_bound;
   SCT_ON_DEVICE_OF(dst);
   SCT_TRY(enter_read(dst, s));
-  const int64_t dst_size = dst->size_bound;
-  const int64_t cap = sct::mol_merge_capacity(dst->capacity, dst_size, src_size);
-  if (cap == 0)
-    return sct::fail(SCT_E_RANGE, "merge: %lld + %lld molecules need a table of more than %lld slots",
-                     (long long)dst_size, (long long)src_size, (long long)sct::kTableMaxCapacity);
-  if (cap > dst->capacity) SCT_TRY(grow(dst, cap / dst->capacity, s));
+  SCT_TRY(make_room(dst, dst->size_bound, src_size, "merge", s));
 
   const int64_t nw = dst->t.nw;
   const u64* keys = src->t.keys;
@@ -1252,13 +1237,12 @@ int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
   const u64* from_reads = src->t.reads;
   const u64* from_words = src->t.words;
   int64_t nrows = src->capacity;
-  void* src_blk = nullptr;
-  void* dst_blk = nullptr;
+  sct::StreamBlock src_blk(ss), dst_blk(s);
   if (dense) {
     const u64* src_cnt = nullptr;  // in src_blk, whose head is the keys
     if (src_size > 0) {
       SCT_ON_DEVICE_OF(src);
-      SCT_TRY(merge_compact(src, src_size, ss, &src_blk, &src_cnt));
+      SCT_TRY(merge_compact(src, src_size, src_blk, &src_cnt));
     }
     {  // src's arrays are read by dst's stream from here on: after what src's stream has enqueued
       SCT_ON_DEVICE_OF(src);
@@ -1267,21 +1251,18 @@ int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
     Carve cv;
     const size_t o_words = cv.take(W_NWORDS * 8), o_reads = cv.take((size_t)nw * 8);
     const size_t o_keys = cv.take((size_t)src_size * 8), o_cnt = src->counted ? cv.take((size_t)src_size * 8) : 0;
-    hipError_t e = sct::pool_alloc(&dst_blk, cv.size, s);
-    uint8_t* b = static_cast<uint8_t*>(dst_blk);
+    hipError_t e = dst_blk.alloc(cv.size);
+    uint8_t* b = dst_blk.bytes();
     if (e == hipSuccess && ss != s) e = hipStreamWaitEvent(s, src->last, 0);
     if (e == hipSuccess) e = hipMemcpyPeerAsync(b + o_words, dst->device, src->t.words, src->device, W_NWORDS * 8, s);
     if (e == hipSuccess) e = hipMemcpyPeerAsync(b + o_reads, dst->device, src->t.reads, src->device, (size_t)nw * 8, s);
     if (e == hipSuccess && src_size > 0)
-      e = hipMemcpyPeerAsync(b + o_keys, dst->device, src_blk, src->device, (size_t)src_size * 8, s);
+      e = hipMemcpyPeerAsync(b + o_keys, dst->device, src_blk.p, src->device, (size_t)src_size * 8, s);
     if (e == hipSuccess && src_size > 0 && src->counted)
       e = hipMemcpyPeerAsync(b + o_cnt, dst->device, src_cnt, src->device, (size_t)src_size * 8, s);
     if (e != hipSuccess) {
-      // nothing of dst has changed; the scratch goes back after what was enqueued
-      if (dst_blk) sct::pool_free(dst_blk, s);
+      // nothing of dst has changed; src's rows go back on its own stream, after the copies that read them
       (void)hipStreamSynchronize(s);
-      SCT_ON_DEVICE_OF(src);
-      if (src_blk) sct::pool_free(src_blk, ss);
       return sct::fail(SCT_E_HIP, "molecule merge, copying the source's rows: %s", hipGetErrorString(e));
     }
     from_words = reinterpret_cast<const u64*>(b + o_words);
@@ -1297,21 +1278,7 @@ int merge(sct_molecules* dst, sct_molecules* src, hipStream_t s) {
     else
       hipLaunchKernelGGL(molecules_merge_kernel<false>, grid, dim3(WG), 0, s, dst->t, keys, nullptr, nrows);
   }
-  hipLaunchKernelGGL(molecules_add_kernel, dim3(grid_for(nw, 4 * WG)), dim3(WG), 0, s, dst->t.reads, dst->t.words,
-                     from_reads, from_words, nw);
-  const hipError_t launched = hipGetLastError();
-  if (dst_blk) sct::pool_free(dst_blk, s);
-  dst->total += src->total;
-  dst->size_bound = dst_size + src_size;  // a bound: the next read of the size word makes it exact
-  int rc = launched == hipSuccess ? SCT_OK : sct::fail(SCT_E_HIP, "molecule merge: %s", hipGetErrorString(launched));
-  if (int rl = leave(dst, s); rc == SCT_OK) rc = rl;
-  {  // src's later work, and its scratch going back, wait for the merge that reads them
-    SCT_ON_DEVICE_OF(src);
-    if (ss != s) (void)hipStreamWaitEvent(ss, dst->last, 0);
-    if (src_blk) sct::pool_free(src_blk, ss);
-    if (int rl = leave(src, ss); rc == SCT_OK) rc = rl;
-  }
-  return rc;
+  return absorbed(dst, src, from_reads, from_words, nw, src->total, src_size, "merge", s, ss, &src_blk);
 }
 
 // ---- downsample
@@ -1342,15 +1309,14 @@ hipError_t curve_pass(const sct_molecules* c, const uint64_t* thresholds, int k,
 int curve_device(sct_molecules* c, const uint64_t* thresholds, int k, u64 seed, uint64_t* d_reads,
                  uint64_t* d_molecules, hipStream_t s) {
   if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
-  void* blk = nullptr;
+  sct::StreamBlock blk(s);
   const size_t bytes = (size_t)k * 8;
-  SCT_HIP(sct::pool_alloc(&blk, 2 * bytes, s));
-  u64* sums = static_cast<u64*>(blk);
-  hipError_t e = hipMemsetAsync(blk, 0, 2 * bytes, s);
+  SCT_HIP(blk.alloc(2 * bytes));
+  u64* sums = static_cast<u64*>(blk.p);
+  hipError_t e = hipMemsetAsync(sums, 0, 2 * bytes, s);
   if (e == hipSuccess && c->size_bound > 0) e = curve_pass(c, thresholds, k, seed, sums, sums + k, s);
   if (e == hipSuccess && d_reads) e = hipMemcpyAsync(d_reads, sums, bytes, hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess && d_molecules) e = hipMemcpyAsync(d_molecules, sums + k, bytes, hipMemcpyDeviceToDevice, s);
-  sct::pool_free(blk, s);
   if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule downsample curve: %s", hipGetErrorString(e));
   return leave(c, s);
 }
@@ -1392,19 +1358,14 @@ int downsample(sct_molecules* dst, sct_molecules* src, u64 threshold, u64 seed, 
     tally_most = std::max(tally_most, tally.n[k]);
   }
   SCT_TRY(enter_read(dst, s));
-  const int64_t dst_size = dst->size_bound;
   // the scratch has the layout of a counter's device words: the kept tallies where molecules_add_kernel
   // looks for them, the kept reads and molecules in the two words before the counter's own
-  void* blk = nullptr;
-  SCT_HIP(sct::pool_alloc(&blk, W_NWORDS * 8, s));
-  u64* kept = static_cast<u64*>(blk);
+  sct::StreamBlock blk(s);
+  SCT_HIP(blk.alloc(W_NWORDS * 8));
+  u64* kept = static_cast<u64*>(blk.p);
   enum { K_READS = 0, K_MOLECULES = 1 };
   static_assert(K_MOLECULES < W_TALLY, "the kept sums lie below the tally");
-  const auto fail_with = [&](int rc) {
-    sct::pool_free(blk, s);
-    return rc;
-  };
-  hipError_t e = hipMemsetAsync(blk, 0, W_NWORDS * 8, s);
+  hipError_t e = hipMemsetAsync(kept, 0, W_NWORDS * 8, s);
   const uint64_t point = threshold;
   if (e == hipSuccess && src_size > 0) e = curve_pass(src, &point, 1, seed, &kept[K_READS], &kept[K_MOLECULES], s);
   if (e == hipSuccess && tally_most > 0) {
@@ -1417,29 +1378,16 @@ int downsample(sct_molecules* dst, sct_molecules* src, u64 threshold, u64 seed, 
   if (e == hipSuccess) e = hipMemcpyAsync(dst->h_words, kept, W_NWORDS * 8, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess)
-    return fail_with(sct::fail(SCT_E_HIP, "molecule downsample, counting the kept reads: %s", hipGetErrorString(e)));
+    return sct::fail(SCT_E_HIP, "molecule downsample, counting the kept reads: %s", hipGetErrorString(e));
   const int64_t survivors = (int64_t)dst->h_words[K_MOLECULES];
   u64 kept_total = dst->h_words[K_READS];
   for (int k = 0; k < 4; ++k) kept_total += dst->h_words[W_TALLY + k];
-  const int64_t cap = sct::mol_merge_capacity(dst->capacity, dst_size, survivors);
-  if (cap == 0)
-    return fail_with(sct::fail(SCT_E_RANGE, "downsample: %lld + %lld molecules need a table of more than %lld slots",
-                               (long long)dst_size, (long long)survivors, (long long)sct::kTableMaxCapacity));
-  if (cap > dst->capacity)
-    if (int rc = grow(dst, cap / dst->capacity, s); rc != SCT_OK) return fail_with(rc);
+  SCT_TRY(make_room(dst, dst->size_bound, survivors, "downsample", s));
   if (survivors > 0)
     hipLaunchKernelGGL(molecules_downsample_kernel, dim3(grid_for(src->capacity, 4 * WG)), dim3(WG), 0, s, dst->t,
                        src->t.keys, src->t.cnt, src->capacity, threshold, seed, downsample_wave_reads());
   // the kept tallies (reads[] was the thinning kernel's: nw = 0 here)
-  hipLaunchKernelGGL(molecules_add_kernel, dim3(1), dim3(WG), 0, s, dst->t.reads, dst->t.words, kept, kept, (int64_t)0);
-  const hipError_t launched = hipGetLastError();
-  sct::pool_free(blk, s);
-  dst->total += (int64_t)kept_total;
-  dst->size_bound = dst_size + survivors;  // a bound: the next read of the size word makes it exact
-  int rc = launched == hipSuccess ? SCT_OK : sct::fail(SCT_E_HIP, "molecule downsample: %s", hipGetErrorString(launched));
-  if (int rl = leave(dst, s); rc == SCT_OK) rc = rl;
-  if (int rl = leave(src, s); rc == SCT_OK) rc = rl;
-  return rc;
+  return absorbed(dst, src, kept, kept, 0, (int64_t)kept_total, survivors, "downsample", s, s);
 }
 
 }  // namespace
@@ -1552,15 +1500,40 @@ extern "C" int sct_molecules_destroy(sct_molecules* c) {
 
 namespace {
 
-// the two update forms' common part: `features` says which form the caller used
-int update_entry(sct_molecules* c, bool features, const int32_t* d_index, const int32_t* d_feature,
-                 const uint64_t* d_umi, int64_t n, void* stream) {
+// The argument checks of an entry-point family, stated once for its device and its host form.
+
+// the update forms; `features` says which form the caller used, and n == 0 passes with no array looked at
+int update_check(const sct_molecules* c, bool features, const int32_t* index, const int32_t* feature,
+                 const uint64_t* umi, int64_t n) {
   SCT_CHECK(n >= 0, "n must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   if (n == 0) return SCT_OK;
-  if (features) SCT_CHECK(d_index != nullptr && d_feature != nullptr && d_umi != nullptr, "NULL index, feature or umi");
-  else SCT_CHECK(d_index != nullptr && d_umi != nullptr, "NULL index or umi");
-  if (int rc = need_features(c, features); rc != SCT_OK) return rc;
+  if (features) SCT_CHECK(index != nullptr && feature != nullptr && umi != nullptr, "NULL index, feature or umi");
+  else SCT_CHECK(index != nullptr && umi != nullptr, "NULL index or umi");
+  return need_features(c, features);
+}
+
+// fetch and fetch_counted (`counted`); the host forms go on to ask for their columns
+int fetch_check(const sct_molecules* c, int method, bool counted, int64_t room) {
+  SCT_CHECK(room >= 0, "room must be >= 0");
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
+  return counted ? need_counted(c) : SCT_OK;
+}
+
+int collapse_check(const sct_molecules* c, int method, const uint64_t* collapsed) {
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
+  if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_CHECK(collapsed != nullptr, "NULL output");
+  return SCT_OK;
+}
+
+// the two update forms' common part
+int update_entry(sct_molecules* c, bool features, const int32_t* d_index, const int32_t* d_feature,
+                 const uint64_t* d_umi, int64_t n, void* stream) {
+  SCT_TRY(update_check(c, features, d_index, d_feature, d_umi, n));
+  if (n == 0) return SCT_OK;
   SCT_ON_DEVICE_OF(c);
   bool range = false;
   const int rc = update_device(c, d_index, d_feature, d_umi, n, sct::as_stream(stream), &range);
@@ -1569,12 +1542,8 @@ int update_entry(sct_molecules* c, bool features, const int32_t* d_index, const 
 
 int update_host_entry(sct_molecules* c, bool features, const int32_t* index, const int32_t* feature,
                       const uint64_t* umi, int64_t n) {
-  SCT_CHECK(n >= 0, "n must be >= 0");
-  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_TRY(update_check(c, features, index, feature, umi, n));
   if (n == 0) return SCT_OK;
-  if (features) SCT_CHECK(index != nullptr && feature != nullptr && umi != nullptr, "NULL index, feature or umi");
-  else SCT_CHECK(index != nullptr && umi != nullptr, "NULL index or umi");
-  if (int rc = need_features(c, features); rc != SCT_OK) return rc;
   SCT_ON_STAGE_OF(c, s);
   // pieces through one pool buffer (umis, then indices, then features): a piece's copies are ordered
   // after the previous piece's kernels.  An out-of-range index in one piece does not stop the others.
@@ -1662,15 +1631,13 @@ extern "C" int sct_molecules_counts_host(sct_molecules* c, uint64_t* reads, uint
 }
 
 extern "C" int sct_molecules_fetch(sct_molecules* c, int32_t* d_index, uint64_t* d_umi, int64_t room, void* stream) {
-  SCT_CHECK(room >= 0, "room must be >= 0");
-  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_TRY(fetch_check(c, SCT_COLLAPSE_ONE_STEP, false, room));
   return fetch_device(c, SCT_COLLAPSE_ONE_STEP, d_index, nullptr, d_umi, nullptr, nullptr, d_index && d_umi, room,
                       sct::as_stream(stream));
 }
 
 extern "C" int sct_molecules_fetch_host(sct_molecules* c, int32_t* index, uint64_t* umi, int64_t room) {
-  SCT_CHECK(room >= 0, "room must be >= 0");
-  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_TRY(fetch_check(c, SCT_COLLAPSE_ONE_STEP, false, room));
   SCT_CHECK(room == 0 || (index && umi), "NULL output");
   return fetch_host(c, SCT_COLLAPSE_ONE_STEP, index, nullptr, umi, nullptr, nullptr, room);
 }
@@ -1679,10 +1646,7 @@ extern "C" int sct_molecules_fetch_host(sct_molecules* c, int32_t* index, uint64
 // ones without are these with SCT_COLLAPSE_ONE_STEP.
 extern "C" int sct_molecules_collapse_by(sct_molecules* c, int method, uint64_t* d_collapsed, uint64_t* d_ncorrected,
                                          void* stream) {
-  SCT_CHECK(c != nullptr, "molecule counter is NULL");
-  if (int rc = method_check(method); rc != SCT_OK) return rc;
-  if (int rc = need_counted(c); rc != SCT_OK) return rc;
-  SCT_CHECK(d_collapsed != nullptr, "NULL output");
+  SCT_TRY(collapse_check(c, method, d_collapsed));
   SCT_ON_DEVICE_OF(c);
   return collapse_device(c, method, d_collapsed, d_ncorrected, sct::as_stream(stream));
 }
@@ -1693,10 +1657,7 @@ extern "C" int sct_molecules_collapse(sct_molecules* c, uint64_t* d_collapsed, u
 
 extern "C" int sct_molecules_collapse_by_host(sct_molecules* c, int method, uint64_t* collapsed,
                                               uint64_t* ncorrected) {
-  SCT_CHECK(c != nullptr, "molecule counter is NULL");
-  if (int rc = method_check(method); rc != SCT_OK) return rc;
-  if (int rc = need_counted(c); rc != SCT_OK) return rc;
-  SCT_CHECK(collapsed != nullptr, "NULL output");
+  SCT_TRY(collapse_check(c, method, collapsed));
   SCT_ON_STAGE_OF(c, s);
   Staged st(s);
   st.add(collapsed, 8, (size_t)c->t.nw), st.add(ncorrected, 8, 1);
@@ -1718,10 +1679,7 @@ extern "C" int sct_molecules_directional_info(sct_molecules* c, int64_t* sweeps,
 
 extern "C" int sct_molecules_fetch_counted_by(sct_molecules* c, int method, int32_t* d_index, uint64_t* d_umi,
                                               uint64_t* d_mreads, uint64_t* d_parent, int64_t room, void* stream) {
-  SCT_CHECK(room >= 0, "room must be >= 0");
-  SCT_CHECK(c != nullptr, "molecule counter is NULL");
-  if (int rc = method_check(method); rc != SCT_OK) return rc;
-  if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_TRY(fetch_check(c, method, true, room));
   return fetch_device(c, method, d_index, nullptr, d_umi, d_mreads, d_parent, d_index && d_umi && d_mreads, room,
                       sct::as_stream(stream));
 }
@@ -1733,10 +1691,7 @@ extern "C" int sct_molecules_fetch_counted(sct_molecules* c, int32_t* d_index, u
 
 extern "C" int sct_molecules_fetch_counted_by_host(sct_molecules* c, int method, int32_t* index, uint64_t* umi,
                                                    uint64_t* mreads, uint64_t* parent, int64_t room) {
-  SCT_CHECK(room >= 0, "room must be >= 0");
-  SCT_CHECK(c != nullptr, "molecule counter is NULL");
-  if (int rc = method_check(method); rc != SCT_OK) return rc;
-  if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_TRY(fetch_check(c, method, true, room));
   SCT_CHECK(room == 0 || (index && umi && mreads), "NULL output");
   return fetch_host(c, method, index, nullptr, umi, mreads, parent, room);
 }
@@ -1867,9 +1822,18 @@ int matrix_device(sct_molecules* c, int method, int64_t* d_indptr, int32_t* d_fe
   return SCT_OK;
 }
 
+// the checks of fetch_features, device and host: `given` its own columns, `counts` mreads or parent asked for
+int fetch_features_check(const sct_molecules* c, int method, bool given, bool counts, int64_t room) {
+  if (int rc = fetch_check(c, method, false, room); rc != SCT_OK) return rc;
+  SCT_CHECK(room == 0 || given, "NULL output");
+  if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
+  return counts ? need_counted(c) : SCT_OK;
+}
+
 // the checks every matrix call makes before it touches the device
-int matrix_check(const sct_molecules* c, const void* indptr, const void* feature, const void* reads,
+int matrix_check(const sct_molecules* c, int method, const void* indptr, const void* feature, const void* reads,
                  const void* collapsed, int64_t room, const int64_t* nnz) {
+  if (int rc = method_check(method); rc != SCT_OK) return rc;
   SCT_CHECK(room >= 0, "room must be >= 0");
   SCT_CHECK(c != nullptr, "molecule counter is NULL");
   SCT_CHECK(nnz != nullptr, "NULL nnz");
@@ -1885,13 +1849,7 @@ int matrix_check(const sct_molecules* c, const void* indptr, const void* feature
 extern "C" int sct_molecules_fetch_features_by(sct_molecules* c, int method, int32_t* d_index, int32_t* d_feature,
                                                uint64_t* d_umi, uint64_t* d_mreads, uint64_t* d_parent, int64_t room,
                                                void* stream) {
-  SCT_CHECK(room >= 0, "room must be >= 0");
-  SCT_CHECK(c != nullptr, "molecule counter is NULL");
-  if (int rc = method_check(method); rc != SCT_OK) return rc;
-  SCT_CHECK(room == 0 || (d_index && d_feature && d_umi), "NULL output");
-  if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
-  if (d_mreads || d_parent)
-    if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_TRY(fetch_features_check(c, method, d_index && d_feature && d_umi, d_mreads || d_parent, room));
   return fetch_device(c, method, d_index, d_feature, d_umi, d_mreads, d_parent, true, room, sct::as_stream(stream));
 }
 
@@ -1903,13 +1861,7 @@ extern "C" int sct_molecules_fetch_features(sct_molecules* c, int32_t* d_index, 
 
 extern "C" int sct_molecules_fetch_features_by_host(sct_molecules* c, int method, int32_t* index, int32_t* feature,
                                                     uint64_t* umi, uint64_t* mreads, uint64_t* parent, int64_t room) {
-  SCT_CHECK(room >= 0, "room must be >= 0");
-  SCT_CHECK(c != nullptr, "molecule counter is NULL");
-  if (int rc = method_check(method); rc != SCT_OK) return rc;
-  SCT_CHECK(room == 0 || (index && feature && umi), "NULL output");
-  if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
-  if (mreads || parent)
-    if (int rc = need_counted(c); rc != SCT_OK) return rc;
+  SCT_TRY(fetch_features_check(c, method, index && feature && umi, mreads || parent, room));
   return fetch_host(c, method, index, feature, umi, mreads, parent, room);
 }
 
@@ -1921,8 +1873,7 @@ extern "C" int sct_molecules_fetch_features_host(sct_molecules* c, int32_t* inde
 extern "C" int sct_molecules_matrix_by(sct_molecules* c, int method, int64_t* d_indptr, int32_t* d_feature,
                                        uint64_t* d_molecules, uint64_t* d_reads, uint64_t* d_collapsed, int64_t room,
                                        int64_t* nnz, void* stream) {
-  if (int rc = method_check(method); rc != SCT_OK) return rc;
-  if (int rc = matrix_check(c, d_indptr, d_feature, d_reads, d_collapsed, room, nnz); rc != SCT_OK) return rc;
+  SCT_TRY(matrix_check(c, method, d_indptr, d_feature, d_reads, d_collapsed, room, nnz));
   SCT_ON_DEVICE_OF(c);
   return matrix_device(c, method, d_indptr, d_feature, d_molecules, d_reads, d_collapsed, room, nnz,
                        sct::as_stream(stream));
@@ -1937,8 +1888,7 @@ extern "C" int sct_molecules_matrix(sct_molecules* c, int64_t* d_indptr, int32_t
 extern "C" int sct_molecules_matrix_by_host(sct_molecules* c, int method, int64_t* indptr, int32_t* feature,
                                             uint64_t* molecules, uint64_t* reads, uint64_t* collapsed, int64_t room,
                                             int64_t* nnz) {
-  if (int rc = method_check(method); rc != SCT_OK) return rc;
-  if (int rc = matrix_check(c, indptr, feature, reads, collapsed, room, nnz); rc != SCT_OK) return rc;
+  SCT_TRY(matrix_check(c, method, indptr, feature, reads, collapsed, room, nnz));
   SCT_ON_STAGE_OF(c, s);
   if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
   // nnz <= nmolecules: the device arrays never need more room than that

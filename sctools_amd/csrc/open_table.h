@@ -139,6 +139,41 @@ __device__ __forceinline__ void add_claims(u64* __restrict__ size_word, int clai
   if ((threadIdx.x & 63) == 0 && claims > 0) atomicAdd(size_word, (u64)claims);
 }
 
+// The walks of a kernel over n items.  Each is called by every lane of every wave, and its callback
+// runs the same number of times in every lane of a wave, so the callback may ballot and shuffle.
+
+// A lane per item, grid stride: f(i, i < n) for i = the lane's number, + the grid's lanes, ...  The
+// trip count is the same for every lane: the wave stays whole, and a lane past the end is told so.
+template <class F>
+__device__ __forceinline__ void for_each_item(int64_t n, F f) {
+  const int64_t stride = (int64_t)gridDim.x * WG;
+  const int64_t gid = (int64_t)blockIdx.x * WG + threadIdx.x;
+  const int64_t iters = (n + stride - 1) / stride;
+  for (int64_t it = 0; it < iters; ++it) {
+    const int64_t i = it * stride + gid;
+    f(i, i < n);
+  }
+}
+
+// A wave per 64 adjacent items: f(base) for the wave's tiles [base, base + 64), base < n a multiple of
+// 64 and wave-uniform; lane l's item is base + l, which lies past the end only in the last tile.
+template <class F>
+__device__ __forceinline__ void for_each_wave_tile(int64_t n, F f) {
+  const int64_t nwaves = (int64_t)gridDim.x * (WG / 64);
+  for (int64_t base = (((int64_t)blockIdx.x * WG + threadIdx.x) >> 6) * 64; base < n; base += nwaves * 64) f(base);
+}
+
+// The lanes of a ballot taken one after the other by the whole wave: f(src) for every set bit of the
+// wave-uniform `mask`, lowest first.
+template <class F>
+__device__ __forceinline__ void wave_serial(u64 mask, F f) {
+  while (mask) {
+    const int src = __ffsll((long long)mask) - 1;
+    mask &= mask - 1;
+    f(src);
+  }
+}
+
 // ---- host
 
 inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap = 256 * 8) {

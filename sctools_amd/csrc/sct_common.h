@@ -220,26 +220,39 @@ constexpr int kMomNCounts = 1 + kMomNProd + kMomOrder;  // [pairs, products..., 
 
 namespace sct {
 
-// The tail every staged *_host call ends with.  One stream-ordered pool block on `s`; note() keeps
-// the first HIP error of the call; finish() gives the block back on the stream, synchronises the
-// stream once and makes that error the status ("what: error") unless the call had failed already.
-// A call that returns before finish() still frees the block and waits for the stream, so no
-// caller pointer is in use after any return.
-struct PoolBlock {
+// Pool scratch of a device form, held for a scope: alloc() takes one stream-ordered block on `s`, and
+// leaving the scope gives it back on `s`, after whatever was enqueued there.  Nothing waits, so the
+// call stays asynchronous.  A block of another device is freed with that device current.
+struct StreamBlock {
   hipStream_t s;
   void* p = nullptr;
+  explicit StreamBlock(hipStream_t stream) : s(stream) {}
+  StreamBlock(const StreamBlock&) = delete;
+  StreamBlock& operator=(const StreamBlock&) = delete;
+  ~StreamBlock() { free(); }
+  hipError_t alloc(size_t bytes) { return pool_alloc(&p, bytes, s); }
+  void free() {
+    if (p) pool_free(p, s);
+    p = nullptr;
+  }
+  uint8_t* bytes() const { return static_cast<uint8_t*>(p); }
+};
+
+// The tail every staged *_host call ends with: such a block (`s`, `p` and bytes() are its) that also
+// waits.  note() keeps the first HIP error of the call; finish() gives the block back on the stream,
+// synchronises the stream once and makes that error the status ("what: error") unless the call had
+// failed already.  A call that returns before finish() still frees the block and waits for the
+// stream, so no caller pointer is in use after any return.
+struct PoolBlock : StreamBlock {
   hipError_t e = hipSuccess;
-  explicit PoolBlock(hipStream_t stream) : s(stream) {}
-  PoolBlock(const PoolBlock&) = delete;
-  PoolBlock& operator=(const PoolBlock&) = delete;
+  explicit PoolBlock(hipStream_t stream) : StreamBlock(stream) {}
   ~PoolBlock() {
     if (p) (void)release();
   }
   int alloc(size_t bytes) {
-    SCT_HIP(pool_alloc(&p, bytes, s));
+    SCT_HIP(StreamBlock::alloc(bytes));
     return SCT_OK;
   }
-  uint8_t* bytes() const { return static_cast<uint8_t*>(p); }
   bool ok() const { return e == hipSuccess; }
   void note(hipError_t x) {
     if (e == hipSuccess) e = x;
@@ -252,8 +265,7 @@ struct PoolBlock {
 
  private:
   hipError_t release() {
-    if (p) pool_free(p, s);
-    p = nullptr;
+    free();
     return hipStreamSynchronize(s);
   }
 };

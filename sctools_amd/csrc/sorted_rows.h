@@ -22,27 +22,22 @@ struct SortedRows {
   size_t sort_bytes = 0;
   Carve cv;
   size_t o_in, o_out, o_slot_in = 0, o_slot_out = 0, o_tmp;
-  uint8_t* b = nullptr;
+  StreamBlock blk;  // given back on `s` when the rows leave scope
 
   // plans the block; tmp_at_least: the caller's other uses of the sort's scratch (after the sort)
   SortedRows(int64_t rows_, int end_bit_, hipStream_t s_, size_t tmp_at_least = 0)
-      : rows(rows_), end_bit(end_bit_), s(s_) {
+      : rows(rows_), end_bit(end_bit_), s(s_), blk(s_) {
     (void)run(nullptr);
     o_in = cv.take((size_t)rows * 8), o_out = cv.take((size_t)rows * 8);
     if (SLOTS) o_slot_in = cv.take((size_t)rows * 4), o_slot_out = cv.take((size_t)rows * 4);
     o_tmp = cv.take(std::max(sort_bytes, tmp_at_least));
   }
-  SortedRows(const SortedRows&) = delete;
-  SortedRows& operator=(const SortedRows&) = delete;
-  ~SortedRows() {
-    if (b) pool_free(b, s);
-  }
   // a piece of the caller's in the same block (before alloc): its offset, for at()
   size_t take(size_t bytes) { return cv.take(bytes); }
-  hipError_t alloc() { return pool_alloc(reinterpret_cast<void**>(&b), cv.size, s); }
+  hipError_t alloc() { return blk.alloc(cv.size); }
   template <class T>
   T* at(size_t offset) const {
-    return reinterpret_cast<T*>(b + offset);
+    return reinterpret_cast<T*>(blk.bytes() + offset);
   }
   // cursor = 0, compact(word_in, slot_in or NULL) enqueues the counter's compaction, then the sort
   template <class Compact>

@@ -850,6 +850,9 @@ CALLS_ABI = UPDATE_CALLS + (
     "sct_molecules_fetch_counted", "sct_molecules_fetch_features", "sct_molecules_collapse", "sct_molecules_matrix",
     "sct_molecules_merge", "sct_counter_create", "sct_counter_update", "sct_counter_info", "sct_counter_fetch",
     "sct_counter_destroy")
+# the calls step's calls that an earlier library may lack: {call: the symbol it needs}
+CALLS_NEWER = {"collapse_directional": "sct_molecules_collapse_by", "downsample_half": "sct_molecules_downsample",
+               "downsample_curve_k16": "sct_molecules_downsample_curve"}
 
 
 def calls_step(args):
@@ -861,10 +864,13 @@ def calls_step(args):
     goes first in every other round, and every timed call follows an untimed one of its own kind):
     sct_molecules_fetch; sct_molecules_fetch_counted without and with parents;
     sct_molecules_fetch_features with every column; sct_molecules_collapse; sct_molecules_matrix with
-    the molecules, with reads, with reads and collapsed; sct_molecules_merge of the plain counter into
-    an empty counter sized up front, the table in place and compacted first (SCT_TUNE_MERGE_ROWS 1);
-    sct_molecules_update of all reads from capacity_hint 0 (the growth path), plain and counted;
-    sct_counter_fetch.  Before the rounds every call runs once in each library and every output
+    the molecules, with reads, with reads and collapsed; sct_molecules_collapse_by with
+    SCT_COLLAPSE_DIRECTIONAL; sct_molecules_merge of the plain counter into an empty counter sized up
+    front, the table in place and compacted first (SCT_TUNE_MERGE_ROWS 1); sct_molecules_downsample of
+    it at threshold 2^31 into such a counter; sct_molecules_downsample_curve at 16 points;
+    sct_molecules_update of all reads into a counter sized up front and from capacity_hint 0 (the
+    growth path), plain and counted; sct_counter_fetch.  A call whose symbol --parent-lib lacks is timed
+    in this library alone.  Before the rounds every call runs once in each library and every output
     array must be equal element for element.  A call agrees when the medians differ by no more than
     the min-max spread of the parent's own rounds; the step fails (its profile written) when a call is
     slower than the parent beyond that spread; one that is faster beyond it is reported.  Every round
@@ -883,9 +889,16 @@ def calls_step(args):
     vp, i64, ref = ctypes.c_void_p, ctypes.c_int64, ctypes.byref
     libs = {"this": _lib.lib()}
     old = _parent_lib(args, CALLS_ABI)
+    lacking = set()  # the calls the parent library has no symbol for
     if old:
         libs["parent"] = old
+        for name, symbol in CALLS_NEWER.items():
+            if hasattr(old, symbol):
+                getattr(old, symbol).argtypes = _lib.SIGNATURES[symbol]
+            else:
+                lacking.add(name)
     ptr = lambda t: vp(t.data_ptr())  # noqa: E731
+    points = np.array([((t + 1) << 32) // 16 for t in range(16)], dtype=np.uint64)  # the curve's thresholds
 
     class Side:
         """One library's counters and output arrays."""
@@ -990,8 +1003,23 @@ def calls_step(args):
             s.lib.sct_tune_set(_lib.TUNE_KEYS["merge_rows"], -1)
         return ms, functools.partial(rows_of, s, h)
 
-    def update(s, counted):
-        h = make(s, counted, 0)
+    def collapse_directional(s):
+        ms = timed(lambda: s.lib.sct_molecules_collapse_by(s.plain, _lib.COLLAPSE_DIRECTIONAL, ptr(s.i64[0]),
+                                                           ptr(s.i64[1]), None))
+        return ms, [s.i64[0, :nw], s.i64[1, :1]]
+
+    def downsample_half(s):
+        h = make(s, True, s.cap)
+        ms = timed(lambda: s.lib.sct_molecules_downsample(h, s.plain, 1 << 31, 7, None))
+        return ms, functools.partial(rows_of, s, h)
+
+    def downsample_curve(s):
+        ms = timed(lambda: s.lib.sct_molecules_downsample_curve(s.plain, _lib._ptr(points), points.size, 7,
+                                                                ptr(s.i64[0]), ptr(s.i64[1]), None))
+        return ms, [s.i64[:2, :points.size]]
+
+    def update(s, counted, capacity=0):
+        h = make(s, counted, capacity)
         ms = timed(lambda: s.lib.sct_molecules_update(h, ptr(di), ptr(du), n, None))
         return ms, functools.partial(rows_of, s, h)
 
@@ -1002,23 +1030,29 @@ def calls_step(args):
 
     calls = {"fetch": fetch, "fetch_counted": functools.partial(fetch_counted, parents=False),
              "fetch_counted_parents": functools.partial(fetch_counted, parents=True), "fetch_features": fetch_features,
-             "collapse": collapse, "matrix_molecules": functools.partial(matrix, values=1),
+             "collapse": collapse, "collapse_directional": collapse_directional,
+             "matrix_molecules": functools.partial(matrix, values=1),
              "matrix_molecules_reads": functools.partial(matrix, values=2),
              "matrix_molecules_reads_collapsed": functools.partial(matrix, values=3),
              "merge": functools.partial(merge, rows=0), "merge_compacted": functools.partial(merge, rows=1),
+             "downsample_half": downsample_half, "downsample_curve_k16": downsample_curve,
+             "update": functools.partial(update, counted=False, capacity=hint),
+             "update_counted": functools.partial(update, counted=True, capacity=hint),
              "update_growing": functools.partial(update, counted=False),
              "update_growing_counted": functools.partial(update, counted=True), "counter_fetch": counter_fetch}
     sides = {name: Side(lib) for name, lib in libs.items()}
     out = {"n": n, "nw": nw, "nf": nf, "umi_length": UL, "capacity_hint": hint, "parent_lib": bool(old),
            "molecules": sides["this"].nplain, "feature_molecules": sides["this"].nfeat, "codes": sides["this"].ncodes,
-           "outputs_equal": {}, "calls": {}}
+           "parent_lacks": sorted(lacking), "outputs_equal": {}, "calls": {}}
+    sides_of = {name: [(lname, s) for lname, s in sides.items() if lname == "this" or name not in lacking]
+                for name in calls}
     # every call once in each library (the warm-up as well): the outputs, element for element
     for name, call in calls.items():
         got = {}
-        for lname, s in sides.items():
+        for lname, s in sides_of[name]:
             arrays = call(s)[1]
             got[lname] = [a.clone() for a in (arrays() if callable(arrays) else arrays)]
-        if old:
+        if "parent" in got:
             same = len(got["this"]) == len(got["parent"]) and all(
                 a.shape == b.shape and bool((a == b).all()) for a, b in zip(got["this"], got["parent"]))
             out["outputs_equal"][name] = same
@@ -1026,10 +1060,9 @@ def calls_step(args):
     lines = []
     for r in range(args.rounds):
         row = {"round": r}
-        order = list(sides.items())[::-1 if r % 2 else 1]  # each library goes first in every other round
         for name, call in calls.items():
             row[name] = {}
-            for lname, s in order:
+            for lname, s in sides_of[name][::-1 if r % 2 else 1]:  # each library goes first in every other round
                 call(s)  # untimed: the timed call follows one of its own kind, not the other library's or another call
                 row[name][lname + "_ms"] = round(call(s)[0], 3)
         lines.append(row)
@@ -1040,9 +1073,10 @@ def calls_step(args):
         for key in lines[0][name]:
             v = [row[name][key] for row in lines]
             res[key] = {"median": round(float(np.median(v)), 3), "min": min(v), "max": max(v)}
-        if old:
+        if "parent_ms" in res:
             res["vs_parent"] = _vs_parent(res["this_ms"], res["parent_ms"])
-    apart = {name: res["vs_parent"] for name, res in out["calls"].items() if old and not res["vs_parent"]["agree"]}
+    apart = {name: res["vs_parent"] for name, res in out["calls"].items()
+             if "vs_parent" in res and not res["vs_parent"]["agree"]}
     slower = ["%s: %s" % (name, v) for name, v in apart.items() if v["median_difference_ms"] > 0]
     out["faster_than_parent"] = sorted(name for name, v in apart.items() if v["median_difference_ms"] < 0)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
