@@ -48,7 +48,7 @@ int sct_set_device(int device);        /* select the device for later calls (hip
 #define SCT_TUNE_ALLPAIRS_FLUSH_ITEMS 4 /* pair kernel: flush lane counters every k items */
 #define SCT_TUNE_ALLPAIRS_GRID 5        /* pair kernel: persistent grid size */
 #define SCT_TUNE_NEAREST_SCHEME 6       /* 0 auto, 1 open addressing, 2 CSR buckets, 3 half keys */
-#define SCT_TUNE_NEAREST_LOAD 7         /* open addressing: table slots per whitelist code */
+#define SCT_TUNE_NEAREST_LOAD 7         /* CSR buckets per distinct block value (default 4); the open-addressing load is fixed at <= 1/2 */
 #define SCT_TUNE_SCALAR_SERVER 8        /* 0: every scalar call is a kernel launch (default 1) */
 #define SCT_TUNE_SCALAR_IDLE_MS 9       /* the scalar server exits after this idle time (5) */
 #define SCT_TUNE_SPECTRAL_COLUMNS 10   /* SPECTRAL column width: 0 auto, 14, or 16 (when int8 fits) */
