@@ -20,20 +20,35 @@
 // verifies every entry of its P buckets with the full distance, so hash collisions never
 // change the result.  A code found through several blocks has one index, so it is never
 // counted as a tie with itself.
+//
+// Three layouts answer this contract: the half-key tables, the open-addressing multi-index and
+// the CSR buckets above (each described where its kernels start).  On the host every layout is
+// one device block that the plan owns, carved into 256-byte-aligned segments, and built with
+// scratch from one block of the library's pool.  Which layout a plan takes, the block split,
+// every table size and offset and the bytes sct_nearest_plan_info reports are pure functions
+// in nearest_index_layout.h; this file holds the kernels and the builders that launch them.
 #include <hipcub/hipcub.hpp>
 
-#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
+#include <type_traits>
+#include <utility>
 
+#include "mix64.h"
+#include "nearest_index_layout.h"
 #include "sct_common.h"
+
+namespace nix = sct::nearest_index;
 
 namespace {
 
+using sct::mix64;
+
 constexpr int WG = 256;
-constexpr int MAX_PARTS = 8;
+constexpr int MAX_PARTS = nix::kMaxParts;
 
 struct Part {
   uint64_t mask;  // the block's bits, in place
@@ -56,10 +71,6 @@ __device__ __forceinline__ int dist3(uint64_t a, uint64_t b) {
   const uint64_t x = a ^ b;
   return __popcll((x | (x >> 1) | (x >> 2)) & 0x9249249249249249ull);
 }
-
-struct Parts {
-  Part p[MAX_PARTS];
-};
 
 __global__ void key_hist_kernel(const uint64_t* __restrict__ wl, int64_t nw, Part part,
                                 uint32_t* __restrict__ counts) {
@@ -166,17 +177,8 @@ __global__ __launch_bounds__(WG) void nearest_query_kernel(const uint64_t* __res
 // round trip per query instead of an offset load followed by a scan of ~11 entries per
 // probe; a group without a free slot continues in the next (rare).
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr int kGroup = 4;  // slots per group (64 B)
-constexpr int MAX_KEYS = 6;  // C(4, 2): max_d = 2
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
+constexpr int kGroup = nix::kGroup;  // slots per group (64 B)
+constexpr int MAX_KEYS = nix::kMaxKeys;  // C(4, 2): max_d = 2
 
 struct OTable {
   uint64_t keymask;  // OR of the key's block masks
@@ -315,7 +317,7 @@ struct Halves {
   const uint32_t* offB;     // [4^GB + 1]
   const uint16_t* entB;     // [nw] A keys, codes sorted by (B, A)
   const uint32_t* permAB;   // [2 nw] whitelist index of each A-order, then B-order position (build only;
-                            // the index pass reads it packed, sct_nearest_plan::perm_packed)
+                            // the index pass reads it packed, perm_packed below)
   int64_t nw;
   // Digit keys: any order of A/C/G/T answers the same (a key only has to be equal or not), so the
   // plan takes the order the whitelist is sorted in, if any -- alphabetical (a 10x whitelist file),
@@ -426,10 +428,8 @@ __device__ __forceinline__ void scan_chunk(const uint4 v, uint32_t c, uint32_t b
   }
 }
 
-// Entries [b, e) of a uint16 table against the half key k (invalid digits `sp` spread to the
-// even bits): z0 / z1 count the entries at half distance 0 / 1, p0 / p1 the position of one.
-// Chunks of 8 entries go three at a time: all three 16-B loads (the ones inside [b, e)) are
-// issued before any is tested, so the later ones (usually in the same line) ride on the first's
+// scan_chunk over a bucket.  Chunks of 8 entries go three at a time: all three 16-B loads (the ones
+// inside [b, e)) are issued before any is tested, so the later ones (usually in the same line) ride on the first's
 // miss instead of making their own dependent L2 requests (one, two, three, four at a time:
 // 2.46 / 2.23 / 2.17 / 2.19 ms per 100M queries, profiles/ab_nearest_chunks_r03.jsonl).  The
 // first chunk starts at b's dword, not its 16-B chunk: a wave runs as many chunks as its fullest
@@ -911,54 +911,76 @@ unsigned grid_for(int64_t n, int64_t cap = 16384) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(b, cap));
 }
 
-}  // namespace
+// f(std::integral_constant<int, KIND>) for a plan's code kind: the one place the templates fork
+template <class F>
+auto with_kind(int kind, F&& f) {
+  return kind == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 3>{});
+}
 
-// dup[j] = 1 if whitelist code j occurs more than once (sorted (code, index), equal
-// neighbours); a device buffer of nw bytes, ready on `s` when this returns.
-static int compute_dups(const uint64_t* d_whitelist, int64_t nw, uint8_t* dup, hipStream_t s) {
+template <class T>
+T* at(void* base, int64_t offset) {
+  return reinterpret_cast<T*>(static_cast<char*>(base) + offset);
+}
+
+// The scratch of the duplicate flags inside a builder's pool block: dup[nw], and for nw >= 2 hipcub's
+// temporary storage, the sorted codes with their indices and the iota.
+struct DupScratch {
+  size_t sort_bytes = 0;
+  int64_t dup, tmp = 0, keys = 0, idx = 0, iota = 0;
+  DupScratch(nix::Carve& c, int64_t nw, hipStream_t s) {
+    dup = c.add(std::max<int64_t>(nw, 1));
+    if (nw < 2) return;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                             (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)nw, 0, 64, s);
+    tmp = c.add((int64_t)sort_bytes);
+    keys = c.add(nw * 8);
+    idx = c.add(nw * 4);
+    iota = c.add(nw * 4);
+  }
+};
+
+// dup[j] = 1 if whitelist code j occurs more than once (sorted (code, index), equal neighbours),
+// enqueued on `s`; the flags at scratch + ds.dup
+int enqueue_dups(const uint64_t* d_whitelist, int64_t nw, const DupScratch& ds, void* scratch, hipStream_t s) {
+  uint8_t* dup = at<uint8_t>(scratch, ds.dup);
   SCT_HIP(hipMemsetAsync(dup, 0, (size_t)std::max<int64_t>(nw, 1), s));
   if (nw < 2) return SCT_OK;
-  size_t sort_bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)nw, 0, 64, s);
-  sct::DevBuf tmp, skeys, sidx, iota;
-  SCT_HIP(tmp.alloc(sort_bytes));
-  SCT_HIP(skeys.alloc((size_t)nw * 8));
-  SCT_HIP(sidx.alloc((size_t)nw * 4));
-  SCT_HIP(iota.alloc((size_t)nw * 4));
-  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, (uint32_t*)iota.p, nw);
-  SCT_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, sort_bytes, d_whitelist, (uint64_t*)skeys.p,
-                                             (const uint32_t*)iota.p, (uint32_t*)sidx.p, (int)nw, 0, 64, s));
-  hipLaunchKernelGGL(flag_dups_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, (const uint64_t*)skeys.p,
-                     (const uint32_t*)sidx.p, nw, dup);
+  size_t sort_bytes = ds.sort_bytes;
+  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, at<uint32_t>(scratch, ds.iota), nw);
+  SCT_HIP(hipcub::DeviceRadixSort::SortPairs(at<void>(scratch, ds.tmp), sort_bytes, d_whitelist,
+                                             at<uint64_t>(scratch, ds.keys), at<const uint32_t>(scratch, ds.iota),
+                                             at<uint32_t>(scratch, ds.idx), (int)nw, 0, 64, s));
+  hipLaunchKernelGGL(flag_dups_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, at<const uint64_t>(scratch, ds.keys),
+                     at<const uint32_t>(scratch, ds.idx), nw, dup);
   SCT_LAUNCH_CHECK();
-  SCT_HIP(hipStreamSynchronize(s));  // the scratch dies here
   return SCT_OK;
 }
 
+}  // namespace
+
+// A plan owns its device memory through members that free themselves: `block` holds every table of
+// the layout it has (carved by nearest_index_layout.h), and the posterior has two buffers.  The
+// kernel argument of its layout (hv, ot or tables) is kept ready-made and points into the block.
 struct sct_nearest_plan {
-  int kind = 2, max_d = 0, nparts = 0, code_bits = 0;
+  int kind = 2, max_d = 0, code_bits = 0;
   int64_t nw = 0;
-  bool halves = false;  // half-key tables (Halves) for max_d <= 1
-  Halves hv{};
-  void* hv_mem[1] = {};  // one block: offA, offB, entA, entB, packed permAB
-  uint32_t* perm_packed = nullptr;  // permAB at pbits per entry (+ 2 dwords of padding), inside hv_mem[0]
-  int pbits = 0;
-  int nkeys = 0;  // > 0: open-addressing multi-index (OTables); 0: CSR per block (Parts)
+  int scheme = 0;  // SCT_NEAREST_HALVES / _OA / _CSR once a builder has filled the plan
+  sct::DevBuf block;
+  Halves hv{};     // half-key tables, max_d <= 1
+  int nkeys = 0;   // open-addressing multi-index: key tables of `slots` slots
+  int64_t slots = 0;
   OTables ot{};
-  Parts parts{};
+  int nparts = 0;  // CSR buckets per block
+  Tables tables{};
   int64_t nbuckets[MAX_PARTS] = {};
-  uint32_t* d_off[MAX_PARTS] = {};
-  uint64_t* d_code[MAX_PARTS] = {};
-  uint32_t* d_index[MAX_PARTS] = {};
   // recorded after every query on its stream: destroy waits on it, so freeing the tables never
   // races a query still in flight (a caller may destroy right after enqueueing one)
   hipEvent_t last_query = nullptr;
   // posterior scoring of sct_nearest_correct (sct_nearest_plan_set_posterior)
   bool post_set = false;
   uint32_t post_num = 0, post_den = 0;
-  uint32_t* d_priorAB = nullptr;  // the priors in table order, [2 nw]; null: all ones
-  uint32_t* d_qweight = nullptr;  // [256]
+  sct::DevBuf priorAB;  // the priors in table order, uint32 [2 nw]; null: all ones
+  sct::DevBuf qweight;  // uint32 [256]
 };
 
 extern "C" int sct_nearest_plan_destroy(sct_nearest_plan* p) {
@@ -967,114 +989,189 @@ extern "C" int sct_nearest_plan_destroy(sct_nearest_plan* p) {
     (void)hipEventSynchronize(p->last_query);
     (void)hipEventDestroy(p->last_query);
   }
-  if (p->d_priorAB) (void)hipFree(p->d_priorAB);
-  if (p->d_qweight) (void)hipFree(p->d_qweight);
-  for (void* m : p->hv_mem)
-    if (m) (void)hipFree(m);
-  for (int k = 0; k < MAX_KEYS; ++k)
-    if (p->ot.t[k].slots) (void)hipFree(p->ot.t[k].slots);
-  for (int k = 0; k < MAX_PARTS; ++k) {
-    if (p->d_off[k]) (void)hipFree(p->d_off[k]);
-    if (p->d_code[k]) (void)hipFree(p->d_code[k]);
-    if (p->d_index[k]) (void)hipFree(p->d_index[k]);
-  }
   delete p;
   return SCT_OK;
 }
 
-// The half-key tables, if the whitelist allows them (SCT_OK with p->halves set), else SCT_OK
-// with p->halves false (the caller takes another layout).  One device allocation for the
-// plan's tables, scratch from the library's pool, one synchronisation (for the layout check).
-static int build_halves(sct_nearest_plan* p, const uint64_t* d_wl, int64_t nw, int G, hipStream_t s) {
+// ---------------------------------------------------------------- the builders
+// Each fills the plan -- its block, its kernel argument, p->scheme -- from the device whitelist on `s`:
+// one allocation for the layout's block (the plan owns it at once, so every return is leak-free),
+// scratch from one block of the library's pool, and that block's finish() as the synchronisation.
+// Sizes, offsets and masks come from nearest_index_layout.h.
+static_assert(nix::kOa == SCT_NEAREST_OA && nix::kCsr == SCT_NEAREST_CSR && nix::kHalves == SCT_NEAREST_HALVES,
+              "the layout header's scheme numbers are the ABI's");
+
+// The half-key tables, if the whitelist allows them: its digits are checked on the device.  Else
+// SCT_OK with p->scheme left 0 and the block given back (the caller takes the next layout).
+static int build_halves(sct_nearest_plan* p, const uint64_t* d_wl, hipStream_t s) {
+  const int64_t nw = p->nw, n = std::max<int64_t>(nw, 1);
+  const nix::HalvesDims d = nix::halves_dims(nix::positions(p->kind, p->code_bits), nw);
+  const nix::HalvesBlock tb = nix::halves_block(d, nw);
+  SCT_HIP(p->block.alloc((size_t)tb.total));
   Halves h{};
-  h.G = G;
-  h.GB = G / 2;
-  h.GA = G - h.GB;
+  h.GA = d.GA;
+  h.GB = d.GB;
+  h.G = d.GA + d.GB;
   h.nw = nw;
-  const int64_t nA = 1LL << (2 * h.GA), nB = 1LL << (2 * h.GB);
-  const size_t n = (size_t)std::max<int64_t>(nw, 1);
-  int pb = 1;  // bits of a packed whitelist index
-  while (pb < 32 && (1LL << pb) < nw) ++pb;
-  const int64_t ndw = (2 * (int64_t)n * pb + 31) / 32 + 2;  // + 2: the last 8-byte load's second dword
-  // the plan's tables: offA, offB, entA, entB (+16 B: the last chunk's load may run past nw), packed permAB
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t oOffA = 0, oOffB = oOffA + al((nA + 1) * 4), oEntA = oOffB + al((nB + 1) * 4);
-  const size_t oEntB = oEntA + al(n * 2 + 16), oPack = oEntB + al(n * 2 + 16), oRank = oPack + al(ndw * 4);
-  const size_t total = oRank + al(n);
-  SCT_HIP(hipMalloc(&p->hv_mem[0], total));
-  char* base = reinterpret_cast<char*>(p->hv_mem[0]);
-  h.offA = reinterpret_cast<const uint32_t*>(base + oOffA);
-  h.offB = reinterpret_cast<const uint32_t*>(base + oOffB);
-  h.entA = reinterpret_cast<const uint16_t*>(base + oEntA);
-  h.entB = reinterpret_cast<const uint16_t*>(base + oEntB);
-  p->perm_packed = reinterpret_cast<uint32_t*>(base + oPack);
-  uint8_t* rankB = reinterpret_cast<uint8_t*>(base + oRank);
-  p->pbits = pb;
-  // scratch: bucket counts / cursors of both tables, permAB unpacked, the layout flag and the
-  // out-of-key-order flag
-  const size_t sCnt = 0, sPerm = sCnt + al((nA + nB) * 4), sBad = sPerm + al(2 * n * 4), sTotal = sBad + 256;  // (flags: 1 + kOrders words)
+  h.offA = at<const uint32_t>(p->block.p, tb.offA);
+  h.offB = at<const uint32_t>(p->block.p, tb.offB);
+  h.entA = at<const uint16_t>(p->block.p, tb.entA);
+  h.entB = at<const uint16_t>(p->block.p, tb.entB);
+  uint32_t* packed = at<uint32_t>(p->block.p, tb.packed);
+  uint8_t* rankB = at<uint8_t>(p->block.p, tb.rankB);
+  // scratch: bucket counts / cursors of both tables, permAB unpacked, the flag words
+  nix::Carve sc;
+  const int64_t sCnt = sc.add((d.nA + d.nB) * 4), sPerm = sc.add(2 * n * 4), sFlags = sc.add(256);
   sct::PoolBlock scratch(s);
-  if (int rc = scratch.alloc(sTotal); rc != SCT_OK) return rc;
-  char* sb = reinterpret_cast<char*>(scratch.p);
-  uint32_t* cntA = reinterpret_cast<uint32_t*>(sb + sCnt);
-  uint32_t* cntB = cntA + nA;
-  uint32_t* perm = reinterpret_cast<uint32_t*>(sb + sPerm);
-  unsigned* bad = reinterpret_cast<unsigned*>(sb + sBad);
-  hipError_t e = hipMemsetAsync(sb, 0, sPerm, s);
-  if (e == hipSuccess) e = hipMemsetAsync(bad, 0, 4 * (2 + 2 * kOrders), s);
+  SCT_TRY(scratch.alloc((size_t)sc.total));
+  uint32_t* cntA = at<uint32_t>(scratch.p, sCnt);
+  uint32_t* cntB = cntA + d.nA;
+  uint32_t* perm = at<uint32_t>(scratch.p, sPerm);
+  // flag words: the layout does not apply | out of key order under each candidate digit order | the
+  // order chosen: dinv, dalpha, ident_a | an A bucket of more than 256 codes
+  constexpr int kFlags = 2 + 2 * kOrders;
+  unsigned* bad = at<unsigned>(scratch.p, sFlags);
+  unsigned* unsorted = bad + 1;
+  unsigned* order = unsorted + kOrders;
+  unsigned* rank_over = order + kOrders;
+  SCT_HIP(hipMemsetAsync(cntA, 0, (size_t)(d.nA + d.nB) * 4, s));
+  SCT_HIP(hipMemsetAsync(bad, 0, 4 * kFlags, s));
   const unsigned g = grid_for(nw, 4096);
   // the digit order: the first candidate the whitelist is sorted in, chosen on the device (no extra
   // synchronisation; the build's kernels and the host read it from `order`)
-  unsigned* order = bad + 1 + kOrders;
-  if (e == hipSuccess) {
-    if (p->kind == 2)
-      hipLaunchKernelGGL(halves_order_kernel<2>, dim3(g), dim3(WG), 0, s, d_wl, nw, h, bad + 1);
-    else
-      hipLaunchKernelGGL(halves_order_kernel<3>, dim3(g), dim3(WG), 0, s, d_wl, nw, h, bad + 1);
-    hipLaunchKernelGGL(halves_pick_order_kernel, dim3(1), dim3(1), 0, s, (const unsigned*)(bad + 1), order);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) {
-    if (p->kind == 2)
-      hipLaunchKernelGGL(halves_count_kernel<2>, dim3(g), dim3(WG), 0, s, d_wl, nw, h, cntA, cntB, bad,
-                         (const unsigned*)order);
-    else
-      hipLaunchKernelGGL(halves_count_kernel<3>, dim3(g), dim3(WG), 0, s, d_wl, nw, h, cntA, cntB, bad,
-                         (const unsigned*)order);
-    hipLaunchKernelGGL(halves_scan_kernel, dim3(1), dim3(1024), 0, s, cntA, nA, (uint32_t*)h.offA, cntB, nB,
-                       (uint32_t*)h.offB);
-    if (p->kind == 2)
-      hipLaunchKernelGGL(halves_scatter_kernel<2>, dim3(g), dim3(WG), 0, s, d_wl, nw, h, cntA, cntB,
-                         (uint16_t*)h.entA, (uint16_t*)h.entB, perm, (const unsigned*)order, rankB,
-                         bad + 1 + 2 * kOrders);
-    else
-      hipLaunchKernelGGL(halves_scatter_kernel<3>, dim3(g), dim3(WG), 0, s, d_wl, nw, h, cntA, cntB,
-                         (uint16_t*)h.entA, (uint16_t*)h.entB, perm, (const unsigned*)order, rankB,
-                         bad + 1 + 2 * kOrders);
-    hipLaunchKernelGGL(pack_perm_kernel, dim3(grid_for(ndw, 4096)), dim3(WG), 0, s, (const uint32_t*)perm,
-                       (int64_t)(2 * n), pb, ndw, p->perm_packed);
-    e = hipGetLastError();
-  }
-  // layout not applicable, (unsorted flags), dinv, dalpha, ident_a, an A bucket of > 256 codes
-  unsigned hflags[2 + 2 * kOrders] = {1u};
-  if (e == hipSuccess) e = hipMemcpyAsync(hflags, bad, sizeof(hflags), hipMemcpyDeviceToHost, s);
-  scratch.note(e);
-  if (int rc = scratch.finish(SCT_OK, "half-key build"); rc != SCT_OK) return rc;
+  with_kind(p->kind, [&](auto K) {
+    hipLaunchKernelGGL(halves_order_kernel<K()>, dim3(g), dim3(WG), 0, s, d_wl, nw, h, unsorted);
+  });
+  hipLaunchKernelGGL(halves_pick_order_kernel, dim3(1), dim3(1), 0, s, (const unsigned*)unsorted, order);
+  SCT_LAUNCH_CHECK();
+  with_kind(p->kind, [&](auto K) {
+    hipLaunchKernelGGL(halves_count_kernel<K()>, dim3(g), dim3(WG), 0, s, d_wl, nw, h, cntA, cntB, bad,
+                       (const unsigned*)order);
+  });
+  hipLaunchKernelGGL(halves_scan_kernel, dim3(1), dim3(1024), 0, s, cntA, d.nA, (uint32_t*)h.offA, cntB, d.nB,
+                     (uint32_t*)h.offB);
+  with_kind(p->kind, [&](auto K) {
+    hipLaunchKernelGGL(halves_scatter_kernel<K()>, dim3(g), dim3(WG), 0, s, d_wl, nw, h, cntA, cntB,
+                       (uint16_t*)h.entA, (uint16_t*)h.entB, perm, (const unsigned*)order, rankB, rank_over);
+  });
+  hipLaunchKernelGGL(pack_perm_kernel, dim3(grid_for(d.ndw, 4096)), dim3(WG), 0, s, (const uint32_t*)perm,
+                     (int64_t)(2 * n), d.pbits, d.ndw, packed);
+  SCT_LAUNCH_CHECK();
+  unsigned hflags[kFlags] = {1u};
+  SCT_HIP(hipMemcpyAsync(hflags, bad, sizeof(hflags), hipMemcpyDeviceToHost, s));
+  SCT_TRY(scratch.finish(SCT_OK, "half-key build"));
   if (hflags[0]) {  // not applicable: another layout
-    (void)hipFree(p->hv_mem[0]);
-    p->hv_mem[0] = nullptr;
-    p->perm_packed = nullptr;
+    p->block.reset();
     return SCT_OK;
   }
-  h.dinv = hflags[1 + kOrders];
-  h.dalpha = hflags[2 + kOrders];
-  h.ident_a = (int)hflags[3 + kOrders];
-  h.rankB = h.ident_a && !hflags[1 + 2 * kOrders] ? rankB : nullptr;
-  h.perm_packed = p->perm_packed;
-  h.pbits = pb;
+  const unsigned* horder = hflags + 1 + kOrders;
+  h.dinv = horder[0];
+  h.dalpha = horder[1];
+  h.ident_a = (int)horder[2];
+  h.rankB = h.ident_a && !horder[kOrders] ? rankB : nullptr;
+  h.perm_packed = packed;
+  h.pbits = d.pbits;
   p->hv = h;
-  p->halves = true;
+  p->scheme = SCT_NEAREST_HALVES;
   return SCT_OK;
+}
+
+// Open addressing: every key's table is cleared, then one insert pass over the whitelist fills it.
+static int build_open_addressing(sct_nearest_plan* p, const uint64_t* d_wl, hipStream_t s) {
+  const int64_t nw = p->nw;
+  nix::OaLayout lay;
+  SCT_CHECK(nix::oa_layout(p->kind, p->code_bits, p->max_d, nw, &lay), "the plan cannot take open addressing");
+  const nix::OaBlock tb = nix::oa_block(lay.nkeys, lay.slots);
+  SCT_HIP(p->block.alloc((size_t)tb.total));
+  nix::Carve sc;
+  const DupScratch ds(sc, nw, s);
+  sct::PoolBlock scratch(s);
+  SCT_TRY(scratch.alloc((size_t)sc.total));
+  SCT_TRY(enqueue_dups(d_wl, nw, ds, scratch.p, s));
+  for (int t = 0; t < lay.nkeys; ++t) {
+    OTable& ot = p->ot.t[t];
+    ot.keymask = lay.keymask[t];
+    ot.gmask = (uint64_t)(lay.groups - 1);
+    ot.slots = at<uint4>(p->block.p, tb.slots[t]);
+    hipLaunchKernelGGL(oa_clear_kernel, dim3(grid_for(lay.slots, 8192)), dim3(WG), 0, s, ot.slots, lay.slots);
+    if (nw)
+      hipLaunchKernelGGL(oa_insert_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, d_wl, nw,
+                         at<const uint8_t>(scratch.p, ds.dup), ot);
+    SCT_LAUNCH_CHECK();
+  }
+  p->nkeys = lay.nkeys;
+  p->slots = lay.slots;
+  p->scheme = SCT_NEAREST_OA;
+  return scratch.finish(SCT_OK, "open-addressing build");
+}
+
+static Part part_of(const nix::CsrPart& c) { return Part{c.mask, c.mul, c.lo_bit, c.nbits, c.shift}; }
+
+// CSR buckets.  Bucket count per part: a provisional table of ~nw/2 buckets counts the occupied ones
+// (~ the distinct block values: 4^8 = 65,536 for an 8-base ThreeBit block of a 737K whitelist, nw
+// itself for max_d = 0), then the part gets ~SCT_TUNE_NEAREST_LOAD (4) buckets per distinct value,
+// never more than the provisional count: the offset tables stay small enough to live in each XCD's
+// L2 while colliding block values add few extra entries.  The block is sized from those counts, so
+// this build waits once for them and once at the end.
+static int build_csr(sct_nearest_plan* p, const uint64_t* d_wl, hipStream_t s) {
+  const int64_t nw = p->nw;
+  const int G = nix::positions(p->kind, p->code_bits), P = p->max_d + 1;
+  const int lg0 = nix::csr_lg0(nw);
+  nix::CsrPart part[MAX_PARTS];  // provisional: 2^lg0 buckets each
+  for (int k = 0; k < P; ++k) part[k] = nix::csr_part(p->kind, G, P, k, lg0);
+  const int64_t nb0 = part[0].buckets;
+  const int load = (int)std::max<int64_t>(1, sct::tune(SCT_TUNE_NEAREST_LOAD, 4));
+  size_t scan_bytes = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                         (int)(nb0 + 1), s);
+  nix::Carve sc;
+  const DupScratch ds(sc, nw, s);
+  const int64_t sScan = sc.add((int64_t)scan_bytes), sCounts = sc.add((nb0 + 1) * 4), sOcc = sc.add(8 * MAX_PARTS);
+  sct::PoolBlock scratch(s);
+  SCT_TRY(scratch.alloc((size_t)sc.total));
+  SCT_TRY(enqueue_dups(d_wl, nw, ds, scratch.p, s));
+  uint32_t* counts = at<uint32_t>(scratch.p, sCounts);
+  auto* d_occ = at<unsigned long long>(scratch.p, sOcc);
+  SCT_HIP(hipMemsetAsync(d_occ, 0, 8 * MAX_PARTS, s));
+  if (nw && lg0 > 0) {  // occupied provisional buckets per part
+    for (int k = 0; k < P; ++k) {
+      SCT_HIP(hipMemsetAsync(counts, 0, (size_t)(nb0 + 1) * 4, s));
+      hipLaunchKernelGGL(key_hist_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, d_wl, nw,
+                         part_of(part[k]), counts);
+      hipLaunchKernelGGL(count_nonzero_kernel, dim3(grid_for(nb0, 1024)), dim3(WG), 0, s, counts, nb0, d_occ + k);
+    }
+    SCT_LAUNCH_CHECK();
+    unsigned long long h_occ[MAX_PARTS] = {};
+    SCT_HIP(hipMemcpyAsync(h_occ, d_occ, 8 * MAX_PARTS, hipMemcpyDeviceToHost, s));
+    SCT_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < P; ++k) part[k] = nix::csr_part(p->kind, G, P, k, nix::csr_lg(lg0, load, h_occ[k]));
+  }
+  for (int k = 0; k < P; ++k) p->nbuckets[k] = part[k].buckets;
+  const nix::CsrBlock tb = nix::csr_block(P, p->nbuckets, nw);
+  SCT_HIP(p->block.alloc((size_t)tb.total));
+  for (int k = 0; k < P; ++k) {
+    const Part pt = part_of(part[k]);
+    const int64_t nbuckets = p->nbuckets[k];
+    uint32_t* off = at<uint32_t>(p->block.p, tb.off[k]);
+    uint64_t* code = at<uint64_t>(p->block.p, tb.code[k]);
+    uint32_t* index = at<uint32_t>(p->block.p, tb.index[k]);
+    SCT_HIP(hipMemsetAsync(counts, 0, (size_t)(nbuckets + 1) * 4, s));
+    if (nw) hipLaunchKernelGGL(key_hist_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, d_wl, nw, pt, counts);
+    size_t b = scan_bytes;
+    SCT_HIP(hipcub::DeviceScan::ExclusiveSum(at<void>(scratch.p, sScan), b, counts, off, (int)(nbuckets + 1), s));
+    SCT_HIP(hipMemcpyAsync(counts, off, (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, s));
+    if (nw)
+      hipLaunchKernelGGL(key_scatter_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, d_wl, nw, pt, counts,
+                         at<const uint8_t>(scratch.p, ds.dup), code, index);
+    SCT_LAUNCH_CHECK();
+    p->tables.part[k] = pt;
+    p->tables.off[k] = off;
+    p->tables.code[k] = code;
+    p->tables.index[k] = index;
+  }
+  p->nparts = P;
+  p->scheme = SCT_NEAREST_CSR;
+  return scratch.finish(SCT_OK, "CSR build");
 }
 
 extern "C" int sct_nearest_plan_create(int kind, const uint64_t* d_whitelist, int64_t nw,
@@ -1086,151 +1183,24 @@ extern "C" int sct_nearest_plan_create(int kind, const uint64_t* d_whitelist, in
   SCT_CHECK(nw >= 0 && nw < (1LL << 31), "whitelist size %lld out of range", (long long)nw);
   SCT_CHECK(nw == 0 || d_whitelist != nullptr, "whitelist is NULL");
   SCT_CHECK(code_bits >= 1 && code_bits <= 64, "code_bits %d outside [1, 64]", code_bits);
-  const int G = (code_bits + kind - 1) / kind;  // base positions
+  const int G = nix::positions(kind, code_bits);
   SCT_CHECK(max_d >= 0 && max_d + 1 <= MAX_PARTS && max_d < G,
             "max_d %d unsupported (needs max_d+1 <= %d and < %d positions)", max_d, MAX_PARTS, G);
   hipStream_t s = sct::as_stream(stream);
-  auto* p = new sct_nearest_plan();
-  auto fail_with = [&](int rc) {
-    sct_nearest_plan_destroy(p);
-    return rc;
-  };
+  // sct_tune_set(SCT_TUNE_NEAREST_SCHEME, 1 / 2 / 3) forces open addressing / CSR / the half keys
+  const int64_t forced = sct::tune(SCT_TUNE_NEAREST_SCHEME, 0);
+  auto p = std::make_unique<sct_nearest_plan>();  // (no query yet: nothing for destroy to wait on)
   p->kind = kind;
   p->max_d = max_d;
   p->nw = nw;
   p->code_bits = code_bits;
-  p->nparts = max_d + 1;
-  {
-    // half-key tables: max_d <= 1, 2..16 positions, an A/C/G/T whitelist (checked on the device)
-    const int64_t forced = sct::tune(SCT_TUNE_NEAREST_SCHEME, 0);
-    if ((forced == 0 || forced == SCT_NEAREST_HALVES) && max_d <= 1 && G >= 2 && G <= 16 && nw > 0) {
-      if (int rc = build_halves(p, d_whitelist, nw, G, s); rc != SCT_OK) return fail_with(rc);
-      if (p->halves) {
-        *out = p;
-        return SCT_OK;
-      }
-    }
+  const nix::Builders todo = nix::builders(kind, code_bits, max_d, nw, forced);
+  for (int i = 0; i < todo.n && !p->scheme; ++i) {
+    if (todo.scheme[i] == nix::kHalves) SCT_TRY(build_halves(p.get(), d_whitelist, s));
+    else if (todo.scheme[i] == nix::kOa) SCT_TRY(build_open_addressing(p.get(), d_whitelist, s));
+    else SCT_TRY(build_csr(p.get(), d_whitelist, s));
   }
-  sct::DevBuf dup;
-  if (dup.alloc((size_t)std::max<int64_t>(nw, 1)) != hipSuccess)
-    return fail_with(sct::fail(SCT_E_NOMEM, "dup flags"));
-  if (int rc = compute_dups(d_whitelist, nw, (uint8_t*)dup.p, s); rc != SCT_OK) return fail_with(rc);
-  // Open addressing when the multi-index keys are nearly unique for random codes: s = 1 block
-  // per key for max_d = 0 (the whole code), s = 2 (pairs of P = max_d + 2 blocks) for max_d 1..2,
-  // if every key spans enough bases that 4^bases >= nw / 2, i.e. at most ~2 random codes share
-  // a key (sct_tune_set(SCT_TUNE_NEAREST_SCHEME, 1 / 2) forces open addressing / CSR).
-  {
-    const int P = max_d == 0 ? 1 : max_d + 2;
-    const int sz = max_d == 0 ? 1 : 2;
-    const int nkeys = sz == 1 ? 1 : P * (P - 1) / 2;
-    int min_bases = G;  // the smallest key: two smallest blocks of a floor split
-    if (sz == 2) min_bases = 2 * (G / P);
-    bool oa = P <= G && nkeys <= MAX_KEYS && 2.0 * min_bases >= std::log2(0.5 * std::max<int64_t>(nw, 2));
-    const int64_t forced = sct::tune(SCT_TUNE_NEAREST_SCHEME, 0);
-    if (forced == SCT_NEAREST_CSR) oa = false;
-    if (forced == SCT_NEAREST_OA) oa = P <= G && nkeys <= MAX_KEYS;
-    if (oa) {
-      uint64_t bmask[MAX_KEYS + 2] = {};
-      for (int b = 0; b < P; ++b) {
-        const int lo = G * b / P * kind, hi = std::min(64, G * (b + 1) / P * kind);
-        bmask[b] = (hi - lo >= 64 ? ~0ull : ((1ull << (hi - lo)) - 1ull)) << lo;
-      }
-      int64_t nslots = kGroup;
-      while (nslots < 2 * nw) nslots *= 2;  // load <= 1/2
-      int t = 0;
-      for (int a = 0; a < P; ++a)
-        for (int b = sz == 1 ? a : a + 1; b < P; ++b) {
-          if (sz == 1 && b != a) continue;
-          OTable& ot = p->ot.t[t++];
-          ot.keymask = bmask[a] | bmask[b];
-          ot.gmask = (uint64_t)(nslots / kGroup - 1);
-          hipError_t e = hipMalloc(&ot.slots, (size_t)nslots * 16);
-          if (e != hipSuccess) return fail_with(sct::fail(SCT_E_NOMEM, "slots: %s", hipGetErrorString(e)));
-          hipLaunchKernelGGL(oa_clear_kernel, dim3(grid_for(nslots, 8192)), dim3(WG), 0, s, ot.slots, nslots);
-          if (nw)
-            hipLaunchKernelGGL(oa_insert_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, d_whitelist, nw,
-                               (const uint8_t*)dup.p, ot);
-          SCT_LAUNCH_CHECK();
-        }
-      p->nkeys = t;
-      SCT_HIP(hipStreamSynchronize(s));
-      *out = p;
-      return SCT_OK;
-    }
-  }
-  // Bucket count per part: a provisional table of ~nw/2 buckets counts the occupied ones
-  // (~ the distinct block values: 4^8 = 65,536 for an 8-base ThreeBit block of a 737K
-  // whitelist, nw itself for max_d = 0), then the part gets ~SCT_TUNE_NEAREST_LOAD (4) buckets per
-  // distinct value, never more than the provisional count: the offset tables stay small
-  // enough to live in each XCD's L2 while colliding block values add few extra entries.
-  int lg0 = 0;
-  while (lg0 < 28 && (1LL << lg0) * 2 < nw) ++lg0;
-  const int load = (int)std::max<int64_t>(1, sct::tune(SCT_TUNE_NEAREST_LOAD, 4));
-  for (int k = 0; k < p->nparts; ++k) {
-    const int pos_lo = G * k / p->nparts, pos_hi = G * (k + 1) / p->nparts;
-    Part& pt = p->parts.p[k];
-    pt.lo_bit = pos_lo * kind;
-    pt.nbits = std::min(64, pos_hi * kind) - pt.lo_bit;
-    pt.mask = (pt.nbits >= 64 ? ~0ull : ((1ull << pt.nbits) - 1ull)) << pt.lo_bit;
-    pt.mul = lg0 == 0 ? 0ull : 0x9E3779B97F4A7C15ull;
-    pt.shift = lg0 == 0 ? 63 : 64 - lg0;
-  }
-  const int64_t nb0 = 1LL << lg0;
-  size_t scan_bytes = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                         (int)(nb0 + 1), s);
-  sct::DevBuf scan_tmp, cursor, occ;
-  hipError_t e = scan_tmp.alloc(scan_bytes);
-  if (e == hipSuccess) e = cursor.alloc((size_t)(nb0 + 1) * 4);
-  if (e == hipSuccess) e = occ.alloc(8 * MAX_PARTS);
-  if (e != hipSuccess) return fail_with(sct::fail(SCT_E_NOMEM, "scratch: %s", hipGetErrorString(e)));
-  uint32_t* counts = (uint32_t*)cursor.p;
-  auto* d_occ = (unsigned long long*)occ.p;
-  SCT_HIP(hipMemsetAsync(d_occ, 0, 8 * MAX_PARTS, s));
-  if (nw && lg0 > 0) {  // occupied provisional buckets per part
-    for (int k = 0; k < p->nparts; ++k) {
-      SCT_HIP(hipMemsetAsync(counts, 0, (size_t)(nb0 + 1) * 4, s));
-      hipLaunchKernelGGL(key_hist_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, d_whitelist, nw,
-                         p->parts.p[k], counts);
-      hipLaunchKernelGGL(count_nonzero_kernel, dim3(grid_for(nb0, 1024)), dim3(WG), 0, s, counts, nb0, d_occ + k);
-    }
-    SCT_LAUNCH_CHECK();
-    unsigned long long h_occ[MAX_PARTS] = {};
-    SCT_HIP(hipMemcpyAsync(h_occ, d_occ, 8 * MAX_PARTS, hipMemcpyDeviceToHost, s));
-    SCT_HIP(hipStreamSynchronize(s));
-    for (int k = 0; k < p->nparts; ++k) {
-      int lg = 0;
-      while (lg < lg0 && (1ULL << lg) < (unsigned long long)load * std::max(1ULL, h_occ[k])) ++lg;
-      Part& pt = p->parts.p[k];
-      pt.mul = lg == 0 ? 0ull : 0x9E3779B97F4A7C15ull;
-      pt.shift = lg == 0 ? 63 : 64 - lg;
-      p->nbuckets[k] = 1LL << lg;
-    }
-  } else {
-    for (int k = 0; k < p->nparts; ++k) p->nbuckets[k] = nb0;
-  }
-  for (int k = 0; k < p->nparts; ++k) {
-    const Part pt = p->parts.p[k];
-    const int64_t nbuckets = p->nbuckets[k];
-    e = hipMalloc(&p->d_off[k], (size_t)(nbuckets + 1) * 4);
-    if (e == hipSuccess) e = hipMalloc(&p->d_code[k], (size_t)std::max<int64_t>(nw, 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&p->d_index[k], (size_t)std::max<int64_t>(nw, 1) * 4);
-    if (e != hipSuccess) return fail_with(sct::fail(SCT_E_NOMEM, "bucket arrays: %s", hipGetErrorString(e)));
-    SCT_HIP(hipMemsetAsync(counts, 0, (size_t)(nbuckets + 1) * 4, s));
-    if (nw)
-      hipLaunchKernelGGL(key_hist_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, d_whitelist, nw,
-                         pt, counts);
-    size_t b = scan_bytes;
-    e = hipcub::DeviceScan::ExclusiveSum(scan_tmp.p, b, counts, p->d_off[k], (int)(nbuckets + 1), s);
-    if (e != hipSuccess) return fail_with(sct::fail(SCT_E_HIP, "scan: %s", hipGetErrorString(e)));
-    SCT_HIP(hipMemcpyAsync(counts, p->d_off[k], (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, s));
-    if (nw)
-      hipLaunchKernelGGL(key_scatter_kernel, dim3(grid_for(nw, 4096)), dim3(WG), 0, s, d_whitelist,
-                         nw, pt, counts, (const uint8_t*)dup.p, p->d_code[k], p->d_index[k]);
-    SCT_LAUNCH_CHECK();
-  }
-  SCT_HIP(hipStreamSynchronize(s));  // the scratch buffers die with this call
-  *out = p;
+  *out = p.release();
   return SCT_OK;
 }
 
@@ -1239,20 +1209,11 @@ int64_t sct::nearest_plan_size(const sct_nearest_plan* p) { return p->nw; }
 
 extern "C" int sct_nearest_plan_info(const sct_nearest_plan* p, int* scheme, int64_t* index_bytes) {
   SCT_CHECK(p != nullptr, "plan is NULL");
-  int64_t bytes = 0;
-  if (p->halves) {
-    bytes = ((1LL << (2 * p->hv.GA)) + (1LL << (2 * p->hv.GB)) + 2) * 4 + p->nw * 4 + (2 * p->nw * p->pbits + 31) / 32 * 4;
-    if (scheme) *scheme = SCT_NEAREST_HALVES;
-    if (index_bytes) *index_bytes = bytes;
-    return SCT_OK;
-  }
-  if (p->nkeys > 0) {
-    for (int k = 0; k < p->nkeys; ++k) bytes += (int64_t)(p->ot.t[k].gmask + 1) * kGroup * 16;
-  } else {
-    for (int k = 0; k < p->nparts; ++k) bytes += (p->nbuckets[k] + 1) * 4 + p->nw * 12;
-  }
-  if (scheme) *scheme = p->nkeys > 0 ? SCT_NEAREST_OA : SCT_NEAREST_CSR;
-  if (index_bytes) *index_bytes = bytes;
+  if (scheme) *scheme = p->scheme;
+  if (!index_bytes) return SCT_OK;
+  if (p->scheme == SCT_NEAREST_HALVES) *index_bytes = nix::halves_index_bytes(p->hv.G, p->nw);
+  else if (p->scheme == SCT_NEAREST_OA) *index_bytes = nix::oa_index_bytes(p->nkeys, p->slots);
+  else *index_bytes = nix::csr_index_bytes(p->nparts, p->nbuckets, p->nw);
   return SCT_OK;
 }
 
@@ -1282,12 +1243,12 @@ static void launch_halves_query(const sct_nearest_plan* p, const uint64_t* d_que
   constexpr bool kDefer = sizeof...(DF) != 0;
   const unsigned blocks = (unsigned)sct::ceil_div(nq, WG);  // one query per thread
   const bool idx = p->hv.ident_a;  // whitelist indices straight from the query kernel
-  auto kern = idx ? (p->kind == 2 ? halves_query_kernel<2, true, kDefer, DF...> : halves_query_kernel<3, true, kDefer, DF...>)
-                  : (p->kind == 2 ? halves_query_kernel<2, false, kDefer, DF...> : halves_query_kernel<3, false, kDefer, DF...>);
+  auto kern = idx ? with_kind(p->kind, [](auto K) { return halves_query_kernel<K(), true, kDefer, DF...>; })
+                  : with_kind(p->kind, [](auto K) { return halves_query_kernel<K(), false, kDefer, DF...>; });
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(WG), 0, s, d_queries, nq, p->hv, p->max_d, d_index, d_dist, df...);
   if (!idx)
     hipLaunchKernelGGL(halves_index_kernel, dim3(grid_for(sct::ceil_div(nq, 4), 8192)), dim3(WG), 0, s, d_index, nq,
-                       (const uint32_t*)p->perm_packed, p->pbits, ((uintptr_t)d_index & 15) == 0);
+                       p->hv.perm_packed, p->hv.pbits, ((uintptr_t)d_index & 15) == 0);
 }
 
 static int nearest_query_launch(sct_nearest_plan* p, const uint64_t* d_queries, int64_t nq, int32_t* d_index,
@@ -1299,46 +1260,32 @@ static int nearest_query_launch(sct_nearest_plan* p, const uint64_t* d_queries, 
   hipStream_t s = sct::as_stream(stream);
   const unsigned blocks = (unsigned)sct::ceil_div(nq, WG);  // one query per thread
   SCT_CHECK(sct::ceil_div(nq, WG) < (1LL << 31), "too many queries for one launch");
-  if (p->halves) {
+  if (p->scheme == SCT_NEAREST_HALVES)
     launch_halves_query(p, d_queries, nq, d_index, d_dist, s);
-    SCT_LAUNCH_CHECK();
-    return SCT_OK;
-  }
-  if (p->nkeys > 0) {
-    if (p->kind == 2)
-      launch_oa_query<2>(p->nkeys, blocks, s, d_queries, nq, p->ot, p->max_d, d_index, d_dist);
-    else
-      launch_oa_query<3>(p->nkeys, blocks, s, d_queries, nq, p->ot, p->max_d, d_index, d_dist);
-    SCT_LAUNCH_CHECK();
-    return SCT_OK;
-  }
-  Tables tb{};
-  for (int k = 0; k < p->nparts; ++k) {
-    tb.part[k] = p->parts.p[k];
-    tb.off[k] = p->d_off[k];
-    tb.code[k] = p->d_code[k];
-    tb.index[k] = p->d_index[k];
-  }
-  if (p->kind == 2)
-    launch_query<2>(p->nparts, blocks, s, d_queries, nq, tb, p->max_d, d_index, d_dist);
+  else if (p->scheme == SCT_NEAREST_OA)
+    with_kind(p->kind, [&](auto K) {
+      launch_oa_query<K()>(p->nkeys, blocks, s, d_queries, nq, p->ot, p->max_d, d_index, d_dist);
+    });
   else
-    launch_query<3>(p->nparts, blocks, s, d_queries, nq, tb, p->max_d, d_index, d_dist);
+    with_kind(p->kind, [&](auto K) {
+      launch_query<K()>(p->nparts, blocks, s, d_queries, nq, p->tables, p->max_d, d_index, d_dist);
+    });
   SCT_LAUNCH_CHECK();
   return SCT_OK;
 }
 
 // ---------------------------------------------------------------- posterior correction
-int sct::nearest_plan_positions(const sct_nearest_plan* p) { return p->halves ? p->hv.G : 0; }
+int sct::nearest_plan_positions(const sct_nearest_plan* p) { return p->scheme == SCT_NEAREST_HALVES ? p->hv.G : 0; }
 
 // the plans sct_nearest_correct takes: the half-key scheme at max_d == 1
 int sct::correct_plan_check(const sct_nearest_plan* p) {
   SCT_CHECK(p != nullptr, "plan is NULL");
-  if (!p->halves || p->max_d != 1)
+  if (p->scheme != SCT_NEAREST_HALVES || p->max_d != 1)
     return sct::fail(SCT_E_RANGE,
                      "posterior correction needs a half-key plan (max_d == 1, an A/C/G/T whitelist of 2..16 "
                      "positions): this plan has max_d %d, %lld codes of %d bits%s",
                      p->max_d, (long long)p->nw, p->code_bits,
-                     p->halves ? "" : " and a whitelist with other digits, or another layout forced");
+                     p->scheme == SCT_NEAREST_HALVES ? "" : " and a whitelist with other digits, or another layout forced");
   return SCT_OK;
 }
 
@@ -1353,7 +1300,7 @@ extern "C" int sct_nearest_plan_set_posterior(sct_nearest_plan* p, const uint32_
   hipStream_t s = sct::as_stream(stream);
   // calls still in flight read the tables this one replaces
   if (p->last_query) SCT_HIP(hipStreamWaitEvent(s, p->last_query, 0));
-  if (!p->d_qweight) SCT_HIP(hipMalloc(&p->d_qweight, 256 * 4));
+  if (!p->qweight.p) SCT_HIP(p->qweight.alloc(256 * 4));
   sct::DevBuf fresh;  // the plan takes it only at the end: every failure before that frees it
   if (d_prior) {
     const int64_t n2 = 2 * p->nw;
@@ -1364,18 +1311,16 @@ extern "C" int sct_nearest_plan_set_posterior(sct_nearest_plan* p, const uint32_
     bad.note(hipMemsetAsync(bad.p, 0, 4, s));
     if (bad.ok()) {
       hipLaunchKernelGGL(prior_permute_kernel, dim3(grid_for(n2, 4096)), dim3(WG), 0, s, d_prior, n2,
-                         (const uint32_t*)p->perm_packed, p->pbits, (uint32_t*)fresh.p, (unsigned*)bad.p);
+                         p->hv.perm_packed, p->hv.pbits, (uint32_t*)fresh.p, (unsigned*)bad.p);
       bad.note(hipGetLastError());
     }
     if (bad.ok()) bad.note(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
     if (int rc = bad.finish(SCT_OK, "set posterior"); rc != SCT_OK) return rc;
     SCT_CHECK(!h_bad, "a prior is >= 2^30");
   }
-  SCT_HIP(hipMemcpyAsync(p->d_qweight, qweight, 256 * 4, hipMemcpyHostToDevice, s));
+  SCT_HIP(hipMemcpyAsync(p->qweight.p, qweight, 256 * 4, hipMemcpyHostToDevice, s));
   SCT_HIP(hipStreamSynchronize(s));  // the old priors are idle now, and qweight is the caller's again
-  if (p->d_priorAB) (void)hipFree(p->d_priorAB);
-  p->d_priorAB = static_cast<uint32_t*>(fresh.p);
-  fresh.p = nullptr;
+  std::swap(p->priorAB.p, fresh.p);  // (the old ones leave with `fresh`)
   p->post_num = (uint32_t)num;
   p->post_den = (uint32_t)den;
   p->post_set = true;
@@ -1400,12 +1345,13 @@ extern "C" int sct_nearest_correct(sct_nearest_plan* p, const uint64_t* d_querie
   void* wl = nullptr;
   SCT_HIP(sct::pool_alloc(&wl, cnt_bytes + (size_t)kSegs * seg_cap * 4, s));
   Defer df{reinterpret_cast<uint32_t*>(static_cast<char*>(wl) + cnt_bytes), static_cast<unsigned*>(wl), seg_cap,
-           p->d_priorAB != nullptr};
-  const Posterior ps{p->d_priorAB, p->d_qweight, p->post_num, p->post_den};
+           p->priorAB.p != nullptr};
+  const Posterior ps{static_cast<const uint32_t*>(p->priorAB.p), static_cast<const uint32_t*>(p->qweight.p), p->post_num,
+                     p->post_den};
   hipError_t e = hipMemsetAsync(wl, 0, cnt_bytes, s);
   if (e == hipSuccess) {
     launch_halves_query(p, d_queries, nq, d_index, d_dist, s, df);
-    auto res = p->kind == 2 ? halves_resolve_kernel<2> : halves_resolve_kernel<3>;
+    auto res = with_kind(p->kind, [](auto K) { return halves_resolve_kernel<K()>; });
     hipLaunchKernelGGL(res, dim3(grid_for(nq, 2048)), dim3(WG), 0, s, d_queries, d_qual, qual_stride, p->hv, ps,
                        df, d_index, d_dist,
                        reinterpret_cast<unsigned long long*>(d_stats));

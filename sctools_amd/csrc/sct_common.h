@@ -29,13 +29,18 @@ inline int fail(int code, const char* fmt, ...) {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-// RAII device buffer for the *_host convenience entry points.
+// RAII device buffer: the *_host convenience entry points' arrays, a nearest plan's tables.
 struct DevBuf {
   void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
   hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+  void reset() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  }
 };
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -6,9 +6,10 @@ open-addressing tables of pair keys (slot count the power of two >= max(4, 2 nw)
 finalizer as the slot hash, groups of 4 slots probed linearly, the exact-hit shortcut over table
 0's first group, the duplicate flag) and the CSR buckets per block (a provisional table of ~nw/2
 buckets, then `load` buckets per occupied one, a multiplicative hash of the block's bits) -- with a
-pure-Python build and query through each.  The mirror only chooses inputs and proves on the CPU
-that they reach a seam (tests/test_nearest_reference_host.py); a GPU answer is never compared with
-it, only with the brute force (oracle.c_nearest).  Each query takes `wrong`, the name of one
+pure-Python build and query through each, and the reported size of the half-key tables.  The mirror
+only chooses inputs and proves on the CPU that they reach a seam
+(tests/test_nearest_reference_host.py); a GPU answer is never compared with it, only with the brute
+force (oracle.c_nearest).  Each query takes `wrong`, the name of one
 deliberately wrong variant: the host test shows that the seam inputs tell each from the brute force.
 
 Part 2, the builders: (whitelist, queries, info) with uint64 arrays and what the mirror says the
@@ -168,11 +169,8 @@ def _bucket(part, code):
     return ((((code & part["mask"]) >> part["lo_bit"]) * part["mul"]) & M64) >> part["shift"]
 
 
-def csr_layout(kind, code_bits, max_d, nw, load, whitelist, wrong=None):
-    """dict(parts: [mask, lo_bit, mul, shift, buckets], index_bytes) of the CSR plan; the bucket of
-    a code in part k is csr_bucket(layout, k, code)."""
-    wl = [int(w) for w in whitelist]
-    assert len(wl) == nw
+def _csr_provisional(kind, code_bits, max_d, nw):
+    """(lg0, parts) of the provisional table: 2**lg0 ~ nw/2 buckets in every part."""
     G = positions(kind, code_bits)
     P = max_d + 1
     assert P <= MAX_PARTS and max_d < G
@@ -184,15 +182,36 @@ def csr_layout(kind, code_bits, max_d, nw, load, whitelist, wrong=None):
         lo, hi = block_range(G, P, k)
         lo_bit = lo * kind
         nbits = min(64, hi * kind) - lo_bit
-        part = {"mask": (((1 << nbits) - 1) << lo_bit) & M64, "lo_bit": lo_bit,
-                "mul": 0 if lg0 == 0 else GOLDEN, "shift": 63 if lg0 == 0 else 64 - lg0, "buckets": 1 << lg0}
-        if nw and lg0 > 0:
-            occupied = len({_bucket(part, w) for w in wl})
+        parts.append({"mask": (((1 << nbits) - 1) << lo_bit) & M64, "lo_bit": lo_bit,
+                      "mul": 0 if lg0 == 0 else GOLDEN, "shift": 63 if lg0 == 0 else 64 - lg0, "buckets": 1 << lg0})
+    return lg0, parts
+
+
+def csr_occupied(kind, code_bits, max_d, whitelist):
+    """Per part the occupied buckets of the provisional table, which the build counts on the device
+    (~ the part's distinct block values); zeros where the provisional table is one bucket and
+    nothing is counted."""
+    wl = [int(w) for w in whitelist]
+    lg0, parts = _csr_provisional(kind, code_bits, max_d, len(wl))
+    if not wl or lg0 == 0:
+        return [0] * len(parts)
+    return [len({_bucket(part, w) for w in wl}) for part in parts]
+
+
+def csr_layout(kind, code_bits, max_d, nw, load, whitelist, wrong=None):
+    """dict(parts: [mask, lo_bit, mul, shift, buckets], index_bytes) of the CSR plan; the bucket of
+    a code in part k is csr_bucket(layout, k, code)."""
+    wl = [int(w) for w in whitelist]
+    assert len(wl) == nw
+    G = positions(kind, code_bits)
+    P = max_d + 1
+    lg0, parts = _csr_provisional(kind, code_bits, max_d, nw)
+    if nw and lg0 > 0:
+        for part, occupied in zip(parts, csr_occupied(kind, code_bits, max_d, wl)):
             lg = 0
             while lg < lg0 and (1 << lg) < max(1, load) * max(1, occupied):
                 lg += 1
             part.update(mul=0 if lg == 0 else GOLDEN, shift=63 if lg == 0 else 64 - lg, buckets=1 << lg)
-        parts.append(part)
     index_bytes = sum((p["buckets"] + 1) * 4 + nw * 12 for p in parts)
     if wrong == "drop_last_block" and P > 1:
         parts = parts[:-1]
@@ -260,6 +279,26 @@ def expected_scheme(forced, kind, code_bits, max_d, nw):
     if forced == "oa" and oa_layout(kind, code_bits, max_d, nw) is not None:
         return "oa"
     return "csr"
+
+
+def halves_packing(nw):
+    """(pbits, ndw) of a half-key plan's permutation: 2 nw whitelist indices at pbits =
+    max(1, ceil(log2 nw)) bits each, in dwords, and two more for the last entry's 8-byte load."""
+    pbits = 1
+    while pbits < 32 and (1 << pbits) < nw:
+        pbits += 1
+    return pbits, (2 * max(nw, 1) * pbits + 31) // 32 + 2
+
+
+def halves_index_bytes(kind, code_bits, nw):
+    """The index_bytes sct_nearest_plan_info reports for a half-key plan: the offsets of both tables
+    (4**GA + 1 and 4**GB + 1 words; A the high ceil(G / 2) positions), nw uint16 entries in each, and
+    the packed permutation in whole dwords, without its padding."""
+    G = positions(kind, code_bits)
+    GB = G // 2
+    GA = G - GB
+    pbits, _ = halves_packing(nw)
+    return (4 ** GA + 4 ** GB + 2) * 4 + nw * 4 + (2 * nw * pbits + 31) // 32 * 4
 
 
 # ---------------------------------------------------------------- part 2: the builders

@@ -45,6 +45,7 @@ def _check_info(info, scheme, kind, code_bits, max_d, wl, load=4):
         elif 2 <= G:
             assert info["scheme"] == "halves"  # (A/C/G/T whitelists only reach here)
         if info["scheme"] == "halves":
+            assert info["index_bytes"] == R.halves_index_bytes(kind, code_bits, wl.size)
             return
         want = info["scheme"]
     else:
