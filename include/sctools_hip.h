@@ -789,7 +789,7 @@ int sct_molecules_downsample_curve_host(sct_molecules* mol, const uint64_t* thre
  *   5.    otherwise                  reads[index] += 1, and molecules[index] += 1 when the three-part key
  *                                    is new.
  * The same UMI under two features of one cell is two molecules (choosing one feature for such a
- * pair is not done here).  Invariant: reads[nw] and molecules[nw] stay per barcode, and the row sums
+ * pair is not done here: see "resolving features" below).  Invariant: reads[nw] and molecules[nw] stay per barcode, and the row sums
  * of the matrix below equal them (and collapse's collapsed[nw] the row sums of the collapsed values).
  * The two-array sct_molecules_update(_host) on a feature counter is SCT_E_INVALID, and so is
  * update_features(_host) on a counter without features; both change nothing.  n == 0 changes nothing
@@ -846,6 +846,66 @@ int sct_molecules_matrix_by(sct_molecules* mol, int method, int64_t* d_indptr, i
 int sct_molecules_matrix_by_host(sct_molecules* mol, int method, int64_t* indptr, int32_t* feature,
                                  uint64_t* molecules, uint64_t* reads, uint64_t* collapsed, int64_t room,
                                  int64_t* nnz);
+
+/* Resolving features: a (cell, UMI) pair is one physical molecule, and when it shows up under several
+ * features -- a chimeric PCR product, an index hop, a mis-assigned read -- at most one of them keeps
+ * it.  The rule is Cell Ranger's: after UMI correction, of the read groups that share barcode and
+ * UMI the feature with the most reads keeps the molecule and the others are discarded; on a tie for
+ * the most reads all of them are discarded.  The contract is restated in plain Python by
+ * tests/feature_resolve_reference.py, and that restatement is the contract (the directional roots
+ * follow this library's tie rule, the larger code, not UMI-tools' insertion order).
+ * Input: a counted feature counter (SCT_MOLECULES_COUNTED, sct_molecules_create_features); anything
+ * else is SCT_E_INVALID and changes nothing.
+ * Method: SCT_COLLAPSE_ONE_STEP, SCT_COLLAPSE_DIRECTIONAL or SCT_COLLAPSE_NONE; any other value is
+ * SCT_E_INVALID.  SCT_COLLAPSE_NONE is taken by the entry points of this block only: every *_by call
+ * goes on rejecting it.
+ * Image: every stored key (index, feature, umi) has an image under its own (index, feature): itself
+ * (NONE), its one-step parent (ONE_STEP, "collapsing UMIs one base apart") or its directional root
+ * (DIRECTIONAL, "directional clusters").
+ * Collapsed molecule: (index, feature, image umi); its reads are the sum of mreads over the keys with
+ * that image.  Collapse comes first: the groups are formed on the images and compared by the summed
+ * reads.
+ * Group: the collapsed molecules that share (index, image umi), over all features.  With top the
+ * largest reads in the group: if exactly one member has top it is *kept* and the others are *lost*;
+ * if two or more have top, every member of the group is *tied*, the members below top included, and
+ * none is kept.  A group of one member keeps it.
+ * Example: barcode 0, a UMI A and A' one base from it; feature 1 has A x 1 and A' x 3, feature 2 has
+ * A' x 3.  NONE: A' ties 3 : 3 and both members drop, A stays: entry (0, 1) = 1, tally (1, 0, 2, 6).
+ * ONE_STEP and DIRECTIONAL: feature 1's image A' carries 4 reads and beats feature 2's 3:
+ * entry (0, 1) = 1, tally (1, 1, 0, 3).  Entry (0, 2) is an explicit 0 under every method.
+ * Outputs, all written and not accumulated:
+ *   resolved[nw]  (uint64) the kept molecules per barcode;
+ *   tally[4]      (uint64, nullable) n_shared = the groups of at least 2 members, n_lost, n_tied, and
+ *                 reads_dropped = the reads of the lost and tied members;
+ *   matrix_resolved: sct_molecules_matrix_by's outputs and rules (room, nnz, the nullable value
+ *                 arrays, the single wait for the stream) and resolved[nnz], the kept molecules of
+ *                 entry (index, feature).  It shares indptr and feature with molecules, reads and
+ *                 collapsed, so an entry that loses everything holds an explicit 0.  collapsed
+ *                 non-NULL with SCT_COLLAPSE_NONE is SCT_E_INVALID.  room < nnz reports nnz and
+ *                 writes nothing, the tally included.
+ * An empty counter gives zeros and an indptr of zeros.  The calls read the table only: twice gives
+ * the same answer, and molecules, collapsed, counts and every other call mean what they meant.
+ * Invariants:
+ *   sum(resolved) + n_lost + n_tied == sum(collapsed) of the same method (nmolecules for NONE);
+ *   the row sums of the matrix's resolved[nnz] are resolved[nw];
+ *   resolved[e] <= collapsed[e] for every entry (<= molecules[e] for NONE);
+ *   with n_shared == 0, resolved equals collapsed entry for entry and the other tally words are 0;
+ *   the answer depends on the table's contents (key -> reads) only: not on the order of updates, the
+ *   capacity, the growth history, or whether the table came from merge or downsample.
+ * Every value is an exact integer.  The device forms order themselves after the counter's earlier
+ * work, as every call does; DIRECTIONAL waits for the stream between its sweeps.  Scratch, from the
+ * library's pool in one block: the sorted rows (24 B per molecule and the sort's own), 1 bit per slot,
+ * 4 B per slot for ONE_STEP (the images) or the directional pass's scratch for DIRECTIONAL. */
+#define SCT_COLLAPSE_NONE 2
+int sct_molecules_resolve(sct_molecules* mol, int method, uint64_t* d_resolved, uint64_t* d_tally, void* stream);
+int sct_molecules_resolve_host(sct_molecules* mol, int method, uint64_t* resolved, uint64_t* tally);
+int sct_molecules_matrix_resolved(sct_molecules* mol, int method, int64_t* d_indptr, int32_t* d_feature,
+                                  uint64_t* d_molecules, uint64_t* d_reads, uint64_t* d_collapsed,
+                                  uint64_t* d_resolved, uint64_t* d_tally, int64_t room, int64_t* nnz,
+                                  void* stream);
+int sct_molecules_matrix_resolved_host(sct_molecules* mol, int method, int64_t* indptr, int32_t* feature,
+                                       uint64_t* molecules, uint64_t* reads, uint64_t* collapsed,
+                                       uint64_t* resolved, uint64_t* tally, int64_t room, int64_t* nnz);
 
 /* ---------------------------------------------------------------- FASTQ barcode extraction
  * Replaces the per-record path reader.Reader.__iter__ (src/sctools/reader.py:56-85) ->

@@ -42,6 +42,7 @@ TUNE_KEYS = {"spectral_chunk": 1, "spectral_min_n": 2, "allpairs_grab": 3, "allp
              "merge_rows": 19, "tile_chain": 20, "directional_form": 21,
              "downsample_wave_reads": 22}
 COLLAPSE_ONE_STEP, COLLAPSE_DIRECTIONAL = 0, 1
+COLLAPSE_NONE = 2  # the resolve calls only
 NEAREST_AUTO, NEAREST_OA, NEAREST_CSR, NEAREST_HALVES = 0, 1, 2, 3
 
 _i32, _i64, _dbl = ctypes.c_int, ctypes.c_int64, ctypes.c_double
@@ -189,6 +190,11 @@ SIGNATURES = {
     "sct_molecules_matrix_by": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64), _vp],
     "sct_molecules_matrix_by_host": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64)],
     "sct_molecules_directional_info": [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    "sct_molecules_resolve": [_vp, _i32, _vp, _vp, _vp],
+    "sct_molecules_resolve_host": [_vp, _i32, _vp, _vp],
+    "sct_molecules_matrix_resolved": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64), _vp],
+    "sct_molecules_matrix_resolved_host": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                           ctypes.POINTER(_i64)],
 }
 _RESTYPES = {"sct_last_error": ctypes.c_char_p}
 

@@ -144,6 +144,18 @@ def collapse_method(name):
     return COLLAPSE_METHODS[name]
 
 
+RESOLVE_METHODS = dict(COLLAPSE_METHODS, none=_lib.COLLAPSE_NONE)
+
+
+def resolve_method(name):
+    """The SCT_COLLAPSE_* number of a method's name for ``resolve`` and ``matrix(resolved=True)``:
+    ``collapse_method``'s two, or 'none' (every UMI is its own molecule).  Anything else raises
+    ValueError."""
+    if not isinstance(name, str) or name not in RESOLVE_METHODS:
+        raise ValueError("method must be 'one_step', 'directional' or 'none', not %r" % (name,))
+    return RESOLVE_METHODS[name]
+
+
 def downsample_threshold(fraction):
     """The integer threshold in [0, 2**32] of a fraction of the reads in [0, 1]:
     ``int(round(fraction * 2**32))``.  The scaling by a power of two is exact, so a fraction always
@@ -188,7 +200,9 @@ class MoleculeCounter:
     (an antibody tag or guide corrected by ``WhitelistCorrector``, or a gene index) as a third key
     part, the same UMI under two features of a cell is two molecules, and ``matrix()`` returns the
     barcode x feature molecules as CSR (include/sctools_hip.h, "counting molecules per feature").
-    Index, feature and UMI bits must fit a 63-bit key together."""
+    Index, feature and UMI bits must fit a 63-bit key together.  With ``read_counts`` as well,
+    ``resolve()`` and ``matrix(resolved=True)`` give a (barcode, UMI) seen under several features to
+    the one with the most reads and drop it on a tie (include/sctools_hip.h, "resolving features")."""
 
     def __init__(self, whitelist_size, umi_length, encoding='ThreeBit', capacity_hint=1 << 20, read_counts=False,
                  device=None, features=None):
@@ -346,7 +360,7 @@ class MoleculeCounter:
         _lib.check(self._lib.sct_molecules_fetch_counted_by(self._h, by, _vp(index_ptr), _vp(umi_ptr), _vp(reads_ptr),
                                                             _vp(parent_ptr or None), int(room), _vp(stream)))
 
-    def matrix(self, reads=False, collapsed=False, room=None, method='one_step'):
+    def matrix(self, reads=False, collapsed=False, room=None, method='one_step', resolved=False):
         """The barcode x feature count matrix of a feature counter as CSR: (indptr int64
         [whitelist_size + 1], feature int32 [nnz], molecules int64 [nnz]) and, if asked (a counter
         with ``read_counts``), reads and collapsed (int64 [nnz]) after them -- the entry's reads and
@@ -354,36 +368,60 @@ class MoleculeCounter:
         ``scipy.sparse.csr_matrix((molecules, feature, indptr), shape=(whitelist_size, features))``
         takes the arrays as they are.  ``room`` (default: the number of molecules, which always
         suffices) sizes the output; fewer than nnz raises ValueError, which names nnz.
-        ``method='directional'``: collapsed is the entry's directional clusters (``collapse``)."""
-        by = collapse_method(method)
+        ``method='directional'``: collapsed is the entry's directional clusters (``collapse``).
+        ``resolved=True`` (a counter with ``read_counts``) adds a last column, the entry's molecules
+        that ``resolve(method)`` keeps; ``method`` may then be 'none' as well, but not together with
+        ``collapsed``.  The column shares indptr and feature with the others, so an entry that loses
+        every molecule holds an explicit 0 (``scipy``'s ``eliminate_zeros()`` drops those)."""
+        by = resolve_method(method) if resolved else collapse_method(method)
         self._need_features("matrix")
         if reads:
             self._need_read_counts("matrix(reads=True)")
         if collapsed:
             self._need_read_counts("matrix(collapsed=True)")
+        if resolved:
+            self._need_read_counts("matrix(resolved=True)")
+            if collapsed and by == _lib.COLLAPSE_NONE:
+                raise ValueError("matrix(collapsed=True) needs a collapse method, not 'none'")
         n = len(self) if room is None else int(room)
         if n < 0:
             raise ValueError("room must be >= 0")
         indptr = np.empty(self.size + 1, np.int64)
         feature = np.empty(max(n, 1), np.int32)
-        values = [np.empty(max(n, 1), np.uint64) if want else None for want in (True, reads, collapsed)]
+        values = [np.empty(max(n, 1), np.uint64) if want else None for want in (True, reads, collapsed, resolved)]
         nnz = _i64(0)
-        _lib.check(self._lib.sct_molecules_matrix_by_host(self._h, by, _lib._ptr(indptr), _lib._ptr(feature),
-                                                          _lib._ptr(values[0]), _lib._ptr(values[1]),
-                                                          _lib._ptr(values[2]), n, ctypes.byref(nnz)))
+        if resolved:
+            _lib.check(self._lib.sct_molecules_matrix_resolved_host(
+                self._h, by, _lib._ptr(indptr), _lib._ptr(feature), _lib._ptr(values[0]), _lib._ptr(values[1]),
+                _lib._ptr(values[2]), _lib._ptr(values[3]), None, n, ctypes.byref(nnz)))
+        else:
+            _lib.check(self._lib.sct_molecules_matrix_by_host(self._h, by, _lib._ptr(indptr), _lib._ptr(feature),
+                                                              _lib._ptr(values[0]), _lib._ptr(values[1]),
+                                                              _lib._ptr(values[2]), n, ctypes.byref(nnz)))
         k = nnz.value
         return (indptr, feature[:k].copy()) + tuple(v[:k].view(np.int64).copy() for v in values if v is not None)
 
     def matrix_device(self, indptr_ptr, feature_ptr, molecules_ptr, reads_ptr, collapsed_ptr, room, stream=0,
-                      method='one_step'):
+                      method='one_step', resolved_ptr=None):
         """matrix() into device arrays with room for ``room`` entries (sct_molecules_matrix_by): int64
         [whitelist_size + 1], int32 [room] and up to three uint64 [room], each of the three 0 / None
-        when not wanted.  Returns nnz; waits for ``stream`` once to learn it."""
-        by = collapse_method(method)
+        when not wanted.  Returns nnz; waits for ``stream`` once to learn it.  ``resolved_ptr`` (not
+        0 / None): one more uint64 [room], matrix(resolved=True)'s last column
+        (sct_molecules_matrix_resolved); ``method`` may then be 'none'."""
+        by = resolve_method(method) if resolved_ptr else collapse_method(method)
         self._need_features("matrix_device")
         if reads_ptr or collapsed_ptr:
             self._need_read_counts("matrix_device with reads or collapsed")
         nnz = _i64(0)
+        if resolved_ptr:
+            self._need_read_counts("matrix_device with resolved")
+            if collapsed_ptr and by == _lib.COLLAPSE_NONE:
+                raise ValueError("matrix_device with collapsed needs a collapse method, not 'none'")
+            _lib.check(self._lib.sct_molecules_matrix_resolved(
+                self._h, by, _vp(indptr_ptr), _vp(feature_ptr or None), _vp(molecules_ptr or None),
+                _vp(reads_ptr or None), _vp(collapsed_ptr or None), _vp(resolved_ptr), None, int(room),
+                ctypes.byref(nnz), _vp(stream)))
+            return nnz.value
         _lib.check(self._lib.sct_molecules_matrix_by(self._h, by, _vp(indptr_ptr), _vp(feature_ptr or None),
                                                      _vp(molecules_ptr or None), _vp(reads_ptr or None),
                                                      _vp(collapsed_ptr or None), int(room), ctypes.byref(nnz),
@@ -403,6 +441,32 @@ class MoleculeCounter:
         ncorr = np.zeros(1, np.uint64)
         _lib.check(self._lib.sct_molecules_collapse_by_host(self._h, by, _lib._ptr(collapsed), _lib._ptr(ncorr)))
         return collapsed.view(np.int64), int(ncorr[0])
+
+    def resolve(self, method='one_step'):
+        """(resolved np.int64[whitelist_size], n_shared, n_lost, n_tied, reads_dropped) of a feature
+        counter with ``read_counts``: a (barcode, UMI) seen under several features is one molecule, so
+        after the UMI collapse of ``method`` ('one_step', 'directional', or 'none' for no collapse)
+        the feature with the most reads keeps it and the others lose it; on a tie for the most reads
+        every feature of the group drops it.  resolved counts the kept molecules per barcode,
+        n_shared the (barcode, UMI) groups under two or more features, n_lost and n_tied the
+        molecules discarded either way and reads_dropped their reads (include/sctools_hip.h,
+        "resolving features").  ``matrix(resolved=True)`` gives the kept molecules per entry."""
+        by = resolve_method(method)
+        self._need_features("resolve")
+        self._need_read_counts("resolve")
+        resolved = np.empty(self.size, np.uint64)
+        tally = np.zeros(4, np.uint64)
+        _lib.check(self._lib.sct_molecules_resolve_host(self._h, by, _lib._ptr(resolved), _lib._ptr(tally)))
+        return (resolved.view(np.int64),) + tuple(int(t) for t in tally)
+
+    def resolve_device(self, resolved_ptr, tally_ptr=None, stream=0, method='one_step'):
+        """resolve() into device memory: uint64[whitelist_size] and, unless 0 / None, uint64[4]
+        (sct_molecules_resolve), on ``stream``; ``method='directional'`` may wait for it."""
+        by = resolve_method(method)
+        self._need_features("resolve_device")
+        self._need_read_counts("resolve_device")
+        _lib.check(self._lib.sct_molecules_resolve(self._h, by, _vp(resolved_ptr), _vp(tally_ptr or None),
+                                                   _vp(stream)))
 
     def collapse_device(self, collapsed_ptr, ncorrected_ptr=None, stream=0, method='one_step'):
         """collapse() into device memory: uint64[whitelist_size] and, unless 0 / None, one uint64

@@ -81,6 +81,17 @@
 // entry count and reduces each entry's rows inside the wave -- run length, cnt[slot], the slot's bit
 // in the collapse pass's bitmap -- to one 64-bit integer atomic add per (wave, entry) and value.
 // A scan of the nw + 1 entry counts is indptr.
+//
+// Resolving features (include/sctools_hip.h, "resolving features") decides which
+// collapsed molecules survive when a (barcode, UMI) was seen under several features.  The method's own
+// pass names every molecule's image; a compaction writes, per occupied slot, the key re-packed as
+// (index, image UMI, feature) (molecules_resolve_key.h) with the slot beside it, and the image slot
+// into a word per table slot where the method has none already; the sorted-rows stage orders the
+// words, so a group's rows are adjacent and a collapsed molecule's rows adjacent inside it.  In the run
+// pass the lane whose row opens a group walks the group, sums cnt[slot] per collapsed molecule, folds
+// (top, how many at top, members, reads) and sets the unique winner's image slot in a bitmap of one
+// bit per slot.  The matrix's fill kernel counts that bitmap per entry as it counts the collapse
+// pass's, in the same block, whose rows the key sort then reuses.
 #include <algorithm>
 #include <type_traits>
 
@@ -90,6 +101,7 @@
 #include "molecules_feature_key.h"
 #include "molecules_key.h"
 #include "molecules_merge_plan.h"
+#include "molecules_resolve_key.h"
 #include "umi_directional.h"
 #include "umi_neighbours.h"
 
@@ -578,6 +590,121 @@ __global__ void __launch_bounds__(WG) molecules_matrix_fill_kernel(Set t, const 
       if (first && n) atomicAdd(&collapsed[e], n);
     }
   });
+}
+
+// ---- resolving features (include/sctools_hip.h, "resolving features"; the word, the head tests and
+// the group fold: molecules_resolve_key.h)
+
+// The compaction of the resolve pass: a wave per 64 slots (the capacity is a multiple of 64), and for
+// every occupied slot s the re-packed word of its key under its image, with s beside it.  The image
+// slot p is s itself (IMAGE_SELF), the one-step parent's by one lane's scan or by the wave's
+// (IMAGE_PARENT, IMAGE_PARENT_WAVE: the two forms of the collapse pass, SCT_TUNE_COLLAPSE_FORM) or the
+// directional label (IMAGE_ROOT, `lab` as directional_labels left it).  A parent is scanned for once
+// per molecule: it is kept in image[s] for the run pass, and its bit is set in `parents` (if not
+// NULL), which is then the collapse pass's bitmap.  At most `room` rows are written.
+enum { IMAGE_SELF, IMAGE_PARENT, IMAGE_PARENT_WAVE, IMAGE_ROOT };
+template <int IMAGE>
+__global__ void __launch_bounds__(WG) molecules_resolve_rows_kernel(Set t, int64_t capacity,
+                                                                    const uint32_t* __restrict__ lab,
+                                                                    uint32_t* __restrict__ image,
+                                                                    uint32_t* __restrict__ parents,
+                                                                    u64* __restrict__ cursor, int64_t room,
+                                                                    u64* __restrict__ out_word,
+                                                                    uint32_t* __restrict__ out_slot) {
+  const int lane = threadIdx.x & 63;
+  for_each_wave_tile(capacity, [&](int64_t base) {
+    const uint32_t s = (uint32_t)(base + lane);
+    const u64 key = t.keys[s];
+    const bool occ = key != EMPTY;
+    uint32_t p = s;
+    u64 image_key = key;
+    if (IMAGE == IMAGE_PARENT && occ) {
+      const Candidate b = parent_scan(t, key, s, 0, 1);
+      p = b.slot, image_key = b.code;
+    }
+    if (IMAGE == IMAGE_PARENT_WAVE)
+      wave_serial(__ballot(occ), [&](int src) {
+        const Candidate b = wave_max(parent_scan(t, __shfl(key, src), (uint32_t)(base + src), lane, 64));
+        if (lane == src) p = b.slot, image_key = b.code;
+      });
+    if (IMAGE == IMAGE_ROOT && occ) {
+      p = lab[s] & kLabelSlot;
+      image_key = t.keys[p];
+    }
+    if ((IMAGE == IMAGE_PARENT || IMAGE == IMAGE_PARENT_WAVE) && occ) {
+      image[s] = p;
+      if (parents) atomicOr(&parents[p >> 5], 1u << (p & 31));
+    }
+    const u64 at = compact_at(occ, cursor);
+    if (occ && (int64_t)at < room) {
+      out_word[at] = sct::mol_resolve_word_of(key, image_key, t.feat_bits, t.umi_bits);
+      out_slot[at] = s;
+    }
+  });
+}
+
+// The run pass over the rows sorted by word, a wave per 64 adjacent rows.  The lane whose row opens a
+// group (the previous row is the lane below's; lane 0 reads it from global memory, as row_is_head
+// does) walks forward over the group's rows to its end, wherever that lies: no tile hands anything to
+// the next.  On the way it sums cnt[slot] over the rows of each collapsed molecule, folds the
+// molecules by mol_resolve_combine and remembers the image slot of the best.  A unique best keeps its
+// molecule: its image slot's bit is set in `kept` (a bit per table slot, zero before) and
+// resolved[index] += 1 (if not NULL), merged per wave and index.  tally[4] += the groups of two or
+// more members, the lost members, the tied members and the reads of both, one add per wave and word.
+// Past the last row stands a word no key packs to (a word's top bit is 0).
+constexpr u64 kNoWord = ~0ull;
+__global__ void __launch_bounds__(WG) molecules_resolve_kernel(Set t, const u64* __restrict__ words,
+                                                               const uint32_t* __restrict__ slots, int64_t rows,
+                                                               const uint32_t* __restrict__ image,
+                                                               uint32_t* __restrict__ kept, u64* __restrict__ resolved,
+                                                               u64* __restrict__ tally) {
+  const int lane = threadIdx.x & 63;
+  u64 sums[4] = {};  // n_shared, n_lost, n_tied, reads_dropped
+  for_each_wave_tile(rows, [&](int64_t base) {
+    const int64_t r = base + lane;
+    const bool in = r < rows;
+    const u64 word = in ? words[r] : 0;
+    u64 prev = __shfl_up(word, 1);
+    if (lane == 0 && in && r > 0) prev = words[r - 1];
+    const bool head = in && (r == 0 || sct::mol_resolve_group_head(word, prev, t.feat_bits));
+    bool keeps = false;
+    if (head) {
+      sct::ResolveGroup g{0, 0, 0, 0};
+      uint32_t winner = 0;
+      int64_t q = r;
+      u64 w = word;
+      for (;;) {  // a collapsed molecule per turn: the rows that carry the word w
+        const uint32_t first = slots[q];
+        const uint32_t p = image ? image[first] & kLabelSlot : first;
+        u64 reads = 0, next;
+        do {
+          reads += t.cnt[slots[q]];
+          next = ++q < rows ? words[q] : kNoWord;
+        } while (!sct::mol_resolve_molecule_head(next, w));
+        if (reads > g.top) winner = p;
+        g = sct::mol_resolve_combine(g, sct::mol_resolve_member(reads));
+        if (sct::mol_resolve_group_head(next, w, t.feat_bits)) break;
+        w = next;
+      }
+      keeps = sct::mol_resolve_unique(g);
+      sums[0] += g.members >= 2;
+      if (keeps) {
+        sums[1] += g.members - 1;
+        sums[3] += g.reads - g.top;
+        atomicOr(&kept[winner >> 5], 1u << (winner & 31));
+      } else {
+        sums[2] += g.members;
+        sums[3] += g.reads;
+      }
+    }
+    const u64 index = sct::mol_resolve_index(word, t.feat_bits, t.umi_bits);
+    const Merged m = wave_merge(keeps, index);
+    if (resolved && m.rep) atomicAdd(&resolved[index], m.count);
+  });
+  for (int k = 0; k < 4; ++k) {
+    for (int o = 32; o > 0; o >>= 1) sums[k] += __shfl_xor(sums[k], o);
+    if (lane == 0 && sums[k]) atomicAdd(&tally[k], sums[k]);
+  }
 }
 
 // ---- merge (include/sctools_hip.h, "merging molecule counters")
@@ -1098,6 +1225,84 @@ int directional_pass(sct_molecules* c, const DirectionalScratch& ds, u64* collap
                      c->capacity, ds.lab, collapsed, &ds.words[DirectionalScratch::D_NCORRECTED]);
   SCT_LAUNCH_CHECK();
   return SCT_OK;
+}
+
+// ---- resolving features
+
+// the methods of the resolve entry points: the two collapse methods and SCT_COLLAPSE_NONE
+int resolve_method_check(int method) {
+  SCT_CHECK(method == SCT_COLLAPSE_ONE_STEP || method == SCT_COLLAPSE_DIRECTIONAL || method == SCT_COLLAPSE_NONE,
+            "unknown resolve method %d (SCT_COLLAPSE_ONE_STEP, SCT_COLLAPSE_DIRECTIONAL or SCT_COLLAPSE_NONE)", method);
+  return SCT_OK;
+}
+
+// The resolve pass's scratch at `b`, in its one layout: the four tally words and the kept bitmap of
+// one bit per slot (zeroed together by the pass) and, for the one-step method, the image slot of
+// every slot (written for every occupied slot before it is read).  The directional method reads its
+// images from the labels and SCT_COLLAPSE_NONE has none.
+struct ResolveScratch {
+  u64* tally;
+  uint32_t* kept;
+  uint32_t* image;
+  static size_t zeroed(const sct_molecules* c) { return 256 + (size_t)c->capacity / 8; }
+  static size_t bytes(const sct_molecules* c, int method) {
+    return up256(zeroed(c)) + (method == SCT_COLLAPSE_ONE_STEP ? (size_t)c->capacity * 4 : 0);
+  }
+  ResolveScratch(const sct_molecules* c, uint8_t* b)
+      : tally(reinterpret_cast<u64*>(b)), kept(reinterpret_cast<uint32_t*>(b + 256)),
+        image(reinterpret_cast<uint32_t*>(b + up256(zeroed(c)))) {}
+};
+
+// The resolve pass of the table as it stands, enqueued on sr's stream in sr's block: the rows under
+// their images sorted by the re-packed word, then the run pass -- rs.kept and rs.tally (zeroed here)
+// and resolved[nw] (nullable; zero before) added to.  `lab`: the directional labels, made before.
+// `parents` (one-step only, nullable, zero before) receives the parents' bits, which makes it the
+// collapse pass's bitmap without a second scan.  sr's rows are free again when this returns.
+hipError_t resolve_pass(const sct_molecules* c, int method, SortedRows<true>& sr, const ResolveScratch& rs,
+                        const uint32_t* lab, uint32_t* parents, u64* resolved) {
+  hipStream_t s = sr.s;
+  hipError_t e = hipMemsetAsync(rs.tally, 0, ResolveScratch::zeroed(c), s);
+  if (e != hipSuccess) return e;
+  const bool wave = sct::tune(SCT_TUNE_COLLAPSE_FORM, 1) == 1;
+  const auto rows_kernel = method == SCT_COLLAPSE_NONE          ? molecules_resolve_rows_kernel<IMAGE_SELF>
+                           : method == SCT_COLLAPSE_DIRECTIONAL ? molecules_resolve_rows_kernel<IMAGE_ROOT>
+                           : wave                               ? molecules_resolve_rows_kernel<IMAGE_PARENT_WAVE>
+                                                                : molecules_resolve_rows_kernel<IMAGE_PARENT>;
+  const uint32_t* image = method == SCT_COLLAPSE_NONE ? nullptr : method == SCT_COLLAPSE_DIRECTIONAL ? lab : rs.image;
+  e = sr.sort(&c->t.words[W_CURSOR], [&](u64* words, uint32_t* slots) {
+    hipLaunchKernelGGL(rows_kernel, dim3(grid_for(c->capacity, WG)), dim3(WG), 0, s, c->t, c->capacity, lab, rs.image,
+                       parents, &c->t.words[W_CURSOR], sr.rows, words, slots);
+  });
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(molecules_resolve_kernel, dim3(grid_for((sr.rows + 63) / 64, WG / 64)), dim3(WG), 0, s, c->t,
+                     sr.word(), sr.slot(), sr.rows, image, rs.kept, resolved, rs.tally);
+  return hipGetLastError();
+}
+
+// resolved[nw] and, if asked, tally[4], written on `s` from the table as it stands
+int resolve_device(sct_molecules* c, int method, uint64_t* d_resolved, uint64_t* d_tally, hipStream_t s) {
+  if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
+  SCT_HIP(hipMemsetAsync(d_resolved, 0, (size_t)c->t.nw * 8, s));
+  if (c->size_bound == 0) {
+    if (d_tally) SCT_HIP(hipMemsetAsync(d_tally, 0, 4 * 8, s));
+    return leave(c, s);
+  }
+  SortedRows<true> sr(c->size_bound, key_bits(c), s);
+  const bool directional = method == SCT_COLLAPSE_DIRECTIONAL;
+  const size_t o_labels = directional ? sr.take(DirectionalScratch::bytes(c)) : 0;
+  const size_t o_resolve = sr.take(ResolveScratch::bytes(c, method));
+  SCT_HIP(sr.alloc());
+  const uint32_t* lab = nullptr;
+  if (directional) {
+    const DirectionalScratch ds(c, sr.at<uint8_t>(o_labels));
+    SCT_TRY(directional_labels(c, ds, s));
+    lab = ds.lab;
+  }
+  const ResolveScratch rs(c, sr.at<uint8_t>(o_resolve));
+  hipError_t e = resolve_pass(c, method, sr, rs, lab, nullptr, reinterpret_cast<u64*>(d_resolved));
+  if (e == hipSuccess && d_tally) e = hipMemcpyAsync(d_tally, rs.tally, 4 * 8, hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule resolve: %s", hipGetErrorString(e));
+  return leave(c, s);
 }
 
 // collapsed[nw] and, if asked, n_corrected of the directional clusters
@@ -1747,14 +1952,27 @@ int need_feature_counter(const sct_molecules* c) {
 // one block of the sorted (key, slot) rows: after them the tile head counts and their scan, the entry
 // count per barcode and, for the collapsed values, the collapse pass's scratch with a collapsed[nw]
 // of its own; both scans run in the sort's scratch.
+// `rv` (the resolved matrix, else NULL): the resolve pass runs first, in the same block -- its rows lie
+// where the rows sorted by key go afterwards, and its scratch behind the pieces above.  It shares what
+// it made with the collapsed values: the labels, or the parents' bitmap (no second neighbour scan).
+// resolved[e] is the entry's slots whose bit is set in the kept bitmap, the fill kernel's count of a
+// bitmap: in its one launch when collapsed is not asked for, else in a second launch of its value part
+// (feature[] is written again with the same values, the entry counts go to a spare array).  tally[4]
+// is copied out after the room check, so a call without room writes nothing.
+struct ResolvedOut {
+  uint64_t* d_resolved;  // [nnz], nullable
+  uint64_t* d_tally;     // [4], nullable
+};
 int matrix_device(sct_molecules* c, int method, int64_t* d_indptr, int32_t* d_feature, uint64_t* d_molecules,
-                  uint64_t* d_reads, uint64_t* d_collapsed, int64_t room, int64_t* nnz, hipStream_t s) {
+                  uint64_t* d_reads, uint64_t* d_collapsed, const ResolvedOut* rv, int64_t room, int64_t* nnz,
+                  hipStream_t s) {
   if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
   const int64_t rows = c->size_bound, nw = c->t.nw;
   SCT_CHECK(nw + 1 < (1LL << 31), "matrix: nw + 1 = %lld row offsets are more than one scan takes", (long long)nw + 1);
   *nnz = 0;
   if (rows == 0) {
     SCT_HIP(hipMemsetAsync(d_indptr, 0, (size_t)(nw + 1) * 8, s));
+    if (rv && rv->d_tally) SCT_HIP(hipMemsetAsync(rv->d_tally, 0, 4 * 8, s));
     return leave(c, s);
   }
   const int64_t ntiles = (rows + 63) / 64;
@@ -1767,7 +1985,10 @@ int matrix_device(sct_molecules* c, int method, int64_t* d_indptr, int32_t* d_fe
   const size_t o_row_entries = sr.take((size_t)(nw + 1) * 8);
   const bool directional = method == SCT_COLLAPSE_DIRECTIONAL;
   const size_t pass_bytes = directional ? DirectionalScratch::bytes(c) : CollapseScratch::bytes(c, true);
-  const size_t o_pass = d_collapsed ? sr.take(pass_bytes) : 0;
+  const size_t o_pass = d_collapsed || (rv && directional) ? sr.take(pass_bytes) : 0;
+  const bool second_fill = rv && rv->d_resolved && d_collapsed;
+  const size_t o_resolve = rv ? sr.take(ResolveScratch::bytes(c, method)) : 0;
+  const size_t o_spare_entries = second_fill ? sr.take((size_t)(nw + 1) * 8) : 0;
   SCT_HIP(sr.alloc());
   u64* heads = sr.at<u64>(o_heads);
   u64* base = sr.at<u64>(o_base);
@@ -1775,8 +1996,29 @@ int matrix_device(sct_molecules* c, int method, int64_t* d_indptr, int32_t* d_fe
   const u64* keys_out = sr.word();
   const uint32_t* slots_out = sr.slot();
   const dim3 tiles_grid(grid_for(ntiles, WG / 64));
+  const uint32_t* bitmap = nullptr;
+  const uint32_t* lab = nullptr;
+  const uint32_t* kept = nullptr;
+  const u64* resolve_tally = nullptr;
+  hipError_t e = hipSuccess;
+  if (rv) {
+    // 0. the resolve pass, with the images it shares with the collapsed values
+    uint32_t* parents = nullptr;
+    if (directional) {
+      const DirectionalScratch ds(c, sr.at<uint8_t>(o_pass));
+      SCT_TRY(directional_labels(c, ds, s));
+      lab = ds.lab;
+    } else if (d_collapsed) {
+      e = hipMemsetAsync(sr.at<void>(o_pass), 0, pass_bytes, s);
+      bitmap = parents = CollapseScratch(c, sr.at<uint8_t>(o_pass)).bitmap;
+    }
+    const ResolveScratch rs(c, sr.at<uint8_t>(o_resolve));
+    if (e == hipSuccess) e = resolve_pass(c, method, sr, rs, lab, parents, nullptr);
+    kept = rs.kept;
+    resolve_tally = rs.tally;
+  }
   // 1. the rows sorted by key, and the entries that open in every tile; their sum is nnz
-  hipError_t e = hipMemsetAsync(&heads[ntiles], 0, 8, s);
+  if (e == hipSuccess) e = hipMemsetAsync(&heads[ntiles], 0, 8, s);
   if (e == hipSuccess) e = sort_rows(c, sr);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(molecules_matrix_heads_kernel, tiles_grid, dim3(WG), 0, s, keys_out, rows, c->t.umi_bits, heads);
@@ -1791,9 +2033,10 @@ int matrix_device(sct_molecules* c, int method, int64_t* d_indptr, int32_t* d_fe
     e = hipMemsetAsync(row_entries, 0, (size_t)(nw + 1) * 8, s);
     if (e == hipSuccess && d_molecules) e = hipMemsetAsync(d_molecules, 0, (size_t)entries * 8, s);
     if (e == hipSuccess && d_reads) e = hipMemsetAsync(d_reads, 0, (size_t)entries * 8, s);
-    const uint32_t* bitmap = nullptr;
-    const uint32_t* lab = nullptr;
-    if (e == hipSuccess && d_collapsed && directional) {
+    if (e == hipSuccess && d_collapsed && rv) {
+      // (the resolve pass made the labels, or the parents' bitmap)
+      e = hipMemsetAsync(d_collapsed, 0, (size_t)entries * 8, s);
+    } else if (e == hipSuccess && d_collapsed && directional) {
       // the entry's roots: the labels alone (the sweeps wait for the stream)
       e = hipMemsetAsync(d_collapsed, 0, (size_t)entries * 8, s);
       const DirectionalScratch ds(c, sr.at<uint8_t>(o_pass));
@@ -1806,13 +2049,23 @@ int matrix_device(sct_molecules* c, int method, int64_t* d_indptr, int32_t* d_fe
       bitmap = cs.bitmap;
       if (e == hipSuccess) e = collapse_pass(c, cs.bitmap, cs.collapsed, cs.ncorrected, s);
     }
+    u64* d_kept = rv ? reinterpret_cast<u64*>(rv->d_resolved) : nullptr;
+    if (e == hipSuccess && d_kept) e = hipMemsetAsync(d_kept, 0, (size_t)entries * 8, s);
     if (e == hipSuccess) {
+      // (without collapsed values the kept bitmap takes the bitmap's place in the one launch)
+      const bool kept_here = d_kept && !second_fill;
       hipLaunchKernelGGL(molecules_matrix_fill_kernel, tiles_grid, dim3(WG), 0, s, c->t, keys_out, slots_out, rows, base,
-                         bitmap, lab, row_entries, d_feature, reinterpret_cast<u64*>(d_molecules),
-                         reinterpret_cast<u64*>(d_reads), reinterpret_cast<u64*>(d_collapsed));
+                         kept_here ? kept : bitmap, kept_here ? nullptr : lab, row_entries, d_feature,
+                         reinterpret_cast<u64*>(d_molecules),
+                         reinterpret_cast<u64*>(d_reads), kept_here ? d_kept : reinterpret_cast<u64*>(d_collapsed));
+      if (second_fill)
+        hipLaunchKernelGGL(molecules_matrix_fill_kernel, tiles_grid, dim3(WG), 0, s, c->t, keys_out, slots_out, rows,
+                           base, kept, nullptr, sr.at<u64>(o_spare_entries), d_feature, nullptr, nullptr, d_kept);
       e = hipcub::DeviceScan::ExclusiveSum(sr.tmp(), scan_rows_bytes, row_entries, reinterpret_cast<u64*>(d_indptr),
                                            (int)(nw + 1), s);
     }
+    if (e == hipSuccess && rv && rv->d_tally)
+      e = hipMemcpyAsync(rv->d_tally, resolve_tally, 4 * 8, hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess) e = hipGetLastError();
   }
   if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule matrix: %s", hipGetErrorString(e));
@@ -1875,7 +2128,7 @@ extern "C" int sct_molecules_matrix_by(sct_molecules* c, int method, int64_t* d_
                                        int64_t* nnz, void* stream) {
   SCT_TRY(matrix_check(c, method, d_indptr, d_feature, d_reads, d_collapsed, room, nnz));
   SCT_ON_DEVICE_OF(c);
-  return matrix_device(c, method, d_indptr, d_feature, d_molecules, d_reads, d_collapsed, room, nnz,
+  return matrix_device(c, method, d_indptr, d_feature, d_molecules, d_reads, d_collapsed, nullptr, room, nnz,
                        sct::as_stream(stream));
 }
 
@@ -1898,7 +2151,7 @@ extern "C" int sct_molecules_matrix_by_host(sct_molecules* c, int method, int64_
   st.add(molecules, 8, r), st.add(reads, 8, r), st.add(collapsed, 8, r);
   if (int rc = st.alloc(); rc != SCT_OK) return rc;
   const int rc = matrix_device(c, method, st.dev<int64_t>(0), st.dev<int32_t>(1), st.dev<uint64_t>(2),
-                               st.dev<uint64_t>(3), st.dev<uint64_t>(4), r, nnz, s);
+                               st.dev<uint64_t>(3), st.dev<uint64_t>(4), nullptr, r, nnz, s);
   for (int i = 1; i < st.n; ++i) st.cols[i].count = (size_t)*nnz;  // what the matrix wrote of its room
   return st.finish(rc, "molecule matrix");
 }
@@ -1906,4 +2159,77 @@ extern "C" int sct_molecules_matrix_by_host(sct_molecules* c, int method, int64_
 extern "C" int sct_molecules_matrix_host(sct_molecules* c, int64_t* indptr, int32_t* feature, uint64_t* molecules,
                                          uint64_t* reads, uint64_t* collapsed, int64_t room, int64_t* nnz) {
   return sct_molecules_matrix_by_host(c, SCT_COLLAPSE_ONE_STEP, indptr, feature, molecules, reads, collapsed, room, nnz);
+}
+
+// ---- resolving features (include/sctools_hip.h): the entry points
+
+namespace {
+
+// what every resolve call needs: a known method and a counted feature counter
+int resolve_check(const sct_molecules* c, int method) {
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  if (int rc = resolve_method_check(method); rc != SCT_OK) return rc;
+  if (int rc = need_feature_counter(c); rc != SCT_OK) return rc;
+  return need_counted(c);
+}
+
+// the checks of the resolved matrix before it touches the device: the matrix's, with the resolve methods
+int matrix_resolved_check(const sct_molecules* c, int method, const void* indptr, const void* feature,
+                          const void* collapsed, int64_t room, const int64_t* nnz) {
+  if (int rc = resolve_check(c, method); rc != SCT_OK) return rc;
+  SCT_CHECK(room >= 0, "room must be >= 0");
+  SCT_CHECK(nnz != nullptr, "NULL nnz");
+  SCT_CHECK(indptr != nullptr && (room == 0 || feature != nullptr), "NULL output");
+  SCT_CHECK(!(collapsed && method == SCT_COLLAPSE_NONE), "SCT_COLLAPSE_NONE collapses nothing: no collapsed values");
+  return SCT_OK;
+}
+
+}  // namespace
+
+extern "C" int sct_molecules_resolve(sct_molecules* c, int method, uint64_t* d_resolved, uint64_t* d_tally,
+                                     void* stream) {
+  SCT_TRY(resolve_check(c, method));
+  SCT_CHECK(d_resolved != nullptr, "NULL output");
+  SCT_ON_DEVICE_OF(c);
+  return resolve_device(c, method, d_resolved, d_tally, sct::as_stream(stream));
+}
+
+extern "C" int sct_molecules_resolve_host(sct_molecules* c, int method, uint64_t* resolved, uint64_t* tally) {
+  SCT_TRY(resolve_check(c, method));
+  SCT_CHECK(resolved != nullptr, "NULL output");
+  SCT_ON_STAGE_OF(c, s);
+  Staged st(s);
+  st.add(resolved, 8, (size_t)c->t.nw), st.add(tally, 8, 4);
+  if (int rc = st.alloc(); rc != SCT_OK) return rc;
+  return st.finish(resolve_device(c, method, st.dev<uint64_t>(0), st.dev<uint64_t>(1), s), "molecule resolve");
+}
+
+extern "C" int sct_molecules_matrix_resolved(sct_molecules* c, int method, int64_t* d_indptr, int32_t* d_feature,
+                                             uint64_t* d_molecules, uint64_t* d_reads, uint64_t* d_collapsed,
+                                             uint64_t* d_resolved, uint64_t* d_tally, int64_t room, int64_t* nnz,
+                                             void* stream) {
+  SCT_TRY(matrix_resolved_check(c, method, d_indptr, d_feature, d_collapsed, room, nnz));
+  SCT_ON_DEVICE_OF(c);
+  const ResolvedOut rv{d_resolved, d_tally};
+  return matrix_device(c, method, d_indptr, d_feature, d_molecules, d_reads, d_collapsed, &rv, room, nnz,
+                       sct::as_stream(stream));
+}
+
+extern "C" int sct_molecules_matrix_resolved_host(sct_molecules* c, int method, int64_t* indptr, int32_t* feature,
+                                                  uint64_t* molecules, uint64_t* reads, uint64_t* collapsed,
+                                                  uint64_t* resolved, uint64_t* tally, int64_t room, int64_t* nnz) {
+  SCT_TRY(matrix_resolved_check(c, method, indptr, feature, collapsed, room, nnz));
+  SCT_ON_STAGE_OF(c, s);
+  if (int rc = enter_read(c, s); rc != SCT_OK) return rc;
+  const int64_t r = std::min(room, c->size_bound);
+  Staged st(s);
+  st.add(indptr, 8, (size_t)c->t.nw + 1), st.add(feature, 4, r);
+  st.add(molecules, 8, r), st.add(reads, 8, r), st.add(collapsed, 8, r), st.add(resolved, 8, r);
+  st.add(tally, 8, 4);
+  if (int rc = st.alloc(); rc != SCT_OK) return rc;
+  const ResolvedOut rv{st.dev<uint64_t>(5), st.dev<uint64_t>(6)};
+  const int rc = matrix_device(c, method, st.dev<int64_t>(0), st.dev<int32_t>(1), st.dev<uint64_t>(2),
+                               st.dev<uint64_t>(3), st.dev<uint64_t>(4), &rv, r, nnz, s);
+  for (int i = 1; i < 6; ++i) st.cols[i].count = (size_t)*nnz;  // what the matrix wrote of its room
+  return st.finish(rc, "molecule matrix");
 }

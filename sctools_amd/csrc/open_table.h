@@ -283,7 +283,7 @@ struct Staged {
   };
   PoolBlock blk;
   Carve cv;
-  Column cols[6];
+  Column cols[8];
   int n = 0;
   explicit Staged(hipStream_t s) : blk(s) {}
   void add(void* host, size_t elem, size_t count) {

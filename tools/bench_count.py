@@ -26,7 +26,10 @@ per UMI base, and the updates and the one-step collapse beside an earlier librar
 profiles/ab_umi_directional.jsonl).  Then downsampling on the same reads: downsample at two fractions,
 the saturation curve, merge and the host route beside them, SCT_TUNE_DOWNSAMPLE_WAVE_READS swept on a
 skewed table, and the updates, the collapse and the merge beside an earlier library (downsample_step;
-profiles/ab_downsample.jsonl).
+profiles/ab_downsample.jsonl).  Then resolving features on the matrix step's reads with --hop of them
+moved to another feature: resolve_device for the three methods, the resolved matrix, the matrix as it
+was and the host route pairs() + np.lexsort + reduceat, device and host answers equal, and the matrix
+call beside an earlier library (resolve_step; profiles/ab_feature_resolve.jsonl).
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends
 the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
@@ -39,6 +42,7 @@ the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>
   python tools/bench_count.py --only calls --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only directional --umi-error 0.01 --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only downsample --parent-lib /path/to/earlier/libsctools_hip.so
+  python tools/bench_count.py --only resolve --hop 0.02 --parent-lib /path/to/earlier/libsctools_hip.so
 """
 import argparse
 import functools
@@ -52,7 +56,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420, "collapse": 600,
-         "merge": 600, "matrix": 600, "calls": 600, "directional": 600, "downsample": 600}  # seconds
+         "merge": 600, "matrix": 600, "calls": 600, "directional": 600, "downsample": 600,
+         "resolve": 900}  # seconds
 MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
 HBM_BYTES_PER_S = 8e12
 
@@ -1429,6 +1434,215 @@ def downsample_step(args):
     return out
 
 
+RESOLVE_PARENT_CALLS = ("sct_tune_set", "sct_molecules_create_features", "sct_molecules_update_features",
+                        "sct_molecules_info", "sct_molecules_matrix", "sct_molecules_destroy")
+
+
+def _resolve_on_host(rows, nw, nf):
+    """The host route of resolving features: (resolved[nw], (n_shared, n_lost, n_tied, reads_dropped),
+    kept cells index * nf + feature ascending, kept molecules per such cell) from the rows
+    (index, feature, image umi, reads) by np.lexsort and reduceat."""
+    import numpy as np
+    index, feature, image, reads = rows
+    order = np.lexsort((feature, image, index))
+    index, feature, image, reads = index[order], feature[order], image[order], reads[order]
+    group_change = np.empty(index.size, bool)
+    group_change[0] = True
+    group_change[1:] = (index[1:] != index[:-1]) | (image[1:] != image[:-1])
+    molecule_head = group_change.copy()
+    molecule_head[1:] |= feature[1:] != feature[:-1]
+    starts = np.flatnonzero(molecule_head)
+    m_reads = np.add.reduceat(reads, starts)  # the collapsed molecules, in (index, image, feature) order
+    m_index, m_feature = index[starts], feature[starts]
+    group_starts = np.flatnonzero(group_change[starts])
+    members = np.diff(np.append(group_starts, starts.size))
+    top = np.maximum.reduceat(m_reads, group_starts)
+    at_top = m_reads == np.repeat(top, members)
+    unique = np.add.reduceat(at_top.astype(np.int64), group_starts) == 1
+    kept = at_top & np.repeat(unique, members)
+    resolved = np.bincount(m_index[kept], minlength=nw).astype(np.int64)
+    tally = (int((members >= 2).sum()), int((members[unique] - 1).sum()), int(members[~unique].sum()),
+             int(m_reads.sum() - top[unique].sum()))
+    cells, per_cell = np.unique(m_index[kept].astype(np.int64) * nf + m_feature[kept], return_counts=True)
+    return resolved, tally, cells, per_cell
+
+
+def resolve_step(args):
+    """Resolving features on the matrix step's reads (nf = 4096, every feature in use) with a share
+    --hop of the reads moved to another feature drawn uniformly: without hops a molecule's feature is a
+    function of its (barcode, UMI) and nothing is shared.  On the table the counted feature update
+    left, alternating within every round: resolve_device for the three methods, matrix_device with
+    every column and the resolved one (one_step and directional; molecules, reads and resolved for
+    none), matrix_device with molecules, reads and collapsed as it was, and the host route on the same
+    counter -- pairs(features=True, reads=True, parents=True) and np.lexsort + reduceat (one_step every
+    round, the yardstick; none and directional once).  Device and host answers must be equal.  With
+    --parent-lib, sct_molecules_matrix with every column runs first, alternating in both libraries
+    (the order swapped every round), each on its own counter of the same reads: the medians agree when they differ by no more than the min-max
+    spread of the parent's own rounds, and the outputs are equal element for element; the step fails
+    (its profile written) when they are not.  Every round is one line of the profile, the summary its
+    last (profiles/ab_feature_resolve.jsonl, or ab_feature_resolve_<tag>.jsonl)."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, counting
+
+    nw, UL, n, hint, pool, inputs = _molecules_input(args)
+    nf = 4096
+    dev = torch.device("cuda")
+    old = _parent_lib(args, RESOLVE_PARENT_CALLS)
+    di, du, _ = inputs["shuffled"]
+    df = _features_of(di, du, nf, nf)
+    g = torch.Generator(device=dev).manual_seed(29)
+    hops = (torch.rand(n, device=dev, generator=g) < args.hop) & (df >= 0)
+    other = (df + 1 + torch.randint(0, nf - 1, (n,), device=dev, generator=g, dtype=torch.int32)) % nf
+    df = torch.where(hops, other, df).contiguous()
+    n_hopped = int(hops.sum())
+    del hops, other
+    mc = counting.MoleculeCounter(nw, UL, capacity_hint=hint, read_counts=True, features=nf)
+    mc.update_device(di.data_ptr(), du.data_ptr(), n, feature_ptr=df.data_ptr())
+    nmol = len(mc)
+    methods = ("none", "one_step", "directional")
+    d_resolved = torch.empty((3, nw), dtype=torch.int64, device=dev)
+    d_tally = torch.empty((3, 4), dtype=torch.int64, device=dev)
+    o_indptr = torch.empty(nw + 1, dtype=torch.int64, device=dev)
+    o_feat = torch.empty(nmol, dtype=torch.int32, device=dev)
+    o_val = torch.empty((4, nmol), dtype=torch.int64, device=dev)
+    got = {}
+
+    def run_resolve(k):
+        def go():
+            mc.resolve_device(d_resolved[k].data_ptr(), d_tally[k].data_ptr(), method=methods[k])
+            torch.cuda.synchronize()
+        return _time_ms(go)
+
+    def run_matrix(method, resolved):
+        collapsed = o_val[2].data_ptr() if method != "none" else None
+        def go():
+            got["nnz"] = mc.matrix_device(o_indptr.data_ptr(), o_feat.data_ptr(), o_val[0].data_ptr(),
+                                          o_val[1].data_ptr(), collapsed, nmol, method=method,
+                                          resolved_ptr=o_val[3].data_ptr() if resolved else None)
+            torch.cuda.synchronize()
+        return _time_ms(go)
+
+    def host_route(method):
+        """(pairs ms, numpy ms, the host answer)"""
+        rows = {}
+        if method == "none":
+            pairs_ms = _time_ms(lambda: rows.update(r=mc.pairs(features=True, reads=True)))
+            pi, pf, pu, pr = rows["r"]
+            image = pu
+        else:
+            pairs_ms = _time_ms(lambda: rows.update(r=mc.pairs(features=True, reads=True, parents=True, method=method)))
+            pi, pf, _, pr, image = rows["r"]
+        numpy_ms = _time_ms(lambda: rows.update(a=_resolve_on_host((pi, pf, image, pr), nw, nf)))
+        return pairs_ms, numpy_ms, rows["a"]
+
+    # the untouched matrix call beside the parent library's, each on a counter of its own library
+    vp = ctypes.c_void_p
+    handles = {}
+    if old:
+        p_indptr, p_feat, p_val = torch.empty_like(o_indptr), torch.empty_like(o_feat), torch.empty_like(o_val[:3])
+        for lname, lib in (("this", _lib.lib()), ("parent", old)):
+            h = vp()
+            assert lib.sct_molecules_create_features(nw, nf, 3, UL, hint, 1, -1, ctypes.byref(h)) == 0
+            assert lib.sct_molecules_update_features(h, vp(di.data_ptr()), vp(df.data_ptr()), vp(du.data_ptr()), n, None) == 0
+            handles[lname] = (lib, h)
+
+    def run_abi_matrix(lname, out_indptr, out_feat, out_val):
+        lib, h = handles[lname]
+        nnz = ctypes.c_int64(0)
+        def go():
+            assert lib.sct_molecules_matrix(h, vp(out_indptr.data_ptr()), vp(out_feat.data_ptr()), vp(out_val[0].data_ptr()),
+                                            vp(out_val[1].data_ptr()), vp(out_val[2].data_ptr()), nmol, ctypes.byref(nnz),
+                                            None) == 0
+            torch.cuda.synchronize()
+        ms = _time_ms(go)
+        return ms, nnz.value
+
+    # (first, before this library's pool has served a resolve call the parent's never sees, and in
+    # alternating order: whichever library runs second in a round runs first in the next)
+    abi_rounds = []
+    if old:
+        abi = {"this": lambda: run_abi_matrix("this", o_indptr, o_feat, o_val)[0],
+               "parent": lambda: run_abi_matrix("parent", p_indptr, p_feat, p_val)[0]}
+        abi["this"](), abi["parent"]()  # warm-up
+        for r in range(args.rounds):
+            order = ("this", "parent") if r % 2 == 0 else ("parent", "this")
+            abi_rounds.append({"abi_matrix_%s_ms" % lname: round(abi[lname](), 3) for lname in order})
+    for k in range(3):
+        run_resolve(k)  # warm-up
+    run_matrix("one_step", True), run_matrix("one_step", False)
+    rounds, host = [], {}
+    for r in range(args.rounds):
+        row = {"what": "resolve", "round": r}
+        for k, method in enumerate(methods):
+            row["resolve_%s_ms" % method] = round(run_resolve(k), 3)
+        for method in methods:
+            row["matrix_resolved_%s_ms" % method] = round(run_matrix(method, True), 3)
+        row["matrix_reads_collapsed_ms"] = round(run_matrix("one_step", False), 3)
+        if old:
+            row.update(abi_rounds[r])
+        pairs_ms, numpy_ms, host["one_step"] = host_route("one_step")
+        row["host_pairs_ms"], row["host_lexsort_reduceat_ms"] = round(pairs_ms, 1), round(numpy_ms, 1)
+        row["host_route_ms"] = round(pairs_ms + numpy_ms, 1)
+        rounds.append(row)
+    out = {"n": n, "nw": nw, "nf": nf, "umi_length": UL, "capacity_hint": hint, "hop": args.hop, "hopped_reads": n_hopped,
+           "molecules": nmol, "capacity": mc.info()["capacity"], "rounds": args.rounds, "parent_lib": bool(old)}
+    for key in rounds[0]:
+        if key.endswith("_ms"):
+            v = [row[key] for row in rounds]
+            out[key] = {"median": round(float(np.median(v)), 3), "min": min(v), "max": max(v)}
+    out["host_route_once_ms"] = {}
+    for method in ("none", "directional"):
+        pairs_ms, numpy_ms, host[method] = host_route(method)
+        out["host_route_once_ms"][method] = round(pairs_ms + numpy_ms, 1)
+    # device == host, for every method: resolve(), and the matrix's resolved column
+    equal = {}
+    for k, method in enumerate(methods):
+        h_resolved, h_tally, h_cells, h_per_cell = host[method]
+        run_resolve(k)
+        run_matrix(method, True)
+        nnz = got["nnz"]
+        rows_of = torch.repeat_interleave(torch.arange(nw, device=dev), o_indptr[1:] - o_indptr[:-1])
+        kept = o_val[3, :nnz]
+        cells = (rows_of * nf + o_feat[:nnz])[kept > 0].cpu().numpy()
+        equal[method] = bool(np.array_equal(d_resolved[k].cpu().numpy(), h_resolved)
+                             and tuple(d_tally[k].cpu().tolist()) == h_tally and np.array_equal(cells, h_cells)
+                             and np.array_equal(kept[kept > 0].cpu().numpy(), h_per_cell)
+                             and int(kept.sum()) == int(h_resolved.sum()))
+        out["answer_" + method] = {"resolved": int(h_resolved.sum()), "n_shared": h_tally[0], "n_lost": h_tally[1],
+                                   "n_tied": h_tally[2], "reads_dropped": h_tally[3], "nnz": nnz,
+                                   "explicit_zeros": int((kept == 0).sum())}
+    out["device_equals_host"] = equal
+    out["host_route_over_resolve"] = round(out["host_route_ms"]["median"] / out["resolve_one_step_ms"]["median"], 1)
+    out["host_route_over_matrix_resolved"] = round(out["host_route_ms"]["median"]
+                                                   / out["matrix_resolved_one_step_ms"]["median"], 1)
+    out["matrix_resolved_over_matrix"] = round(out["matrix_resolved_one_step_ms"]["median"]
+                                               / out["matrix_reads_collapsed_ms"]["median"], 2)
+    if old:
+        n_this, n_parent = run_abi_matrix("this", o_indptr, o_feat, o_val)[1], run_abi_matrix("parent", p_indptr, p_feat, p_val)[1]
+        out["abi_matrix_outputs_equal"] = bool(n_this == n_parent and torch.equal(o_indptr, p_indptr)
+                                               and torch.equal(o_feat[:n_this], p_feat[:n_this])
+                                               and torch.equal(o_val[:3, :n_this], p_val[:, :n_this]))
+        out["abi_matrix_vs_parent"] = _vs_parent(out["abi_matrix_this_ms"], out["abi_matrix_parent_ms"])
+        for lib, h in handles.values():
+            lib.sct_molecules_destroy(h)
+    mc.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    name = "ab_feature_resolve.jsonl" if args.tag == "run" else "ab_feature_resolve_%s.jsonl" % args.tag
+    with open(os.path.join(ROOT, "profiles", name), "w") as f:
+        for row in rounds:
+            f.write(json.dumps(row, sort_keys=True) + "\n")
+        f.write(json.dumps(out, sort_keys=True) + "\n")
+    assert all(equal.values()), "the device and the host route disagree: %r" % (equal,)
+    if old:
+        assert out["abi_matrix_outputs_equal"], "sct_molecules_matrix differs from --parent-lib"
+        assert out["abi_matrix_vs_parent"]["agree"], ("sct_molecules_matrix differs from --parent-lib beyond that "
+                                                      "library's own spread: %r" % (out["abi_matrix_vs_parent"],))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tag", default="run")
@@ -1444,11 +1658,14 @@ def main():
                          "beside this one")
     ap.add_argument("--umi-error", type=float, default=0.01,
                     help="directional step: the probability that a UMI base of a read is substituted")
+    ap.add_argument("--hop", type=float, default=0.02,
+                    help="resolve step: the share of the reads moved to another feature, drawn uniformly")
     ap.add_argument("--only", nargs="+", choices=sorted(STEPS), help="launch only these steps")
     args = ap.parse_args()
     if args.step:
         whole = {"molecules": molecules_step, "collapse": collapse_step, "merge": merge_step, "matrix": matrix_step,
-                 "calls": calls_step, "directional": directional_step, "downsample": downsample_step}
+                 "calls": calls_step, "directional": directional_step, "downsample": downsample_step,
+                 "resolve": resolve_step}
         if args.step in whole:
             res = whole[args.step](args)
         else:
@@ -1465,7 +1682,7 @@ def main():
                "--n-a", str(args.n_a), "--n-counter", str(args.n_counter), "--n-unique", str(args.n_unique),
                "--n-tally", str(args.n_tally), "--rounds", str(args.rounds),
                "--n-collapse-host", str(args.n_collapse_host), "--parent-lib", args.parent_lib,
-               "--umi-error", str(args.umi_error)]
+               "--umi-error", str(args.umi_error), "--hop", str(args.hop)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not lines:
@@ -1480,7 +1697,14 @@ def main():
         f.write("\n")
     short = {"tag": args.tag, "ok": rc == 0, "detail": os.path.relpath(path, ROOT)}
     for step, res in detail["steps"].items():
-        if "matrix_device_ms" in res:
+        if "device_equals_host" in res:
+            short[step] = {"n": res["n"], "molecules": res["molecules"], "hop": res["hop"],
+                           "device_equals_host": all(res["device_equals_host"].values()),
+                           "n_shared": res["answer_one_step"]["n_shared"],
+                           "ms": {k[:-3]: v["median"] for k, v in res.items() if k.endswith("_ms") and "median" in v},
+                           "host_route_over_resolve": res["host_route_over_resolve"],
+                           "host_route_over_matrix_resolved": res["host_route_over_matrix_resolved"]}
+        elif "matrix_device_ms" in res:
             short[step] = {"n": res["n"], "nf": res["nf"], "matrix_device_ms": res["matrix_device_ms"],
                            "nnz": {k: v["nnz"] for k, v in res["matrix"].items()},
                            "host_route_ms": {k: v["host_route"]["total_ms"] for k, v in res["matrix"].items()},
