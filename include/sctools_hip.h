@@ -311,6 +311,13 @@ int sct_allpairs_range_pairs(const sct_allpairs_plan* plan, int64_t item_begin, 
 int sct_allpairs_time_kernels(sct_allpairs_plan* plan, int64_t item_begin, int64_t item_end,
                               uint64_t* d_counts, int repeats, double* out, void* stream);
 
+/* Test aid: the seed values of slices [slice_begin, slice_end) of a built SPECTRAL plan with int8
+ * seeds on 14-bit columns, by the seed kernel sct_allpairs_count would launch, into d_out:
+ * d_out[(z - slice_begin) * 16384 + c] for slice z and column c, (slice_end - slice_begin) * 16384
+ * bytes.  Plans with other seeds: SCT_E_INVALID. */
+int sct_allpairs_seed_slices(sct_allpairs_plan* plan, int64_t slice_begin, int64_t slice_end, int8_t* d_out,
+                             void* stream);
+
 /* SPECTRAL plans: bytes per seed value of the seed -> tile intermediate (1, 2 or 4: the
  * densest transform column bounds it), slices per seed / tile launch, codes in the densest
  * column.  Other schemes: SCT_E_INVALID. */

@@ -90,6 +90,7 @@ SIGNATURES = {
     "sct_allpairs_count": [_vp, _i64, _i64, _vp, _i32, _vp],
     "sct_allpairs_range_pairs": [_vp, _i64, _i64, ctypes.POINTER(_i64)],
     "sct_allpairs_time_kernels": [_vp, _i64, _i64, _vp, _i32, ctypes.POINTER(ctypes.c_double), _vp],
+    "sct_allpairs_seed_slices": [_vp, _i64, _i64, _vp, _vp],
     "sct_allpairs_timing": [_vp, _i32, ctypes.POINTER(ctypes.c_double)],
     "sct_allpairs_spectral_info": [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i64), ctypes.POINTER(_i32)],
     "sct_allpairs_spectral_columns": [_vp, ctypes.POINTER(_i32)],
@@ -1090,6 +1091,10 @@ class AllPairsPlan:
         check(self._lib.sct_allpairs_time_kernels(self._h, begin, end, _vp(d_scratch_ptr), repeats, out,
                                                   _vp(stream)))
         return {"kernel_ms": out[0], "seed_ms": out[1], "units": int(out[2])}
+
+    def seed_slices(self, d_out_ptr, begin, end, stream=0):
+        """Test aid: the int8 seeds of slices [begin, end) into (end - begin) * 16384 device bytes."""
+        check(self._lib.sct_allpairs_seed_slices(self._h, begin, end, _vp(d_out_ptr), _vp(stream)))
 
     def timing(self, mode):
         """Per-launch HIP-event timing of this plan's kernels (sct_allpairs_timing): mode 1

@@ -219,6 +219,10 @@ int build(State& st, const uint64_t* d_codes, hipStream_t s);
 // d_counts[0] += n when z_begin == 0
 int count(State& st, int64_t z_begin, int64_t z_end, unsigned long long* d_counts, hipStream_t s);
 
+// test aid: the plan's int8 seed of slices [z_begin, z_end) into d_out ((z_end - z_begin) 2^14
+// bytes), by the kernel count() would launch (14-bit columns only)
+int seed_slices(State& st, int64_t z_begin, int64_t z_end, int8_t* d_out, hipStream_t s);
+
 // bench aid: ms per launch of the seed and tile kernels over the first chunk of
 // [z_begin, z_end) (`slices` of them), each timed as `repeats` back-to-back launches
 int time_kernels(State& st, int64_t z_begin, int64_t z_end, unsigned long long* d_counts, int repeats,

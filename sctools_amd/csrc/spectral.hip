@@ -31,6 +31,9 @@
 #include "sct_common.h"
 #include "spectral.h"
 #include "spectral_seed.h"
+#ifdef SCT_SEED_MX_VARIANT
+#include "spectral_seed_mx.h"
+#endif
 
 namespace sct_spectral {
 namespace {
@@ -345,6 +348,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void s
     int z1, int8_t* __restrict__ buf, int lp) {
   seed_sm_body<Cols>(planes, gofs, off, z0, z1, buf, lp);
 }
+
+#ifdef SCT_SEED_MX_VARIANT
+// timing variant: int8 seeds as int8 MFMA products (seed_mx_body, spectral_seed_mx.h): 16 waves, 4 per SIMD
+__global__ __launch_bounds__(64 * kMxWaves) void seed_mx_kernel(const uint32_t* __restrict__ planes,
+                                                                const uint32_t* __restrict__ gofs,
+                                                                const uint32_t* __restrict__ off, int z0, int z1,
+                                                                int8_t* __restrict__ buf, int sb) {
+  seed_mx_body<Cols>(planes, gofs, off, z0, z1, buf, sb);
+}
+#endif
 
 template <typename T>
 __global__ __launch_bounds__(256) void seed_kernel(const uint32_t* __restrict__ planes,
@@ -802,10 +815,13 @@ __global__ __launch_bounds__(256) void probe_max_kernel(const uint32_t* __restri
 }
 
 template <typename T>
-int launch_seed(State& st, int z0, int z1, hipStream_t s) {
-  T* buf = reinterpret_cast<T*>(st.d_buf);
+int launch_seed(State& st, T* buf, int z0, int z1, hipStream_t s) {
   if constexpr (sizeof(T) == 1) {
+#ifdef SCT_SEED_MX_VARIANT
+    return launch_seed_mx<Cols>(seed_mx_kernel, st, buf, z0, z1, s);
+#else
     return launch_seed_sm<Cols>(seed_sm_kernel, st, buf, z0, z1, s);
+#endif
   } else {
     // 16 walks per workgroup for a full chunk; smaller chunks keep >= 64 workgroup rows (as
     // launch_seed_sm)
@@ -840,7 +856,7 @@ int launch_tile(State& st, int z0, int z1, unsigned long long* counts, hipStream
 template <typename T>
 int launch_chunk(State& st, int z0, int z1, unsigned long long* counts, hipStream_t s, unsigned long long add_n) {
   return launch_seed_tile(
-      st, s, [&] { return launch_seed<T>(st, z0, z1, s); },
+      st, s, [&] { return launch_seed<T>(st, reinterpret_cast<T*>(st.d_buf), z0, z1, s); },
       [&] { return launch_tile<T>(st, z0, z1, counts, s, add_n); });
 }
 
@@ -848,7 +864,7 @@ template <typename T>
 int time_chunk(State& st, int z0, int z1, unsigned long long* counts, int repeats, hipStream_t s,
                double* seed_ms, double* tile_ms) {
   return time_seed_tile(
-      st, repeats, s, [&] { return launch_seed<T>(st, z0, z1, s); },
+      st, repeats, s, [&] { return launch_seed<T>(st, reinterpret_cast<T*>(st.d_buf), z0, z1, s); },
       [&] { return launch_tile<T>(st, z0, z1, counts, s); }, seed_ms, tile_ms);
 }
 
@@ -1208,6 +1224,13 @@ int count(State& st, int64_t z_begin, int64_t z_end, unsigned long long* d_count
     if (rc != SCT_OK) return rc;
   }
   return SCT_OK;
+}
+
+int seed_slices(State& st, int64_t z_begin, int64_t z_end, int8_t* d_out, hipStream_t s) {
+  SCT_CHECK(0 <= z_begin && z_begin < z_end && z_end <= kSlices, "seed_slices: slice range [%lld, %lld)",
+            (long long)z_begin, (long long)z_end);
+  SCT_CHECK(st.n >= 2 && st.lo_bits == kLoBits && st.elem_bytes == 1, "seed_slices: not an int8 plan on 14-bit columns");
+  return launch_seed<int8_t>(st, d_out, (int)z_begin, (int)z_end, s);
 }
 
 int time_kernels(State& st, int64_t z_begin, int64_t z_end, unsigned long long* d_counts, int repeats,

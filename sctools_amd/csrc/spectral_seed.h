@@ -22,6 +22,7 @@ struct Columns {
   static constexpr int kPlaneWords = (kHiBits + 3) / 4 * 4;
 };
 
+typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
 constexpr int kWalk = 64;             // slices per Gray walk
 constexpr int kWalkBits = 6;
 constexpr int kRegGroupsSM = 3;       // int8 seed: 32-code groups whose planes stay in registers
@@ -152,7 +153,10 @@ __device__ __forceinline__ void seed_finish(const uint32_t* __restrict__ planes,
     const uint4 v = *reinterpret_cast<const uint4*>(st8 + row * NT + mcb);
     const uint4 o = make_uint4((mx[0] - (v.x + v.x)) ^ 0x80808080u, (mx[1] - (v.y + v.y)) ^ 0x80808080u,
                                (mx[2] - (v.z + v.z)) ^ 0x80808080u, (mx[3] - (v.w + v.w)) ^ 0x80808080u);
-    if (z >= z0 && z < z1) *reinterpret_cast<uint4*>(buf + (int64_t)(z - z0) * C::kLo + c0 + mcb) = o;
+    // non-temporal: the 4 GiB of seeds are read back once, by the tile, long after they left the caches
+    if (z >= z0 && z < z1)
+      __builtin_nontemporal_store(v4u_t{o.x, o.y, o.z, o.w},
+                                  reinterpret_cast<v4u_t*>(buf + (int64_t)(z - z0) * C::kLo + c0 + mcb));
   }
 }
 
