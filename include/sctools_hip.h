@@ -317,6 +317,21 @@ int sct_allpairs_time_kernels(sct_allpairs_plan* plan, int64_t item_begin, int64
  * bytes.  Plans with other seeds: SCT_E_INVALID. */
 int sct_allpairs_seed_slices(sct_allpairs_plan* plan, int64_t slice_begin, int64_t slice_end, int8_t* d_out,
                              void* stream);
+/* Test aid: the seed rows of slices [slice_begin, slice_end) of a built SPECTRAL plan, whatever its
+ * seed, exactly as the tile kernel reads them, by the seed kernel and grid sct_allpairs_count would
+ * launch for that range.  The slices are the transform's real slices: 2^18 on 14-bit columns, 2^16
+ * on 16-bit columns (sct_allpairs_spectral_columns).  A row is 2^column_bits values of elem_bytes
+ * (sct_allpairs_spectral_info) bytes, little-endian signed: the row of slice z starts at d_out +
+ * (z - slice_begin) * 2^column_bits * elem_bytes.  int8 rows hold column c at position c.  int16
+ * and int32 rows (14-bit columns) hold it at position pos(c), so that one 16-byte chunk carries
+ * V = 16 / elem_bytes columns of one tile thread (L = log2 V):
+ *   pos(c) = (c & (V-1)) | (((c >> 4) & 255) << L) | (((c >> L) & (16/V - 1)) << (L + 8)) | ((c >> 12) << 12)
+ * i.e. the column's low L bits, then its bits 4..11, then its bits L..3, then its bits 12, 13.
+ * out_bytes must equal (slice_end - slice_begin) * row bytes.  SCT_E_INVALID, and nothing is
+ * written: a plan that is not SPECTRAL or holds fewer than 2 codes, an empty range or one outside
+ * the plan's slices, any other out_bytes. */
+int sct_allpairs_seed_rows(sct_allpairs_plan* plan, int64_t slice_begin, int64_t slice_end, void* d_out,
+                           int64_t out_bytes, void* stream);
 
 /* SPECTRAL plans: bytes per seed value of the seed -> tile intermediate (1, 2 or 4: the
  * densest transform column bounds it), slices per seed / tile launch, codes in the densest

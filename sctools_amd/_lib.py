@@ -91,6 +91,7 @@ SIGNATURES = {
     "sct_allpairs_range_pairs": [_vp, _i64, _i64, ctypes.POINTER(_i64)],
     "sct_allpairs_time_kernels": [_vp, _i64, _i64, _vp, _i32, ctypes.POINTER(ctypes.c_double), _vp],
     "sct_allpairs_seed_slices": [_vp, _i64, _i64, _vp, _vp],
+    "sct_allpairs_seed_rows": [_vp, _i64, _i64, _vp, _i64, _vp],
     "sct_allpairs_timing": [_vp, _i32, ctypes.POINTER(ctypes.c_double)],
     "sct_allpairs_spectral_info": [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i64), ctypes.POINTER(_i32)],
     "sct_allpairs_spectral_columns": [_vp, ctypes.POINTER(_i32)],
@@ -1095,6 +1096,11 @@ class AllPairsPlan:
     def seed_slices(self, d_out_ptr, begin, end, stream=0):
         """Test aid: the int8 seeds of slices [begin, end) into (end - begin) * 16384 device bytes."""
         check(self._lib.sct_allpairs_seed_slices(self._h, begin, end, _vp(d_out_ptr), _vp(stream)))
+
+    def seed_rows(self, d_out_ptr, out_bytes, begin, end, stream=0):
+        """Test aid: the seed rows of the transform's real slices [begin, end), as the tile reads them,
+        into exactly `out_bytes` = (end - begin) * 2^column_bits * elem_bytes device bytes."""
+        check(self._lib.sct_allpairs_seed_rows(self._h, begin, end, _vp(d_out_ptr), out_bytes, _vp(stream)))
 
     def timing(self, mode):
         """Per-launch HIP-event timing of this plan's kernels (sct_allpairs_timing): mode 1

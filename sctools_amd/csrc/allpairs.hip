@@ -1291,6 +1291,17 @@ extern "C" int sct_allpairs_seed_slices(sct_allpairs_plan* plan, int64_t slice_b
   return rc;
 }
 
+extern "C" int sct_allpairs_seed_rows(sct_allpairs_plan* plan, int64_t slice_begin, int64_t slice_end, void* d_out,
+                                      int64_t out_bytes, void* stream) {
+  sct::scalar_quiesce();
+  SCT_CHECK(plan != nullptr && d_out != nullptr, "NULL pointer");
+  SCT_CHECK(plan->scheme == SCT_ALLPAIRS_SPECTRAL, "not a SPECTRAL plan");
+  hipStream_t s = sct::as_stream(stream);
+  const int rc = sct_spectral::seed_rows(plan->spec, slice_begin, slice_end, d_out, out_bytes, s);
+  if (rc == SCT_OK) sct_spectral::note_stream(plan->spec, s);
+  return rc;
+}
+
 extern "C" int sct_allpairs_geometry(int64_t n, int code_bits, int* nbins, int64_t* items,
                                      int* rows_per_item, int* cols_per_item) {
   SCT_CHECK(n >= 0, "n must be >= 0");

@@ -222,6 +222,13 @@ int count(State& st, int64_t z_begin, int64_t z_end, unsigned long long* d_count
 // test aid: the plan's int8 seed of slices [z_begin, z_end) into d_out ((z_end - z_begin) 2^14
 // bytes), by the kernel count() would launch (14-bit columns only)
 int seed_slices(State& st, int64_t z_begin, int64_t z_end, int8_t* d_out, hipStream_t s);
+// test aid: the seed rows of the plan's real slices [z_begin, z_end) (of 2^18 on 14-bit columns,
+// of 2^16 on 16-bit columns) into d_out as the tile reads them, by the kernel and grid count()
+// launches for that range.  A row is 2^lo_bits values of elem_bytes; an int16 / int32 row holds
+// column c at position column_pos<T>(c) (spectral.hip).  out_bytes must be exactly the rows' size.
+int seed_rows(State& st, int64_t z_begin, int64_t z_end, void* d_out, int64_t out_bytes, hipStream_t s);
+// its 16-bit-column form (spectral16.hip): real slices [z0, z1) of 2^16 int8 values each
+int seed_rows16(State& st, int z0, int z1, int8_t* d_out, hipStream_t s);
 
 // bench aid: ms per launch of the seed and tile kernels over the first chunk of
 // [z_begin, z_end) (`slices` of them), each timed as `repeats` back-to-back launches

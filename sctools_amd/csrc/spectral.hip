@@ -1233,6 +1233,21 @@ int seed_slices(State& st, int64_t z_begin, int64_t z_end, int8_t* d_out, hipStr
   return launch_seed<int8_t>(st, d_out, (int)z_begin, (int)z_end, s);
 }
 
+int seed_rows(State& st, int64_t z_begin, int64_t z_end, void* d_out, int64_t out_bytes, hipStream_t s) {
+  SCT_CHECK(st.n >= 2, "seed_rows: a plan of fewer than 2 codes has no seed");
+  const int64_t slices = st.lo_bits == kLoBits16 ? kSlices16 : kSlices;
+  SCT_CHECK(0 <= z_begin && z_begin < z_end && z_end <= slices, "seed_rows: slice range [%lld, %lld) outside [0, %lld)",
+            (long long)z_begin, (long long)z_end, (long long)slices);
+  const int64_t row = ((int64_t)1 << st.lo_bits) * st.elem_bytes;
+  SCT_CHECK(out_bytes == (z_end - z_begin) * row, "seed_rows: %lld bytes for %lld rows of %lld", (long long)out_bytes,
+            (long long)(z_end - z_begin), (long long)row);
+  const int z0 = (int)z_begin, z1 = (int)z_end;
+  if (st.lo_bits == kLoBits16) return seed_rows16(st, z0, z1, static_cast<int8_t*>(d_out), s);
+  return st.elem_bytes == 1   ? launch_seed<int8_t>(st, static_cast<int8_t*>(d_out), z0, z1, s)
+         : st.elem_bytes == 2 ? launch_seed<int16_t>(st, static_cast<int16_t*>(d_out), z0, z1, s)
+                              : launch_seed<int32_t>(st, static_cast<int32_t*>(d_out), z0, z1, s);
+}
+
 int time_kernels(State& st, int64_t z_begin, int64_t z_end, unsigned long long* d_counts, int repeats,
                  hipStream_t s, double* seed_ms, double* tile_ms, int64_t* slices) {
   SCT_CHECK(0 <= z_begin && z_begin < z_end && z_end <= kSlices && repeats > 0 && st.n >= 2,

@@ -401,8 +401,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
   add_job_constants(counts, add_n, sumsq);
 }
 
-int launch_seed16(State& st, int z0, int z1, hipStream_t s) {
-  return launch_seed_sm<Cols>(seed16_sm_kernel, st, reinterpret_cast<int8_t*>(st.d_buf), z0, z1, s);
+int launch_seed16(State& st, int8_t* buf, int z0, int z1, hipStream_t s) {
+  return launch_seed_sm<Cols>(seed16_sm_kernel, st, buf, z0, z1, s);
 }
 
 int launch_tile16(State& st, int z0, int z1, unsigned long long* counts, hipStream_t s, unsigned long long add_n) {
@@ -471,7 +471,7 @@ int count16(State& st, int64_t z_begin, int64_t z_end, unsigned long long* d_cou
     const int z1 = (int)std::min<int64_t>(re, z0 + st.chunk16);
     const unsigned long long add_n = z0 == 0 ? (unsigned long long)st.n : 0ull;
     const int rc = launch_seed_tile(
-        st, s, [&] { return launch_seed16(st, (int)z0, z1, s); },
+        st, s, [&] { return launch_seed16(st, reinterpret_cast<int8_t*>(st.d_buf), (int)z0, z1, s); },
         [&] { return launch_tile16(st, (int)z0, z1, d_counts, s, add_n); });
     if (rc != SCT_OK) return rc;
   }
@@ -484,8 +484,10 @@ int time_kernels16(State& st, int64_t z_begin, int64_t z_end, unsigned long long
   SCT_CHECK(rb < re, "time_kernels: empty 16-bit slice range");
   *slices = 4 * (re - rb);  // virtual slices (the bench prices 16 KiB per virtual slice)
   return time_seed_tile(
-      st, repeats, s, [&] { return launch_seed16(st, (int)rb, (int)re, s); },
+      st, repeats, s, [&] { return launch_seed16(st, reinterpret_cast<int8_t*>(st.d_buf), (int)rb, (int)re, s); },
       [&] { return launch_tile16(st, (int)rb, (int)re, d_counts, s, 0); }, seed_ms, tile_ms);
 }
+
+int seed_rows16(State& st, int z0, int z1, int8_t* d_out, hipStream_t s) { return launch_seed16(st, d_out, z0, z1, s); }
 
 }  // namespace sct_spectral
