@@ -303,6 +303,28 @@ int sct_allpairs_geometry(int64_t n, int code_bits, int* nbins, int64_t* items, 
 int sct_allpairs_range_pairs(const sct_allpairs_plan* plan, int64_t item_begin, int64_t item_end,
                              int64_t* pairs);
 
+/* Close pairs of a SUBSETS plan (its table keeps the caller's order; MOMENTS and SPECTRAL plans:
+ * SCT_E_INVALID).
+ * Every unordered pair i<j of the plan's codes in items [item_begin, item_end) with
+ * TwoBit distance <= max_d (0..3; else SCT_E_RANGE).  n < 2^31 and room < 2^31 (else SCT_E_RANGE).
+ * The call overwrites all its outputs:
+ *   d_stats (6 uint64): [0] pairs found, [1] pairs stored = min(found, room), [2+d] pairs at distance d;
+ *   d_i, d_j, d_dist (room entries; nullable when room == 0): the stored pairs.  When found <= room
+ *     they are all of them, ascending by (i, j); when found > room WHICH pairs are stored is
+ *     unspecified, each is a true close pair and none repeats, and nothing past `room` is written;
+ *   d_degree (nullable; n * (max_d+1) uint32): [k*(max_d+1)+d] = positions at distance d from k
+ *     among the pairs of this item range (both ends counted; exact whatever `room`).
+ * Results of disjoint item ranges concatenate (pairs) and add (stats, degree).
+ * May wait on `stream` (the sort needs the count).  Needs a built plan. */
+int sct_allpairs_close_pairs(sct_allpairs_plan* plan, int64_t item_begin, int64_t item_end, int max_d,
+                             int32_t* d_i, int32_t* d_j, uint8_t* d_dist, int64_t room,
+                             uint64_t* d_stats, uint32_t* d_degree, void* stream);
+/* One-shot, host pointers, current device: the same over all pairs of the n codes (a SUBSETS plan of
+ * the call's own, built, run over every item and destroyed).  n < 2: no pairs, SCT_OK. */
+int sct_close_pairs_host(const uint64_t* codes, int64_t n, int code_bits, int max_d,
+                         int32_t* i, int32_t* j, uint8_t* dist, int64_t room,
+                         uint64_t* stats, uint32_t* degree);
+
 /* Bench aid (d_counts receives garbage): the dominant kernel's ms per launch, timed as
  * `repeats` back-to-back launches bracketed by HIP events on `stream`.  SPECTRAL: out[0] =
  * tile kernel, out[1] = seed kernel, both on the first chunk of the range (out[2] = its

@@ -89,6 +89,8 @@ SIGNATURES = {
     "sct_allpairs_build_items": [_vp, _i64, _i64, _vp],
     "sct_allpairs_count": [_vp, _i64, _i64, _vp, _i32, _vp],
     "sct_allpairs_range_pairs": [_vp, _i64, _i64, ctypes.POINTER(_i64)],
+    "sct_allpairs_close_pairs": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "sct_close_pairs_host": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
     "sct_allpairs_time_kernels": [_vp, _i64, _i64, _vp, _i32, ctypes.POINTER(ctypes.c_double), _vp],
     "sct_allpairs_seed_slices": [_vp, _i64, _i64, _vp, _vp],
     "sct_allpairs_seed_rows": [_vp, _i64, _i64, _vp, _i64, _vp],
@@ -690,6 +692,29 @@ def hamming_hist_allpairs(codes, code_bits=None, distinct=False, devices=None):
     return hist
 
 
+CLOSE_PAIRS_MAX_D = 3
+
+
+def close_pairs(codes, code_bits=None, max_d=1, room=0, degree=False):
+    """The pairs of `codes` within max_d bases of each other (sct_close_pairs_host, current device):
+    (i, j, dist, stats, degree).  i, j (int32) and dist (uint8) hold the stats[1] = min(stats[0],
+    room) stored pairs, ascending by (i, j) when all were stored; stats (uint64[6]) = found, stored and
+    the pairs at distance 0..3; degree (uint32 (n, max_d + 1), or None) counts both ends of every pair."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint64).reshape(-1)
+    if code_bits is None:
+        code_bits = int(codes.max()).bit_length() if codes.size else 1
+    room = int(room)
+    i, j = np.empty(room, dtype=np.int32), np.empty(room, dtype=np.int32)
+    dist = np.empty(room, dtype=np.uint8)
+    stats = np.zeros(6, dtype=np.uint64)
+    deg = np.zeros((codes.size, max_d + 1), dtype=np.uint32) if degree and 0 <= max_d <= CLOSE_PAIRS_MAX_D else None
+    check(lib().sct_close_pairs_host(_ptr(codes), codes.size, max(1, code_bits), max_d, _ptr(i) if room else None,
+                                     _ptr(j) if room else None, _ptr(dist) if room else None, room, _ptr(stats),
+                                     _ptr(deg)))
+    m = int(stats[1])
+    return i[:m], j[:m], dist[:m], stats, deg
+
+
 def release_plan_cache():
     """Free the device buffers all-pairs plans keep cached between calls (sct_allpairs_cache_release)."""
     check(lib().sct_allpairs_cache_release())
@@ -1080,6 +1105,15 @@ class AllPairsPlan:
     def count(self, d_counts_ptr, begin=0, end=None, grid=0, stream=0):
         end = self.items if end is None else end
         check(self._lib.sct_allpairs_count(self._h, begin, end, _vp(d_counts_ptr), grid, _vp(stream)))
+
+    def close_pairs(self, max_d, d_stats_ptr, d_i_ptr=0, d_j_ptr=0, d_dist_ptr=0, room=0, d_degree_ptr=0,
+                    begin=0, end=None, stream=0):
+        """SUBSETS plans: the pairs of items [begin, end) within max_d bases (sct_allpairs_close_pairs):
+        6 uint64 stats, up to `room` (int32 i, int32 j, uint8 dist) rows, n * (max_d + 1) uint32 degrees."""
+        end = self.items if end is None else end
+        check(self._lib.sct_allpairs_close_pairs(self._h, begin, end, max_d, _vp(d_i_ptr), _vp(d_j_ptr),
+                                                 _vp(d_dist_ptr), room, _vp(d_stats_ptr), _vp(d_degree_ptr),
+                                                 _vp(stream)))
 
     def counts_to_hist(self, counts):
         return counts_to_hist(counts, self.scheme, self.nbins)

@@ -159,6 +159,37 @@ class Barcodes:
             raise ValueError('nearest needs barcode codes below 2**64')
         return nearest_whitelist(queries, codes, max_distance=max_distance, encoding='TwoBit')
 
+    def _close_codes(self, what, max_distance):
+        if not isinstance(max_distance, (int, np.integer)) or not 0 <= max_distance <= _lib.CLOSE_PAIRS_MAX_D:
+            raise ValueError('%s needs max_distance in 0..%d (got %r)' % (what, _lib.CLOSE_PAIRS_MAX_D, max_distance))
+        codes, bits = self._codes_and_bits(mask_negative=True)  # XORs within the set are kept
+        if codes.ndim != 1:
+            raise ValueError('%s needs barcode codes below 2**64' % what)
+        return codes, bits
+
+    def close_pairs(self, max_distance=1, room=None):
+        """Which barcodes of this set lie within ``max_distance`` bases of each other
+        (TwoBit.hamming_distance, 0..3): ``(i, j, dist)``, every pair ``i < j`` of indices into
+        ``codes_array()`` (the iteration order) once, ascending by ``(i, j)``; ``i``, ``j`` np.int32,
+        ``dist`` np.uint8.  No reference counterpart: ``summarize_hamming_distances`` says how many
+        pairs are one base apart, this names them -- the barcodes a corrector answers -2 for.
+
+        Runs on the current device.  ``room`` is the first guess of the number of pairs (default:
+        four per barcode, at least 65536); a set with more is swept once more with room for all."""
+        codes, bits = self._close_codes('close_pairs', max_distance)
+        room = max(65536, 4 * codes.size) if room is None else int(room)
+        i, j, dist, stats, _ = _lib.close_pairs(codes, bits, int(max_distance), room)
+        if int(stats[0]) > room:
+            i, j, dist, stats, _ = _lib.close_pairs(codes, bits, int(max_distance), int(stats[0]))
+        return i, j, dist
+
+    def neighbour_counts(self, max_distance=1):
+        """np.int64 ``(n, max_distance + 1)``: entry ``[k, d]`` is the number of other barcodes at
+        distance exactly ``d`` from barcode ``k`` of ``codes_array()`` (``max_distance`` in 0..3),
+        i.e. the bincount of ``close_pairs`` at both ends of every pair, without listing a pair."""
+        codes, bits = self._close_codes('neighbour_counts', max_distance)
+        return _lib.close_pairs(codes, bits, int(max_distance), 0, degree=True)[4].astype(np.int64)
+
     def base_frequency(self, weighted=False):
         """(barcode_length, 4) uint64 base counts by position, columns A, C, T, G
         (barcode.py:48-70)."""

@@ -33,6 +33,10 @@
 //   full adders (2 VALU ops each) sums them into B planes d_0..d_{B-1} of the 32
 //   distances, and counts[m] += popcount(AND_{b in m} d_b) for m = 1..2*NPP
 //   (v_bcnt_u32_b32 accumulates in place).  sct_counts_to_hist inverts the counts.
+//
+// Close pairs (sct_allpairs_close_pairs): the same sweep over a SUBSETS table with the counting
+// replaced by the threshold near = [distance <= max_d] of close_pairs_mask.h; only lanes with a
+// set bit name their pairs (allpairs_close_kernel below).
 #include <stdlib.h>
 
 #include <algorithm>
@@ -41,6 +45,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "close_pairs_mask.h"
 #include "sct_common.h"
 #include "spectral.h"
 
@@ -449,6 +454,171 @@ void allpairs_count_kernel(const uint64_t* __restrict__ codes,
   flush_counts<G>(cnt, cnt0, reinterpret_cast<unsigned long long*>(tile), out);
 }
 
+// ---------------------------------------------------------------- close pairs
+// The same sweep over a SUBSETS table (unsorted codes: table position = caller index), with the
+// counting replaced by a threshold: near = [distance <= max_d] of the 32 pairs of a group
+// (close_pairs_mask.h), and only a lane that holds a set bit goes on to name its pairs.  Per hit
+// lane and group pair: one atomic add on the found counter takes a run of slots, the pairs that
+// fall below `room` are stored there as sort words (any order; the host sorts them), and the two
+// degree entries of each pair are bumped -- row i's in registers until the item ends.
+struct CloseOut {
+  unsigned long long* words;  // room sort words (close_pairs::pack_pair)
+  unsigned long long room;
+  unsigned long long* stats;  // [0] pairs found = the slot counter, [2 + d] pairs at distance d
+  uint32_t* degree;           // nullable: [k * width + d]
+  int width;                  // max_d + 1
+};
+
+// near: bits 0..31 group a (columns jg..), bits 32..63 group b (columns jg + 32..); pa / pb: planes
+// 0 and 1 of the two groups' distances (a close pair's distance is <= 3)
+__device__ __forceinline__ void emit_close(uint64_t near, const uint32_t (&pa)[2], const uint32_t (&pb)[2],
+                                           int64_t i, int64_t jg, const CloseOut& o, uint32_t (&di)[4]) {
+  unsigned long long slot = __hip_atomic_fetch_add(o.stats, (unsigned long long)__popcll(near), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
+  do {
+    const int k = __builtin_ctzll(near);
+    near &= near - 1;
+    const uint32_t dist = k < 32 ? sct::close_pairs::dist_at<2>(pa, k) : sct::close_pairs::dist_at<2>(pb, k - 32);
+    const int64_t j = jg + k;
+    if (slot < o.room) o.words[slot] = sct::close_pairs::pack_pair((uint32_t)i, (uint32_t)j, dist);
+    ++slot;
+    if (o.degree)
+      __hip_atomic_fetch_add(o.degree + j * o.width + dist, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) di[d] += dist == (uint32_t)d;
+  } while (near);
+}
+
+template <int NPP, bool MASKED>
+__device__ __forceinline__ void close_item(const uint4* __restrict__ tile, uint64_t q, int64_t i, int64_t j0,
+                                           int64_t n, const sct::close_pairs::LeSelect& sel, const CloseOut& o,
+                                           uint32_t (&di)[4]) {
+  using Gm = Geom<NPP, false>;
+  constexpr int NL = Gm::NL, B = Gm::B;
+  static_assert(B >= 2, "emit_close reads planes 0 and 1");
+  int off[NL];
+#pragma unroll
+  for (int g = 0; g < NL; ++g) off[g] = lookup_off<NPP, false>(q, g);
+#pragma unroll 2
+  for (int h = 0; h < Gm::CT / 2; ++h) {
+    uint32_t s0a[NL], s1a[NL], s0b[NL], s1b[NL];
+#pragma unroll
+    for (int g = 0; g < NL; ++g) {
+      const uint4 e = tile[h * Gm::ROW + off[g]];
+      s0a[g] = comp(e, plane_slot(0, g));
+      s1a[g] = comp(e, plane_slot(1, g));
+      s0b[g] = comp(e, plane_slot(2, g));
+      s1b[g] = comp(e, plane_slot(3, g));
+    }
+    uint32_t da[B], db[B];
+    adder_tree<NL, B>(s0a, s1a, da);
+    adder_tree<NL, B>(s0b, s1b, db);
+    uint32_t na = sct::close_pairs::le_mask<B>(da, sel), nb = sct::close_pairs::le_mask<B>(db, sel);
+    if constexpr (MASKED) {
+      na &= pair_mask(i, j0 + 64 * h, n);
+      nb &= pair_mask(i, j0 + 64 * h + 32, n);
+    }
+    if (na | nb) {  // rare on a whitelist: a handful of ops and this compare is the common case
+      const uint32_t pa[2] = {da[0], da[1]}, pb[2] = {db[0], db[1]};
+      emit_close((uint64_t)nb << 32 | na, pa, pb, i, j0 + 64 * h, o, di);
+    }
+  }
+}
+
+template <int NPP>
+__global__ __launch_bounds__(RB) void allpairs_close_kernel(const uint64_t* __restrict__ codes,
+                                                            const uint4* __restrict__ table, int64_t n,
+                                                            int64_t nchunks, int64_t item_begin, int64_t item_end,
+                                                            int64_t grab, unsigned long long* __restrict__ queue,
+                                                            int max_d, CloseOut o) {
+  using Gm = Geom<NPP, false>;
+  __shared__ __attribute__((aligned(16))) uint4 tile[Gm::TILE];
+  __shared__ int64_t s_grab;
+
+  const int tid = threadIdx.x;
+  const sct::close_pairs::LeSelect sel = sct::close_pairs::le_select(max_d);
+  unsigned long long nd[4] = {0, 0, 0, 0};  // this lane's pairs per distance
+  const int64_t last_rows = ((n - 1) + RB - 1) / RB;  // R(last chunk)
+  int64_t loaded = -1;
+
+  // the count kernel's schedule: `grab` consecutive items per pull, the tile reloaded at chunk seams
+  for (;;) {
+    __syncthreads();  // everyone is done with s_grab (and, below, with the tile)
+    if (tid == 0)
+      s_grab = item_begin + (int64_t)__hip_atomic_fetch_add(queue, (unsigned long long)grab,
+                                                             __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const int64_t t0 = s_grab;
+    if (t0 >= item_end) break;
+    const int64_t t1 = t0 + grab < item_end ? t0 + grab : item_end;
+    ItemCursor cur = locate_item(t0, Gm::K, nchunks);
+    int64_t i = cur.r * RB + tid;
+    uint64_t q = i < n ? codes[i] : 0ull;
+    for (int64_t t = t0; t < t1; ++t) {
+      const int64_t c = cur.c, r = cur.r;
+      if (c != loaded) {
+        __syncthreads();  // previous chunk no longer read
+        const uint4* src = table + c * Gm::TILE;
+#pragma unroll
+        for (int k = 0; k < Gm::TILE / RB; ++k) tile[k * RB + tid] = src[k * RB + tid];
+        if constexpr (Gm::TILE % RB != 0) {
+          const int k = Gm::TILE / RB * RB + tid;
+          if (k < Gm::TILE) tile[k] = src[k];
+        }
+        __syncthreads();
+        loaded = c;
+      }
+      const int64_t rows_c = (c == nchunks - 1) ? last_rows : (c + 1) * Gm::K;
+      if (++cur.r >= rows_c) {
+        cur.c += 1;
+        cur.r = 0;
+      }
+      const int64_t i_next = cur.r * RB + tid;
+      const uint64_t q_next = (t + 1 < t1 && i_next < n) ? codes[i_next] : 0ull;
+      const int64_t j0 = c * Gm::CB;
+      const bool masked = ((r + 1) * RB > j0) || (j0 + Gm::CB > n);
+      uint32_t di[4] = {0, 0, 0, 0};  // row i's pairs per distance in this item
+      if (masked)
+        close_item<NPP, true>(tile, q, i, j0, n, sel, o, di);
+      else
+        close_item<NPP, false>(tile, q, i, j0, n, sel, o, di);
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        if (di[d]) {  // (di[d] != 0 only for d <= max_d and i < n)
+          if (o.degree)
+            __hip_atomic_fetch_add(o.degree + i * o.width + d, di[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          nd[d] += di[d];
+        }
+      q = q_next;
+      i = i_next;
+    }
+  }
+
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    unsigned long long v = nd[d];
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    if ((tid & 63) == 0 && v)
+      __hip_atomic_fetch_add(o.stats + 2 + d, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// the sorted words back into the caller's columns; thread 0 records how many were stored
+__global__ __launch_bounds__(256) void close_unpack_kernel(const unsigned long long* __restrict__ words, int64_t m,
+                                                           int32_t* __restrict__ oi, int32_t* __restrict__ oj,
+                                                           uint8_t* __restrict__ od,
+                                                           unsigned long long* __restrict__ stats) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k == 0) stats[1] = (unsigned long long)m;
+  if (k >= m) return;
+  const uint64_t w = words[k];
+  oi[k] = (int32_t)sct::close_pairs::pair_i(w);
+  oj[k] = (int32_t)sct::close_pairs::pair_j(w);
+  od[k] = (uint8_t)sct::close_pairs::pair_dist(w);
+}
+
 // table[h][pp][c] = bit-sliced 2-bit mismatch counts of nibble pp of the 64 codes of
 // group pair h against combo c (see file header).  One thread per entry.
 __global__ void allpairs_build_kernel(const uint64_t* __restrict__ codes, int64_t n, int npp,
@@ -732,6 +902,7 @@ struct sct_allpairs_plan {
   unsigned long long* d_queue = nullptr;  // work-queue head, zeroed before every launch
   int scheme = SCT_ALLPAIRS_SUBSETS;
   int ncounts = 0;
+  int close_grid = 0;  // persistent grid of the close-pairs kernel (set by its first launch)
   // MOMENTS scheme: position triples, pair/single sources, and the global triple bins
   MomTriple* d_mtri = nullptr;
   MomSource* d_msrc = nullptr;  // kMomNPair pair sources, then kMomG single sources
@@ -862,6 +1033,30 @@ int grid_for(int npp, int cus, int variant, int scheme) {
 int dispatch_count(sct_allpairs_plan* p, int64_t b, int64_t e, uint64_t* d, int grid,
                    hipStream_t s) {
   SCT_NPP_SWITCH(p->npp, launch_count, p, b, e, d, grid, s);
+  return sct::fail(SCT_E_RANGE, "unsupported npp %d", p->npp);
+}
+
+// the close-pairs kernel over items [b, e) of a SUBSETS plan: a persistent grid on the plan's queue
+template <int NPP>
+int launch_close(sct_allpairs_plan* p, int64_t b, int64_t e, int max_d, const CloseOut& o, hipStream_t s) {
+  auto fn = allpairs_close_kernel<NPP>;
+  if (p->close_grid <= 0) {
+    int cus = 0, per_cu = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || cus <= 0)
+      cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RB, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
+    p->close_grid = cus * per_cu;
+  }
+  const int grid = (int)std::min<int64_t>(p->close_grid, e - b);
+  SCT_HIP(hipMemsetAsync(p->d_queue, 0, sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(RB), 0, s, (const uint64_t*)p->d_codes, (const uint4*)p->d_table, p->n,
+                     p->nchunks, b, e, p->grab, p->d_queue, max_d, o);
+  SCT_LAUNCH_CHECK();
+  return SCT_OK;
+}
+
+int dispatch_close(sct_allpairs_plan* p, int64_t b, int64_t e, int max_d, const CloseOut& o, hipStream_t s) {
+  SCT_NPP_SWITCH(p->npp, launch_close, p, b, e, max_d, o, s);
   return sct::fail(SCT_E_RANGE, "unsupported npp %d", p->npp);
 }
 
@@ -1244,6 +1439,103 @@ extern "C" int sct_allpairs_count(sct_allpairs_plan* plan, int64_t item_begin, i
                      : dispatch_count(plan, item_begin, item_end, d_counts, grid, s);
   sct_spectral::note_stream(plan->spec, s);
   return rc;
+}
+
+extern "C" int sct_allpairs_close_pairs(sct_allpairs_plan* plan, int64_t item_begin, int64_t item_end, int max_d,
+                                        int32_t* d_i, int32_t* d_j, uint8_t* d_dist, int64_t room,
+                                        uint64_t* d_stats, uint32_t* d_degree, void* stream) {
+  namespace cp = sct::close_pairs;
+  SCT_CHECK(plan != nullptr, "plan is NULL");
+  SCT_CHECK(plan->scheme == SCT_ALLPAIRS_SUBSETS,
+            "close pairs need a SUBSETS plan: its table keeps the caller's order (this plan's scheme is %d)",
+            plan->scheme);
+  if (max_d < 0 || max_d > cp::kMaxD) return sct::fail(SCT_E_RANGE, "max_d %d outside [0, %d]", max_d, cp::kMaxD);
+  if (plan->n >= (1LL << 31)) return sct::fail(SCT_E_RANGE, "close pairs index %lld codes with int32", (long long)plan->n);
+  if (room >= (1LL << 31)) return sct::fail(SCT_E_RANGE, "room %lld: at most 2^31 - 1 pairs per call", (long long)room);
+  SCT_CHECK(d_stats != nullptr, "stats is NULL");
+  SCT_CHECK(room >= 0 && (room == 0 || (d_i != nullptr && d_j != nullptr && d_dist != nullptr)),
+            "room %lld needs its three pair arrays", (long long)room);
+  SCT_CHECK(0 <= item_begin && item_begin <= item_end && item_end <= plan->items,
+            "item range [%lld, %lld) outside [0, %lld)", (long long)item_begin, (long long)item_end,
+            (long long)plan->items);
+  sct::scalar_quiesce();  // a persistent grid, as the count's
+  hipStream_t s = sct::as_stream(stream);
+  SCT_HIP(hipMemsetAsync(d_stats, 0, 6 * sizeof(uint64_t), s));
+  if (d_degree && plan->n > 0)
+    SCT_HIP(hipMemsetAsync(d_degree, 0, (size_t)plan->n * (size_t)(max_d + 1) * sizeof(uint32_t), s));
+  sct_spectral::note_stream(plan->spec, s);
+  if (item_begin == item_end) return SCT_OK;
+  sct::StreamBlock emitted(s), sorted(s);  // given back on `s` behind the work enqueued below
+  if (room > 0) SCT_HIP(emitted.alloc((size_t)room * 8));
+  const CloseOut o{reinterpret_cast<unsigned long long*>(emitted.p), (unsigned long long)room,
+                   reinterpret_cast<unsigned long long*>(d_stats), d_degree, max_d + 1};
+  SCT_TRY(dispatch_close(plan, item_begin, item_end, max_d, o, s));
+  if (room == 0) return SCT_OK;
+  // the sort takes its length from the count: the one wait of the call
+  unsigned long long found = 0;
+  SCT_HIP(hipMemcpyAsync(&found, d_stats, sizeof(found), hipMemcpyDeviceToHost, s));
+  SCT_HIP(hipStreamSynchronize(s));
+  const int64_t m = (int64_t)std::min<unsigned long long>(found, (unsigned long long)room);
+  if (m == 0) return SCT_OK;
+  const int end_bit = cp::pair_word_bits(plan->n);
+  size_t tmp_bytes = 0;
+  SCT_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)m,
+                                            0, end_bit, s));
+  const size_t tmp_at = ((size_t)m * 8 + 255) & ~(size_t)255;
+  SCT_HIP(sorted.alloc(tmp_at + std::max<size_t>(tmp_bytes, 16)));
+  SCT_HIP(hipcub::DeviceRadixSort::SortKeys(sorted.bytes() + tmp_at, tmp_bytes,
+                                            reinterpret_cast<const uint64_t*>(emitted.p),
+                                            reinterpret_cast<uint64_t*>(sorted.p), (int)m, 0, end_bit, s));
+  hipLaunchKernelGGL(close_unpack_kernel, dim3((unsigned)sct::ceil_div(m, 256)), dim3(256), 0, s,
+                     reinterpret_cast<const unsigned long long*>(sorted.p), m, d_i, d_j, d_dist,
+                     reinterpret_cast<unsigned long long*>(d_stats));
+  SCT_LAUNCH_CHECK();
+  return SCT_OK;
+}
+
+extern "C" int sct_close_pairs_host(const uint64_t* codes, int64_t n, int code_bits, int max_d, int32_t* i,
+                                    int32_t* j, uint8_t* dist, int64_t room, uint64_t* stats, uint32_t* degree) {
+  namespace cp = sct::close_pairs;
+  SCT_CHECK(stats != nullptr, "stats is NULL");
+  SCT_CHECK(n >= 0 && (n == 0 || codes != nullptr), "bad codes");
+  if (max_d < 0 || max_d > cp::kMaxD) return sct::fail(SCT_E_RANGE, "max_d %d outside [0, %d]", max_d, cp::kMaxD);
+  if (n >= (1LL << 31)) return sct::fail(SCT_E_RANGE, "close pairs index %lld codes with int32", (long long)n);
+  if (room >= (1LL << 31)) return sct::fail(SCT_E_RANGE, "room %lld: at most 2^31 - 1 pairs per call", (long long)room);
+  SCT_CHECK(room >= 0 && (room == 0 || (i != nullptr && j != nullptr && dist != nullptr)),
+            "room %lld needs its three pair arrays", (long long)room);
+  const size_t width = (size_t)max_d + 1;
+  for (int k = 0; k < 6; ++k) stats[k] = 0;
+  if (degree) std::fill(degree, degree + (size_t)n * width, 0u);
+  if (n < 2) return SCT_OK;
+  // one block: codes | stats | degree | i | j | dist
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_stats = up((size_t)n * 8), o_deg = o_stats + 256;
+  const size_t o_i = o_deg + up(degree ? (size_t)n * width * 4 : 0), o_j = o_i + up((size_t)room * 4);
+  const size_t o_d = o_j + up((size_t)room * 4), total = o_d + up((size_t)room);
+  sct::DevBuf buf;
+  SCT_HIP(buf.alloc(total));
+  uint8_t* base = static_cast<uint8_t*>(buf.p);
+  SCT_HIP(hipMemcpyAsync(base, codes, (size_t)n * 8, hipMemcpyHostToDevice, 0));
+  sct_allpairs_plan* plan = nullptr;
+  SCT_TRY(sct_allpairs_plan_create_ex2(reinterpret_cast<const uint64_t*>(base), n, code_bits, SCT_ALLPAIRS_SUBSETS,
+                                       SCT_ALLPAIRS_NO_CACHE, &plan));
+  struct Guard {
+    sct_allpairs_plan* p;
+    ~Guard() { sct_allpairs_plan_destroy(p); }  // (waits for the plan's work: before `buf` is freed)
+  } guard{plan};
+  SCT_TRY(sct_allpairs_build(plan, nullptr));
+  SCT_TRY(sct_allpairs_close_pairs(plan, 0, plan->items, max_d, reinterpret_cast<int32_t*>(base + o_i),
+                                   reinterpret_cast<int32_t*>(base + o_j), base + o_d, room,
+                                   reinterpret_cast<uint64_t*>(base + o_stats),
+                                   degree ? reinterpret_cast<uint32_t*>(base + o_deg) : nullptr, nullptr));
+  SCT_HIP(hipMemcpy(stats, base + o_stats, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (degree) SCT_HIP(hipMemcpy(degree, base + o_deg, (size_t)n * width * 4, hipMemcpyDeviceToHost));
+  if (const size_t m = (size_t)stats[1]) {
+    SCT_HIP(hipMemcpy(i, base + o_i, m * 4, hipMemcpyDeviceToHost));
+    SCT_HIP(hipMemcpy(j, base + o_j, m * 4, hipMemcpyDeviceToHost));
+    SCT_HIP(hipMemcpy(dist, base + o_d, m, hipMemcpyDeviceToHost));
+  }
+  return SCT_OK;
 }
 
 extern "C" int sct_allpairs_time_kernels(sct_allpairs_plan* plan, int64_t item_begin, int64_t item_end,
