@@ -951,6 +951,74 @@ int sct_molecules_matrix_resolved_host(sct_molecules* mol, int method, int64_t* 
                                        uint64_t* molecules, uint64_t* reads, uint64_t* collapsed,
                                        uint64_t* resolved, uint64_t* tally, int64_t room, int64_t* nnz);
 
+/* Read groups: every read tagged with its molecule.  The calls above answer per barcode or per matrix
+ * entry; a read-groups object answers per read -- the corrected UMI of the read (the UB tag, the output
+ * of `umi_tools group`), whether its molecule survived "resolving features", how many reads the
+ * molecule has and whether the read is the first of it (duplicate marking).  The contract is restated
+ * in plain Python by tests/read_groups_reference.py, and that restatement is the contract.
+ * Create: a *snapshot* of the counter `mol` as it stands on `stream`, under `method`
+ * (SCT_COLLAPSE_NONE, SCT_COLLAPSE_ONE_STEP or SCT_COLLAPSE_DIRECTIONAL; the images are those of
+ * "resolving features") and `flags`:
+ *   SCT_GROUPS_RESOLVED  the final molecules that sct_molecules_resolve(method) does not keep give
+ *                        SCT_READ_LOST; needs a counted feature counter;
+ *   SCT_GROUPS_READS     tag writes the reads of every read's final molecule; needs a counted counter;
+ *   SCT_GROUPS_FIRST     tag marks the first read of every final molecule.
+ * A collapsing method needs a counted counter.  Anything else is SCT_E_INVALID.  The object owns
+ * every array tag reads: the counter may afterwards be updated, grown, merged into or destroyed, and
+ * tag goes on giving the snapshot's answers.  It lives on the counter's device; every call works
+ * whatever device is current and leaves it as it was.  Create waits for `stream` (it reads the size;
+ * DIRECTIONAL also between its sweeps).
+ * Final molecule of a stored key (index, feature, umi): (index, feature, image umi).  Its reads: the
+ * sum of mreads over the stored keys with that image -- one step, not followed further.
+ * Tag: per read, in this order of precedence,
+ *   index == -1                                        SCT_READ_NO_BARCODE
+ *   index == -2                                        SCT_READ_AMBIGUOUS
+ *   index outside [-2, nw) or feature outside [-2, nf) SCT_READ_BAD_INDEX
+ *   a bad UMI (as sct_molecules_update's rule)         SCT_READ_BAD_UMI
+ *   feature < 0                                        SCT_READ_NO_FEATURE
+ *   the key is not stored in the snapshot              SCT_READ_ABSENT (a UMI one base from a stored
+ *                                                      one is not corrected: only stored keys have images)
+ *   RESOLVED and the final molecule is not kept        SCT_READ_LOST
+ *   otherwise                                          SCT_READ_GROUPED
+ * final_umi is the image UMI for LOST and GROUPED and the input UMI otherwise; reads is the final
+ * molecule's reads for LOST and GROUPED and 0 otherwise.  d_feature is NULL exactly when the counter has
+ * no features; d_reads / d_first are non-NULL exactly when the flag asked for the column (SCT_E_INVALID
+ * otherwise).
+ * First: every read given to tag gets an ordinal, the number of reads the object was given before it
+ * (of any status; position in a call and the order of the calls both count).  first is 1 for exactly
+ * one read of every final molecule that has a GROUPED read, the one with the lowest ordinal, and 0 for
+ * every other read.  It depends on neither the table layout, the launch shape nor the batch cut.
+ * A batch with a BAD_INDEX read is tagged whole, the ordinals advance by the whole batch, and then the
+ * call returns SCT_E_RANGE.  tag waits for `stream` once (it reads the tallies back to learn that).
+ * Calls on different streams are ordered by an event, as a counter's are.  An empty counter gives
+ * SCT_READ_ABSENT for every otherwise good read.
+ * info: the reads given to tag so far, and tally[8] (nullable), the reads per status.
+ * Invariants, when every counted read is tagged exactly once: count(first) is sum(molecules),
+ * sum(collapsed) of the method, or sum(resolved) with RESOLVED; count(LOST) == reads_dropped; and the
+ * reads of the first reads' molecules + reads_dropped == sum(reads).
+ * Memory: 16 B per table slot (the keys, and a word with the final UMI and the kept flag), 8 B more for
+ * READS and 12 B more for FIRST (the lowest ordinal, and the image's slot). */
+#define SCT_GROUPS_RESOLVED 1
+#define SCT_GROUPS_READS 2
+#define SCT_GROUPS_FIRST 4
+#define SCT_READ_GROUPED 0
+#define SCT_READ_NO_BARCODE 1
+#define SCT_READ_AMBIGUOUS 2
+#define SCT_READ_BAD_UMI 3
+#define SCT_READ_NO_FEATURE 4
+#define SCT_READ_ABSENT 5
+#define SCT_READ_LOST 6
+#define SCT_READ_BAD_INDEX 7
+typedef struct sct_read_groups sct_read_groups;
+int sct_read_groups_create(sct_molecules* mol, int method, int flags, sct_read_groups** groups, void* stream);
+int sct_read_groups_tag(sct_read_groups* g, const int32_t* d_index, const int32_t* d_feature, const uint64_t* d_umi,
+                        int64_t n, uint64_t* d_final_umi, uint8_t* d_status, uint64_t* d_reads, uint8_t* d_first,
+                        void* stream);
+int sct_read_groups_tag_host(sct_read_groups* g, const int32_t* index, const int32_t* feature, const uint64_t* umi,
+                             int64_t n, uint64_t* final_umi, uint8_t* status, uint64_t* reads, uint8_t* first);
+int sct_read_groups_info(sct_read_groups* g, int64_t* tagged, uint64_t* tally);
+int sct_read_groups_destroy(sct_read_groups* g);
+
 /* ---------------------------------------------------------------- FASTQ barcode extraction
  * Replaces the per-record path reader.Reader.__iter__ (src/sctools/reader.py:56-85) ->
  * fastq.Reader.record_grouper (src/sctools/fastq.py:143-150) -> Record name check

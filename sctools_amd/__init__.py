@@ -9,7 +9,7 @@ Unlike the reference's ``__init__`` this package does not import pysam.
 """
 
 from . import encodings, barcode, stats, counting  # noqa: F401
-from .counting import DeviceCounter, MoleculeCounter  # noqa: F401
+from .counting import DeviceCounter, MoleculeCounter, ReadGroups  # noqa: F401
 
 
 def release_device_memory():

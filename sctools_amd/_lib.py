@@ -42,7 +42,8 @@ TUNE_KEYS = {"spectral_chunk": 1, "spectral_min_n": 2, "allpairs_grab": 3, "allp
              "merge_rows": 19, "tile_chain": 20, "directional_form": 21,
              "downsample_wave_reads": 22}
 COLLAPSE_ONE_STEP, COLLAPSE_DIRECTIONAL = 0, 1
-COLLAPSE_NONE = 2  # the resolve calls only
+COLLAPSE_NONE = 2  # the resolve and read-group calls only
+GROUPS_RESOLVED, GROUPS_READS, GROUPS_FIRST = 1, 2, 4
 NEAREST_AUTO, NEAREST_OA, NEAREST_CSR, NEAREST_HALVES = 0, 1, 2, 3
 
 _i32, _i64, _dbl = ctypes.c_int, ctypes.c_int64, ctypes.c_double
@@ -199,6 +200,11 @@ SIGNATURES = {
     "sct_molecules_matrix_resolved": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_i64), _vp],
     "sct_molecules_matrix_resolved_host": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                            ctypes.POINTER(_i64)],
+    "sct_read_groups_create": [_vp, _i32, _i32, ctypes.POINTER(_vp), _vp],
+    "sct_read_groups_tag": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "sct_read_groups_tag_host": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "sct_read_groups_info": [_vp, ctypes.POINTER(_i64), _vp],
+    "sct_read_groups_destroy": [_vp],
 }
 _RESTYPES = {"sct_last_error": ctypes.c_char_p}
 

@@ -15,7 +15,10 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["DeviceCounter", "MoleculeCounter"]
+__all__ = ["DeviceCounter", "MoleculeCounter", "ReadGroups"]
+
+# the status of a read under ReadGroups.tag (include/sctools_hip.h, SCT_READ_*)
+GROUPED, NO_BARCODE, AMBIGUOUS, BAD_UMI, NO_FEATURE, ABSENT, LOST, BAD_INDEX = range(8)
 
 _vp, _i64 = ctypes.c_void_p, ctypes.c_int64
 
@@ -568,6 +571,11 @@ class MoleculeCounter:
                                                                  _lib._ptr(reads), _lib._ptr(molecules)))
         return reads.view(np.int64), molecules.view(np.int64)
 
+    def read_groups(self, method='one_step', resolved=False, reads=False, first=False):
+        """A ``ReadGroups`` snapshot of this counter under ``method`` ('none', 'one_step' or
+        'directional'): ``tag`` then gives every read its corrected UMI and status on the device."""
+        return ReadGroups(self, method=method, resolved=resolved, reads=reads, first=first)
+
     def info(self):
         """dict(nmolecules, total, capacity)."""
         nm, tot, cap = _i64(0), _i64(0), _i64(0)
@@ -590,6 +598,127 @@ class MoleculeCounter:
     def close(self):
         if self._h:
             self._lib.sct_molecules_destroy(self._h)
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ReadGroups:
+    """Every read tagged with its molecule (sct_read_groups_*; include/sctools_hip.h, "read groups"):
+    a snapshot of a ``MoleculeCounter``'s molecules under a collapse ``method`` ('none', 'one_step' or
+    'directional', the names ``resolve`` takes), against which batches of reads -- the same pieces
+    ``update`` was fed, in any order -- are tagged on the device.
+
+    ``resolved=True`` (a feature counter with ``read_counts``): reads of the molecules that
+    ``resolve(method)`` discards get the status LOST.  ``reads=True`` (``read_counts``) adds the reads
+    of every read's final molecule, ``first=True`` marks the first read of every molecule over all
+    the reads tagged so far (duplicate marking).  'one_step' and 'directional' need ``read_counts``.
+
+    The object describes the counter as it stood when it was made and owns what it reads: the counter
+    may be updated, merged into or closed afterwards.  It lives on the counter's device; every method
+    works whatever device is current.  Use as a context manager or ``close()`` it."""
+
+    def __init__(self, counter, method='one_step', resolved=False, reads=False, first=False):
+        if not isinstance(counter, MoleculeCounter):
+            raise TypeError("ReadGroups needs a MoleculeCounter, not %s" % type(counter).__name__)
+        self._h = _vp()
+        by = resolve_method(method)
+        if not counter._h:
+            raise ValueError("read_groups: the counter is closed")
+        if by != _lib.COLLAPSE_NONE:
+            counter._need_read_counts("read_groups(method=%r)" % method)
+        if resolved:
+            counter._need_features("read_groups(resolved=True)")
+            counter._need_read_counts("read_groups(resolved=True)")
+        if reads:
+            counter._need_read_counts("read_groups(reads=True)")
+        self.method, self.resolved, self.reads, self.first = method, bool(resolved), bool(reads), bool(first)
+        self._nf = counter._nf
+        self.device = counter.device
+        self._lib = counter._lib
+        flags = (_lib.GROUPS_RESOLVED * self.resolved | _lib.GROUPS_READS * self.reads
+                 | _lib.GROUPS_FIRST * self.first)
+        _lib.check(self._lib.sct_read_groups_create(counter._h, by, flags, ctypes.byref(self._h), None))
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the read groups are closed")
+        return self._h
+
+    def tag(self, index, umis, features=None):
+        """Tag a host batch: ``index`` int32, the reads' uint64 UMI codes and, for a feature
+        counter's groups, int32 ``features`` (rejected otherwise), as ``update`` takes them.  Returns
+        (final_umi uint64, status uint8[, mol_reads int64 with ``reads``][, first bool with
+        ``first``]) per read; the statuses are this module's GROUPED .. BAD_INDEX.  A BAD_INDEX read
+        raises ValueError after the whole batch was tagged."""
+        if (features is None) != (self._nf is None):
+            raise ValueError("tag: features= is %s" % ("needed by a feature counter's read groups" if features is None
+                                                       else "only taken by MoleculeCounter(..., features=nf)"))
+        idx = _exact(index, np.int32, "index")
+        umi = _exact(umis, np.uint64, "umis")
+        if idx.size != umi.size:
+            raise ValueError("index and umis differ in length: %d vs %d" % (idx.size, umi.size))
+        feat = None
+        if features is not None:
+            feat = _exact(features, np.int32, "features")
+            if feat.size != idx.size:
+                raise ValueError("index and features differ in length: %d vs %d" % (idx.size, feat.size))
+        n = idx.size
+        final, status = np.empty(n, np.uint64), np.empty(n, np.uint8)
+        mreads = np.empty(n, np.uint64) if self.reads else None
+        first = np.empty(n, np.uint8) if self.first else None
+        h, p = self._handle(), _lib._ptr
+        if n:
+            _lib.check(self._lib.sct_read_groups_tag_host(h, p(idx), p(feat), p(umi), n, p(final), p(status),
+                                                          p(mreads), p(first)))
+        columns = (final, status, mreads.view(np.int64) if self.reads else None,
+                   first.view(np.bool_) if self.first else None)
+        return tuple(col for col in columns if col is not None)
+
+    def tag_device(self, index_ptr, umi_ptr, n, final_umi_ptr, status_ptr, reads_ptr=None, first_ptr=None,
+                   feature_ptr=None, stream=0):
+        """Tag ``n`` reads from device pointers into device pointers, on ``stream`` (sct_read_groups_tag):
+        uint64 final UMIs, uint8 statuses and, exactly when the groups were made with them, uint64
+        reads and uint8 first flags.  Waits for ``stream`` once; a BAD_INDEX read raises ValueError
+        after the whole batch was tagged."""
+        if (feature_ptr is None) != (self._nf is None):
+            raise ValueError("tag_device: feature_ptr= is %s" % (
+                "needed by a feature counter's read groups" if feature_ptr is None
+                else "only taken by MoleculeCounter(..., features=nf)"))
+        h = self._handle()
+        if n:
+            _lib.check(self._lib.sct_read_groups_tag(h, _vp(index_ptr), _vp(feature_ptr), _vp(umi_ptr), int(n),
+                                                     _vp(final_umi_ptr), _vp(status_ptr), _vp(reads_ptr or None),
+                                                     _vp(first_ptr or None), _vp(stream)))
+        return self
+
+    def tally(self):
+        """np.int64[8]: the reads per status over everything tagged so far."""
+        out = np.zeros(8, np.uint64)
+        _lib.check(self._lib.sct_read_groups_info(self._handle(), None, _lib._ptr(out)))
+        return out.view(np.int64)
+
+    @property
+    def tagged(self):
+        """Reads given to ``tag`` / ``tag_device`` so far."""
+        n = _i64(0)
+        _lib.check(self._lib.sct_read_groups_info(self._handle(), ctypes.byref(n), None))
+        return n.value
+
+    def close(self):
+        if self._h:
+            self._lib.sct_read_groups_destroy(self._h)
             self._h = _vp()
 
     def __enter__(self):

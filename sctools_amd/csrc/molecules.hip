@@ -92,6 +92,11 @@
 // (top, how many at top, members, reads) and sets the unique winner's image slot in a bitmap of one
 // bit per slot.  The matrix's fill kernel counts that bitmap per entry as it counts the collapse
 // pass's, in the same block, whose rows the key sort then reuses.
+//
+// Read groups (include/sctools_hip.h, "read groups") keep what those passes make
+// instead of throwing it away: a snapshot object with its own copy of the keys and, per slot, the
+// final UMI with the kept flag and the final molecule's reads, against which batches of reads are
+// tagged by a probe and one or two loads each.  Its kernels and entry points are at the end of the file.
 #include <algorithm>
 #include <type_traits>
 
@@ -102,6 +107,7 @@
 #include "molecules_key.h"
 #include "molecules_merge_plan.h"
 #include "molecules_resolve_key.h"
+#include "read_group_status.h"
 #include "umi_directional.h"
 #include "umi_neighbours.h"
 
@@ -2232,4 +2238,350 @@ extern "C" int sct_molecules_matrix_resolved_host(sct_molecules* c, int method, 
                                st.dev<uint64_t>(3), st.dev<uint64_t>(4), &rv, r, nnz, s);
   for (int i = 1; i < 6; ++i) st.cols[i].count = (size_t)*nnz;  // what the matrix wrote of its room
   return st.finish(rc, "molecule matrix");
+}
+
+// ---- read groups (include/sctools_hip.h, "read groups"; the status rule and the slot word:
+// read_group_status.h)
+//
+// A snapshot keeps its own copy of the counter's keys and, per slot, what a read that finds the slot
+// needs, written at the slot itself: the word (the final UMI with the kept flag) and, if asked, the
+// final molecule's reads.  A read costs the probe and one line per column; nothing is chased through
+// the image.  Only the lowest ordinal is shared by the reads of a final molecule, so it lives at the
+// image's slot, whose number is kept per slot beside it.
+
+namespace {
+
+static_assert(SCT_READ_GROUPED == sct::READ_GROUPED && SCT_READ_NO_BARCODE == sct::READ_NO_BARCODE &&
+                  SCT_READ_AMBIGUOUS == sct::READ_AMBIGUOUS && SCT_READ_BAD_UMI == sct::READ_BAD_UMI &&
+                  SCT_READ_NO_FEATURE == sct::READ_NO_FEATURE && SCT_READ_ABSENT == sct::READ_ABSENT &&
+                  SCT_READ_LOST == sct::READ_LOST && SCT_READ_BAD_INDEX == sct::READ_BAD_INDEX,
+              "the header's status numbers are read_group_status.h's");
+static_assert(W_NWORDS == sct::READ_NSTATUS, "a snapshot's device words are its eight status tallies");
+
+// sum[image slot] += cnt[s] over the occupied slots s: the reads of every final molecule, at its
+// image's slot (sum is zero before; `image` as the resolve pass or the directional labels left it)
+__global__ void __launch_bounds__(WG) read_groups_sum_kernel(Set t, int64_t capacity,
+                                                             const uint32_t* __restrict__ image,
+                                                             u64* __restrict__ sum) {
+  for_each_item(capacity, [&](int64_t s, bool in) {
+    if (in && t.keys[s] != EMPTY) atomicAdd(&sum[image[s] & kLabelSlot], t.cnt[s]);
+  });
+}
+
+// The snapshot's columns of every occupied slot s, with p its image's slot (s itself without `image`):
+// word[s] = the UMI of keys[p] with the kept flag (p's bit in `kept`; set without a bitmap), and each
+// if asked reads[s] = sum[p] (cnt[s] without `sum`: every key its own image) and image_out[s] = p.
+__global__ void __launch_bounds__(WG) read_groups_fill_kernel(Set t, int64_t capacity,
+                                                              const uint32_t* __restrict__ image,
+                                                              const uint32_t* __restrict__ kept,
+                                                              const u64* __restrict__ sum, u64* __restrict__ word,
+                                                              u64* __restrict__ reads,
+                                                              uint32_t* __restrict__ image_out) {
+  for_each_item(capacity, [&](int64_t s, bool in) {
+    if (!in || t.keys[s] == EMPTY) return;
+    const uint32_t p = image ? image[s] & kLabelSlot : (uint32_t)s;
+    const bool keeps = kept ? (kept[p >> 5] >> (p & 31)) & 1u : true;
+    word[s] = sct::read_group_word(sct::mol_key_umi(t.keys[p], t.umi_bits), keeps);
+    if (reads) reads[s] = sum ? sum[p] : t.cnt[s];
+    if (image_out) image_out[s] = p;
+  });
+}
+
+// what the tag kernels read of a snapshot: t.keys is the snapshot's copy, t.words its tallies
+struct Groups {
+  Set t;
+  const u64* word;
+  const u64* reads;       // NULL unless READS
+  u64* first;             // per image slot, the lowest ordinal of a GROUPED read; NULL unless FIRST
+  const uint32_t* image;  // the image's slot of every slot; NULL unless FIRST
+};
+
+// Read i of a batch has the ordinal base + i.  TAG_MIN: the GROUPED reads atomicMin their ordinal into
+// their final molecule's word and nothing else is written.  TAG_EMIT: the columns asked for and the
+// status tallies, summed per wave and added once per wave and status; first[i] says that the word
+// holds this read's ordinal, which is final for this batch once every TAG_MIN launch of it is done --
+// a later batch's ordinals are all larger.
+enum { TAG_EMIT, TAG_MIN };
+template <bool FEATURES, int PASS>
+__global__ void __launch_bounds__(WG) read_groups_tag_kernel(Groups g, const int32_t* __restrict__ index,
+                                                             const int32_t* __restrict__ feature,
+                                                             const u64* __restrict__ umi, int64_t n, u64 base,
+                                                             u64* __restrict__ final_umi, uint8_t* __restrict__ status,
+                                                             u64* __restrict__ reads, uint8_t* __restrict__ first) {
+  const Set& t = g.t;
+  uint32_t tally[sct::READ_NSTATUS] = {};
+  for_each_item(n, [&](int64_t i, bool in) {
+    int what = -1;
+    if (in) {
+      const int32_t v = __builtin_nontemporal_load(&index[i]);
+      const int32_t f = FEATURES ? __builtin_nontemporal_load(&feature[i]) : 0;
+      const u64 u = __builtin_nontemporal_load(&umi[i]);
+      what = sct::read_group_read_status(v, f, t.nw, FEATURES ? t.nf : 0, sct::mol_umi_bad(u, t.kind, t.umi_bits));
+      u64 out_umi = u, out_reads = 0, slot = NO_SLOT;
+      if (what == sct::READ_LOOKUP) {
+        const u64 key = FEATURES ? sct::mol_fkey((uint32_t)v, (uint32_t)f, u, t.feat_bits, t.umi_bits)
+                                 : sct::mol_key((uint32_t)v, u, t.umi_bits);
+        slot = find(t.keys, t.mask, key);
+        const u64 w = slot != NO_SLOT ? g.word[slot] : 0;
+        what = sct::read_group_slot_status(slot != NO_SLOT, sct::read_group_word_kept(w));
+        if (slot != NO_SLOT) {
+          out_umi = sct::read_group_word_umi(w);
+          if (PASS == TAG_EMIT && reads) out_reads = g.reads[slot];
+        }
+      }
+      const bool grouped = what == sct::READ_GROUPED;
+      if (PASS == TAG_MIN) {
+        if (grouped) atomicMin(&g.first[g.image[slot]], base + (u64)i);
+      } else {
+        __builtin_nontemporal_store(out_umi, &final_umi[i]);
+        __builtin_nontemporal_store((uint8_t)what, &status[i]);
+        if (reads) __builtin_nontemporal_store(out_reads, &reads[i]);
+        if (first)
+          __builtin_nontemporal_store((uint8_t)(grouped && g.first[g.image[slot]] == base + (u64)i), &first[i]);
+      }
+    }
+    if (PASS == TAG_EMIT)
+      for (int k = 0; k < sct::READ_NSTATUS; ++k) tally[k] += (uint32_t)__popcll(__ballot(what == k));
+  });
+  if (PASS != TAG_EMIT || (threadIdx.x & 63) != 0) return;
+  for (int k = 0; k < sct::READ_NSTATUS; ++k)
+    if (tally[k]) atomicAdd(&t.words[k], (u64)tally[k]);
+}
+
+}  // namespace
+
+// Host::words are the eight status tallies, Host::total the reads tagged so far (the next ordinal)
+struct sct_read_groups : Host {
+  sct_read_groups() : Host("read groups") {}
+  Groups g{};
+  int flags = 0;
+  u64 bad_index_seen = 0;  // the BAD_INDEX tally as the last tag call read it
+  u64* keys = nullptr;
+  u64* word = nullptr;
+  u64* reads = nullptr;
+  u64* first = nullptr;
+  uint32_t* image = nullptr;
+};
+
+namespace {
+
+// The columns of the snapshot `g` from mol's table as it stands on `s` (it holds molecules, and its
+// size is exact): the method's images by the pass that makes them for resolve, the kept bitmap by the
+// resolve pass itself, the final molecules' reads by one sum over the occupied slots.  All scratch
+// is stream-ordered pool memory.
+int read_groups_build(sct_molecules* c, sct_read_groups* g, int method, hipStream_t s) {
+  const bool resolved = (g->flags & SCT_GROUPS_RESOLVED) != 0;
+  const bool directional = method == SCT_COLLAPSE_DIRECTIONAL, one_step = method == SCT_COLLAPSE_ONE_STEP;
+  const size_t slots8 = (size_t)c->capacity * 8;
+  Carve cv;
+  const size_t o_labels = directional ? cv.take(DirectionalScratch::bytes(c)) : 0;
+  const size_t o_resolve = resolved || one_step ? cv.take(ResolveScratch::bytes(c, method)) : 0;
+  const size_t o_sum = g->reads && method != SCT_COLLAPSE_NONE ? cv.take(slots8) : 0;
+  sct::StreamBlock blk(s);
+  SCT_HIP(blk.alloc(std::max<size_t>(cv.size, 1)));
+  const uint32_t* image = nullptr;
+  const uint32_t* kept = nullptr;
+  if (directional) {
+    const DirectionalScratch ds(c, blk.bytes() + o_labels);
+    SCT_TRY(directional_labels(c, ds, s));
+    image = ds.lab;
+  }
+  hipError_t e = hipSuccess;
+  if (resolved) {
+    const ResolveScratch rs(c, blk.bytes() + o_resolve);
+    SortedRows<true> sr(c->size_bound, key_bits(c), s);
+    SCT_HIP(sr.alloc());
+    e = resolve_pass(c, method, sr, rs, image, nullptr, nullptr);
+    if (one_step) image = rs.image;
+    kept = rs.kept;
+  } else if (one_step) {
+    // the resolve pass's rows kernel with room for no row: it leaves the parents in rs.image
+    const ResolveScratch rs(c, blk.bytes() + o_resolve);
+    const bool wave = sct::tune(SCT_TUNE_COLLAPSE_FORM, 1) == 1;
+    const auto rows_kernel = wave ? molecules_resolve_rows_kernel<IMAGE_PARENT_WAVE> : molecules_resolve_rows_kernel<IMAGE_PARENT>;
+    hipLaunchKernelGGL(rows_kernel, dim3(grid_for(c->capacity, WG)), dim3(WG), 0, s, c->t, c->capacity, nullptr,
+                       rs.image, nullptr, &c->t.words[W_CURSOR], (int64_t)0, nullptr, nullptr);
+    e = hipGetLastError();
+    image = rs.image;
+  }
+  u64* sum = nullptr;
+  if (e == hipSuccess && o_sum) {
+    sum = reinterpret_cast<u64*>(blk.bytes() + o_sum);
+    e = hipMemsetAsync(sum, 0, slots8, s);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(read_groups_sum_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t, c->capacity,
+                         image, sum);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(read_groups_fill_kernel, dim3(grid_for(c->capacity, 1024)), dim3(WG), 0, s, c->t, c->capacity,
+                       image, kept, sum, g->word, g->reads, g->image);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "read groups: %s", hipGetErrorString(e));
+  return SCT_OK;
+}
+
+int read_groups_check(const sct_read_groups* g, const void* index, const void* feature, const void* umi, int64_t n,
+                      const void* final_umi, const void* status, const void* reads, const void* first) {
+  SCT_CHECK(n >= 0, "n must be >= 0");
+  SCT_CHECK(g != nullptr, "read groups is NULL");
+  SCT_CHECK((reads != nullptr) == ((g->flags & SCT_GROUPS_READS) != 0),
+            "the reads column is written exactly when the read groups were made with SCT_GROUPS_READS");
+  SCT_CHECK((first != nullptr) == ((g->flags & SCT_GROUPS_FIRST) != 0),
+            "the first column is written exactly when the read groups were made with SCT_GROUPS_FIRST");
+  SCT_CHECK((feature != nullptr) == (g->g.t.nf != 0) || (n == 0 && feature == nullptr),
+            g->g.t.nf ? "read groups of a feature counter are tagged with a feature per read"
+                      : "the read groups' counter has no features");
+  if (n == 0) return SCT_OK;
+  SCT_CHECK(index != nullptr && umi != nullptr, "NULL index or umi");
+  SCT_CHECK(final_umi != nullptr && status != nullptr, "NULL output");
+  return SCT_OK;
+}
+
+// n > 0 reads on `s`, on the snapshot's device; *range: the batch held a BAD_INDEX read
+int read_groups_tag_device(sct_read_groups* g, const int32_t* d_index, const int32_t* d_feature, const uint64_t* d_umi,
+                           int64_t n, uint64_t* d_final_umi, uint8_t* d_status, uint64_t* d_reads, uint8_t* d_first,
+                           hipStream_t s, bool* range) {
+  if (int rc = enter(g, s); rc != SCT_OK) return rc;
+  const dim3 grid(grid_for(n, 4 * WG));
+  const u64 base = (u64)g->total;
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(WG), 0, s, g->g, d_index, d_feature, reinterpret_cast<const u64*>(d_umi), n,
+                       base, reinterpret_cast<u64*>(d_final_umi), d_status, reinterpret_cast<u64*>(d_reads), d_first);
+  };
+  if (d_first) {
+    d_feature ? launch(read_groups_tag_kernel<true, TAG_MIN>) : launch(read_groups_tag_kernel<false, TAG_MIN>);
+    SCT_LAUNCH_CHECK();
+  }
+  d_feature ? launch(read_groups_tag_kernel<true, TAG_EMIT>) : launch(read_groups_tag_kernel<false, TAG_EMIT>);
+  SCT_LAUNCH_CHECK();
+  g->total += n;
+  SCT_HIP(hipMemcpyAsync(g->h_words, g->words, W_NWORDS * 8, hipMemcpyDeviceToHost, s));
+  SCT_HIP(hipStreamSynchronize(s));
+  *range = g->h_words[sct::READ_BAD_INDEX] != g->bad_index_seen;
+  g->bad_index_seen = g->h_words[sct::READ_BAD_INDEX];
+  return leave(g, s);
+}
+
+int read_groups_range_error(const sct_read_groups* g) {
+  if (g->g.t.nf)
+    return sct::fail(SCT_E_RANGE, "index outside [-2, %lld) or feature outside [-2, %lld) (tagged SCT_READ_BAD_INDEX)",
+                     (long long)g->g.t.nw, (long long)g->g.t.nf);
+  return sct::fail(SCT_E_RANGE, "index outside [-2, %lld) (tagged SCT_READ_BAD_INDEX)", (long long)g->g.t.nw);
+}
+
+}  // namespace
+
+extern "C" int sct_read_groups_destroy(sct_read_groups* g) {
+  if (!g) return SCT_OK;
+  DeviceGuard on_device(g->device);
+  close_words(g);
+  if (g->keys) (void)hipFree(g->keys);
+  if (g->word) (void)hipFree(g->word);
+  if (g->reads) (void)hipFree(g->reads);
+  if (g->first) (void)hipFree(g->first);
+  if (g->image) (void)hipFree(g->image);
+  delete g;
+  return SCT_OK;
+}
+
+extern "C" int sct_read_groups_create(sct_molecules* c, int method, int flags, sct_read_groups** out, void* stream) {
+  SCT_CHECK(out != nullptr, "read groups is NULL");
+  *out = nullptr;
+  SCT_CHECK(c != nullptr, "molecule counter is NULL");
+  SCT_TRY(resolve_method_check(method));
+  SCT_CHECK((flags & ~(SCT_GROUPS_RESOLVED | SCT_GROUPS_READS | SCT_GROUPS_FIRST)) == 0, "unknown flags 0x%x",
+            (unsigned)flags);
+  if (flags & SCT_GROUPS_RESOLVED) SCT_TRY(need_feature_counter(c));
+  if ((flags & (SCT_GROUPS_RESOLVED | SCT_GROUPS_READS)) || method != SCT_COLLAPSE_NONE) SCT_TRY(need_counted(c));
+  SCT_ON_DEVICE_OF(c);
+  hipStream_t s = sct::as_stream(stream);
+  SCT_TRY(enter_read(c, s));
+  auto* g = new sct_read_groups();
+  const auto fail_with = [&](int rc) {
+    sct_read_groups_destroy(g);
+    return rc;
+  };
+  g->device = c->device;
+  g->capacity = c->capacity;
+  g->flags = flags;
+  const size_t slots8 = (size_t)c->capacity * 8;
+  hipError_t e = hipMalloc((void**)&g->keys, slots8);
+  if (e == hipSuccess) e = hipMalloc((void**)&g->word, slots8);
+  if (e == hipSuccess && (flags & SCT_GROUPS_READS)) e = hipMalloc((void**)&g->reads, slots8);
+  if (e == hipSuccess && (flags & SCT_GROUPS_FIRST)) e = hipMalloc((void**)&g->first, slots8);
+  if (e == hipSuccess && (flags & SCT_GROUPS_FIRST)) e = hipMalloc((void**)&g->image, slots8 / 2);
+  if (e == hipSuccess) e = open_words(g);
+  if (e == hipSuccess) e = hipMemsetAsync(g->words, 0, W_NWORDS * 8, s);
+  if (e == hipSuccess && g->first) e = hipMemsetAsync(g->first, 0xFF, slots8, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(g->keys, c->t.keys, slots8, hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess)
+    return fail_with(sct::fail(e == hipErrorOutOfMemory ? SCT_E_NOMEM : SCT_E_HIP, "read groups of %lld slots: %s",
+                               (long long)c->capacity, hipGetErrorString(e)));
+  g->g.t = c->t;
+  g->g.t.keys = g->keys;
+  g->g.t.cnt = g->g.t.reads = g->g.t.molecules = nullptr;
+  g->g.t.words = g->words;
+  g->g.word = g->word, g->g.reads = g->reads, g->g.first = g->first, g->g.image = g->image;
+  int rc = c->size_bound > 0 ? read_groups_build(c, g, method, s) : SCT_OK;
+  // the counter's arrays are read until here; the snapshot's are written until here
+  if (int rl = leave(c, s); rc == SCT_OK) rc = rl;
+  if (int rl = leave(g, s); rc == SCT_OK) rc = rl;
+  if (rc != SCT_OK) return fail_with(rc);
+  *out = g;
+  return SCT_OK;
+}
+
+extern "C" int sct_read_groups_tag(sct_read_groups* g, const int32_t* d_index, const int32_t* d_feature,
+                                   const uint64_t* d_umi, int64_t n, uint64_t* d_final_umi, uint8_t* d_status,
+                                   uint64_t* d_reads, uint8_t* d_first, void* stream) {
+  SCT_TRY(read_groups_check(g, d_index, d_feature, d_umi, n, d_final_umi, d_status, d_reads, d_first));
+  if (n == 0) return SCT_OK;
+  SCT_ON_DEVICE_OF(g);
+  bool range = false;
+  const int rc = read_groups_tag_device(g, d_index, d_feature, d_umi, n, d_final_umi, d_status, d_reads, d_first,
+                                        sct::as_stream(stream), &range);
+  return rc == SCT_OK && range ? read_groups_range_error(g) : rc;
+}
+
+extern "C" int sct_read_groups_tag_host(sct_read_groups* g, const int32_t* index, const int32_t* feature,
+                                        const uint64_t* umi, int64_t n, uint64_t* final_umi, uint8_t* status,
+                                        uint64_t* reads, uint8_t* first) {
+  SCT_TRY(read_groups_check(g, index, feature, umi, n, final_umi, status, reads, first));
+  if (n == 0) return SCT_OK;
+  SCT_ON_STAGE_OF(g, s);
+  // one staged call: the up to four outputs, then the three inputs, which travel one way only
+  Staged st(s);
+  st.add(final_umi, 8, (size_t)n), st.add(reads, 8, (size_t)n), st.add(status, 1, (size_t)n), st.add(first, 1, (size_t)n);
+  st.add(const_cast<uint64_t*>(umi), 8, (size_t)n), st.add(const_cast<int32_t*>(index), 4, (size_t)n);
+  st.add(const_cast<int32_t*>(feature), 4, (size_t)n);
+  if (int rc = st.alloc(); rc != SCT_OK) return rc;
+  for (int i = 4; i < st.n; ++i) {
+    const Staged::Column& col = st.cols[i];
+    if (col.host && st.blk.ok())
+      st.blk.note(hipMemcpyAsync(st.dev<uint8_t>(i), col.host, col.elem * col.count, hipMemcpyHostToDevice, s));
+    st.cols[i].count = 0;  // (not copied back)
+  }
+  bool range = false;
+  int rc = SCT_OK;
+  if (st.blk.ok())
+    rc = read_groups_tag_device(g, st.dev<int32_t>(5), st.dev<int32_t>(6), st.dev<uint64_t>(4), n, st.dev<uint64_t>(0),
+                                st.dev<uint8_t>(2), st.dev<uint64_t>(1), st.dev<uint8_t>(3), s, &range);
+  rc = st.finish(rc, "read groups tag");
+  return rc == SCT_OK && range ? read_groups_range_error(g) : rc;
+}
+
+extern "C" int sct_read_groups_info(sct_read_groups* g, int64_t* tagged, uint64_t* tally) {
+  SCT_CHECK(g != nullptr, "read groups is NULL");
+  if (tally) {
+    SCT_ON_STAGE_OF(g, s);
+    SCT_TRY(enter(g, s));
+    SCT_HIP(hipMemcpyAsync(g->h_words, g->words, W_NWORDS * 8, hipMemcpyDeviceToHost, s));
+    SCT_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < W_NWORDS; ++k) tally[k] = g->h_words[k];
+  }
+  if (tagged) *tagged = g->total;
+  return SCT_OK;
 }

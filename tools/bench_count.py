@@ -29,7 +29,11 @@ skewed table, and the updates, the collapse and the merge beside an earlier libr
 profiles/ab_downsample.jsonl).  Then resolving features on the matrix step's reads with --hop of them
 moved to another feature: resolve_device for the three methods, the resolved matrix, the matrix as it
 was and the host route pairs() + np.lexsort + reduceat, device and host answers equal, and the matrix
-call beside an earlier library (resolve_step; profiles/ab_feature_resolve.jsonl).
+call beside an earlier library (resolve_step; profiles/ab_feature_resolve.jsonl).  Then read groups on
+the same input: read_groups() for every method, tag_device with each set of columns beside
+update_features of the same reads, the host route pairs() + np.searchsorted + np.lexsort + np.unique
+with equal answers, and the updates, collapse, resolve and matrix beside an earlier library
+(groups_step; profiles/ab_read_groups.jsonl).
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends
 the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
@@ -43,6 +47,7 @@ the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>
   python tools/bench_count.py --only directional --umi-error 0.01 --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only downsample --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only resolve --hop 0.02 --parent-lib /path/to/earlier/libsctools_hip.so
+  python tools/bench_count.py --only groups --hop 0.02 --parent-lib /path/to/earlier/libsctools_hip.so
 """
 import argparse
 import functools
@@ -57,7 +62,7 @@ sys.path.insert(0, ROOT)
 
 STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420, "collapse": 600,
          "merge": 600, "matrix": 600, "calls": 600, "directional": 600, "downsample": 600,
-         "resolve": 900}  # seconds
+         "resolve": 900, "groups": 1100}  # seconds
 MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
 HBM_BYTES_PER_S = 8e12
 
@@ -1643,6 +1648,260 @@ def resolve_step(args):
     return out
 
 
+GROUPS_PARENT_CALLS = ("sct_tune_set", "sct_molecules_create", "sct_molecules_create_counted", "sct_molecules_update",
+                       "sct_molecules_create_features", "sct_molecules_update_features", "sct_molecules_info",
+                       "sct_molecules_collapse", "sct_molecules_resolve", "sct_molecules_matrix",
+                       "sct_molecules_destroy")
+
+
+def _groups_on_host(rows, reads, nf, umi_bits, resolved):
+    """The host route of tagging reads: (final_umi uint64, status uint8, mol_reads int64, first bool) of
+    the reads (index, feature, umi) from the counter's rows (index, feature, umi, reads, image umi) in
+    key order -- key packing and np.searchsorted for the stored key, np.unique + bincount for the final
+    molecules' reads, the winner rule by np.lexsort and reduceat, np.unique(return_index=True) for first."""
+    import numpy as np
+    pi, pf, pu, pr, image = rows
+    ri, rf, ru = reads
+    umi_mask = np.int64((1 << umi_bits) - 1)
+    keys = ((pi.astype(np.int64) * nf + pf) << umi_bits) | pu.view(np.int64)
+    # the final molecules: the rows' keys under their images
+    final_keys, row_mol = np.unique((keys & ~umi_mask) | image.view(np.int64), return_inverse=True)
+    mol_reads = np.bincount(row_mol, weights=pr.astype(np.float64), minlength=final_keys.size).astype(np.int64)
+    kept = np.ones(final_keys.size, bool)
+    if resolved:
+        m_feature = (final_keys >> umi_bits) & (nf - 1)
+        group = ((final_keys >> umi_bits) // nf << umi_bits) | (final_keys & umi_mask)  # (index, image)
+        order = np.lexsort((m_feature, group))
+        g_sorted, r_sorted = group[order], mol_reads[order]
+        head = np.empty(order.size, bool)
+        head[0] = True
+        head[1:] = g_sorted[1:] != g_sorted[:-1]
+        starts = np.flatnonzero(head)
+        members = np.diff(np.append(starts, order.size))
+        top = np.maximum.reduceat(r_sorted, starts)
+        at_top = r_sorted == np.repeat(top, members)
+        unique = np.add.reduceat(at_top.astype(np.int64), starts) == 1
+        kept[order] = at_top & np.repeat(unique, members)
+    # the reads
+    status = np.zeros(ri.size, np.uint8)
+    ones = np.uint64(0x1249249249249249 & ((1 << umi_bits) - 1))
+    bad_umi = ((ru >> np.uint64(umi_bits)) != 0) | ((((ru >> np.uint64(2)) ^ ((ru >> np.uint64(1)) | ru)) & ones) != ones)
+    good = (ri >= 0) & ~bad_umi & (rf >= 0)
+    status[rf < 0] = 4
+    status[bad_umi] = 3
+    status[ri == -2] = 2
+    status[ri == -1] = 1
+    at = np.flatnonzero(good)
+    rkey = ((ri[at].astype(np.int64) * nf + rf[at]) << umi_bits) | ru[at].view(np.int64)
+    pos = np.minimum(np.searchsorted(keys, rkey), keys.size - 1)
+    found = keys[pos] == rkey
+    status[at[~found]] = 5
+    at, mol = at[found], row_mol[pos[found]]
+    status[at[~kept[mol]]] = 6
+    final = ru.copy()
+    final[at] = (final_keys[mol] & umi_mask).view(np.uint64)
+    out_reads = np.zeros(ri.size, np.int64)
+    out_reads[at] = mol_reads[mol]
+    first = np.zeros(ri.size, bool)
+    grouped = kept[mol]
+    _, where = np.unique(mol[grouped], return_index=True)
+    first[at[grouped][where]] = True
+    return final, status, out_reads, first
+
+
+def groups_step(args):
+    """Read groups on the resolve step's input (nf = 4096, --hop of the reads moved to another feature),
+    against the table the counted feature update left.  Alternating within every round: read_groups()
+    for the three methods with and without resolved (every column); tag_device of all the reads in one
+    batch, as the other steps feed them, with no optional column, with reads, and with reads and first
+    (one_step, resolved); update_features of the same reads into a fresh counter -- the same access
+    pattern plus atomics; and with --parent-lib the plain, counted and feature updates, the collapse,
+    resolve and the matrix through the C ABI in this library and in that one, the order swapped every
+    round (they agree when the medians differ by no more than the min-max spread of the parent's own
+    rounds; a call that does not is named in the summary).  Once, the host route -- pairs(features=True,
+    reads=True, parents=True), key packing and np.searchsorted, np.lexsort + reduceat, np.unique -- whose
+    four columns must equal the device's.  Every round is one line of the profile, the summary its
+    last (profiles/ab_read_groups.jsonl, or ab_read_groups_<tag>.jsonl)."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, counting
+
+    nw, UL, n, hint, pool, inputs = _molecules_input(args)
+    nf = 4096
+    dev = torch.device("cuda")
+    this, old = _lib.lib(), _parent_lib(args, GROUPS_PARENT_CALLS)
+    di, du, _ = inputs["shuffled"]
+    df = _features_of(di, du, nf, nf)
+    g = torch.Generator(device=dev).manual_seed(29)
+    hops = (torch.rand(n, device=dev, generator=g) < args.hop) & (df >= 0)
+    other = (df + 1 + torch.randint(0, nf - 1, (n,), device=dev, generator=g, dtype=torch.int32)) % nf
+    df = torch.where(hops, other, df).contiguous()
+    del hops, other, inputs
+    mc = counting.MoleculeCounter(nw, UL, capacity_hint=hint, read_counts=True, features=nf)
+    mc.update_device(di.data_ptr(), du.data_ptr(), n, feature_ptr=df.data_ptr())
+    nmol = len(mc)
+    methods = ("none", "one_step", "directional")
+    o_final = torch.empty(n, dtype=torch.int64, device=dev)
+    o_reads = torch.empty(n, dtype=torch.int64, device=dev)
+    o_status = torch.empty(n, dtype=torch.uint8, device=dev)
+    o_first = torch.empty(n, dtype=torch.uint8, device=dev)
+    name = "ab_read_groups.jsonl" if args.tag == "run" else "ab_read_groups_%s.jsonl" % args.tag
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    profile = open(os.path.join(ROOT, "profiles", name), "w")
+
+    def run_create(method, resolved):
+        made = {}
+        def go():
+            made["g"] = mc.read_groups(method=method, resolved=resolved, reads=True, first=True)
+            torch.cuda.synchronize()
+        ms = _time_ms(go)
+        made["g"].close()
+        return ms
+
+    forms = {"plain": dict(), "reads": dict(reads=True), "reads_first": dict(reads=True, first=True)}
+    taggers = {k: mc.read_groups(method="one_step", resolved=True, **kw) for k, kw in forms.items()}
+
+    def run_tag(groups):
+        def go():
+            groups.tag_device(di.data_ptr(), du.data_ptr(), n, o_final.data_ptr(), o_status.data_ptr(),
+                              reads_ptr=o_reads.data_ptr() if groups.reads else None,
+                              first_ptr=o_first.data_ptr() if groups.first else None, feature_ptr=df.data_ptr())
+            torch.cuda.synchronize()
+        return _time_ms(go)
+
+    vp = ctypes.c_void_p
+
+    def run_update(lib, what):
+        """ms of one update of all the reads into a fresh counter of `lib`: plain, counted or features (counted)"""
+        h = vp()
+        if what == "features":
+            assert lib.sct_molecules_create_features(nw, nf, 3, UL, hint, 1, -1, ctypes.byref(h)) == 0
+        else:
+            create = lib.sct_molecules_create_counted if what == "counted" else lib.sct_molecules_create
+            assert create(nw, 3, UL, hint, ctypes.byref(h)) == 0
+        try:
+            def go():
+                if what == "features":
+                    assert lib.sct_molecules_update_features(h, vp(di.data_ptr()), vp(df.data_ptr()), vp(du.data_ptr()), n,
+                                                             None) == 0
+                else:
+                    assert lib.sct_molecules_update(h, vp(di.data_ptr()), vp(du.data_ptr()), n, None) == 0
+                torch.cuda.synchronize()
+            return _time_ms(go)
+        finally:
+            lib.sct_molecules_destroy(h)
+
+    # the read-back calls of both libraries, each on a feature counter of its own library
+    libs = {"this": this}
+    if old:
+        libs["parent"] = old
+    handles, outs = {}, {}
+    for lname, lib in libs.items():
+        h = vp()
+        assert lib.sct_molecules_create_features(nw, nf, 3, UL, hint, 1, -1, ctypes.byref(h)) == 0
+        assert lib.sct_molecules_update_features(h, vp(di.data_ptr()), vp(df.data_ptr()), vp(du.data_ptr()), n, None) == 0
+        handles[lname] = h
+        outs[lname] = {"collapsed": torch.empty(nw, dtype=torch.int64, device=dev),
+                       "resolved": torch.empty(nw, dtype=torch.int64, device=dev),
+                       "tally": torch.empty(4, dtype=torch.int64, device=dev),
+                       "indptr": torch.empty(nw + 1, dtype=torch.int64, device=dev),
+                       "feature": torch.empty(nmol, dtype=torch.int32, device=dev),
+                       "values": torch.empty((3, nmol), dtype=torch.int64, device=dev)}
+
+    def run_call(lname, what):
+        lib, h, o = libs[lname], handles[lname], outs[lname]
+        nnz = ctypes.c_int64(0)
+        def go():
+            if what == "collapse":
+                rc = lib.sct_molecules_collapse(h, vp(o["collapsed"].data_ptr()), None, None)
+            elif what == "resolve":
+                rc = lib.sct_molecules_resolve(h, _lib.COLLAPSE_ONE_STEP, vp(o["resolved"].data_ptr()),
+                                               vp(o["tally"].data_ptr()), None)
+            else:
+                v = o["values"]
+                rc = lib.sct_molecules_matrix(h, vp(o["indptr"].data_ptr()), vp(o["feature"].data_ptr()),
+                                              vp(v[0].data_ptr()), vp(v[1].data_ptr()), vp(v[2].data_ptr()), nmol,
+                                              ctypes.byref(nnz), None)
+            assert rc == 0
+            torch.cuda.synchronize()
+        return _time_ms(go)
+
+    existing = [("update_%s" % w, lambda lname, w=w: run_update(libs[lname], w)) for w in ("plain", "counted", "features")]
+    existing += [(w, lambda lname, w=w: run_call(lname, w)) for w in ("collapse", "resolve", "matrix")]
+    # warm-up: every call once
+    for k in taggers:
+        run_tag(taggers[k])
+    run_create("one_step", True)
+    for lname in libs:
+        for _, call in existing:
+            call(lname)
+    rounds = []
+    for r in range(args.rounds):
+        row = {"what": "groups", "round": r}
+        for method in methods:
+            for resolved in (False, True):
+                row["create_%s%s_ms" % (method, "_resolved" if resolved else "")] = round(run_create(method, resolved), 3)
+        for k in taggers:
+            row["tag_%s_ms" % k] = round(run_tag(taggers[k]), 3)
+        order = list(libs) if r % 2 == 0 else list(libs)[::-1]
+        for what, call in existing:
+            for lname in order:
+                row["%s_%s_ms" % (what, lname)] = round(call(lname), 3)
+        rounds.append(row)
+        profile.write(json.dumps(row, sort_keys=True) + "\n")
+        profile.flush()
+    for groups in taggers.values():
+        groups.close()
+    out = {"n": n, "nw": nw, "nf": nf, "umi_length": UL, "capacity_hint": hint, "hop": args.hop, "molecules": nmol,
+           "capacity": mc.info()["capacity"], "rounds": args.rounds, "parent_lib": bool(old)}
+    for key in rounds[0]:
+        if key.endswith("_ms"):
+            v = [row[key] for row in rounds]
+            out[key] = {"median": round(float(np.median(v)), 3), "min": min(v), "max": max(v)}
+    out["tag_plain_over_update_features"] = round(out["tag_plain_ms"]["median"] / out["update_features_this_ms"]["median"], 3)
+    if old:
+        out["vs_parent"] = {what: _vs_parent(out["%s_this_ms" % what], out["%s_parent_ms" % what]) for what, _ in existing}
+        out["apart_from_parent"] = sorted(what for what, v in out["vs_parent"].items() if not v["agree"])
+        o, p = outs["this"], outs["parent"]
+        out["abi_outputs_equal"] = bool(torch.equal(o["collapsed"], p["collapsed"]) and torch.equal(o["resolved"], p["resolved"])
+                                        and torch.equal(o["tally"], p["tally"]) and torch.equal(o["indptr"], p["indptr"]))
+    for lname, lib in libs.items():
+        lib.sct_molecules_destroy(handles[lname])
+    del outs
+    # the host route, once (one_step, resolved, every column), and its answers beside the device's
+    with mc.read_groups(method="one_step", resolved=True, reads=True, first=True) as groups:
+        run_tag(groups)
+        tally = groups.tally().tolist()
+    host = {}
+    host["pairs_ms"] = round(_time_ms(lambda: host.update(rows=mc.pairs(features=True, reads=True, parents=True))), 1)
+    host["reads_to_host_ms"] = round(_time_ms(lambda: host.update(
+        reads=(di.cpu().numpy(), df.cpu().numpy(), du.cpu().numpy().view(np.uint64)))), 1)
+    host["numpy_ms"] = round(_time_ms(lambda: host.update(a=_groups_on_host(host["rows"], host["reads"], nf, 3 * UL, True))), 1)
+    h_final, h_status, h_reads, h_first = host.pop("a")
+    del host["rows"], host["reads"]
+    host["total_ms"] = round(host["pairs_ms"] + host["reads_to_host_ms"] + host["numpy_ms"], 1)
+    out["host_route_once"] = host
+    out["groups_device_equals_host"] = {
+        "final_umi": bool(np.array_equal(o_final.cpu().numpy().view(np.uint64), h_final)),
+        "status": bool(np.array_equal(o_status.cpu().numpy(), h_status)),
+        "mol_reads": bool(np.array_equal(o_reads.cpu().numpy(), h_reads)),
+        "first": bool(np.array_equal(o_first.cpu().numpy().astype(bool), h_first))}
+    out["tally"] = tally
+    out["moved_reads"] = int((h_final != du.cpu().numpy().view(np.uint64)).sum())
+    out["first_reads"] = int(h_first.sum())
+    out["host_route_over_tag_reads_first"] = round(host["total_ms"] / out["tag_reads_first_ms"]["median"], 1)
+    mc.close()
+    profile.write(json.dumps(out, sort_keys=True) + "\n")
+    profile.close()
+    assert all(out["groups_device_equals_host"].values()), "the device and the host route disagree: %r" % (
+        out["groups_device_equals_host"],)
+    if old:
+        assert out["abi_outputs_equal"], "an existing call's outputs differ from --parent-lib"
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tag", default="run")
@@ -1659,13 +1918,13 @@ def main():
     ap.add_argument("--umi-error", type=float, default=0.01,
                     help="directional step: the probability that a UMI base of a read is substituted")
     ap.add_argument("--hop", type=float, default=0.02,
-                    help="resolve step: the share of the reads moved to another feature, drawn uniformly")
+                    help="resolve and groups steps: the share of the reads moved to another feature, drawn uniformly")
     ap.add_argument("--only", nargs="+", choices=sorted(STEPS), help="launch only these steps")
     args = ap.parse_args()
     if args.step:
         whole = {"molecules": molecules_step, "collapse": collapse_step, "merge": merge_step, "matrix": matrix_step,
                  "calls": calls_step, "directional": directional_step, "downsample": downsample_step,
-                 "resolve": resolve_step}
+                 "resolve": resolve_step, "groups": groups_step}
         if args.step in whole:
             res = whole[args.step](args)
         else:
