@@ -810,6 +810,49 @@ int sct_molecules_downsample_curve(sct_molecules* mol, const uint64_t* threshold
 int sct_molecules_downsample_curve_host(sct_molecules* mol, const uint64_t* thresholds, int64_t k, uint64_t seed,
                                         uint64_t* reads, uint64_t* molecules);
 
+/* Removing swapped molecules: libraries multiplexed on one patterned-flowcell lane exchange a share of
+ * their molecules by index hopping, and the same (cell barcode, UMI, feature) then shows up in two
+ * samples.  The rule is DropletUtils' swappedDrops: the sample that holds at least num / den of a
+ * molecule's reads over the samples of the lane keeps it, every other sample loses it, and when no
+ * sample reaches the fraction all lose it.  This is the step between downsample (equal depth) and
+ * merge (one table).  The contract is restated in plain Python by tests/swapped_reference.py; the
+ * judgement is csrc/swapped_keep.h.  All arithmetic is exact; nothing is computed modulo 2^64.
+ * The call takes s counters src[0 .. s), 1 <= s <= 16, all counted, with equal nw, kind, L and nf, on
+ * one device, and judges the molecules of src[k].  For the molecule `key` stored in src[k] with
+ * r = mreads:
+ *   others = the sum of mreads of `key` in every src[t], t != k (0 where it is not stored), as a
+ *            saturating add at 2^64 - 1;
+ *   the molecule is *shared* when others > 0;
+ *   it is *kept* exactly when r * (den - num) >= num * others, compared in the integers (both
+ *   products are below 2^96: a high and a low word) -- r / (r + others) >= num / den with no
+ *   division.  others == 0 always keeps; num == den keeps the unshared molecules only.
+ * 1 <= num <= den <= 2^32 and 2 * num > den, so at most one sample keeps a key.  Keys are compared
+ * whole: in a feature counter the feature is part of the molecule, as in swappedDrops, and the same
+ * (index, UMI) under two features in two samples is not shared; without features the molecule is
+ * (index, UMI).  No UMI collapse is applied before the judgement: a one-base variant of a swapped UMI
+ * is its own key and is judged on its own reads.  The cleaned counter supports collapse afterwards.
+ * Afterwards dst is the counter that was fed dst's updates followed by the kept molecules of src[k]
+ * (downsample's wording and rule): every kept key is claimed in dst by the update's own rule
+ * (molecules[index] += 1 from the lane whose compare-and-swap took the slot, and from no other),
+ * mreads of the key in dst += r and reads[index] += r; a removed molecule leaves no trace.
+ * dst.tally[j] += src[k].tally[j] for all four tallies -- those reads are not molecules and are not
+ * judged -- and total grows by the kept reads plus the carried tallies; reads of src[k] that rule 3
+ * refused are not carried, as in downsample.  tally (a host uint64[3], nullable) is written, not
+ * accumulated: the shared molecules of src[k], the removed ones, and the reads of the removed ones.
+ * No src is changed; the same call twice adds the same reads again and no molecule.
+ * Growth: the survivors are known after the marking pass, before anything is claimed, and dst is
+ * grown by update's rehash so that dst.nmolecules + survivors <= capacity / 2 -- merge's rule on the
+ * survivors, not on the source's size; more than 2^31 slots is SCT_E_RANGE.
+ * SCT_E_INVALID: a NULL pointer, s or k out of range, the same counter twice in src, dst among src, a
+ * counter without read counts, differing parameters (merge's messages), two devices ("merge each into
+ * a counter on one device first"), a bad num / den.  A src whose table overflowed is SCT_E_RANGE.
+ * After any of these every counter is as it was.
+ * The call orders itself after every involved counter's earlier work on any stream and their later
+ * work after itself, and waits for `stream` once, to learn the survivors and the tally.  The other
+ * samples' tables are probed in place, read-only; no union table is built. */
+int sct_molecules_swapped(sct_molecules* const* src, int64_t s, int64_t k, sct_molecules* dst, uint64_t num,
+                          uint64_t den, uint64_t* tally /* host uint64[3], nullable */, void* stream);
+
 /* Counting molecules per feature: the barcode x feature matrix of a single-cell run -- molecules per
  * (cell, antibody tag / CRISPR guide / hashtag / gene) -- as CSR on the device.  The contract is
  * restated in plain Python by tests/count_matrix_reference.py.

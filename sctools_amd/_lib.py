@@ -178,6 +178,7 @@ SIGNATURES = {
     "sct_molecules_downsample": [_vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp],
     "sct_molecules_downsample_curve": [_vp, _vp, _i64, ctypes.c_uint64, _vp, _vp, _vp],
     "sct_molecules_downsample_curve_host": [_vp, _vp, _i64, ctypes.c_uint64, _vp, _vp],
+    "sct_molecules_swapped": [_vp, _i64, _i64, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp],
     "sct_molecules_create_features": [_i64, _i64, _i32, _i32, _i64, _i32, _i32, ctypes.POINTER(_vp)],
     "sct_molecules_update_features": [_vp, _vp, _vp, _vp, _i64, _vp],
     "sct_molecules_update_features_host": [_vp, _vp, _vp, _vp, _i64],

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["DeviceCounter", "MoleculeCounter", "ReadGroups"]
+__all__ = ["DeviceCounter", "MoleculeCounter", "ReadGroups", "remove_swapped"]
 
 # the status of a read under ReadGroups.tag (include/sctools_hip.h, SCT_READ_*)
 GROUPED, NO_BARCODE, AMBIGUOUS, BAD_UMI, NO_FEATURE, ABSENT, LOST, BAD_INDEX = range(8)
@@ -176,6 +176,87 @@ def _seed(value, what="seed"):
     return ctypes.c_uint64(int(value))
 
 
+def _fraction(min_fraction):
+    """``min_fraction`` as (num, den): a pair of ints with 1 <= num <= den <= 2**32 and 2 * num > den
+    (include/sctools_hip.h, "removing swapped molecules"); ValueError otherwise.  Not a float: the
+    judgement is exact."""
+    try:
+        num, den = min_fraction
+    except (TypeError, ValueError):
+        raise ValueError("min_fraction must be a pair of ints (num, den), not %r" % (min_fraction,)) from None
+    for v in (num, den):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("min_fraction must be a pair of ints (num, den), not %r" % (min_fraction,))
+    num, den = int(num), int(den)
+    if not (1 <= num <= den <= 2 ** 32 and 2 * num > den):
+        raise ValueError("min_fraction %d / %d must have 1 <= num <= den <= 2**32 and 2 * num > den" % (num, den))
+    return num, den
+
+
+def _check_swapped(samples, targets):
+    """What sct_molecules_swapped asks of the samples of a lane and of the counters their kept
+    molecules go into, in merge_device's pattern: TypeError for a non-counter; ValueError for a wrong
+    number of samples, a closed or repeated counter, a target among the samples, missing
+    ``read_counts`` or parameters that differ from the first sample's."""
+    for c in samples + targets:
+        if not isinstance(c, MoleculeCounter):
+            raise TypeError("remove_swapped needs MoleculeCounters, not %s" % type(c).__name__)
+    if not 1 <= len(samples) <= 16:
+        raise ValueError("remove_swapped takes 1 to 16 samples, not %d" % len(samples))
+    for c in samples + targets:
+        if not c._h:
+            raise ValueError("remove_swapped: %s counter is closed" % ("a target" if c in targets else "a sample's"))
+    if len({id(c) for c in samples + targets}) != len(samples) + len(targets):
+        raise ValueError("remove_swapped: a counter is repeated among the samples and targets")
+    for c in samples + targets:
+        c._need_read_counts("remove_swapped")
+    first = samples[0]
+    mine = (first.size, first.kind, first.umi_length, first._nf)
+    for c in samples[1:] + targets:
+        theirs = (c.size, c.kind, c.umi_length, c._nf)
+        for name, a, b in zip(("whitelist_size", "encoding", "umi_length", "features"), mine, theirs):
+            if a != b:
+                raise ValueError("remove_swapped: the counters' %s differ (%r and %r)" % (name, a, b))
+
+
+def remove_swapped(counters, min_fraction=(4, 5), into=None):
+    """The samples of one lane without the molecules that hopped between them (DropletUtils'
+    ``swappedDrops``, on the device): ``counters`` is a sequence of 1 to 16 ``MoleculeCounter`` with
+    ``read_counts``, equal whitelist_size, umi_length, encoding and features, on one device.  A
+    (barcode, UMI[, feature]) seen in several of them stays in the sample that holds at least
+    ``min_fraction`` = (num, den) of its reads and leaves every other one; when no sample reaches the
+    fraction all lose it.  No UMI collapse is applied first; ``collapse`` works on the results.
+
+    Returns (cleaned, tally): ``cleaned[k]`` is a new counter like ``counters[k]`` holding its kept
+    molecules, with its reads, tallies and total -- an ordinary counter -- or, with ``into=`` (a list
+    of as many counters), ``into[k]`` after the kept molecules were added to it.  ``tally`` is
+    np.int64[(len(counters), 3)]: per sample the shared molecules, the removed ones and the removed
+    reads.  The sources are not changed.  TypeError for anything but counters; ValueError for a closed
+    or repeated counter, differing parameters, missing ``read_counts`` or a bad fraction; counters
+    made by the call are closed when it fails."""
+    num, den = _fraction(min_fraction)
+    counters = list(counters)
+    made = into is None
+    into = [] if made else list(into)
+    if not made and len(into) != len(counters):
+        raise ValueError("remove_swapped: into= holds %d counters for %d samples" % (len(into), len(counters)))
+    _check_swapped(counters, into)  # every check before any sample is judged: a failure changes nothing
+    tally = np.zeros((len(counters), 3), np.int64)
+    try:
+        for k, c in enumerate(counters):
+            if made:
+                # (the smallest table: the call grows it to what survives)
+                into.append(MoleculeCounter(c.size, c.umi_length, encoding={3: 'ThreeBit', 2: 'TwoBit'}[c.kind],
+                                            capacity_hint=0, read_counts=True, device=c.device, features=c._nf))
+            tally[k] = c.remove_swapped_device(counters[:k] + counters[k + 1:], into[k], num, den)
+    except Exception:
+        if made:
+            for c in into:
+                c.close()
+        raise
+    return into, tally
+
+
 class MoleculeCounter:
     """Molecules per whitelist barcode on the device (sct_molecules_*): the distinct
     (corrected barcode index, UMI code) pairs, which removes PCR duplicates.
@@ -197,7 +278,9 @@ class MoleculeCounter:
     different pieces of the reads -- one per file or lane, or one per GPU -- become one with
     ``merge``.  With ``read_counts``, ``downsample(fraction)`` gives the counter a fraction of the
     reads would have made, and ``saturation_curve(fractions)`` the reads and molecules at every depth
-    in one pass (include/sctools_hip.h, "downsampling reads").
+    in one pass (include/sctools_hip.h, "downsampling reads").  The counters of the samples of one
+    lane are cleaned of the molecules that hopped between them by ``remove_swapped`` (this module's
+    function; include/sctools_hip.h, "removing swapped molecules").
 
     ``features=nf`` (1 .. 2**31 - 1) makes a *feature counter*: every read carries a feature index
     (an antibody tag or guide corrected by ``WhitelistCorrector``, or a gene index) as a third key
@@ -548,6 +631,21 @@ class MoleculeCounter:
             if made:
                 into.close()
             raise
+
+    def remove_swapped_device(self, others, into, num, den, stream=0):
+        """This sample's molecules that the ``others`` (the lane's other samples, a sequence of at
+        most 15 counters) do not take from it, added to ``into`` on ``stream``
+        (sct_molecules_swapped): a molecule with r reads here and t in the others together is kept
+        when r / (r + t) >= num / den.  Returns np.int64[3]: this sample's shared molecules, the
+        removed ones and the reads of the removed ones.  Waits for ``stream`` once."""
+        num, den = _fraction((num, den))
+        samples = [self] + list(others)
+        _check_swapped(samples, [into])
+        handles = (_vp * len(samples))(*[c._h for c in samples])
+        tally = np.zeros(3, np.uint64)
+        _lib.check(self._lib.sct_molecules_swapped(handles, len(samples), 0, into._h, num, den, _lib._ptr(tally),
+                                                   _vp(stream)))
+        return tally.view(np.int64)
 
     def saturation_curve_device(self, thresholds, reads_ptr, molecules_ptr, seed=0, stream=0):
         """``saturation_curve`` into device memory, on ``stream``: ``thresholds`` is a non-decreasing

@@ -68,6 +68,13 @@
 // it (absorbed); the scratch of every device form is a sct::StreamBlock, given back stream-ordered
 // on every path out of its scope.
 //
+// Removing swapped molecules (include/sctools_hip.h, "removing swapped molecules")
+// is the same walk with a judgement in place of the draw (swapped_keep.h): the lane of a stored molecule
+// probes the tables of the lane's other samples in place, read-only, sums the molecule's reads there and
+// keeps it when its own share reaches the fraction.  The marking pass writes a bit per slot and the
+// sums; the survivors are known before the target grows, and the claim pass takes the marked slots
+// through the same set_take a downsample's survivors go through.
+//
 // A *feature counter* (include/sctools_hip.h, "counting molecules per feature") has a third key part
 // between the index and the UMI (molecules_feature_key.h).  FEATURES is a template parameter of the
 // insert kernels as COUNTED is: a counter without features runs the instantiations without it, and
@@ -108,6 +115,7 @@
 #include "molecules_merge_plan.h"
 #include "molecules_resolve_key.h"
 #include "read_group_status.h"
+#include "swapped_keep.h"
 #include "umi_directional.h"
 #include "umi_neighbours.h"
 
@@ -715,6 +723,25 @@ __global__ void __launch_bounds__(WG) molecules_resolve_kernel(Set t, const u64*
 
 // ---- merge (include/sctools_hip.h, "merging molecule counters")
 
+// Slot i of another counted table read in place, once and past the caches: its key (EMPTY for an empty
+// slot or a lane past the end) and the molecule's reads.
+__device__ __forceinline__ void counted_row(const u64* __restrict__ keys, const u64* __restrict__ cnt, int64_t i,
+                                            bool in, u64* key, u64* r) {
+  *key = EMPTY, *r = 0;
+  if (!in) return;
+  *key = __builtin_nontemporal_load(&keys[i]);
+  *r = __builtin_nontemporal_load(&cnt[i]);
+}
+
+// `count` reads of a molecule of another counted table into `t`: the claim, and reads[index] += count
+// (the index comes out of a stored key: index < nw).  What a downsample and a swapped-molecule removal
+// do with a survivor; the merge adds whole reads[] arrays instead.
+__device__ __forceinline__ int set_take(const Set& t, u64 key, u64 count) {
+  const uint32_t index = sct::mol_key_index(key, t.idx_shift);
+  atomicAdd(&t.reads[index], count);
+  return set_claim<true>(t, key, index, count);
+}
+
 // The rows (keys[], cnt[] or NULL, n) of another counter into the table `t`: its own table as it
 // stands (n = its capacity; a row equal to EMPTY is an empty slot and is skipped) or its occupied
 // rows, dense.  A row is one molecule: the key is claimed in `t` by the insert's rule -- the lane
@@ -766,11 +793,8 @@ __device__ __forceinline__ void downsample_walk(const u64* __restrict__ keys, co
                                                 u64 seed, u64 wave_reads, Share share, Molecule molecule) {
   const int lane = threadIdx.x & 63;
   for_each_item(n, [&](int64_t i, bool in) {
-    u64 key = EMPTY, r = 0;
-    if (in) {
-      key = __builtin_nontemporal_load(&keys[i]);
-      r = __builtin_nontemporal_load(&cnt[i]);
-    }
+    u64 key, r;
+    counted_row(keys, cnt, i, in, &key, &r);
     const bool occ = key != EMPTY;
     const u64 stream = sct::downsample_stream(seed, key);
     const bool heavy = occ && r >= wave_reads;
@@ -800,10 +824,7 @@ __global__ void __launch_bounds__(WG) molecules_downsample_kernel(Set t, const u
         return Thinned{sct::downsample_thin_stride(stream, j0, step, r, threshold), 0};
       },
       [&](u64 key, const Thinned& m) {
-        if (m.kept == 0) return;
-        const uint32_t index = sct::mol_key_index(key, t.idx_shift);
-        atomicAdd(&t.reads[index], m.kept);
-        claims += set_claim<true>(t, key, index, m.kept);
+        if (m.kept != 0) claims += set_take(t, key, m.kept);
       });
   add_claims(&t.words[W_SIZE], claims);
 }
@@ -893,6 +914,88 @@ __global__ void __launch_bounds__(WG) molecules_downsample_tally_kernel(TallyRea
     for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);
     if ((threadIdx.x & 63) == 0 && kept) atomicAdd(&words[W_TALLY + k], kept);
   }
+}
+
+// ---- removing swapped molecules (include/sctools_hip.h, "removing swapped molecules"; the judgement:
+// swapped_keep.h)
+
+// the other samples' tables, by value: at most 15 of them are probed, 24 B each
+struct ProbedTables {
+  struct {
+    const u64* keys;
+    const u64* cnt;
+    u64 mask;
+  } of[sct::kSwappedMaxSamples];
+};
+enum { S_SHARED = 0, S_REMOVED, S_REMOVED_READS, S_KEPT_READS, S_NWORDS };
+
+// The marking pass over one sample's table in place (n = its capacity, a multiple of 64): the walk of
+// downsample_walk, a lane per slot with the wave kept whole.  The lane of an occupied slot loads the
+// key's home slot in every other table before it looks at any of them -- one random line per table, in
+// flight together -- then finishes each probe as find() would and, where the key is stored, loads its
+// reads there; these loads too are issued before their sum is taken.  The kept flags of a wave's 64
+// slots are one ballot: the walk's tiles start on multiples of 64 (the grid's stride is a multiple of
+// WG), so the word kept[i >> 6] is this wave's alone and lane 0 stores it plainly.  Every word of
+// kept[n / 64] is written.  sums[S_NWORDS] += the shared and the removed molecules, the reads of the
+// removed and of the kept ones, summed in registers, one add per wave and non-zero word.
+__global__ void __launch_bounds__(WG) molecules_swapped_mark_kernel(const u64* __restrict__ keys,
+                                                                    const u64* __restrict__ cnt, int64_t n,
+                                                                    ProbedTables others, int nothers, u64 num, u64 den,
+                                                                    u64* __restrict__ kept, u64* __restrict__ sums) {
+  constexpr int kMost = sct::kSwappedMaxSamples - 1;
+  const int lane = threadIdx.x & 63;
+  u64 acc[S_NWORDS] = {};
+  for_each_item(n, [&](int64_t i, bool in) {
+    u64 key, r;
+    counted_row(keys, cnt, i, in, &key, &r);
+    const bool occ = key != EMPTY;
+    bool keep = false;
+    if (occ) {
+      const u64 h = sct::mix64(key);
+      u64 first[kMost], slot[kMost], theirs[kMost];
+#pragma unroll
+      for (int t = 0; t < kMost; ++t)
+        if (t < nothers) first[t] = others.of[t].keys[h & others.of[t].mask];
+#pragma unroll
+      for (int t = 0; t < kMost; ++t)
+        if (t < nothers) slot[t] = find_from(others.of[t].keys, others.of[t].mask, key, h & others.of[t].mask, first[t]);
+#pragma unroll
+      for (int t = 0; t < kMost; ++t)
+        if (t < nothers) theirs[t] = slot[t] != NO_SLOT ? others.of[t].cnt[slot[t]] : 0;
+      u64 sum = 0;
+#pragma unroll
+      for (int t = 0; t < kMost; ++t)
+        if (t < nothers) sum = sct::swapped_add_sat(sum, theirs[t]);
+      keep = sct::swapped_keeps(r, sum, num, den);
+      acc[S_SHARED] += sum != 0;
+      acc[S_REMOVED] += !keep;
+      acc[keep ? S_KEPT_READS : S_REMOVED_READS] += r;
+    }
+    const u64 word = __ballot(keep);
+    if (lane == 0 && in) kept[i >> 6] = word;
+  });
+  for (int k = 0; k < S_NWORDS; ++k) {
+    for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+    if (lane == 0 && acc[k]) atomicAdd(&sums[k], acc[k]);
+  }
+}
+
+// The claim, molecules_merge_kernel<true> with the marking pass's word in front: the molecule of a
+// slot whose bit is set in kept[] is claimed in `t` by the insert's rule with its reads as its count,
+// and reads[index] += them (set_take, as a downsample's survivor).  The keys and reads of the other
+// slots are not loaded.  Claims are summed per wave into the size word; the tally and total are not
+// this kernel's.
+__global__ void __launch_bounds__(WG) molecules_swapped_claim_kernel(Set t, const u64* __restrict__ keys,
+                                                                     const u64* __restrict__ cnt, int64_t n,
+                                                                     const u64* __restrict__ kept) {
+  int claims = 0;
+  for_each_item(n, [&](int64_t i, bool in) {
+    const bool mine = in && ((kept[i >> 6] >> (i & 63)) & 1);
+    u64 key, r;
+    counted_row(keys, cnt, i, mine, &key, &r);
+    if (key != EMPTY) claims += set_take(t, key, r);
+  });
+  add_claims(&t.words[W_SIZE], claims);
 }
 
 }  // namespace
@@ -1601,6 +1704,87 @@ int downsample(sct_molecules* dst, sct_molecules* src, u64 threshold, u64 seed, 
   return absorbed(dst, src, kept, kept, 0, (int64_t)kept_total, survivors, "downsample", s, s);
 }
 
+// ---- removing swapped molecules
+
+int swapped_check(sct_molecules* const* src, int64_t ns, int64_t k, const sct_molecules* dst, uint64_t num,
+                  uint64_t den) {
+  SCT_CHECK(src != nullptr && dst != nullptr, "molecule counter is NULL");
+  SCT_CHECK(ns >= 1 && ns <= sct::kSwappedMaxSamples, "remove swapped: %lld samples, outside [1, %d]", (long long)ns,
+            sct::kSwappedMaxSamples);
+  SCT_CHECK(k >= 0 && k < ns, "remove swapped: sample %lld outside [0, %lld)", (long long)k, (long long)ns);
+  SCT_CHECK(sct::swapped_params_ok(ns, num, den),
+            "remove swapped: the fraction %llu / %llu must have 1 <= num <= den <= 2^32 and 2 * num > den",
+            (unsigned long long)num, (unsigned long long)den);
+  for (int64_t t = 0; t < ns; ++t) SCT_CHECK(src[t] != nullptr, "molecule counter is NULL");
+  for (int64_t t = 0; t < ns; ++t) {
+    SCT_CHECK(src[t] != dst, "remove swapped: the target is sample %lld itself", (long long)t);
+    for (int64_t u = 0; u < t; ++u)
+      SCT_CHECK(src[u] != src[t], "remove swapped: samples %lld and %lld are the same counter", (long long)u,
+                (long long)t);
+  }
+  if (int rc = need_counted(dst); rc != SCT_OK) return rc;
+  for (int64_t t = 0; t < ns; ++t) {
+    if (int rc = need_counted(src[t]); rc != SCT_OK) return rc;
+    if (int rc = merge_check(dst, src[t]); rc != SCT_OK) return rc;
+  }
+  for (int64_t t = 0; t < ns; ++t)
+    SCT_CHECK(dst->device == src[t]->device,
+              "remove swapped: the counters live on devices %d and %d (merge each into a counter on one device first)",
+              dst->device, src[t]->device);
+  return SCT_OK;
+}
+
+// dst <- dst + the molecules of src[k] that the other samples do not take from it, on `s` (the
+// contract: include/sctools_hip.h).  All counters are counted and live on the device that is current.
+// The marking pass writes a bit per slot of src[k] and four sums into scratch; they are read back once,
+// and until then nothing of dst has changed.
+int swapped(sct_molecules* const* src, int64_t ns, int64_t k, sct_molecules* dst, u64 num, u64 den, uint64_t* tally,
+            hipStream_t s) {
+  sct_molecules* mine = src[k];
+  for (int64_t t = 0; t < ns; ++t) SCT_TRY(enter_read(src[t], s));  // SCT_E_RANGE for a sample that overflowed
+  const int64_t src_size = mine->size_bound;
+  u64 carried = 0;  // the reads of src[k] that never became molecules
+  for (int j = 0; j < 4; ++j) carried += mine->h_words[W_TALLY + j];
+  SCT_TRY(enter_read(dst, s));
+  Carve cv;
+  const size_t o_sums = cv.take(S_NWORDS * 8), o_kept = cv.take((size_t)mine->capacity / 8);
+  sct::StreamBlock blk(s);
+  SCT_HIP(blk.alloc(cv.size));
+  u64* sums = reinterpret_cast<u64*>(blk.bytes() + o_sums);
+  u64* kept = reinterpret_cast<u64*>(blk.bytes() + o_kept);
+  hipError_t e = hipMemsetAsync(sums, 0, S_NWORDS * 8, s);
+  if (e == hipSuccess && src_size > 0) {
+    ProbedTables others{};
+    int nothers = 0;
+    for (int64_t t = 0; t < ns; ++t)
+      if (t != k && src[t]->size_bound > 0)  // (an empty sample holds nothing to find)
+        others.of[nothers++] = {src[t]->t.keys, src[t]->t.cnt, src[t]->t.mask};
+    hipLaunchKernelGGL(molecules_swapped_mark_kernel, dim3(grid_for(mine->capacity, 4 * WG)), dim3(WG), 0, s,
+                       mine->t.keys, mine->t.cnt, mine->capacity, others, nothers, num, den, kept, sums);
+    e = hipGetLastError();
+  }
+  // (dst's read-back words are free between two read_words)
+  static_assert(S_NWORDS <= W_NWORDS, "the sums fit the read-back words");
+  if (e == hipSuccess) e = hipMemcpyAsync(dst->h_words, sums, S_NWORDS * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return sct::fail(SCT_E_HIP, "molecule remove swapped, marking: %s", hipGetErrorString(e));
+  const u64 shared = dst->h_words[S_SHARED], removed = dst->h_words[S_REMOVED];
+  const u64 removed_reads = dst->h_words[S_REMOVED_READS], kept_reads = dst->h_words[S_KEPT_READS];
+  const int64_t survivors = src_size - (int64_t)removed;
+  SCT_TRY(make_room(dst, dst->size_bound, survivors, "remove swapped", s));
+  if (tally) tally[0] = shared, tally[1] = removed, tally[2] = removed_reads;
+  if (survivors > 0)
+    hipLaunchKernelGGL(molecules_swapped_claim_kernel, dim3(grid_for(mine->capacity, 4 * WG)), dim3(WG), 0, s, dst->t,
+                       mine->t.keys, mine->t.cnt, mine->capacity, kept);
+  // src[k]'s tallies from its own device words (reads[] was the claim kernel's: nw = 0 here)
+  int rc = absorbed(dst, mine, mine->t.reads, mine->t.words, 0, (int64_t)(kept_reads + carried), survivors,
+                    "remove swapped", s, s);
+  for (int64_t t = 0; t < ns; ++t)
+    if (t != k)
+      if (int rl = leave(src[t], s); rc == SCT_OK) rc = rl;
+  return rc;
+}
+
 }  // namespace
 
 namespace {
@@ -1941,6 +2125,13 @@ extern "C" int sct_molecules_downsample_curve_host(sct_molecules* c, const uint6
   if (int rc = st.alloc(); rc != SCT_OK) return rc;
   return st.finish(curve_device(c, thresholds, (int)k, (u64)seed, st.dev<uint64_t>(0), st.dev<uint64_t>(1), s),
                    "molecule downsample curve");
+}
+
+extern "C" int sct_molecules_swapped(sct_molecules* const* src, int64_t s, int64_t k, sct_molecules* dst, uint64_t num,
+                                     uint64_t den, uint64_t* tally, void* stream) {
+  if (int rc = swapped_check(src, s, k, dst, num, den); rc != SCT_OK) return rc;
+  SCT_ON_DEVICE_OF(dst);
+  return swapped(src, s, k, dst, (u64)num, (u64)den, tally, sct::as_stream(stream));
 }
 
 // ---- counting molecules per feature: the rows with their feature, and the count matrix

@@ -77,6 +77,19 @@ __device__ __forceinline__ u64 find(const u64* __restrict__ keys, u64 mask, u64 
   return NO_SLOT;
 }
 
+// find() for a caller that issued the first load itself: `s` is the key's home slot, mix64(key) & mask,
+// and `k` what keys[s] showed.  A lane that probes several tables loads every home slot first and
+// resolves them afterwards, so that the loads are in flight together.
+__device__ __forceinline__ u64 find_from(const u64* __restrict__ keys, u64 mask, u64 key, u64 s, u64 k) {
+  for (u64 probe = 0; probe <= mask; ++probe) {
+    if (k == key) return s;
+    if (k == EMPTY) return NO_SLOT;
+    s = (s + 1) & mask;
+    k = keys[s];
+  }
+  return NO_SLOT;
+}
+
 // Equal keys of a wave merged: the lowest active lane holding a key is its `rep` and carries the
 // `count` of its copies, the others add nothing.  Called by every lane of the wave.  The leader is
 // one lane of 64, and saying so keeps the pass a branch: as selects it runs a percent slower on a

@@ -33,7 +33,11 @@ call beside an earlier library (resolve_step; profiles/ab_feature_resolve.jsonl)
 the same input: read_groups() for every method, tag_device with each set of columns beside
 update_features of the same reads, the host route pairs() + np.searchsorted + np.lexsort + np.unique
 with equal answers, and the updates, collapse, resolve and matrix beside an earlier library
-(groups_step; profiles/ab_read_groups.jsonl).
+(groups_step; profiles/ab_read_groups.jsonl).  Then removing swapped molecules: the molecules step's
+reads split over 2 and 4 counters with --hop of them moved to another sample, remove_swapped per
+sample and whole beside the merge of the same counters, the host route pairs() + np.unique +
+np.searchsorted with equal answers, and the existing calls beside an earlier library (swapped_step;
+profiles/ab_swapped.jsonl).
 
 Every step runs in a child process of its own under its own time limit; a step that fails ends
 the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>.json.
@@ -48,6 +52,7 @@ the run.  One short JSON line on stdout; the detail goes to profiles/count_<tag>
   python tools/bench_count.py --only downsample --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only resolve --hop 0.02 --parent-lib /path/to/earlier/libsctools_hip.so
   python tools/bench_count.py --only groups --hop 0.02 --parent-lib /path/to/earlier/libsctools_hip.so
+  python tools/bench_count.py --only swapped --hop 0.02 --parent-lib /path/to/earlier/libsctools_hip.so
 """
 import argparse
 import functools
@@ -62,7 +67,7 @@ sys.path.insert(0, ROOT)
 
 STEPS = {"counter_A": 420, "counter_B": 300, "tally": 300, "molecules": 420, "collapse": 600,
          "merge": 600, "matrix": 600, "calls": 600, "directional": 600, "downsample": 600,
-         "resolve": 900, "groups": 1100}  # seconds
+         "resolve": 900, "groups": 1100, "swapped": 1100}  # seconds
 MODES = {0: "none", 1: "wave_merge", 2: "lds_table"}
 HBM_BYTES_PER_S = 8e12
 
@@ -1902,6 +1907,268 @@ def groups_step(args):
     return out
 
 
+SWAPPED_PARENT_CALLS = GROUPS_PARENT_CALLS + ("sct_molecules_merge", "sct_molecules_downsample",
+                                               "sct_read_groups_create", "sct_read_groups_tag", "sct_read_groups_destroy")
+
+
+def _swapped_on_host(tables, num, den):
+    """The host route of removing swapped molecules: per sample (kept keys ascending, their reads,
+    [shared, removed, removed reads]) from every sample's (packed keys ascending, reads) -- np.unique over
+    all keys, np.searchsorted per sample, the judgement in Python integers where a product could pass
+    2^63 and in int64 otherwise."""
+    import numpy as np
+    keys = np.unique(np.concatenate([k for k, _ in tables]))
+    per = np.zeros((len(tables), keys.size), np.int64)
+    for t, (k, r) in enumerate(tables):
+        per[t, np.searchsorted(keys, k)] = r
+    total = per.sum(axis=0)
+    assert int(total.max()) * max(num, den) < 2 ** 63
+    out = []
+    for t, (k, r) in enumerate(tables):
+        others = (total - per[t])[np.searchsorted(keys, k)]
+        keep = r * (den - num) >= num * others
+        out.append((k[keep], r[keep], [int((others > 0).sum()), int((~keep).sum()), int(r[~keep].sum())]))
+    return out
+
+
+def swapped_step(args):
+    """Removing swapped molecules on the molecules step's reads as drawn, split over s = 2 and s = 4
+    counted counters: a molecule's reads go to the sample its key hashes to, and --hop of the reads to
+    another sample, drawn uniformly.  Per round and s: remove_swapped_device of every sample into an
+    empty 64-slot counter (the device time per sample, and their sum, the whole call), and the merge of
+    the same s counters into one empty counter as a yardstick, with the ratio to it; there is no pass
+    mark.  Once per s, the host route -- pairs(reads=True) of every counter, key packing, np.unique and
+    np.searchsorted -- whose kept molecules, reads and tallies must equal the device's.  With
+    --parent-lib, alternating within every round through the C ABI in this library and in that one: the
+    plain, counted and feature updates, the collapse, merge, downsample at 0.5, matrix, resolve, and
+    read groups (create and tag); they agree when the medians differ by no more than the min-max spread
+    of the parent's own rounds, and a call that does not is named in the summary.  Every round is one
+    line of the profile, the summary its last (profiles/ab_swapped.jsonl, or ab_swapped_<tag>.jsonl)."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    from sctools_amd import _lib, counting
+
+    nw, UL, n, hint, pool, inputs = _molecules_input(args)
+    dev = torch.device("cuda")
+    this, old = _lib.lib(), _parent_lib(args, SWAPPED_PARENT_CALLS)
+    di, du, dk = inputs["shuffled"]
+    del inputs
+    num, den = 4, 5
+    g = torch.Generator(device=dev).manual_seed(31)
+    mixed = (dk * -7046029254386353131) >> 33  # a molecule's hash: its home sample is this modulo s
+    hops = torch.rand(n, device=dev, generator=g) < args.hop
+    jump = torch.randint(1, 4, (n,), device=dev, generator=g)
+    name = "ab_swapped.jsonl" if args.tag == "run" else "ab_swapped_%s.jsonl" % args.tag
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    profile = open(os.path.join(ROOT, "profiles", name), "w")
+
+    def synced(call):
+        def go():
+            call()
+            torch.cuda.synchronize()
+        return _time_ms(go)
+
+    samples = {}
+    for s in (2, 4):
+        side = torch.where(hops, (mixed + 1 + jump % (s - 1)) % s, mixed % s)
+        made = []
+        for t in range(s):
+            at = side == t
+            ti, tu = di[at].contiguous(), du[at].contiguous()
+            mc = counting.MoleculeCounter(nw, UL, capacity_hint=max(64, hint // s), read_counts=True)
+            mc.update_device(ti.data_ptr(), tu.data_ptr(), ti.numel())
+            torch.cuda.synchronize()
+            made.append(mc)
+            del ti, tu, at
+        samples[s] = made
+        del side
+    del hops, jump, mixed, dk
+    torch.cuda.empty_cache()
+
+    def run_swapped(s, keep=False):
+        """({what: ms}, tallies[, the cleaned counters]) of one removal over the s samples"""
+        ms, tallies, cleaned = {}, [], []
+        for k, mc in enumerate(samples[s]):
+            into = counting.MoleculeCounter(nw, UL, capacity_hint=64, read_counts=True)
+            others = samples[s][:k] + samples[s][k + 1:]
+            got = {}
+            ms["s%d_sample%d" % (s, k)] = synced(lambda: got.update(t=mc.remove_swapped_device(others, into, num, den)))
+            tallies.append(got["t"].tolist())
+            cleaned.append(into)
+        ms["s%d_whole" % s] = sum(ms.values())
+        if not keep:
+            for c in cleaned:
+                c.close()
+        return (ms, tallies, cleaned) if keep else (ms, tallies)
+
+    def run_merge(s):
+        with counting.MoleculeCounter(nw, UL, capacity_hint=64, read_counts=True) as into:
+            def go():
+                for mc in samples[s]:
+                    into.merge_device(mc)
+            return synced(go)
+
+    # ---- the existing calls of both libraries through the C ABI (--parent-lib), on all n reads
+    vp = ctypes.c_void_p
+    nf = 4096
+    libs = {"this": this}
+    if old:
+        libs["parent"] = old
+    existing = []
+    if old:
+        df = _features_of(di, du, nf, nf)
+        o_final = torch.empty(n, dtype=torch.int64, device=dev)
+        o_status = torch.empty(n, dtype=torch.uint8, device=dev)
+        handles, outs = {}, {}
+        for lname, lib in libs.items():
+            hf, hc = vp(), vp()
+            assert lib.sct_molecules_create_features(nw, nf, 3, UL, hint, 1, -1, ctypes.byref(hf)) == 0
+            assert lib.sct_molecules_update_features(hf, vp(di.data_ptr()), vp(df.data_ptr()), vp(du.data_ptr()), n, None) == 0
+            assert lib.sct_molecules_create_counted(nw, 3, UL, hint, ctypes.byref(hc)) == 0
+            assert lib.sct_molecules_update(hc, vp(di.data_ptr()), vp(du.data_ptr()), n, None) == 0
+            nm = ctypes.c_int64(0)
+            tot, cap = ctypes.c_int64(0), ctypes.c_int64(0)
+            assert lib.sct_molecules_info(hf, ctypes.byref(nm), ctypes.byref(tot), ctypes.byref(cap)) == 0
+            handles[lname] = (hf, hc)
+            outs[lname] = {"collapsed": torch.empty(nw, dtype=torch.int64, device=dev),
+                           "resolved": torch.empty(nw, dtype=torch.int64, device=dev),
+                           "tally": torch.empty(4, dtype=torch.int64, device=dev),
+                           "indptr": torch.empty(nw + 1, dtype=torch.int64, device=dev),
+                           "feature": torch.empty(nm.value, dtype=torch.int32, device=dev),
+                           "values": torch.empty((3, nm.value), dtype=torch.int64, device=dev), "nmol": nm.value}
+
+        def run_update(lname, what):
+            lib, h = libs[lname], vp()
+            if what == "features":
+                assert lib.sct_molecules_create_features(nw, nf, 3, UL, hint, 1, -1, ctypes.byref(h)) == 0
+            else:
+                create = lib.sct_molecules_create_counted if what == "counted" else lib.sct_molecules_create
+                assert create(nw, 3, UL, hint, ctypes.byref(h)) == 0
+            try:
+                if what == "features":
+                    return synced(lambda: lib.sct_molecules_update_features(h, vp(di.data_ptr()), vp(df.data_ptr()),
+                                                                            vp(du.data_ptr()), n, None))
+                return synced(lambda: lib.sct_molecules_update(h, vp(di.data_ptr()), vp(du.data_ptr()), n, None))
+            finally:
+                lib.sct_molecules_destroy(h)
+
+        def run_call(lname, what):
+            lib, (hf, hc), o = libs[lname], handles[lname], outs[lname]
+            nnz, e, grp = ctypes.c_int64(0), vp(), vp()
+            status = []
+            try:
+                if what == "collapse":
+                    return synced(lambda: status.append(lib.sct_molecules_collapse(hf, vp(o["collapsed"].data_ptr()), None, None)))
+                if what == "resolve":
+                    return synced(lambda: status.append(lib.sct_molecules_resolve(
+                        hf, _lib.COLLAPSE_ONE_STEP, vp(o["resolved"].data_ptr()), vp(o["tally"].data_ptr()), None)))
+                if what == "matrix":
+                    v = o["values"]
+                    return synced(lambda: status.append(lib.sct_molecules_matrix(
+                        hf, vp(o["indptr"].data_ptr()), vp(o["feature"].data_ptr()), vp(v[0].data_ptr()),
+                        vp(v[1].data_ptr()), vp(v[2].data_ptr()), o["nmol"], ctypes.byref(nnz), None)))
+                if what in ("merge", "downsample"):
+                    assert lib.sct_molecules_create_counted(nw, 3, UL, 64, ctypes.byref(e)) == 0
+                    if what == "merge":
+                        return synced(lambda: status.append(lib.sct_molecules_merge(e, hc, None)))
+                    return synced(lambda: status.append(lib.sct_molecules_downsample(e, hc, 2 ** 31, 0, None)))
+                if what == "groups_create":
+                    return synced(lambda: status.append(lib.sct_read_groups_create(hf, _lib.COLLAPSE_ONE_STEP, 0,
+                                                                                   ctypes.byref(grp), None)))
+                assert lib.sct_read_groups_create(hf, _lib.COLLAPSE_ONE_STEP, 0, ctypes.byref(grp), None) == 0
+                return synced(lambda: status.append(lib.sct_read_groups_tag(
+                    grp, vp(di.data_ptr()), vp(df.data_ptr()), vp(du.data_ptr()), n, vp(o_final.data_ptr()),
+                    vp(o_status.data_ptr()), None, None, None)))
+            finally:
+                assert status == [0], (what, status)
+                if e:
+                    lib.sct_molecules_destroy(e)
+                if grp:
+                    lib.sct_read_groups_destroy(grp)
+
+        existing = [("update_%s" % w, lambda lname, w=w: run_update(lname, w)) for w in ("plain", "counted", "features")]
+        existing += [(w, lambda lname, w=w: run_call(lname, w))
+                     for w in ("collapse", "merge", "downsample", "matrix", "resolve", "groups_create", "groups_tag")]
+
+    # warm-up: every call once
+    facts = {}
+    for s in samples:
+        facts[s] = run_swapped(s)[1]
+        run_merge(s)
+    for lname in libs:
+        for _, call in existing:
+            call(lname)
+    rounds = []
+    for r in range(args.rounds):
+        row = {"what": "swapped", "round": r}
+        for s in samples:
+            ms, tallies = run_swapped(s)
+            assert tallies == facts[s], (tallies, facts[s])  # every round: the same numbers
+            row.update({k + "_ms": round(v, 3) for k, v in ms.items()})
+            row["s%d_merge_ms" % s] = round(run_merge(s), 3)
+        order = list(libs) if r % 2 == 0 else list(libs)[::-1]
+        for what, call in existing:
+            for lname in order:
+                row["%s_%s_ms" % (what, lname)] = round(call(lname), 3)
+        rounds.append(row)
+        profile.write(json.dumps(row, sort_keys=True) + "\n")
+        profile.flush()
+    out = {"n": n, "nw": nw, "umi_length": UL, "hop": args.hop, "min_fraction": [num, den], "rounds": args.rounds,
+           "parent_lib": bool(old), "measured": True}
+    for key in rounds[0]:
+        if key.endswith("_ms"):
+            v = [row[key] for row in rounds]
+            out[key] = {"median": round(float(np.median(v)), 3), "min": min(v), "max": max(v)}
+    for s in samples:
+        out["s%d" % s] = {"molecules": [len(mc) for mc in samples[s]], "capacity": [mc.info()["capacity"] for mc in samples[s]],
+                          "tally": facts[s]}
+        out["s%d_whole_over_merge" % s] = round(out["s%d_whole_ms" % s]["median"] / out["s%d_merge_ms" % s]["median"], 3)
+    if old:
+        out["vs_parent"] = {what: _vs_parent(out["%s_this_ms" % what], out["%s_parent_ms" % what]) for what, _ in existing}
+        out["apart_from_parent"] = sorted(what for what, v in out["vs_parent"].items() if not v["agree"])
+        o, p = outs["this"], outs["parent"]
+        out["abi_outputs_equal"] = bool(torch.equal(o["collapsed"], p["collapsed"]) and torch.equal(o["resolved"], p["resolved"])
+                                        and torch.equal(o["tally"], p["tally"]) and torch.equal(o["indptr"], p["indptr"]))
+        for lname, lib in libs.items():
+            for h in handles[lname]:
+                lib.sct_molecules_destroy(h)
+        del outs
+    # the host route, once per s, and its answers beside the device's
+    umi_bits = 3 * UL
+    for s in samples:
+        host, tables = {}, []
+        def fetch():
+            for mc in samples[s]:
+                index, umi, reads = mc.pairs(reads=True)
+                tables.append(((index.astype(np.int64) << umi_bits) | umi.view(np.int64), reads))
+        host["pairs_ms"] = round(_time_ms(fetch), 1)
+        host["numpy_ms"] = round(_time_ms(lambda: host.update(a=_swapped_on_host(tables, num, den))), 1)
+        answers = host.pop("a")
+        host["total_ms"] = round(host["pairs_ms"] + host["numpy_ms"], 1)
+        _, tallies, cleaned = run_swapped(s, keep=True)
+        equal = tallies == [a[2] for a in answers]
+        for mc, (keys, reads, _) in zip(cleaned, answers):
+            index, umi, got = mc.pairs(reads=True)
+            equal = equal and np.array_equal((index.astype(np.int64) << umi_bits) | umi.view(np.int64), keys) \
+                and np.array_equal(got, reads)
+            mc.close()
+        host["equals_device"] = bool(equal)
+        host["over_device_whole"] = round(host["total_ms"] / out["s%d_whole_ms" % s]["median"], 1)
+        out["s%d_host_route_once" % s] = host
+        del tables, answers
+    for made in samples.values():
+        for mc in made:
+            mc.close()
+    profile.write(json.dumps(out, sort_keys=True) + "\n")
+    profile.close()
+    assert all(out["s%d_host_route_once" % s]["equals_device"] for s in samples), "the device and the host route disagree"
+    if old:
+        assert out["abi_outputs_equal"], "an existing call's outputs differ from --parent-lib"
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tag", default="run")
@@ -1918,13 +2185,14 @@ def main():
     ap.add_argument("--umi-error", type=float, default=0.01,
                     help="directional step: the probability that a UMI base of a read is substituted")
     ap.add_argument("--hop", type=float, default=0.02,
-                    help="resolve and groups steps: the share of the reads moved to another feature, drawn uniformly")
+                    help="resolve and groups steps: the share of the reads moved to another feature, drawn uniformly; "
+                         "swapped step: the share moved to another sample")
     ap.add_argument("--only", nargs="+", choices=sorted(STEPS), help="launch only these steps")
     args = ap.parse_args()
     if args.step:
         whole = {"molecules": molecules_step, "collapse": collapse_step, "merge": merge_step, "matrix": matrix_step,
                  "calls": calls_step, "directional": directional_step, "downsample": downsample_step,
-                 "resolve": resolve_step, "groups": groups_step}
+                 "resolve": resolve_step, "groups": groups_step, "swapped": swapped_step}
         if args.step in whole:
             res = whole[args.step](args)
         else:
