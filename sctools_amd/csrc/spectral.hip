@@ -489,8 +489,19 @@ typedef short v2s_t __attribute__((ext_vector_type(2)));
 //     (added after stage 1) and sum_{R' != 0} F(R')^2 = 4 sum_R G_R^2 - F(0)^2.  So every
 //     (P', Q') adds F(0)^2 to weight w and 4 sum G_R^2 - F(0)^2 to weight w + 1: five stage-2
 //     transforms per slice (4 planes + the sum), no exchange between planes.
-//   Per plane 8 + 16 MFMAs (one N-tile nt at a time: its two M-tiles' chains interleave), per
-//     slice 4 * 8 + 5 * 16 = 112 (94 issued: see H below), and the next plane's loads are in
+//   Half step: stage 2 is H_2 x H_32 with column bit 11 outermost (M-tile t out, K-step ks in):
+//     the M-tiles are U + V and U - V for U = H_32 B[0], V = H_32 B[1].  Bits (10, 11) are one
+//     digit of value nt + 2 t: for nt = 1 it is 1 or 3, non-zero either way, so both M-tiles fall
+//     into one bin, which needs only (U + V)^2 + (U - V)^2 = 2 (U^2 + V^2).  N-tile 1 therefore
+//     stops at U and V -- two chains of two MFMAs on the +H_32 block (high and low byte of one
+//     K-step) instead of two of four -- and its squares count twice (integers throughout: the
+//     histogram is bit for bit what the full butterfly gives).  N-tile 0 (digit 0 or 2: two
+//     bins) keeps the butterfly.
+//   Per plane 8 + 16 MFMAs by the tiling (one N-tile nt at a time, its two chains interleaved),
+//     per slice 4 * 8 + 5 * 16 = 112; 79 issued: the half step takes 4 from each of the five
+//     N-tile-1 calls and equal H blocks 13 more (see H below: 5 in N-tile 0, 8 in stage 1).  Stage 1 of
+//     both N-tiles runs before either stage 2, so N-tile 1 waits as 16 VGPRs of int16 pairs,
+//     not as 32 of shared first K-step + 8 of bytes.  The next plane's loads are in
 //     flight while this one is transformed -- across slices too: the next slice's first plane
 //     is loaded during this slice's last plane and the plane-sum transforms.
 // Weight of (P', Q', R'): digits (0, 1), (2, 3), (4, 5) = l & 3, (l >> 2) & 3, l >> 4 (thread
@@ -550,21 +561,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
                        512 * ((lane >> 2) & 1);
   const int gw = blockIdx.x * 4 + wave, GW = gridDim.x * 4;
   const int ub = (int)((int64_t)nslices * gw / GW), ue = (int)((int64_t)nslices * (gw + 1) / GW);
-  // the squares of the two interleaved M-tiles go to separate sums (two dependency chains per
-  // weight instead of one), added at the flush.  Chain: both go to accB -- accB2's 8 VGPRs are
-  // what the two 64 H blocks take, and the kernel stays at 168 without scratch
-  unsigned long long accA[4] = {0, 0, 0, 0}, accB[4] = {0, 0, 0, 0}, accB2[4] = {0, 0, 0, 0};
+  // accA: the plane-sum transform's squares (its N-tile 1 as (2 U) U, see stage2); accB: the
+  // planes' N-tile 0, both M-tiles; Bn: the planes' N-tile 1, U^2 + V^2 at weight index wi (entry
+  // wi + 1), doubled at the flush.  6 VGPRs where the parent held 8 of a second N-tile-0 sum.
+  unsigned long long accA[4] = {0, 0, 0, 0}, accB[4] = {0, 0, 0, 0}, Bn[3] = {0, 0, 0};
   int cur_w = -1;
   auto flush = [&]() {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (accA[k]) atomicAdd(&bins[cur_w + wt_thread + k], accA[k]);
-      const unsigned long long b = 4 * (accB[k] + accB2[k]) - accA[k];
+      const unsigned long long n1 = k ? 2 * Bn[k - 1] : 0;  // N-tile 1: entries 1..3
+      const unsigned long long b = 4 * (accB[k] + n1) - accA[k];
       if (b) atomicAdd(&bins[cur_w + wt_thread + k + 1], b);
       accA[k] = 0;
       accB[k] = 0;
-      accB2[k] = 0;
     }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Bn[k] = 0;
   };
   // d[2 mt + ks]: M-tile mt (column bit 11), K-step ks (column bit 10)
   auto load_plane = [&](int sl, int R, v4i_t* dst) {
@@ -573,18 +586,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
     for (int k = 0; k < 4; ++k)
       dst[k] = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(p + 1024 * k));
   };
-  // stage 2 of N-tile nt from its byte splits (Bl / Bh [K-step]), both M-tiles' chains
-  // interleaved, then their squares (M-tile 0 into acc, 1 into acc2); chain_c: the high bytes
-  // as 64 H against 4 h instead of the shift (the caller's |v| <= 64 kChainMaxM)
-  auto stage2 = [&](const v4i_t* Bl, const v4i_t* Bh, auto nt_c, auto chain_c, unsigned long long* acc,
-                    unsigned long long* acc2) {
+  // stage 2 of N-tile nt from its byte splits (Bl / Bh [K-step]), two chains interleaved, then
+  // their squares into acc; chain_c: the high bytes as 64 H against 4 h instead of the shift (the
+  // caller's |v| <= 64 kChainMaxM).
+  //   nt = 0: the chains are the two M-tiles, digit (10, 11) = 0 and 2: c[t] = H_64 rows 32 t.
+  //   nt = 1: the M-tiles would be digit values 1 and 3, both non-zero: one weight, one bin.  With
+  //     U = H_32 B[0], V = H_32 B[1] they are U + V and U - V, and the bin needs only
+  //     (U + V)^2 + (U - V)^2 = 2 (U^2 + V^2): the last butterfly (column bit 11) is left out.
+  //     c[ks] = H_32 B[ks], each a chain of two MFMAs (high, low byte of its own K-step) on the
+  //     +H_32 block alone; row i and the lane weigh as before.  sum_c: acc is Bn, indexed by wi,
+  //     the flush doubles it; else the factor 2 goes into the square, (2 U) U at entry wi + 1.
+  auto stage2 = [&](const v4i_t* Bl, const v4i_t* Bh, auto nt_c, auto chain_c, auto sum_c,
+                    unsigned long long* acc) {
     constexpr int nt = decltype(nt_c)::value;
+    constexpr bool chain = decltype(chain_c)::value, half = nt == 1;
     v16i_t c[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int i = 0; i < 16; ++i) c[t][i] = 0;
-    if constexpr (decltype(chain_c)::value) {
+    // nt = 1: chain t takes K-step ks = t alone
+    if constexpr (chain) {
       v4i_t Bh4[2];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
@@ -594,12 +616,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
-          c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(H64[t][ks], Bh4[ks], c[t], 0, 0, 0);
+          if (!half || t == ks)
+            c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(half ? H64[0][0] : H64[t][ks], Bh4[ks], c[t], 0, 0, 0);
     } else {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(H[t][ks], Bh[ks], c[t], 0, 0, 0);
+        for (int t = 0; t < 2; ++t)
+          if (!half || t == ks)
+            c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(half ? H[0][0] : H[t][ks], Bh[ks], c[t], 0, 0, 0);
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -608,20 +633,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int t = 0; t < 2; ++t) c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(H[t][ks], Bl[ks], c[t], 0, 0, 0);
+      for (int t = 0; t < 2; ++t)
+        if (!half || t == ks)
+          c[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(half ? H[0][0] : H[t][ks], Bl[ks], c[t], 0, 0, 0);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       // digits (6, 7) = i & 3, (8, 9) = i >> 2, (10, 11) = nt + 2 M-tile
       constexpr int w0 = digit_weight_c((uint32_t)nt), w1 = digit_weight_c((uint32_t)(nt | 2));
+      static_assert(!half || (w0 == 1 && w1 == 1), "N-tile 1: both M-tiles in one bin");
+      constexpr bool sum = half && decltype(sum_c)::value, dbl = half && !sum;
       const int wi = digit_weight_c((uint32_t)(i & 3)) + digit_weight_c((uint32_t)(i >> 2));
 #ifdef SCT_TILE_SQ_ABL
       // timing-only ablation (wrong results): the squares replaced by one full-rate XOR, the floor
       // of any exact F^2 accumulate (ab_tile_squares_r06)
-      acc[wi + w0] ^= (uint32_t)c[0][i];
-      acc2[wi + w1] ^= (uint32_t)c[1][i];
+      acc[wi + (sum ? 0 : w0)] ^= (uint32_t)c[0][i];
+      acc[wi + (sum ? 0 : w1)] ^= (uint32_t)c[1][i];
 #else
-      acc[wi + w0] += (unsigned long long)((int64_t)c[0][i] * c[0][i]);
-      acc2[wi + w1] += (unsigned long long)((int64_t)c[1][i] * c[1][i]);
+      acc[wi + (sum ? 0 : w0)] += (unsigned long long)((int64_t)(dbl ? 2 * c[0][i] : c[0][i]) * c[0][i]);
+      acc[wi + (sum ? 0 : w1)] += (unsigned long long)((int64_t)(dbl ? 2 * c[1][i] : c[1][i]) * c[1][i]);
 #endif
     }
   };
@@ -669,7 +698,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
 #pragma unroll
       for (int k = 0; k < 4; ++k) d[k] = dn[k];
       if (R < 3 || more) load_plane(R < 3 ? s : s_next, R < 3 ? R + 1 : 0, dn);
-      auto ntile = [&](auto nt_c) {
+      // stage 1 of both N-tiles first, down to their int16 pairs: N-tile 1's 16 VGPRs of pairs
+      // wait through N-tile 0's stage 2 instead of the 32 of the shared first K-step + 8 of bytes
+      uint32_t pr[2][2][8];
+      auto stage1 = [&](auto nt_c) {
         constexpr int nt = decltype(nt_c)::value;
         v16i_t c1[2];
 #pragma unroll
@@ -681,30 +713,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
 #pragma unroll
           for (int mt = 0; mt < 2; ++mt)
             c1[mt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(d[2 * mt + ks], H[nt][ks], c1[mt], 0, 0, 0);
-        v4i_t Bl[2], Bh[2];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
-          uint32_t pr[8];
-          pairs16(c1[mt], pr);
+          pairs16(c1[mt], pr[nt][mt]);
 #pragma unroll
           for (int k = 0; k < 8; ++k)
             csp[nt][mt][k] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(v2s_t, csp[nt][mt][k]) +
-                                                              __builtin_bit_cast(v2s_t, pr[k]));
-          split16(pr, Bl[mt], Bh[mt]);
+                                                              __builtin_bit_cast(v2s_t, pr[nt][mt][k]));
         }
-        stage2(Bl, Bh, nt_c, std::bool_constant<Chain>(), accB, Chain ? accB : accB2);
+      };
+      auto ntile = [&](auto nt_c) {
+        constexpr int nt = decltype(nt_c)::value;
+        v4i_t Bl[2], Bh[2];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) split16(pr[nt][mt], Bl[mt], Bh[mt]);
+        stage2(Bl, Bh, nt_c, std::bool_constant<Chain>(), std::true_type(), nt ? Bn : accB);
         __builtin_amdgcn_sched_barrier(0);
       };
+      stage1(std::integral_constant<int, 1>());
+      stage1(std::integral_constant<int, 0>());
+      __builtin_amdgcn_sched_barrier(0);
       ntile(std::integral_constant<int, 0>());
       ntile(std::integral_constant<int, 1>());
     }
     v4i_t Bl[2], Bh[2];
     split16(csp[0][0], Bl[0], Bh[0]);
     split16(csp[0][1], Bl[1], Bh[1]);
-    stage2(Bl, Bh, std::integral_constant<int, 0>(), std::false_type(), accA, accA);
+    stage2(Bl, Bh, std::integral_constant<int, 0>(), std::false_type(), std::false_type(), accA);
     split16(csp[1][0], Bl[0], Bh[0]);
     split16(csp[1][1], Bl[1], Bh[1]);
-    stage2(Bl, Bh, std::integral_constant<int, 1>(), std::false_type(), accA, accA);
+    stage2(Bl, Bh, std::integral_constant<int, 1>(), std::false_type(), std::false_type(), accA);
   }
   if (cur_w >= 0) flush();
   __syncthreads();
