@@ -23,9 +23,8 @@
 // Work decomposition
 //   Unordered pairs i<j are covered by items (row block r of RB=256 queries,
 //   column chunk c of CB=32*CT codes), enumerated chunk-major: chunk c holds rows
-//   r < R(c) = ceil((min((c+1)CB, n) - 1) / RB).  A launch counts any item range
-//   [begin, end); each workgroup takes a contiguous sub-range, so it loads a chunk
-//   into LDS once and reuses it for every row block of that chunk it visits.
+//   r < R(c) = ceil((min((c+1)CB, n) - 1) / RB).  A launch sweeps any item range
+//   [begin, end) by the schedule stated above the sweep_* steps below.
 //
 // Per (query lane, group of 32 codes):
 //   NPP ds_read_b64 select the lane's {s0,s1} planes (the lane's nibble is the LDS
@@ -34,9 +33,7 @@
 //   distances, and counts[m] += popcount(AND_{b in m} d_b) for m = 1..2*NPP
 //   (v_bcnt_u32_b32 accumulates in place).  sct_counts_to_hist inverts the counts.
 //
-// Close pairs (sct_allpairs_close_pairs): the same sweep over a SUBSETS table with the counting
-// replaced by the threshold near = [distance <= max_d] of close_pairs_mask.h; only lanes with a
-// set bit name their pairs (allpairs_close_kernel below).
+// Close pairs (sct_allpairs_close_pairs): the same sweep, naming the pairs within max_d.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -215,6 +212,19 @@ __device__ __forceinline__ void count_mom(const uint32_t (&d)[4], uint32_t (&cnt
   bcnt_acc(cnt[12], p7 & d[3]);              // 15
 }
 
+// ---------------------------------------------------------------- the pair sweep's schedule
+// The schedule of allpairs_count_kernel and allpairs_close_kernel: each has its own loops over pulls and over
+// a pull's items, and its own per-pull and per-item work between the steps.  The close kernel calls the
+// steps below; the count kernel still has them written out (see there).
+//   Items are chunk-major (file header): item t is (chunk c, row block r < R(c)), t + 1 is (c, r + 1) or
+//     (c + 1, 0); lane tid of the workgroup owns row r * RB + tid.
+//   A pull takes the workgroup `grab` consecutive items off a device-scope queue word (zeroed on the stream
+//     before every launch); the pull that reaches item_end is cut there, one that starts at or past it ends
+//     the workgroup.
+//   The tile holds one column chunk and is restaged only when an item's chunk is not the one loaded: at a
+//     chunk seam, inside or between pulls, or after the kernel used the tile as scratch.
+//   sweep_pull and sweep_stage hold barriers: all lanes call them, under workgroup-uniform control flow.
+//     The other steps are per lane.
 struct ItemCursor {
   int64_t c, r;
 };
@@ -228,6 +238,48 @@ __device__ __forceinline__ ItemCursor locate_item(int64_t t, int64_t K, int64_t 
   while (c > 0 && K * c * (c + 1) / 2 > t) --c;
   while (c < nchunks - 1 && K * (c + 1) * (c + 2) / 2 <= t) ++c;
   return {c, t - K * c * (c + 1) / 2};
+}
+
+// Pull: the first item of the workgroup's next `grab` (s_grab: a word of the kernel's LDS)
+__device__ __forceinline__ int64_t sweep_pull(int64_t& s_grab, int64_t item_begin, int64_t grab,
+                                              unsigned long long* __restrict__ queue) {
+  __syncthreads();  // everyone is done with s_grab (and with the tile)
+  if (threadIdx.x == 0)
+    s_grab = item_begin + (int64_t)__hip_atomic_fetch_add(queue, (unsigned long long)grab, __ATOMIC_RELAXED,
+                                                           __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  return s_grab;
+}
+
+// Stage: column chunk c of the table into the LDS tile (the kernel keeps which chunk is loaded)
+template <class Gm>
+__device__ __forceinline__ void sweep_stage(uint4* tile, const uint4* __restrict__ table, int64_t c) {
+  const int tid = threadIdx.x;
+  __syncthreads();  // previous chunk no longer read
+  const uint4* src = table + c * Gm::TILE;
+#pragma unroll
+  for (int k = 0; k < Gm::TILE / RB; ++k) tile[k * RB + tid] = src[k * RB + tid];
+  if constexpr (Gm::TILE % RB != 0) {
+    const int k = Gm::TILE / RB * RB + tid;
+    if (k < Gm::TILE) tile[k] = src[k];
+  }
+  __syncthreads();
+}
+
+// Advance: the cursor past its item (last_rows = R(last chunk))
+__device__ __forceinline__ void sweep_advance(ItemCursor& cur, int64_t K, int64_t nchunks, int64_t last_rows) {
+  const int64_t rows_c = (cur.c == nchunks - 1) ? last_rows : (cur.c + 1) * K;
+  if (++cur.r >= rows_c) cur = {cur.c + 1, 0};
+}
+
+// row i's query (`live` = false: the prefetch past a pull's last item), and whether item (c, r) needs
+// pair_mask: it touches the diagonal or the tail of the codes
+__device__ __forceinline__ uint64_t sweep_query(const uint64_t* __restrict__ codes, int64_t i, int64_t n, bool live) {
+  return (live && i < n) ? codes[i] : 0ull;
+}
+template <class Gm>
+__device__ __forceinline__ bool sweep_masked(int64_t c, int64_t r, int64_t n) {
+  return ((r + 1) * RB > c * Gm::CB) || (c * Gm::CB + Gm::CB > n);
 }
 
 // valid-pair mask of the 32 codes j0..j0+31 for row i: i < j < n (and i < n)
@@ -394,9 +446,10 @@ void allpairs_count_kernel(const uint64_t* __restrict__ codes,
   // (flush_items <= 0xFFFFFFFF / CB; the host may pass less to exercise the path)
   int64_t since_flush = 0;
 
-  // Dynamic schedule: each workgroup pulls `grab` consecutive items at a time from a
-  // device-scope counter (zeroed by a memset node before every launch); consecutive
-  // items share a column chunk, so the LDS tile is reloaded only at chunk seams.
+  // The schedule above with its steps written out, as before they were cut for the close kernel: with
+  // sweep_pull, sweep_stage and sweep_query called here the tile loops compile to the same instructions,
+  // yet the 16-base kernels ran 3-4% slower (profiles/ab_pair_sweep.jsonl); sweep_advance and
+  // sweep_masked also reorder those loops.  A change to a step is made here too.
   for (;;) {
     __syncthreads();  // everyone is done with s_grab (and, below, with the tile)
     if (tid == 0)
@@ -541,45 +594,25 @@ __global__ __launch_bounds__(RB) void allpairs_close_kernel(const uint64_t* __re
   const int64_t last_rows = ((n - 1) + RB - 1) / RB;  // R(last chunk)
   int64_t loaded = -1;
 
-  // the count kernel's schedule: `grab` consecutive items per pull, the tile reloaded at chunk seams
   for (;;) {
-    __syncthreads();  // everyone is done with s_grab (and, below, with the tile)
-    if (tid == 0)
-      s_grab = item_begin + (int64_t)__hip_atomic_fetch_add(queue, (unsigned long long)grab,
-                                                             __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const int64_t t0 = s_grab;
+    const int64_t t0 = sweep_pull(s_grab, item_begin, grab, queue);
     if (t0 >= item_end) break;
     const int64_t t1 = t0 + grab < item_end ? t0 + grab : item_end;
     ItemCursor cur = locate_item(t0, Gm::K, nchunks);
     int64_t i = cur.r * RB + tid;
-    uint64_t q = i < n ? codes[i] : 0ull;
+    uint64_t q = sweep_query(codes, i, n, true);
     for (int64_t t = t0; t < t1; ++t) {
       const int64_t c = cur.c, r = cur.r;
       if (c != loaded) {
-        __syncthreads();  // previous chunk no longer read
-        const uint4* src = table + c * Gm::TILE;
-#pragma unroll
-        for (int k = 0; k < Gm::TILE / RB; ++k) tile[k * RB + tid] = src[k * RB + tid];
-        if constexpr (Gm::TILE % RB != 0) {
-          const int k = Gm::TILE / RB * RB + tid;
-          if (k < Gm::TILE) tile[k] = src[k];
-        }
-        __syncthreads();
+        sweep_stage<Gm>(tile, table, c);
         loaded = c;
       }
-      const int64_t rows_c = (c == nchunks - 1) ? last_rows : (c + 1) * Gm::K;
-      if (++cur.r >= rows_c) {
-        cur.c += 1;
-        cur.r = 0;
-      }
+      sweep_advance(cur, Gm::K, nchunks, last_rows);
       const int64_t i_next = cur.r * RB + tid;
-      const uint64_t q_next = (t + 1 < t1 && i_next < n) ? codes[i_next] : 0ull;
+      const uint64_t q_next = sweep_query(codes, i_next, n, t + 1 < t1);
       const int64_t j0 = c * Gm::CB;
-      const bool masked = ((r + 1) * RB > j0) || (j0 + Gm::CB > n);
       uint32_t di[4] = {0, 0, 0, 0};  // row i's pairs per distance in this item
-      if (masked)
+      if (sweep_masked<Gm>(c, r, n))
         close_item<NPP, true>(tile, q, i, j0, n, sel, o, di);
       else
         close_item<NPP, false>(tile, q, i, j0, n, sel, o, di);
@@ -889,7 +922,8 @@ struct sct_allpairs_plan {
   int64_t cb = 0;
   int64_t nchunks = 0;
   int64_t items = 0;
-  int grid = 0;
+  int cus = 0;   // compute units of `device`
+  int grid = 0;  // persistent grid of the count kernel (fixed at plan creation)
   uint64_t* d_codes = nullptr;
   uint64_t* d_sorted = nullptr;  // MOMENTS: the codes sorted (rows of a wave share high bases)
   void* d_sort_tmp = nullptr;
@@ -972,19 +1006,36 @@ struct CountKernels {
   }
 };
 
+// A persistent launch on the plan's queue: every workgroup of kernel `fn` resident (CUs x its
+// occupancy), pulling items off the queue word.  resident_grid sizes that grid; persistent_grid
+// readies a launch over `items` items on `s`: it sizes `sized` if the plan has not yet (once per
+// plan and kernel), zeroes the queue word, and gives min(sized, items) workgroups.
+template <class Fn>
+int resident_grid(const sct_allpairs_plan* p, Fn fn) {
+  int per_cu = 0;
+  if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RB, 0) != hipSuccess || per_cu <= 0)
+    per_cu = 4;
+  return p->cus * per_cu;
+}
+template <class Fn>
+int persistent_grid(sct_allpairs_plan* p, int& sized, Fn fn, int64_t items, hipStream_t s, int* grid) {
+  if (sized <= 0) sized = resident_grid(p, fn);
+  SCT_HIP(hipMemsetAsync(p->d_queue, 0, sizeof(unsigned long long), s));
+  *grid = (int)std::min<int64_t>(sized, items);
+  return SCT_OK;
+}
+
 template <int NPP>
 int launch_count(sct_allpairs_plan* p, int64_t b, int64_t e, uint64_t* d_counts, int grid,
                  hipStream_t s) {
   auto fn = CountKernels<NPP>::get(p->variant, p->scheme);
   if (!fn) return sct::fail(SCT_E_INVALID, "MOMENTS scheme needs 16-base codes");
-  if (grid <= 0) grid = p->grid;
-  const int64_t total = e - b;
-  if (grid > total) grid = (int)total;
+  int sized = grid > 0 ? grid : p->grid;  // (a caller's grid holds for this launch only)
   SCT_CHECK(p->grab > 0 && p->grab * p->cb < 0xFFFFFFFFLL, "grab too large");
   // a lane adds at most cb pairs per item to each u32 counter: flush before 2^32
   int64_t flush = 0xFFFFFFFFLL / p->cb - p->grab;
   if (p->flush_items > 0 && p->flush_items < flush) flush = p->flush_items;
-  SCT_HIP(hipMemsetAsync(p->d_queue, 0, sizeof(unsigned long long), s));
+  SCT_TRY(persistent_grid(p, sized, fn, e - b, s, &grid));
   const uint64_t* codes = p->d_sorted ? p->d_sorted : p->d_codes;
   hipEvent_t t0 = p->timer.start(s);
   hipLaunchKernelGGL(fn, dim3(grid), dim3(RB), 0, s, codes, p->d_table, p->n, p->nchunks, b, e,
@@ -995,13 +1046,8 @@ int launch_count(sct_allpairs_plan* p, int64_t b, int64_t e, uint64_t* d_counts,
 }
 
 template <int NPP>
-int occupancy_grid(int cus, int variant, int scheme) {
-  int per_cu = 0;
-  auto fn = CountKernels<NPP>::get(variant, scheme);
-  if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RB, 0) != hipSuccess ||
-      per_cu <= 0)
-    per_cu = 4;
-  return cus * per_cu;  // persistent: every workgroup resident, pulling from the queue
+int count_grid(const sct_allpairs_plan* p) {
+  return resident_grid(p, CountKernels<NPP>::get(p->variant, p->scheme));
 }
 
 #define SCT_NPP_SWITCH(npp, FN, ...)     \
@@ -1025,9 +1071,9 @@ int occupancy_grid(int cus, int variant, int scheme) {
     default: break;                      \
   }
 
-int grid_for(int npp, int cus, int variant, int scheme) {
-  SCT_NPP_SWITCH(npp, occupancy_grid, cus, variant, scheme);
-  return cus * 4;
+int grid_for(const sct_allpairs_plan* p) {
+  SCT_NPP_SWITCH(p->npp, count_grid, p);
+  return p->cus * 4;
 }
 
 int dispatch_count(sct_allpairs_plan* p, int64_t b, int64_t e, uint64_t* d, int grid,
@@ -1036,19 +1082,12 @@ int dispatch_count(sct_allpairs_plan* p, int64_t b, int64_t e, uint64_t* d, int 
   return sct::fail(SCT_E_RANGE, "unsupported npp %d", p->npp);
 }
 
-// the close-pairs kernel over items [b, e) of a SUBSETS plan: a persistent grid on the plan's queue
+// the close-pairs kernel over items [b, e) of a SUBSETS plan
 template <int NPP>
 int launch_close(sct_allpairs_plan* p, int64_t b, int64_t e, int max_d, const CloseOut& o, hipStream_t s) {
   auto fn = allpairs_close_kernel<NPP>;
-  if (p->close_grid <= 0) {
-    int cus = 0, per_cu = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || cus <= 0)
-      cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RB, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
-    p->close_grid = cus * per_cu;
-  }
-  const int grid = (int)std::min<int64_t>(p->close_grid, e - b);
-  SCT_HIP(hipMemsetAsync(p->d_queue, 0, sizeof(unsigned long long), s));
+  int grid = 0;
+  SCT_TRY(persistent_grid(p, p->close_grid, fn, e - b, s, &grid));
   hipLaunchKernelGGL(fn, dim3(grid), dim3(RB), 0, s, (const uint64_t*)p->d_codes, (const uint4*)p->d_table, p->n,
                      p->nchunks, b, e, p->grab, p->d_queue, max_d, o);
   SCT_LAUNCH_CHECK();
@@ -1178,16 +1217,15 @@ extern "C" int sct_allpairs_plan_create_ex2(const uint64_t* d_codes, int64_t n, 
     return cleanup(sct::fail(SCT_E_INVALID, "SPECTRAL scheme needs code_bits in 29..32 (got %d) "
                              "and n <= 1e8", code_bits));
   p->scheme = scheme == SCT_ALLPAIRS_AUTO ? auto_scheme(p->npp, n) : scheme;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess ||
-      cus <= 0)
-    cus = 256;
+  if (hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess ||
+      p->cus <= 0)
+    p->cus = 256;
   if (p->scheme == SCT_ALLPAIRS_SPECTRAL) {
     // items = the 4096 transform slices; no selection table
     p->ncounts = sct_spectral::kNCounts;
     p->items = n >= 2 ? sct_spectral::kSlices : 0;
     p->spec.distinct = (flags & SCT_ALLPAIRS_DISTINCT) != 0;
-    const int rc = sct_spectral::create(p->spec, p->d_codes, n, chunk_knob, cus,
+    const int rc = sct_spectral::create(p->spec, p->d_codes, n, chunk_knob, p->cus,
                                         (unsigned)probe[1], (unsigned)probe[2]);
     if (rc != SCT_OK) return cleanup(rc);
     p->spec.timer = &p->timer;
@@ -1252,7 +1290,7 @@ extern "C" int sct_allpairs_plan_create_ex2(const uint64_t* d_codes, int64_t n, 
       p->variant = vv;
   }
 #endif
-  p->grid = grid_for(p->npp, cus, p->variant, p->scheme);
+  p->grid = grid_for(p);
   p->flush_items = sct::tune(SCT_TUNE_ALLPAIRS_FLUSH_ITEMS, 0);
   if (const int64_t g = sct::tune(SCT_TUNE_ALLPAIRS_GRAB, 0); g > 0) p->grab = g;
   if (const int64_t g = sct::tune(SCT_TUNE_ALLPAIRS_GRID, 0); g > 0) p->grid = (int)g;
@@ -1335,6 +1373,26 @@ int64_t chunk_of_item(const sct_allpairs_plan* p, int64_t t) {
   while (c < p->nchunks - 1 && base + rows_of_chunk(p, c) <= t) base += rows_of_chunk(p, c++);
   return c;
 }
+
+// an entry point's item range lies in the plan; `also` / `or_what`: what else that entry point asks
+int check_item_range(const sct_allpairs_plan* plan, int64_t item_begin, int64_t item_end, bool also = true,
+                     const char* or_what = "") {
+  SCT_CHECK(0 <= item_begin && item_begin <= item_end && item_end <= plan->items && also,
+            "item range [%lld, %lld) outside [0, %lld)%s", (long long)item_begin, (long long)item_end,
+            (long long)plan->items, or_what);
+  return SCT_OK;
+}
+
+// the close-pairs arguments of the plan call and of the one-shot host call
+int check_close_args(int64_t n, int max_d, const int32_t* i, const int32_t* j, const uint8_t* dist, int64_t room) {
+  constexpr int kMaxD = sct::close_pairs::kMaxD;
+  if (max_d < 0 || max_d > kMaxD) return sct::fail(SCT_E_RANGE, "max_d %d outside [0, %d]", max_d, kMaxD);
+  if (n >= (1LL << 31)) return sct::fail(SCT_E_RANGE, "close pairs index %lld codes with int32", (long long)n);
+  if (room >= (1LL << 31)) return sct::fail(SCT_E_RANGE, "room %lld: at most 2^31 - 1 pairs per call", (long long)room);
+  SCT_CHECK(room >= 0 && (room == 0 || (i != nullptr && j != nullptr && dist != nullptr)),
+            "room %lld needs its three pair arrays", (long long)room);
+  return SCT_OK;
+}
 }  // namespace
 
 extern "C" int sct_allpairs_build(sct_allpairs_plan* plan, void* stream) {
@@ -1345,9 +1403,7 @@ extern "C" int sct_allpairs_build(sct_allpairs_plan* plan, void* stream) {
 extern "C" int sct_allpairs_build_items(sct_allpairs_plan* plan, int64_t item_begin, int64_t item_end,
                                         void* stream) {
   SCT_CHECK(plan != nullptr, "plan is NULL");
-  SCT_CHECK(0 <= item_begin && item_begin <= item_end && item_end <= plan->items,
-            "item range [%lld, %lld) outside [0, %lld)", (long long)item_begin, (long long)item_end,
-            (long long)plan->items);
+  SCT_TRY(check_item_range(plan, item_begin, item_end));
   hipStream_t s = sct::as_stream(stream);
   if (plan->scheme == SCT_ALLPAIRS_SPECTRAL) {
     const int rc = sct_spectral::build(plan->spec, plan->d_codes, s);
@@ -1428,9 +1484,7 @@ extern "C" int sct_allpairs_count(sct_allpairs_plan* plan, int64_t item_begin, i
   SCT_CHECK(plan != nullptr, "plan is NULL");
   sct::scalar_quiesce();  // persistent grids below size themselves to the resident slots
   SCT_CHECK(d_counts != nullptr, "counts is NULL");
-  SCT_CHECK(0 <= item_begin && item_begin <= item_end && item_end <= plan->items,
-            "item range [%lld, %lld) outside [0, %lld)", (long long)item_begin,
-            (long long)item_end, (long long)plan->items);
+  SCT_TRY(check_item_range(plan, item_begin, item_end));
   if (item_begin == item_end) return SCT_OK;
   hipStream_t s = sct::as_stream(stream);
   const int rc = plan->scheme == SCT_ALLPAIRS_SPECTRAL
@@ -1449,15 +1503,9 @@ extern "C" int sct_allpairs_close_pairs(sct_allpairs_plan* plan, int64_t item_be
   SCT_CHECK(plan->scheme == SCT_ALLPAIRS_SUBSETS,
             "close pairs need a SUBSETS plan: its table keeps the caller's order (this plan's scheme is %d)",
             plan->scheme);
-  if (max_d < 0 || max_d > cp::kMaxD) return sct::fail(SCT_E_RANGE, "max_d %d outside [0, %d]", max_d, cp::kMaxD);
-  if (plan->n >= (1LL << 31)) return sct::fail(SCT_E_RANGE, "close pairs index %lld codes with int32", (long long)plan->n);
-  if (room >= (1LL << 31)) return sct::fail(SCT_E_RANGE, "room %lld: at most 2^31 - 1 pairs per call", (long long)room);
+  SCT_TRY(check_close_args(plan->n, max_d, d_i, d_j, d_dist, room));
   SCT_CHECK(d_stats != nullptr, "stats is NULL");
-  SCT_CHECK(room >= 0 && (room == 0 || (d_i != nullptr && d_j != nullptr && d_dist != nullptr)),
-            "room %lld needs its three pair arrays", (long long)room);
-  SCT_CHECK(0 <= item_begin && item_begin <= item_end && item_end <= plan->items,
-            "item range [%lld, %lld) outside [0, %lld)", (long long)item_begin, (long long)item_end,
-            (long long)plan->items);
+  SCT_TRY(check_item_range(plan, item_begin, item_end));
   sct::scalar_quiesce();  // a persistent grid, as the count's
   hipStream_t s = sct::as_stream(stream);
   SCT_HIP(hipMemsetAsync(d_stats, 0, 6 * sizeof(uint64_t), s));
@@ -1495,14 +1543,9 @@ extern "C" int sct_allpairs_close_pairs(sct_allpairs_plan* plan, int64_t item_be
 
 extern "C" int sct_close_pairs_host(const uint64_t* codes, int64_t n, int code_bits, int max_d, int32_t* i,
                                     int32_t* j, uint8_t* dist, int64_t room, uint64_t* stats, uint32_t* degree) {
-  namespace cp = sct::close_pairs;
   SCT_CHECK(stats != nullptr, "stats is NULL");
   SCT_CHECK(n >= 0 && (n == 0 || codes != nullptr), "bad codes");
-  if (max_d < 0 || max_d > cp::kMaxD) return sct::fail(SCT_E_RANGE, "max_d %d outside [0, %d]", max_d, cp::kMaxD);
-  if (n >= (1LL << 31)) return sct::fail(SCT_E_RANGE, "close pairs index %lld codes with int32", (long long)n);
-  if (room >= (1LL << 31)) return sct::fail(SCT_E_RANGE, "room %lld: at most 2^31 - 1 pairs per call", (long long)room);
-  SCT_CHECK(room >= 0 && (room == 0 || (i != nullptr && j != nullptr && dist != nullptr)),
-            "room %lld needs its three pair arrays", (long long)room);
+  SCT_TRY(check_close_args(n, max_d, i, j, dist, room));
   const size_t width = (size_t)max_d + 1;
   for (int k = 0; k < 6; ++k) stats[k] = 0;
   if (degree) std::fill(degree, degree + (size_t)n * width, 0u);
@@ -1542,9 +1585,7 @@ extern "C" int sct_allpairs_time_kernels(sct_allpairs_plan* plan, int64_t item_b
                                          uint64_t* d_counts, int repeats, double* out, void* stream) {
   sct::scalar_quiesce();
   SCT_CHECK(plan != nullptr && d_counts != nullptr && out != nullptr, "NULL pointer");
-  SCT_CHECK(0 <= item_begin && item_begin < item_end && item_end <= plan->items && repeats > 0,
-            "item range [%lld, %lld) outside [0, %lld) or repeats < 1", (long long)item_begin,
-            (long long)item_end, (long long)plan->items);
+  SCT_TRY(check_item_range(plan, item_begin, item_end, item_begin < item_end && repeats > 0, " or repeats < 1"));
   hipStream_t s = sct::as_stream(stream);
   sct_spectral::note_stream(plan->spec, s);  // (the call synchronises before it returns)
   if (plan->scheme == SCT_ALLPAIRS_SPECTRAL) {
